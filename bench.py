@@ -2,6 +2,8 @@
 4096-point x 3-frame fluid clips, batch 8 per GPU (BASELINE.json configs[1]; weak scaling).
 
     python bench.py --gpus 1 --steps 200 --warmup 5
+    python bench.py --full                           # + roofline / per-kernel table / cpu_baseline legs
+    python bench.py --dump-outputs DIR               # + the last timed step's outputs as DIR/<name>.npy
     python bench.py --config cfg4 | cfg5shard        # the other single-GPU workloads of BASELINE.json
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
@@ -10,7 +12,13 @@ One "step" = `tempo_gan_step` semantics with generator AND both discriminators u
 (even iteration > 10, gate open, all-keep mask regime -- SURVEY.md section 8d).  Inputs are
 resident in HBM before the timed region.  Rank 0 prints ONE JSON line.
 
-Extra legs (rank 0, N == 1 only):
+A plain run sets up, warms up, times --steps steps and prints the line (`value`, `ms_per_step`).
+--dump-outputs DIR then also writes what the last timed step computed, one .npy per array (rank 0):
+  loss_<name>.npy          the six losses the step returns (float64, 0-d)
+  <net>.<tensor>.npy       every parameter and buffer of G, Ds, Dt after the step (float32; counters float64)
+Models, clips and host draws are seeded, so the same arguments give the same inputs from run to run.
+
+Extra legs, only with --full (rank 0, N == 1 only):
   roofline      the hand-written kernel with the largest TOTAL time among ALL hand-written kernels,
                 timed live with HIP events on its launch stream while the captured step body runs
                 launch by launch; `roofline_streaming` is the same for the largest HBM-streaming
@@ -288,6 +296,20 @@ def pmc_traffic(kernel):
         return None
 
 
+def dump_outputs(path, models, last):
+    """--dump-outputs: the losses the last timed step returned and the networks it left behind, one .npy per array."""
+    os.makedirs(path, exist_ok=True)
+    for k, v in last.items():
+        np.save(os.path.join(path, f"loss_{k}.npy"), np.asarray(float(v), dtype=np.float64))
+    nbytes, count = 0, 0
+    for tag, m in zip(("G", "Ds", "Dt"), models[:3]):
+        for name, t in list(m.named_parameters()) + list(m.named_buffers()):
+            a = t.detach().cpu().numpy().astype(np.float32 if t.is_floating_point() else np.float64)
+            np.save(os.path.join(path, f"{tag}.{name}.npy"), a)
+            nbytes, count = nbytes + a.nbytes, count + 1
+    log(f"dumped {len(last)} losses and {count} state tensors ({nbytes / 2**20:.1f} MiB) to {path}")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -298,7 +320,11 @@ def main():
     ap.add_argument("--batch", type=int, default=None, help="clips per GPU (default: the workload's, 8)")
     ap.add_argument("--points", type=int, default=None, help="high-res points per frame (default: the workload's)")
     ap.add_argument("--dtype", choices=["bf16", "fp32"], default="bf16")
-    ap.add_argument("--no-extra", action="store_true", help="skip roofline and cpu_baseline legs")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the roofline / per-kernel and cpu_baseline legs (a plain run times the steps only)")
+    ap.add_argument("--no-extra", action="store_true", help="skip roofline and cpu_baseline legs (even with --full)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's losses and the networks' state after it as DIR/<name>.npy")
     ap.add_argument("--cpu-sample-batch", type=int, default=2,
                     help="clips per CPU-baseline step (7 steps are run: 2 warm-up + 5 timed)")
     ap.add_argument("--no-graph", action="store_true",
@@ -309,6 +335,8 @@ def main():
     ap.add_argument("--miopen", action="store_true",
                     help="let PyTorch use MIOpen for conv/BN (first use JIT-compiles per shape: minutes)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     global CONFIG
     CONFIG = args.config
     spec = configs.SPECS[CONFIG]
@@ -406,7 +434,9 @@ def main():
         line["multi_gpu_breakdown"]["note"] = ("mean over the timed steps, max over ranks; HIP events on the step's stream: "
                                                "forward+backward graph, the ONE flat gradient all-reduce (RCCL), optimizer graph")
         log(f"rank {rank}: per-step breakdown {line['multi_gpu_breakdown']}")
-    if rank == 0 and world == 1 and not args.no_extra:
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, models, last)
+    if rank == 0 and world == 1 and args.full and not args.no_extra:
         extra, table = roofline_leg(models, clips, min(args.steps, 5), sync, amp_dtype)
         line.update(extra)
         line["kernels"] = table

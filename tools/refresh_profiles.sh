@@ -49,7 +49,7 @@ PYEOF
 # bench.py quotes the library GEMM time and the PMC traffic from profiles/: give it the files just measured
 cp "$OUT"/${TAG}_*_kernel_stats.csv "$OUT/${TAG}_meta.json" "$OUT/${TAG%_final}_pmc_traffic.json" "$ROOT/profiles/"
 
-python3 "$ROOT/bench.py" > "$OUT/${TAG%_final}_bench_cfg2_bf16.json" 2> "$OUT/bench_cfg2.err"
+python3 "$ROOT/bench.py" --full > "$OUT/${TAG%_final}_bench_cfg2_bf16.json" 2> "$OUT/bench_cfg2.err"
 python3 "$ROOT/bench.py" --config cfg4 --steps 100 --warmup 5 --no-extra > "$OUT/${TAG%_final}_bench_cfg4.json" 2> "$OUT/bench_cfg4.err"
 python3 "$ROOT/bench.py" --config cfg5shard --steps 60 --warmup 5 --no-extra > "$OUT/${TAG%_final}_bench_cfg5shard.json" 2> "$OUT/bench_cfg5shard.err"
 echo "bench lines done"
