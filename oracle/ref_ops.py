@@ -5,6 +5,7 @@ Every function takes/returns numpy arrays with the layouts of include/tpgan_ops.
 import ctypes as C
 
 import numpy as np
+import torch
 
 from . import build
 
@@ -344,3 +345,292 @@ def spectral_norm_bwd(G, Wsn, u, v, sigma):
     G64, W64 = np.asarray(G, np.float64), np.asarray(Wsn, np.float64)
     d = (G64 * W64).sum()
     return ((G64 - d * np.outer(u, v)) / float(sigma)).astype(np.float32)
+
+
+# ---- the fused MLP tail's backward (csrc/mlp_fused.hip): per-launch restatements ------------------------------------
+# Unlike the numpy functions above, these take and return torch tensors: float64 carriers on any device (the GPU tests
+# run the 65535-row contractions on the GPU in float64).  The build uses -ffp-contract=off, so the kernels' only fused
+# operations are the explicit __builtin_fmaf calls and every other fp32 operation rounds once: `Arith(True)` restates
+# that arithmetic exactly, `Arith(False)` is the same formula with every rounding switched off (the algebra alone, for
+# the comparison with torch.autograd).
+U32 = 2.0 ** -24          # unit roundoff of fp32
+BF16_REL = 2.0 ** -8      # one round-to-nearest-even to bf16 moves a value by at most 2^-8 of itself
+
+
+def _f64(t, like=None):
+    if not isinstance(t, torch.Tensor):
+        t = torch.as_tensor(np.asarray(t))
+    return t.to(device=like.device if like is not None else t.device, dtype=torch.float64)
+
+
+def r32(v):
+    """Round float64 values to fp32 (round to nearest even), kept in float64."""
+    return v.to(torch.float32).to(torch.float64)
+
+
+def rbf16(v):
+    """pack_bf16x2 (csrc/mlp_fused.hip:45): round-to-nearest-even of fp32 values to bf16, kept in float64."""
+    return v.to(torch.float32).to(torch.bfloat16).to(torch.float64)
+
+
+def fma32(a, b, c):
+    """__builtin_fmaf on fp32 values held in float64, exact: p = a*b is exact in fp64 (24 + 24 significand bits);
+    s = p + c rounds once in fp64 and t is its TwoSum error.  Rounding s to fp32 is then right unless s lies exactly
+    halfway between two fp32 values while t != 0: s is then moved one fp64 ulp towards t first."""
+    p = a * b
+    s = p + c
+    bb = s - p
+    t = (p - (s - bb)) + (c - bb)
+    half = (s.contiguous().view(torch.int64) & ((1 << 29) - 1)) == (1 << 28)      # fp32 normal range: 29 extra bits
+    inf = torch.full_like(s, float("inf"))
+    s = torch.where(half & (t != 0), torch.nextafter(s, torch.where(t > 0, inf, -inf)), s)
+    return r32(s)
+
+
+class Arith:
+    """The kernels' fp32 operations on float64 carriers (emulate=True), or exact float64 (emulate=False)."""
+
+    def __init__(self, emulate):
+        self.emulate = emulate
+
+    def r(self, v):
+        return r32(v) if self.emulate else v
+
+    def mul(self, a, b):
+        return self.r(a * b)
+
+    def sub(self, a, b):
+        return self.r(a - b)
+
+    def add(self, a, b):
+        return self.r(a + b)
+
+    def fma(self, a, b, c):
+        return fma32(a, b, c) if self.emulate else a * b + c
+
+    def bf16(self, v):
+        return rbf16(v) if self.emulate else v
+
+
+FP32, FP64 = Arith(True), Arith(False)
+
+
+def _rows(c, P):
+    """(nseg, C) per-segment constants -> one row per row of the (nseg*P, C) tensor."""
+    return c.repeat_interleave(P, 0)
+
+
+def _cb(a, mu, rs, c12, ar):
+    c1, c2 = c12[:, 0], c12[:, 1]
+    f = ar.mul(ar.mul(a, rs), c2)                                  # a * rs * c2, left to right
+    return torch.stack([a, ar.mul(f, mu), ar.mul(-a, c1), f], 1)   # a | f*mu | e = -a*c1 | f
+
+
+def mlp_consts(mean, rstd, gamma, beta, c12, ar=FP32):
+    """tpg_mlp_consts, op for op as csrc/mlp_fused.hip:797-817 (mlp_consts_kernel): mean, rstd (nseg,C), gamma, beta
+    (C) or None, c12 (nseg,2,C) or None -> ci (nseg,4,C) = sc | sh | mu | rs, cb (nseg,4,C) = a | f*mu | e | f with
+    a = gamma*rs, f = (a*rs)*c2, e = -a*c1 (cb None without c12)."""
+    mu, rs = _f64(mean), _f64(rstd)
+    a = rs if gamma is None else ar.mul(_f64(gamma, mu)[None], rs)
+    bz = ar.sub(torch.zeros_like(mu) if beta is None else _f64(beta, mu)[None].expand_as(mu), ar.mul(mu, a))
+    ci = torch.stack([a, bz, mu, rs], 1)
+    return ci, (None if c12 is None else _cb(a, mu, rs, _f64(c12, mu), ar))
+
+
+def mlp_finalize_cb(ci, c12, ar=FP32):
+    """The cb that mlp_bwd_finalize_kernel (csrc/mlp_fused.hip:778-785) derives from its own c12 and the ci of the same
+    BatchNorm: a = ci[0], mu = ci[2], f = (a*ci[3])*c2."""
+    ci = _f64(ci)
+    return _cb(ci[:, 0], ci[:, 2], ci[:, 3], _f64(c12, ci), ar)
+
+
+def mlp_max_prep(g, y, cb, slope, nseg, ar=FP32):
+    """tpg_mlp_max_prep, csrc/mlp_fused.hip:419-442: ag = bf16(a * (y > 0 ? g : g*slope)) per (group, channel)."""
+    g, y, cb = _f64(g), _f64(y), _f64(cb)
+    a = _rows(cb[:, 0], g.shape[0] // nseg)
+    s = float(np.float32(slope)) if ar.emulate else float(slope)       # the launch takes the slope as a float
+    return ar.bf16(ar.mul(a, torch.where(y > 0, g, ar.mul(g, s))))
+
+
+def mlp_bn_bwd_apply(g, x, ci, c12, nseg, K=0, ar=FP32):
+    """tpg_mlp_bn_bwd_apply (csrc/mlp_fused.hip:1010-1067): f = (a*rs)*c2, e = a*(((mu*rs)*c2) - c1),
+    dx = bf16(fma(a, g, fma(-f, x, e))).  K > 0: tpg_mlp_bn_bwd_apply_rowsum (1073-1134) -> (dx, qneg) with
+    qneg = -sum_k dx_bf16 over each group of K rows, fp32, k ascending."""
+    g, x, ci, c12 = _f64(g), _f64(x), _f64(ci), _f64(c12)
+    P = x.shape[0] // nseg
+    a, mu, rs, c1, c2 = ci[:, 0], ci[:, 2], ci[:, 3], c12[:, 0], c12[:, 1]
+    f = ar.mul(ar.mul(a, rs), c2)
+    e = ar.mul(a, ar.sub(ar.mul(ar.mul(mu, rs), c2), c1))
+    dx = ar.bf16(ar.fma(_rows(a, P), g, ar.fma(-_rows(f, P), x, _rows(e, P))))
+    if not K:
+        return dx
+    dk = dx.view(-1, K, x.shape[1])
+    q = torch.zeros_like(dk[:, 0])
+    for k in range(K):
+        q = ar.sub(q, dk[:, k])
+    return dx, q
+
+
+def mlp_bwd_operands(x_out, g_out, arg, K, cbo, x_in, cbi, slope_in, nseg, ar=FP32, round_d=True):
+    """The MFMA operands of tpg_mlp_dgrad / tpg_mlp_wgrad as the kernels define them (both read the same).
+
+    d = dx_out - e per row and output channel (d_out8<MODE>, csrc/mlp_fused.hip:390-414):
+        DENSE  fma(a, g, fma(-f, x, f*mu))       MAX  fma(-f, x, f*mu) + (arg == row % K ? ag : 0)
+      round_d=True: in the kernel's fp32 and rounded to bf16 (the `emulated` level); round_d=False: exact in float64
+      (the `contract` level), with R_d bounding what the kernel's fp32 steps and bf16 rounding may move each element:
+      |d_kernel - d| <= 2^-8 |d| + 2^-22 (|c| + |d|), c = -f (x - mu) (one rounding of c, one of c + a g, one to bf16).
+    z_in = fma(x_in, sc, sh) in fp32, the lrelu' mask m = z_in > 0 ? 1 : slope_in, a_in = bf16(max(z, z*slope_in))
+    (the mlp_wgrad_kernel prologue, 921-937); W is rounded to bf16 by the consumers below."""
+    x_out, x_in, cbo, cbi = _f64(x_out), _f64(x_in), _f64(cbo), _f64(cbi)
+    P = x_out.shape[0] // nseg
+    a, fm, e, f = (_rows(cbo[:, i], P) for i in range(4))
+    if round_d:
+        c = ar.fma(-f, x_out, fm)
+    else:
+        c = fm - f * x_out
+    if arg is None:
+        g_out = _f64(g_out, x_out)
+        d = ar.fma(a, g_out, c) if round_d else a * g_out + c
+    else:
+        rows = torch.arange(x_out.shape[0], device=x_out.device)
+        grp = rows // K                                  # segments hold whole groups: global group = row // K
+        hit = arg.to(x_out.device).long()[grp] == (rows % P % K)[:, None]
+        gg = torch.where(hit, _f64(g_out, x_out)[grp], torch.zeros_like(x_out))
+        d = ar.add(c, gg) if round_d else c + gg
+    if round_d:
+        d, R = ar.bf16(d), torch.zeros_like(d)
+    else:
+        R = BF16_REL * d.abs() + 2.0 ** -22 * (c.abs() + d.abs())
+    s = float(np.float32(slope_in)) if ar.emulate else float(slope_in)
+    sc, sh, mu = (_rows(cbi[:, i], P) for i in range(3))
+    z = ar.fma(x_in, sc, sh)
+    m = torch.where(z > 0, torch.ones_like(z), torch.full_like(z, s))
+    a_in = ar.bf16(torch.where(z > 0, z, ar.mul(z, s)))
+    xm = ar.sub(x_in, mu)                                # x_in - mu in fp32, as the dgrad epilogue's sums take it
+    return dict(d=d, R=R, e=_f64(cbo[:, 2]), m=m, a_in=a_in, xm=xm, rs=cbi[:, 3], nseg=nseg, P=P, ar=ar)
+
+
+def mlp_dgrad_ref(ops, W, round_w=True):
+    """tpg_mlp_dgrad from mlp_bwd_operands: g_in = ((d + e) . W_bf) * m before its rounding to bf16 (the kernel adds
+    e^T W as a bias in its epilogue, 494-500 and 639-659), the magnitude M = (|d| |W_bf| + |e| |W_bf|) |m| and the
+    contract level's allowance R = (R_d |W_bf|) |m| of every element; then BN_in's backward sums of the launch's
+    finalize (730-792): c12 = (sum g / P | rs * sum g (x - mu) / P), dbeta = sum over segments of sum g, dgamma = of
+    rs * sum g (x - mu).  The kernel sums the UNROUNDED fp32 g of its epilogue, not the stored bf16 rows: so does this.
+    S1 / S2 (nseg, C): sum (M + |g|) resp. rs * sum (M + |g|) |x - mu| per segment, what the sums' bounds scale with."""
+    nseg, P, ar = ops["nseg"], ops["P"], ops["ar"]
+    Wb = ar.bf16(_f64(W, ops["d"])) if round_w else _f64(W, ops["d"])
+    Wb = Wb.view(-1, *Wb.shape[-2:])
+    g, M, R = [], [], []
+    for s in range(nseg):
+        w = Wb[s if Wb.shape[0] > 1 else 0]
+        sl = slice(s * P, (s + 1) * P)
+        d, m, e = ops["d"][sl], ops["m"][sl], ops["e"][s]
+        g.append((d @ w + (e @ w)[None]) * m)
+        M.append((d.abs() @ w.abs() + (e.abs() @ w.abs())[None]) * m.abs())
+        R.append((ops["R"][sl] @ w.abs()) * m.abs())
+    g, M, R = torch.cat(g), torch.cat(M), torch.cat(R)
+    rs, xm = ops["rs"], ops["xm"]
+    Cin = g.shape[1]
+    s1 = g.view(nseg, P, Cin).sum(1)
+    sx = (g * xm).view(nseg, P, Cin).sum(1) * rs
+    w1 = M + g.abs()
+    S1 = w1.view(nseg, P, Cin).sum(1)
+    S2 = (w1 * xm.abs()).view(nseg, P, Cin).sum(1) * rs
+    return dict(g=g, M=M, R=R, c12=ar.r(torch.stack([s1 / P, sx / P], 1)), dbeta=ar.r(s1.sum(0)),
+                dgamma=ar.r(sx.sum(0)), S1=S1, S2=S2)
+
+
+def mlp_wgrad_ref(ops):
+    """tpg_mlp_wgrad from mlp_bwd_operands (mlp_wgrad_kernel 845-980 + mlp_wgrad_reduce_kernel 984-1006):
+    dW[s] = d^T a_in + e (x) sum_rows a_in per segment, M = |d|^T |a_in| + |e| (x) sum |a_in|, R = R_d^T |a_in|."""
+    nseg, P = ops["nseg"], ops["P"]
+    dW, M, R = [], [], []
+    for s in range(nseg):
+        sl = slice(s * P, (s + 1) * P)
+        d, A, e = ops["d"][sl], ops["a_in"][sl], ops["e"][s]
+        dW.append(d.t() @ A + e[:, None] * A.sum(0)[None])
+        M.append(d.abs().t() @ A.abs() + e.abs()[:, None] * A.abs().sum(0)[None])
+        R.append(ops["R"][sl].t() @ A.abs())
+    return dict(dW=torch.stack(dW), M=torch.stack(M), R=torch.stack(R))
+
+
+# The fp32 accumulation bound: a sum of n terms computed in fp32 along a summation tree of depth h, in any order, is
+# within h * 2^-24 * sum |terms| of the exact sum (to first order).  The deepest chains of these launches are the data
+# gradient's Cout + 2 (the MFMA k-loop over the output channels, the e^T W bias summed sequentially, its addition, the
+# lrelu' product) and the weight gradient's rows of a workgroup + 1 + ceil(G/4) + 3 (a workgroup's row tiles into one
+# accumulator, the rank-one fma, then mlp_wgrad_reduce_kernel's four strided groups of slabs and their combination):
+# at most ~340 for every launch geometry of the tests (which assert h <= 512), so kappa = 512 * 2^-24 = 2^-15.
+MLP_KAPPA = 2.0 ** -15
+
+
+def mlp_bwd_case(Cin, Cout, P, nseg, per_seg, K, mode_max, slope_out, seed, device="cpu", mu_channel=5):
+    """Inputs of one dgrad / wgrad launch: bf16 rows x_in (nseg*P, Cin), x_out (nseg*P, Cout) with per-channel offsets,
+    x_out's channel `mu_channel` at |mu| / sigma ~ 1e3 (1 +- 2^-7 on one row in 61); fp32 mean / rstd of the rows' own
+    fp64 statistics per segment (eps 1e-5), gamma / beta; c12_out of the arriving gradient gg in fp64.
+    DENSE: g_out (nseg*P, Cout) bf16, on the |mu| >> sigma channel correlated with xhat (so that c2, and with it the
+    f*(x - mu) term that the centring protects, is O(1) there).  MAX: gout, y = lrelu(.) of slope_out, arg (nseg*P/K,
+    Cout); gg = gout * lrelu'(y) on each group's arg-max row.  W (nseg or 1, Cout, Cin) fp32.  All on `device`."""
+    g = torch.Generator().manual_seed(seed)
+    N = nseg * P
+    x_in = (torch.randn(N, Cin, generator=g) * 0.8 + 0.5 * torch.randn(Cin, generator=g)).bfloat16()
+    x_out = (torch.randn(N, Cout, generator=g) + torch.randn(Cout, generator=g)).bfloat16()
+    r = torch.arange(N) % P
+    k = torch.where(r % 122 == 0, 1.0, torch.where(r % 122 == 61, -1.0, 0.0))
+    x_out[:, mu_channel] = (1.0 + k * 2.0 ** -7).bfloat16()
+
+    def stats(x):
+        xv = x.double().view(nseg, P, -1)
+        return xv.mean(1).float(), (1.0 / torch.sqrt(xv.var(1, unbiased=False) + 1e-5)).float()
+    mean_in, rstd_in = stats(x_in)
+    mean_out, rstd_out = stats(x_out)
+    gamma_in, beta_in = torch.rand(Cin, generator=g) + 0.5, 0.3 * torch.randn(Cin, generator=g)
+    gamma_out, beta_out = torch.rand(Cout, generator=g) + 0.5, 0.3 * torch.randn(Cout, generator=g)
+    xhat = (x_out.double() - mean_out.double().repeat_interleave(P, 0)) * rstd_out.double().repeat_interleave(P, 0)
+    case = dict(x_in=x_in, x_out=x_out, mean_in=mean_in, rstd_in=rstd_in, mean_out=mean_out, rstd_out=rstd_out,
+                gamma_in=gamma_in, beta_in=beta_in, gamma_out=gamma_out, beta_out=beta_out, K=K if mode_max else 0)
+    if mode_max:
+        G = P // K
+        gout = torch.randn(nseg * G, Cout, generator=g).bfloat16()
+        y = torch.randn(nseg * G, Cout, generator=g)
+        y = torch.where(y > 0, y, y * slope_out).bfloat16()
+        arg = torch.randint(0, K, (nseg * G, Cout), generator=g).to(torch.uint8)
+        gg = torch.zeros(nseg * G, K, Cout, dtype=torch.float64)
+        gg.scatter_(1, arg.long()[:, None], (gout.double() * torch.where(y > 0, 1.0, float(slope_out)).double())[:, None])
+        gg = gg.view(N, Cout)
+        case.update(gout=gout, y=y, arg=arg)
+    else:
+        g_out = torch.randn(N, Cout, generator=g)
+        g_out[:, mu_channel] = 0.5 * xhat[:, mu_channel].float() + 0.5 * g_out[:, mu_channel]
+        g_out = g_out.bfloat16()
+        gg = g_out.double()
+        case.update(g_out=g_out, arg=None)
+    c12 = torch.stack([gg.view(nseg, P, -1).mean(1), (gg * xhat).view(nseg, P, -1).mean(1)], 1).float()
+    W = torch.randn(nseg if per_seg else 1, Cout, Cin, generator=g) / Cin ** 0.5
+    case.update(c12_out=c12, W=W if (per_seg or nseg == 1) else W[0])
+    return {n: (v.to(device) if isinstance(v, torch.Tensor) else v) for n, v in case.items()}
+
+
+# comparison helpers shared by tests/test_oracle_cpu.py (planted defects) and tests/test_mlp_gpu.py (the kernels)
+def gin_bound(ref, M, R, kappa):
+    """A bf16-stored g_in: one RNE rounding (2^-8 of the fp32 value, itself within kappa*M + R of ref) plus the fp32
+    accumulation (kappa*M) plus, at the contract level, the rounding allowance of d carried through W (R)."""
+    return BF16_REL * ref.abs() + (1.0 + BF16_REL) * (kappa * M + R)
+
+
+def dw_bound(M, R, kappa):
+    """An fp32 dW: the accumulation over rows, slabs and the rank-one term (kappa*M) plus R (contract level)."""
+    return kappa * M + R
+
+
+def sums_bound(S, ref, kappa):
+    """BN_in's backward sums: each summed g within kappa*M of the reference, summed in fp32 at a depth that kappa also
+    bounds (kappa * (1 + kappa) * S, S = sum (M + |g|) times the sum's weight), then rounded once to fp32."""
+    return kappa * (1.0 + kappa) * S + U32 * ref.abs()
+
+
+def err_ratio(got, ref, bound):
+    """max over the elements of |got - ref| / bound (0 where equal, inf where bound == 0 and they differ): <= 1 passes."""
+    err = (_f64(got) - _f64(ref, _f64(got))).abs()
+    bound = _f64(bound, err)
+    r = torch.where(err == 0, torch.zeros_like(err), err / bound)
+    return float(r.max()) if r.numel() else 0.0

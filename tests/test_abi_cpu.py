@@ -135,3 +135,30 @@ def test_new_entries_reject_bad_arguments_before_any_launch(hip_lib):
                                              p, 1, None) == -1      # no cb
     assert hip_lib.tpg_rowbn_bwd_sums_consts(p, 1, p, 1, p, None, 1, 64, 8, 64, 1, p, p, p, p, 0.2, None, None, p, p, p,
                                              p, 1, None) == -3      # ag wanted, no y to take lrelu' from
+    # the fused tail's backward entries (csrc/mlp_fused.hip): every call below is malformed in exactly one way
+    q = C.c_void_p(p.value + 4)                                       # not 8-byte aligned
+
+    def dgrad(x_out=p, arg=None, K=0, W=p, P=64, Cin=64, Cout=64, nseg=1, mode=0, g_in=p):
+        return hip_lib.tpg_mlp_dgrad(x_out, p, arg, K, p, p, p, 0.01, W, 0, P, Cin, Cout, nseg, mode, g_in, None, None,
+                                     None, None, p, None)
+
+    def wgrad(x_out=p, arg=None, K=0, W=p, P=64, Cin=64, Cout=64, nseg=1, mode=0, g_in=p):
+        return hip_lib.tpg_mlp_wgrad(x_out, p, arg, K, p, p, p, 0.01, P, Cin, Cout, nseg, mode, g_in, p, None)
+    for fn in (dgrad, wgrad):
+        assert fn(P=65, nseg=2) == -1                                 # P % nseg
+        assert fn(mode=2) == -1                                       # unknown mode
+        assert fn(mode=1, arg=p, K=5) == -1                           # (P / nseg) % K
+        assert fn(mode=1, arg=p, K=0) == -1
+        assert fn(mode=1, arg=p, K=257, P=257 * 2) == -1
+        assert fn(mode=1, arg=None, K=8) == -1                        # MAX without arg
+        assert fn(x_out=None) == -1 and fn(g_in=None) == -1           # required pointers
+        for ci, co in ((64, 256), (256, 64), (96, 128)):
+            assert fn(Cin=ci, Cout=co) == -3, (fn.__name__, ci, co)
+        assert fn(x_out=q) == -3 and fn(g_in=q) == -3 and fn(mode=1, arg=q, K=8) == -3
+    assert dgrad(W=None) == -1 and dgrad(W=q) == -3
+    assert hip_lib.tpg_mlp_max_prep(p, p, p, 0.01, 65, 64, 2, p, None) == -1     # rows % nseg
+    assert hip_lib.tpg_mlp_max_prep(p, p, p, 0.01, 64, 60, 1, p, None) == -1     # C % 8
+    assert hip_lib.tpg_mlp_consts(p, p, p, p, None, 64, 1, None, p, None) == -1   # cb without c12
+    assert hip_lib.tpg_mlp_consts(p, p, p, p, p, 64, 1, None, None, None) == -1  # nothing wanted
+    assert hip_lib.tpg_mlp_bn_bwd_apply(p, p, p, p, 64, 60, 1, p, None) == -3
+    assert hip_lib.tpg_mlp_bn_bwd_apply(p, p, p, p, 65, 64, 2, p, None) == -1

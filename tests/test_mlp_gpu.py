@@ -75,6 +75,29 @@ def test_mlp_fwd_matches_torch(hip, Cin, Cout, P, nseg):
     assert int(nbt) == nseg
 
 
+def test_mlp_fwd_mean_shift_enters_the_running_mean_only(hip):
+    """mean_shift (set_abstraction.py hands the conv biases left out of the product through it): the running mean tracks
+    mean_s(y) + shift, chained segment by segment as (1 - m) rm + m (mean_s(y) + shift); mean, rstd and the folded
+    constants are those of the launch without the shift, bit for bit; the running variance is unchanged by it."""
+    P, nseg, Cin, Cout = 3 * 4096, 3, 64, 128
+    x, W, ss = _layer_inputs(P, Cin, Cout, nseg, seed=11)
+    shift = torch.randn(Cout, device="cuda")
+    gamma, beta = torch.rand(Cout, device="cuda") + 0.5, torch.randn(Cout, device="cuda") * 0.1
+    res = []
+    for sh in (None, shift):
+        rm, rv = torch.full((Cout,), 0.5, device="cuda"), torch.ones(Cout, device="cuda")
+        y, ci, mean, rstd = hip.mlp_fwd(x, ss, 0.01, W, nseg, 1e-5, 0.1, rm, rv, None, sh, gamma, beta, mean_rstd=True)
+        res.append((y, ci, mean, rstd, rm, rv))
+    (y0, ci0, m0, r0, rm0, rv0), (y1, ci1, m1, r1, rm1, rv1) = res
+    assert torch.equal(y0, y1) and torch.equal(ci0, ci1) and torch.equal(m0, m1) and torch.equal(r0, r1)
+    assert torch.equal(rv0, rv1)
+    ms = y1.double().view(nseg, P // nseg, Cout).mean(1).cpu()
+    erm = torch.full((Cout,), 0.5, dtype=torch.float64)
+    for s in range(nseg):
+        erm = 0.9 * erm + 0.1 * (ms[s] + shift.double().cpu())
+    assert torch.allclose(rm1.double().cpu(), erm, rtol=0, atol=1e-5), float((rm1.double().cpu() - erm).abs().max())
+
+
 def test_mlp_fwd_statistics_survive_a_large_mean(hip):
     """|mean| / sigma = 1e3 in the OUTPUT: the pivoted, Chan-combined sums keep the variance."""
     P, Cin, Cout = 65536, 64, 128
@@ -442,3 +465,125 @@ def test_row_linear_is_bitwise_reproducible():
         res.append((y.detach().clone(),) + tuple(g.clone() for g in torch.autograd.grad(y, [xa, W, b], gy)))
     for a, c in zip(*res):
         assert torch.equal(a, c)
+
+
+# ------------------------------------------------------------------ the tail's backward launches against the fp64 oracle
+# Each backward entry of csrc/mlp_fused.hip, called directly, against its restatement in oracle.ref_ops (contractions in
+# float64 on the GPU).  Elementwise launches: bit for bit.  Contractions: per element, against the `emulated` oracle (d
+# rounded to bf16 exactly as d_out8 rounds it) within one bf16 rounding of the stored value + kappa * M, and against the
+# `contract` oracle (d exact) within that + the rounding allowance of d (oracle.ref_ops.mlp_bwd_operands).
+# kappa = ref_ops.MLP_KAPPA = 2^-15 = 512 fp32 unit roundoffs: the depth of the deepest fp32 summation chain of a
+# launch, which every case asserts from the launch geometry (`_depths`); the planted-defect tests in
+# tests/test_oracle_cpu.py show that these bounds reject one duplicated or dropped row at the grid's shapes.
+_MLP_PAIRS = [(64, 64), (64, 128), (128, 64), (128, 128), (128, 256), (256, 128), (256, 256)]
+# rows per segment, nseg, per-segment W, K (MAX mode)
+_BWD_SHAPES = [(4096, 1, False, 32), (1000, 1, False, 8), (37, 1, False, 37), (65535, 1, False, 255),
+               (2997, 3, True, 9), (192, 70, True, 3), (256, 2, False, 256)]
+_WORST = {}
+
+
+def _note(check, ratio):
+    _WORST[check] = max(_WORST.get(check, 0.0), ratio)
+    assert ratio <= 1.0, (check, ratio)
+
+
+@pytest.fixture(scope="module", autouse=True)
+def _report_worst():
+    yield
+    if _WORST:
+        print("\nlargest error / bound per check: " + ", ".join(f"{k} {v:.3g}" for k, v in sorted(_WORST.items())))
+
+
+def _depths(hip, P, nseg, Cin, Cout):
+    """Deepest fp32 summation chains of one dgrad / wgrad launch (the launchers' geometry, csrc/mlp_fused.hip)."""
+    G = hip.lib.tpg_mlp_wgrad_workspace_bytes(P * nseg, Cin, Cout, nseg) // (4 * nseg * Cin * Cout)
+    rows_wg = -(-(-(-P // 64)) // G) * 64
+    h_w = rows_wg + 1 + -(-G // 4) + 3
+    strips = 2 if (Cin == 64 and Cout <= 128) else 1
+    smem = Cin * (Cout + 8) * 2 + 4 * (4 * Cout + Cin + 8 * Cin)
+    slots = 256 if (smem > 60 * 1024 or Cin == 256) else 512
+    tiles = -(-P // (64 * strips))
+    Gd = min(tiles, max(16, slots // nseg))
+    h_s = -(-tiles // Gd) * 4 * strips + 6          # a lane's rows, 2 shuffles, 4 waves (then fp64)
+    return Cout + 2, h_w, h_s
+
+
+def _bits(t):
+    return t.contiguous().view(torch.int16 if t.element_size() == 2 else torch.int32)
+
+
+def _same_bits(got, ref64):
+    """Kernel output == oracle value, bit for bit (ref64: float64 holding a value of got's type)."""
+    return torch.equal(_bits(got), _bits(ref64.to(got.dtype)))
+
+
+def _run_bwd_case(hip, Cin, Cout, P, nseg, per_seg, K, mode_max, slope_in=0.01, slope_out=0.01):
+    from oracle import ref_ops as R
+    kap = R.MLP_KAPPA
+    for h in _depths(hip, P, nseg, Cin, Cout):
+        assert h * R.U32 <= kap, h
+    c = R.mlp_bwd_case(Cin, Cout, P, nseg, per_seg, K, mode_max, slope_out, seed=Cin * 7 + Cout + P + nseg, device="cuda")
+    K = c["K"]
+    # constants: the kernel's, equal to the oracle's bit for bit, then used by both
+    ci_in = hip.mlp_consts(c["mean_in"], c["rstd_in"], c["gamma_in"], c["beta_in"], None, True, False)[0]
+    ci_o, cb_o = hip.mlp_consts(c["mean_out"], c["rstd_out"], c["gamma_out"], c["beta_out"], c["c12_out"], True, True)
+    r_ci, _ = R.mlp_consts(c["mean_in"], c["rstd_in"], c["gamma_in"], c["beta_in"], None)
+    r_cio, r_cbo = R.mlp_consts(c["mean_out"], c["rstd_out"], c["gamma_out"], c["beta_out"], c["c12_out"])
+    assert _same_bits(ci_in, r_ci) and _same_bits(ci_o, r_cio) and _same_bits(cb_o, r_cbo), "mlp_consts"
+    if mode_max:
+        ag = hip.mlp_max_prep(c["gout"], c["y"], cb_o, slope_out, nseg)
+        assert _same_bits(ag, R.mlp_max_prep(c["gout"], c["y"], cb_o, slope_out, nseg)), "mlp_max_prep"
+        # the by-product of the last BatchNorm's backward sums: the same bits
+        *_, ag2 = hip.rowbn_bwd_sums(c["gout"], c["x_out"], c["arg"], c["y"], K, c["mean_out"], c["rstd_out"],
+                                     c["gamma_out"], c["beta_out"], slope_out, True, nseg, want_cb=True)
+        assert ag2 is not None and torch.equal(_bits(ag2), _bits(ag)), "rowbn_bwd_sums_consts ag"
+        g_arg = ag
+    else:
+        g_arg = c["g_out"]
+    args = (c["x_out"], g_arg, c["arg"], K, cb_o, c["x_in"], ci_in, slope_in)
+    g_in, c12, cb_in, dgam, dbet = hip.mlp_dgrad(*args, c["W"], nseg, True)
+    dW = hip.mlp_wgrad(*args, nseg)
+    torch.cuda.synchronize()
+    again = hip.mlp_dgrad(*args, c["W"], nseg, True)
+    assert all(torch.equal(_bits(u), _bits(v)) for u, v in zip((g_in, c12, cb_in, dgam, dbet), again)), "dgrad repro"
+    assert torch.equal(_bits(dW), _bits(hip.mlp_wgrad(*args, nseg))), "wgrad repro"
+    assert _same_bits(cb_in, R.mlp_finalize_cb(ci_in, c12)), "finalize cb"
+    for level, round_d in (("emulated", True), ("contract", False)):
+        ops = R.mlp_bwd_operands(*args, nseg, round_d=round_d)
+        dg, wg = R.mlp_dgrad_ref(ops, c["W"]), R.mlp_wgrad_ref(ops)
+        _note(f"g_in/{level}", R.err_ratio(g_in, dg["g"], R.gin_bound(dg["g"], dg["M"], dg["R"], kap)))
+        _note(f"dW/{level}", R.err_ratio(dW, wg["dW"], R.dw_bound(wg["M"], wg["R"], kap)))
+        if round_d:
+            S1, S2 = dg["S1"], dg["S2"]
+            _note("c1", R.err_ratio(c12[:, 0], dg["c12"][:, 0], R.sums_bound(S1 / P, dg["c12"][:, 0], kap)))
+            _note("c2", R.err_ratio(c12[:, 1], dg["c12"][:, 1], R.sums_bound(S2 / P, dg["c12"][:, 1], kap)))
+            _note("dbeta", R.err_ratio(dbet, dg["dbeta"], R.sums_bound(S1.sum(0), dg["dbeta"], kap)))
+            _note("dgamma", R.err_ratio(dgam, dg["dgamma"], R.sums_bound(S2.sum(0), dg["dgamma"], kap)))
+        del ops, dg, wg
+    if mode_max:
+        # the tail's first BatchNorm on the kernel's own g_in / c12: both apply launches bit for bit
+        dx = hip.mlp_bn_bwd_apply(g_in, c["x_in"], ci_in, c12, nseg)
+        dx2, qneg = hip.mlp_bn_bwd_apply(g_in, c["x_in"], ci_in, c12, nseg, K)
+        rdx, rq = R.mlp_bn_bwd_apply(g_in, c["x_in"], ci_in, c12, nseg, K)
+        assert _same_bits(dx, rdx) and _same_bits(dx2, rdx) and _same_bits(qneg, rq), "mlp_bn_bwd_apply"
+
+
+@pytest.mark.parametrize("P,nseg,per_seg,K,mode_max", [s + (m,) for s in _BWD_SHAPES for m in (False, True)
+                                                      if m or s[3] != 256])
+@pytest.mark.parametrize("Cin,Cout", _MLP_PAIRS)
+def test_mlp_bwd_launches_match_fp64_oracle(hip, Cin, Cout, P, nseg, per_seg, K, mode_max):
+    """The grid: every channel pair x DENSE / MAX x rows per segment 4096 (baseline), 1000 (partial last tile of the
+    64- / 128-row tiles and of WG_ROWS), 37 (less than one tile), 65535 (several tiles per workgroup at the grid's cap,
+    the deferred stores of 128 -> 256 over several tiles, a partial last tile, K = 255), 3 x 2997 (ragged segments with
+    their own weights), 70 x 192 (two sweeps of the finalize kernels), 2 x 256 with K = 256 (MAX only: the ABI's limit,
+    arg-max bytes 0..255).  slope_in = 0.01."""
+    _run_bwd_case(hip, Cin, Cout, P, nseg, per_seg, K, mode_max)
+
+
+@pytest.mark.parametrize("slope", [0.0, 1.0])
+@pytest.mark.parametrize("mode_max", [False, True], ids=["dense", "max"])
+@pytest.mark.parametrize("Cin,Cout", _MLP_PAIRS)
+def test_mlp_bwd_launches_at_slopes_0_and_1(hip, Cin, Cout, mode_max, slope):
+    """LeakyReLU slopes 0 (ReLU: y == 0 on the negative side, the gradient 0 either way) and 1 (no activation), for the
+    input's activation and the max-prep slope, at 1000 rows, K = 8."""
+    _run_bwd_case(hip, Cin, Cout, 1000, 1, False, 8, mode_max, slope_in=slope, slope_out=slope)

@@ -253,3 +253,218 @@ def test_dataset_fps_oracle_matches_the_reference_fixture():
         pts, k, start = g[f"{tag}/pts"], int(g[f"{tag}/k"]), int(g[f"{tag}/start"])
         got = R.fps_start(pts[None], k, np.array([start], np.int32), skip_origin=False)[0]
         assert np.array_equal(got, g[f"{tag}/idx"]), tag
+
+
+# ------------------------------------------------------------------ the fused MLP tail's backward, launch by launch
+def _tail_autograd(x0, gammas, betas, Ws, slopes, K, nseg, eps):
+    """BatchNorm1d(train) -> LeakyReLU -> Linear(no bias) -> ... -> BatchNorm1d -> LeakyReLU -> max over K, float64,
+    nseg calls on equal consecutive row blocks (one weight per call or one for all)."""
+    import torch
+    import torch.nn.functional as F
+    P = x0.shape[0] // nseg
+    outs = []
+    for s in range(nseg):
+        a = x0[s * P:(s + 1) * P]
+        for l in range(len(gammas)):
+            z = F.batch_norm(a, None, None, gammas[l], betas[l], training=True, eps=eps)
+            a = F.leaky_relu(z, slopes[l])
+            if l < len(Ws):
+                a = a @ (Ws[l][s] if Ws[l].dim() == 3 else Ws[l]).t()
+        outs.append(a.view(P // K, K, -1).max(1)[0])
+    return torch.cat(outs)
+
+
+@pytest.mark.parametrize("chain", [(8, 16), (16, 8, 24)])
+@pytest.mark.parametrize("nseg,per_seg", [(1, False), (3, False), (3, True)])
+@pytest.mark.parametrize("K", [1, 7])
+@pytest.mark.parametrize("slope", [0.01, 0.0])
+def test_mlp_tail_backward_restatements_chain_to_autograd(chain, nseg, per_seg, K, slope):
+    """The per-launch restatements of the fused tail's backward (oracle.ref_ops: mlp_consts, mlp_max_prep, the dgrad /
+    wgrad contractions, the finalize's c12 / cb, mlp_bn_bwd_apply), with every rounding switched off, chained exactly as
+    ops._MlpTail.backward chains the launches, against torch.autograd in float64 on the plain statement of the tail.
+    This pins the folded constants (a, f*mu, e, f, c12) and both rank-one terms (e^T W, e (x) sum a_in) independently
+    of any GPU: any algebra slip is O(1), rounding is off, so the bound is 1e-10 relative."""
+    import torch
+    A = R.FP64
+    eps = 1e-5
+    L = len(chain) - 1
+    g = torch.Generator().manual_seed(sum(chain) * 10 + nseg + K)
+    P = 9 * K if K > 1 else 40                     # rows per segment
+    x0 = torch.randn(nseg * P, chain[0], generator=g, dtype=torch.float64) + torch.randn(chain[0], generator=g, dtype=torch.float64)
+    gam = [torch.rand(c, generator=g, dtype=torch.float64) + 0.5 for c in chain]
+    bet = [0.3 * torch.randn(c, generator=g, dtype=torch.float64) for c in chain]
+    Ws = [torch.randn(*((nseg,) if per_seg else ()), chain[l + 1], chain[l], generator=g, dtype=torch.float64) / chain[l] ** 0.5
+          for l in range(L)]
+    slopes = [slope] * (L + 1)
+    # ---- forward as the kernels fold it: statistics -> ci, x_{l+1} = W . lrelu(sc*x + sh)
+    xs, cis, stats = [x0], [], []
+    for l in range(L + 1):
+        xv = xs[-1].view(nseg, P, -1)
+        mean, rstd = xv.mean(1), 1.0 / torch.sqrt(xv.var(1, unbiased=False) + eps)
+        stats.append((mean, rstd))
+        cis.append(R.mlp_consts(mean, rstd, gam[l], bet[l], None, A)[0])
+        if l < L:
+            sc, sh = (R._rows(cis[-1][:, i], P) for i in (0, 1))
+            z = xs[-1] * sc + sh
+            a = torch.where(z > 0, z, z * slope)
+            xs.append(torch.cat([a[s * P:(s + 1) * P] @ (Ws[l][s] if per_seg else Ws[l]).t() for s in range(nseg)]))
+    sc, sh = (R._rows(cis[L][:, i], P) for i in (0, 1))
+    z = xs[L] * sc + sh
+    yk = torch.where(z > 0, z, z * slope).view(-1, K, chain[-1])
+    out, arg = yk.max(1)
+    if K > 1:        # no ties in the max (slope 0: tied zeros pass no gradient whichever row wins)
+        top = yk.topk(2, 1)[0]
+        assert ((top[:, 0] > top[:, 1]) | (top[:, 0] == 0)).all()
+    gout = torch.randn(out.shape, generator=g, dtype=torch.float64)
+    # ---- the last BatchNorm's backward sums (tpg_rowbn_bwd_sums_consts): gg lives on the arg-max rows
+    full = torch.zeros(nseg * P // K, K, chain[-1], dtype=torch.float64)
+    full.scatter_(1, arg[:, None], gout[:, None])
+    mean, rstd = stats[L]
+    xhat = (xs[L] - R._rows(mean, P)) * R._rows(rstd, P)
+    gg = full.view(-1, chain[-1]) * torch.where(z > 0, torch.ones_like(z), torch.full_like(z, slope))
+    s1, sx = gg.view(nseg, P, -1).sum(1), (gg * xhat).view(nseg, P, -1).sum(1)
+    c12 = torch.stack([s1 / P, sx / P], 1)
+    got = {f"dgamma{L}": sx.sum(0), f"dbeta{L}": s1.sum(0)}
+    cb = R.mlp_consts(mean, rstd, gam[L], bet[L], c12, A)[1]
+    gnext = R.mlp_max_prep(gout, out, cb, slope, nseg, A)
+    argn, Kn = arg.to(torch.uint8), K
+    for l in range(L, 0, -1):
+        ops = R.mlp_bwd_operands(xs[l], gnext, argn, Kn, cb, xs[l - 1], cis[l - 1], slope, nseg, A, round_d=False)
+        dW = R.mlp_wgrad_ref(ops)["dW"]
+        got[f"dW{l}"] = dW if per_seg else dW.sum(0)
+        dg = R.mlp_dgrad_ref(ops, Ws[l - 1])
+        got[f"dgamma{l - 1}"], got[f"dbeta{l - 1}"] = dg["dgamma"], dg["dbeta"]
+        c12 = dg["c12"]
+        cb = R.mlp_finalize_cb(cis[l - 1], c12, A)
+        gnext, argn, Kn = dg["g"], None, 0
+    got["dx0"] = R.mlp_bn_bwd_apply(gnext, x0, cis[0], c12, nseg, 0, A)
+    # ---- autograd on the plain statement
+    leaves = [x0.clone().requires_grad_(True)] + [w.clone().requires_grad_(True) for w in Ws] + \
+             [t.clone().requires_grad_(True) for t in gam + bet]
+    ref = _tail_autograd(leaves[0], leaves[1 + L:2 + 2 * L], leaves[2 + 2 * L:], leaves[1:1 + L], slopes, K, nseg, eps)
+    assert torch.allclose(ref, out, rtol=1e-12, atol=1e-12)
+    grads = torch.autograd.grad(ref, leaves, gout)
+    names = ["dx0"] + [f"dW{l + 1}" for l in range(L)] + [f"dgamma{l}" for l in range(L + 1)] + [f"dbeta{l}" for l in range(L + 1)]
+    for name, w in zip(names, grads):
+        rel = float((got[name] - w).abs().max() / w.abs().max())
+        assert rel <= 1e-10, (name, rel)
+
+
+def _emulated(case, nseg, cbo=None, arg=None):
+    """The oracle's emulated level of one launch pair on a case of R.mlp_bwd_case (constants folded by the oracle)."""
+    ci_in = R.mlp_consts(case["mean_in"], case["rstd_in"], case["gamma_in"], case["beta_in"], None)[0]
+    cb_out = R.mlp_consts(case["mean_out"], case["rstd_out"], case["gamma_out"], case["beta_out"], case["c12_out"])[1]
+    cb_out = cb_out if cbo is None else cbo
+    K = case["K"]
+    g_arg = R.mlp_max_prep(case["gout"], case["y"], cb_out, 0.01, nseg) if K else case["g_out"]
+    ops = R.mlp_bwd_operands(case["x_out"], g_arg, case["arg"] if arg is None else arg, K, cb_out, case["x_in"], ci_in,
+                             0.01, nseg)
+    return ops, cb_out
+
+
+@pytest.mark.parametrize("Cin,Cout,P,nseg,per_seg,K", [(64, 128, 4096, 1, False, 32), (128, 128, 2997, 3, True, 9)])
+def test_mlp_bwd_bounds_reject_planted_defects(Cin, Cout, P, nseg, per_seg, K):
+    """The per-element bounds that tests/test_mlp_gpu.py applies to tpg_mlp_dgrad / tpg_mlp_wgrad (R.gin_bound,
+    R.dw_bound at kappa = R.MLP_KAPPA) accept the oracle's own output, stored as the kernels store it, and reject each
+    defect planted into it at the shapes of the GPU grid -- the evidence that the bounds mean something.  The old
+    test's L2 bound of 3e-2 lets the one-row defects through (asserted too)."""
+    import torch
+    kap = R.MLP_KAPPA
+    case = R.mlp_bwd_case(Cin, Cout, P, nseg, per_seg, K, True, 0.01, seed=P + Cin)
+    ops, cb_out = _emulated(case, nseg)
+    dg, wg = R.mlp_dgrad_ref(ops, case["W"]), R.mlp_wgrad_ref(ops)
+    g_ok, dW_ok = R.rbf16(R.r32(dg["g"])), R.r32(wg["dW"])           # stored as the kernels store them
+
+    def g_ratio(g):
+        return R.err_ratio(g, dg["g"], R.gin_bound(dg["g"], dg["M"], dg["R"], kap))
+
+    def w_ratio(dW):
+        return R.err_ratio(dW, wg["dW"], R.dw_bound(wg["M"], wg["R"], kap))
+
+    def l2(a, b):
+        return float((a - b).norm() / b.norm())
+    assert g_ratio(g_ok) <= 1.0 and w_ratio(dW_ok) <= 1.0
+    d, A, m = ops["d"], ops["a_in"], ops["m"]
+    seg = nseg - 1
+    last = seg * P + P - 1                         # the ragged last tile's last row (P % 64 != 0 at 2997)
+    row = seg * P + P // 3
+
+    def row_term(r):
+        return torch.outer(d[r] + ops["e"][r // P], A[r])
+    # one row counted twice; one row dropped
+    for r in (row, last):
+        dW = dW_ok.clone()
+        dW[r // P] += row_term(r)
+        assert w_ratio(dW) > 1.0, ("row twice", r)
+        assert l2(dW, wg["dW"]) < 3e-2              # what the 3e-2 L2 bound of the tail tests let through
+        dW = dW_ok.clone()
+        dW[r // P] -= row_term(r)
+        g = g_ok.clone()
+        g[r] = 0.0
+        assert w_ratio(dW) > 1.0 and g_ratio(g) > 1.0, ("row dropped", r)
+    # segment s reading segment s+1's constants (nseg > 1), or a perturbation of the same size (nseg = 1: 2 %)
+    cbo = cb_out.clone()
+    if nseg > 1:
+        cbo[0] = cb_out[1]
+    else:
+        cbo[0] = cb_out[0] * 1.02
+    ops2, _ = _emulated(case, nseg, cbo=cbo)
+    assert g_ratio(R.rbf16(R.r32(R.mlp_dgrad_ref(ops2, case["W"])["g"]))) > 1.0, "cb of segment s+1"
+    assert w_ratio(R.r32(R.mlp_wgrad_ref(ops2)["dW"])) > 1.0, "cb of segment s+1"
+    # the rank-one terms left out
+    sA = torch.stack([A[s * P:(s + 1) * P].sum(0) for s in range(nseg)])
+    assert w_ratio(dW_ok - ops["e"][:, :, None] * sA[:, None, :]) > 1.0, "e (x) sum a_in left out"
+    Wb = R.rbf16(R._f64(case["W"])).view(-1, Cout, Cin)
+    eW = torch.cat([(ops["e"][s] @ Wb[s if Wb.shape[0] > 1 else 0])[None].expand(P, Cin) for s in range(nseg)])
+    assert g_ratio(R.rbf16(R.r32(dg["g"] - eW * m))) > 1.0, "e^T W left out"
+    # one 16-channel output tile of dW zeroed
+    dW = dW_ok.clone()
+    dW[:, 16:32] = 0.0
+    assert w_ratio(dW) > 1.0, "16-channel tile"
+    # the arg-max of one group routed to k+1
+    arg = case["arg"].clone()
+    grp = (seg * P + P // 2) // K
+    arg[grp] = (arg[grp].long() + 1) % K
+    ops3, _ = _emulated(case, nseg, arg=arg)
+    assert g_ratio(R.rbf16(R.r32(R.mlp_dgrad_ref(ops3, case["W"])["g"]))) > 1.0, "arg-max to k+1"
+    # W left in fp32
+    assert g_ratio(R.rbf16(R.r32(R.mlp_dgrad_ref(ops, case["W"], round_w=False)["g"]))) > 1.0, "W not rounded"
+
+
+def test_mlp_wgrad_bound_rejects_a_duplicated_row_tile():
+    """65535 rows of the 128 -> 256 layer (several tiles per workgroup, a partial last tile, K = 255): one 64-row tile
+    counted twice must fail the per-element dW bound (it passes the old 3e-2 L2 bound)."""
+    import torch
+    P, K = 65535, 255
+    case = R.mlp_bwd_case(128, 256, P, 1, False, K, True, 0.01, seed=7)
+    ops, _ = _emulated(case, 1)
+    wg = R.mlp_wgrad_ref(ops)
+    bound = R.dw_bound(wg["M"], wg["R"], R.MLP_KAPPA)
+    assert R.err_ratio(R.r32(wg["dW"]), wg["dW"], bound) <= 1.0
+    rows = slice(64 * 500, 64 * 501)
+    dup = (ops["d"][rows] + ops["e"][0]).t() @ ops["a_in"][rows]
+    bad = wg["dW"][0] + dup
+    assert R.err_ratio(bad[None], wg["dW"], bound) > 1.0
+    assert float(dup.norm() / wg["dW"].norm()) < 3e-2
+
+
+def test_mlp_contract_bound_rejects_an_uncentred_operand():
+    """The channel of x_out with |mu| / sigma ~ 1e3 (R.mlp_bwd_case): were the MFMA operand formed uncentred again --
+    the bf16 rounding taken on a*g - f*x, of size |f mu|, before f*mu is added back -- the contract-level dW bound
+    would fail, while the kernels' centred operand (the emulated oracle) passes it."""
+    import torch
+    P, nseg = 4096, 1
+    case = R.mlp_bwd_case(64, 128, P, nseg, False, 0, False, 0.01, seed=3)
+    ci_in = R.mlp_consts(case["mean_in"], case["rstd_in"], case["gamma_in"], case["beta_in"], None)[0]
+    cb = R.mlp_consts(case["mean_out"], case["rstd_out"], case["gamma_out"], case["beta_out"], case["c12_out"])[1]
+    args = (case["x_out"], case["g_out"], None, 0, cb, case["x_in"], ci_in, 0.01, nseg)
+    exact = R.mlp_bwd_operands(*args, round_d=False)
+    wg = R.mlp_wgrad_ref(exact)
+    bound = R.dw_bound(wg["M"], wg["R"], R.MLP_KAPPA)
+    centred = R.mlp_bwd_operands(*args)
+    assert R.err_ratio(R.r32(R.mlp_wgrad_ref(centred)["dW"]), wg["dW"], bound) <= 1.0
+    a, fm, f = (R._rows(R._f64(cb)[:, i], P) for i in (0, 1, 3))
+    x, g = R._f64(case["x_out"]), R._f64(case["g_out"])
+    unc = dict(centred)
+    unc["d"] = R.r32(R.rbf16(R.fma32(a, g, R.r32(-f * x))) + fm)
+    assert R.err_ratio(R.r32(R.mlp_wgrad_ref(unc)["dW"]), wg["dW"], bound) > 1.0
