@@ -450,6 +450,23 @@ int tpg_rowlinear_dgrad(const void *gy, const void *y, int dtype_g, const float 
 int tpg_rowlinear_wgrad(const void *x, int dtype_x, const void *gy, const void *y, int dtype_g, long long P, int nseg,
                         int Cin, int Cout, float slope, float *dW, float *db, void *ws, void *stream);
 
+/* ---- rollout: hard-masked expansion with the 25-frame running mask average (csrc/rollout.hip) ----------------
+ * upsampling_network.py:159-174 (`forward_with_context`, the demo notebooks' sequence upsampling) for a chunk of T
+ * consecutive frames t0 .. t0+T-1 of ONE sequence of N points per frame, upsampling ratio r (2 <= r <= 16):
+ *     c_f = clamp of the raw mask to {0, 0.6} (NaN kept);  avg_t = mean of c_f over f in [max(0, t-24), t]
+ *     keep_t(i) = avg_t(i) > 0.01  <=>  some f of the window has m_f(i) >= 0.6 and none has m_f(i) NaN
+ *     out_t = [pos_t(i) + edge_t(i, j) * (keep_t(i) ? 1.0f : 0.0f)  for i, for j < r  if keep_t(i) or j == 0]
+ * pos (T,N,3), edge (T,N*r,3), mask (T,N) f32.  state (2,N) int32, read and updated: [0] = last frame with a hit,
+ * [1] = last frame with a NaN, TPG_CTX_NONE = none (a fresh sequence is all TPG_CTX_NONE); carrying it from one call
+ * to the next (t0 advancing by T) gives what one call over all frames gives.  out: room for T*N*r points, packed frame
+ * after frame, point-major, slot-minor; offsets (T+1) int64: frame t is out[offsets[t] .. offsets[t+1]).
+ * Deterministic, bit-identical to the formula (no FMA).  ws: tpg_context_expand_workspace_bytes(T, N) bytes, 8-byte
+ * aligned.  T <= 65535. */
+#define TPG_CTX_NONE (-2147483647 - 1)
+size_t tpg_context_expand_workspace_bytes(int T, int N);
+int tpg_context_expand_f32(const float *pos, const float *edge, const float *mask, int T, int N, int r, int t0,
+                           int32_t *state, float *out, int64_t *offsets, void *ws, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

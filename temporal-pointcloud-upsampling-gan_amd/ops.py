@@ -257,6 +257,20 @@ class HipBackend:
                    _ptr(xyz), B, N, m, _ptr(temp), _ptr(idx), _ptr(prefix_in), _ptr(flag))
         return idx, flag
 
+    def context_expand(self, pos, edge, mask, state, t0):
+        """Hard-masked expansion of T rollout frames with the running mask average (tpg_context_expand_f32):
+        -> (points (T*N*r, 3): frame t is rows offsets[t]..offsets[t+1], offsets (T+1,) int64); `state` is updated."""
+        T, N, _ = pos.shape
+        r = edge.shape[1] // max(N, 1)
+        out = torch.empty((T * N * r, 3), dtype=torch.float32, device=pos.device)
+        offsets = torch.empty((T + 1,), dtype=torch.int64, device=pos.device)
+        ws = torch.empty((max(self.lib.tpg_context_expand_workspace_bytes(T, N), 8) + 7) // 8, dtype=torch.int64,
+                         device=pos.device)
+        self._call("tpg_context_expand_f32", "context_expand", 4 * T * N * (2 * 3 * r + 3 + 1) + 16 * N, pos,
+                   _ptr(pos), _ptr(edge), _ptr(mask), T, N, r, int(t0), _ptr(state), _ptr(out), _ptr(offsets),
+                   _ptr(ws))
+        return out, offsets
+
     def fps(self, xyz, m, start=None, skip_origin=True):
         B, N, _ = xyz.shape
         idx = torch.empty((B, m), dtype=torch.int32, device=xyz.device)
@@ -883,6 +897,72 @@ def furthest_point_sample_prefix(xyz, npoint, prefix_flag=None):
         if hasattr(be, "fps_prefix"):
             return be.fps_prefix(xyz.detach(), int(npoint), prefix_flag)
         return be.fps(xyz.detach(), int(npoint)), None
+
+
+# --------------------------------------------------- rollout: running mask average (upsampling_network.py:159-174)
+CONTEXT_WINDOW = 25            # frames in the reference's running mask average
+CONTEXT_NONE = -2 ** 31        # state value "no such frame" (TPG_CTX_NONE)
+
+
+def context_state(N, device):
+    """The (2, N) int32 rollout state of a fresh sequence: no frame with a hit, no frame with a NaN."""
+    return torch.full((2, N), CONTEXT_NONE, dtype=torch.int32, device=device)
+
+
+def context_keep(mask, state, t0):
+    """Keep decisions of T frames (t0 .. t0+T-1) from the raw masks (T, N) and the carried state (torch ops; updates
+    `state` in place) -> (T, N) bool.  keep_t(i) <=> a frame of the window [t-24, t] has m >= 0.6 and none has NaN:
+    what the reference's clamp to {0, 0.6}, 25-frame mean and `> 0.01` decide (0.6 / 25 > 0.01, NaN poisons the mean)."""
+    T = mask.shape[0]
+    t = torch.arange(t0, t0 + T, dtype=torch.int32, device=mask.device).view(T, 1)
+    none = torch.full_like(mask, CONTEXT_NONE, dtype=torch.int32)
+    hit = torch.cummax(torch.cat([state[:1], torch.where(mask >= 0.6, t, none)]), 0).values[1:]
+    nan = torch.cummax(torch.cat([state[1:], torch.where(torch.isnan(mask), t, none)]), 0).values[1:]
+    lo = t - (CONTEXT_WINDOW - 1)
+    state.copy_(torch.stack([hit[-1], nan[-1]]))
+    return (hit >= lo) & (nan < lo)
+
+
+def _context_expand_torch(pos, edge, mask, state, t0):
+    """`context_expand` composed of torch ops (backends without the fused kernel): the reference's
+    expand_pos_with_masking(hard_masking=True) per frame on the keep decisions of `context_keep`."""
+    T, N, _ = pos.shape
+    r = edge.shape[1] // N
+    keep = context_keep(mask, state, t0).view(T, N, 1)
+    expanded = pos.repeat(1, 1, r).view(T, -1, 3) + (edge.view(T, N, 3 * r) * keep.float()).view(T, -1, 3)
+    hard = keep.repeat(1, 1, r)
+    hard[:, :, 0] = True
+    counts = hard.view(T, -1).sum(1)
+    offsets = torch.cat([counts.new_zeros(1), torch.cumsum(counts, 0)])
+    return expanded[hard.view(T, -1)], offsets
+
+
+def context_expand(pos, edge, mask, state, t0):
+    """Hard-masked position expansion of T consecutive frames of one rollout with the reference's 25-frame running
+    mask average (upsampling_network.py:159-174), all frames at once.
+
+    pos (T,N,3), edge (T,N*r,3), mask (T,N) raw mask-head outputs, fp32; state (2,N) int32 from `context_state`,
+    updated in place (carry it to the next call with t0 advanced by T); t0 = index of the chunk's first frame in the
+    sequence.  -> (points (P,3), offsets (T+1,) int64 on the device): frame t's surviving points are
+    points[offsets[t]:offsets[t+1]], point-major, slot-minor, as the reference's `expanded[hard]`."""
+    _check_float(pos, "pos", 3)
+    _check_float(edge, "edge", 3)
+    _check_int(state, "state", 2)
+    if mask.dim() == 3 and mask.shape[2] == 1:
+        mask = mask.view(mask.shape[0], mask.shape[1])
+    _check_float(mask, "mask", 2)
+    _same_device(pos, edge, mask, state)
+    T, N, _ = pos.shape
+    _need(pos.shape[2] == 3 and edge.shape[2] == 3, "pos and edge must hold 3-D points")
+    _need(N > 0 and edge.shape[0] == T and edge.shape[1] % N == 0, "edge must be (T, N*r, 3)")
+    _need(tuple(mask.shape) == (T, N) and tuple(state.shape) == (2, N), "mask must be (T, N) and state (2, N)")
+    _need(2 <= edge.shape[1] // N <= 16, "upsampling ratio must be 2..16")
+    _need(int(t0) >= 0, "t0 must be >= 0")
+    be = backend_for(pos)
+    with torch.no_grad():
+        if hasattr(be, "context_expand"):
+            return be.context_expand(pos.detach(), edge.detach(), mask.detach(), state, int(t0))
+        return _context_expand_torch(pos.detach(), edge.detach(), mask.detach(), state, int(t0))
 
 
 def farthest_point_sampling(pts, k, initial_idx=None):
