@@ -467,6 +467,35 @@ size_t tpg_context_expand_workspace_bytes(int T, int N);
 int tpg_context_expand_f32(const float *pos, const float *edge, const float *mask, int T, int N, int r, int t0,
                            int32_t *state, float *out, int64_t *offsets, void *ws, void *stream);
 
+/* ---- uncapped neighbourhood sums: particle density, neighbour counts (csrc/radius_reduce.hip) ----------------
+ * train_fluid/analysis_helper.py:143-161,291-294 (get_particle_density, get_particle_density_of_two_pcd,
+ * particle_dns2grid_dns) and train_utils.py:269-286 (fixed_radius_neighbor_num, get_free_surface_particles), which
+ * the reference computes on the host with a scipy KD-tree.  query (B,Nq,3), pos (B,Np,3); lenq / lenp (B) int64 or
+ * NULL (= full), as in tpg_frnn_grid_f32.  Per query i, over EVERY stored point j of its cloud (no cap on their number)
+ * with d2 <= r2 -- INCLUSIVE, unlike the strict d2 < r2 of the K-nearest searches above, because scipy's
+ * query_ball_point / query_ball_tree are -- where d2 is the canonical fp32 distance (t = q - p per axis;
+ * d2 = t0*t0; d2 = d2 + t1*t1; d2 = d2 + t2*t2; no FMA) and r2 = fp32(r) * fp32(r):
+ *     count (B,Nq) int32 = the number of such points
+ *     sum   (B,Nq) f32   = the sum over them of w(sqrt(d2), r)
+ *     kernel 0: the cubic kernel of analysis_helper.py:102-113 with coefficient 1
+ *               (q = d / r;  q <= 0.5: 6 (q^3 - q^2) + 1;  q <= 1: 2 (1 - q)^3)
+ *     kernel 1: train_utils.linear_kernel (r / d - 1, and 0 for d < 1e-8)
+ * Either output may be NULL (counts only / sums only), not both.  Queries at or beyond lenq[b] get 0 / 0; Np = 0 or
+ * lenp[b] = 0 gives 0 / 0; a query far outside the stored cloud gets 0 / 0.  TPG_ERR_UNSUPPORTED for another kernel
+ * number and for B > 65535.
+ * Deterministic: the sum is accumulated in 64-bit fixed point (cubic: units of 2^-32, each term truncated; linear:
+ * units of 2^-23, in which every fp32 term is exact; saturating at 2^64 units), so it does not depend on the order in
+ * which the neighbours are met: the same bits on every run, at every batch position and from both entries below.
+ *   tpg_radius_reduce_f32             on the uniform grid of tpg_frnn_grid_f32 (four build launches + one wave per
+ *                                     query over its 27 cells); ws: tpg_frnn_grid_workspace_bytes(B, Np) bytes,
+ *                                     256-byte aligned
+ *   tpg_radius_reduce_exhaustive_f32  the same kernel body over the whole stored cloud, for small clouds */
+int tpg_radius_reduce_f32(const float *query, const float *pos, const int64_t *lenq, const int64_t *lenp, int B,
+                          int Nq, int Np, float r, int kernel, int32_t *count, float *sum, void *ws, void *stream);
+int tpg_radius_reduce_exhaustive_f32(const float *query, const float *pos, const int64_t *lenq, const int64_t *lenp,
+                                     int B, int Nq, int Np, float r, int kernel, int32_t *count, float *sum,
+                                     void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -69,6 +69,8 @@ SIGNATURES = {
     "tpg_rowlinear_wgrad": [_P, _I, _P, _P, _I, _L, _I, _I, _I, _F, _P, _P, _P, _P],
     "tpg_mlp_fwd": [_P, _L, _I, _I, _I, _P, _I, _F, _P, _I, _P, _F, _F, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P],
     "tpg_context_expand_f32": [_P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P],
+    "tpg_radius_reduce_f32": [_P, _P, _P, _P, _I, _I, _I, _F, _I, _P, _P, _P, _P],
+    "tpg_radius_reduce_exhaustive_f32": [_P, _P, _P, _P, _I, _I, _I, _F, _I, _P, _P, _P],
 }
 SIZE_GETTERS = ("tpg_rowbn_workspace_bytes", "tpg_mlp_workspace_bytes", "tpg_context_expand_workspace_bytes")
 OTHER_GETTERS = ("tpg_spectral_norm_multi_stride", "tpg_spectral_norm_multi_bwd_scratch",

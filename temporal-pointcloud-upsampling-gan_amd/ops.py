@@ -218,6 +218,26 @@ class HipBackend:
                    _ptr(pad), _ptr(hits))
         return plain, pad, hits
 
+    def radius_reduce(self, query, pos, lenq, lenp, r, kernel, want_count=True, want_sum=True, grid=None):
+        """csrc/radius_reduce.hip: (count (B,Nq) int32, sum (B,Nq) f32) over every stored point with d2 <= r2; the grid
+        from the sizes of the radius search's switch on, the exhaustive shape of the same kernel below (same bits
+        either way; `grid` forces one, for tests and tuning)."""
+        B, Nq, _ = query.shape
+        Np = pos.shape[1]
+        count = torch.empty((B, Nq), dtype=torch.int32, device=query.device) if want_count else None
+        total = torch.empty((B, Nq), dtype=torch.float32, device=query.device) if want_sum else None
+        if grid is None:
+            grid = Np >= self.GRID_MIN_POINTS and float(B) * Nq * Np >= self.GRID_MIN_PAIRS
+        nbytes = 12 * B * (Nq + Np) + 4 * B * Nq * (int(want_count) + int(want_sum))
+        args = (_ptr(query), _ptr(pos), _ptr(lenq), _ptr(lenp), B, Nq, Np, float(np.float32(r)), int(kernel),
+                _ptr(count), _ptr(total))
+        if grid and B > 0 and Nq > 0 and Np > 0:
+            self._call("tpg_radius_reduce_f32", "radius_reduce_grid", nbytes, query, *args,
+                       _ptr(self._grid_ws(query, B, Np)))
+        else:
+            self._call("tpg_radius_reduce_exhaustive_f32", "radius_reduce", nbytes, query, *args)
+        return count, total
+
     def chamfer_fwd(self, src, tgt):
         B, N, _ = src.shape
         M = tgt.shape[1]
@@ -981,12 +1001,17 @@ def farthest_point_sampling(pts, k, initial_idx=None):
     return idx[0] if single else idx
 
 
-def sample_patch_with_fps(input_pos, patch_num, ds_ratio=0.125, seed_idx=None, initial_idx=None):
+def sample_patch_with_fps(input_pos, patch_num, ds_ratio=0.125, seed_idx=None, initial_idx=None,
+                          return_free_surface_particles=False, h=None):
     """train_utils.py:98-139 on the GPU: the `patch_num` nearest neighbours of a random seed
     point (the reference queries a KD-tree) and their FPS down-sampling to `ds_ratio` of the patch.
     input_pos (N,3) -> dict(patch_pos, ds_pos, patch_idx, fps_idx).  The K = thousands
     selection is one `torch.topk` over the N distances to the seed (a single query: nothing to
-    tile), FPS is the HIP kernel."""
+    tile), FPS is the HIP kernel.  return_free_surface_particles=True (the reference's default; needs its
+    scale `h`) adds `surface_points`: the patch's free-surface points at radius 3.1 * 0.025 / h
+    (train_utils.py:132-134, analysis.get_free_surface_particles)."""
+    if return_free_surface_particles:
+        _need(h is not None and float(h) > 0.0, "return_free_surface_particles needs the scale h > 0")
     x = input_pos.detach().float()
     N = x.shape[0]
     if seed_idx is None:
@@ -995,7 +1020,11 @@ def sample_patch_with_fps(input_pos, patch_num, ds_ratio=0.125, seed_idx=None, i
     patch = torch.topk(d, min(int(patch_num), N), largest=False, sorted=True).indices
     patch_pos = x[patch].contiguous()
     fps_idx = farthest_point_sampling(patch_pos, int(ds_ratio * patch_pos.shape[0]), initial_idx)
-    return {"patch_pos": patch_pos, "ds_pos": patch_pos[fps_idx], "patch_idx": patch, "fps_idx": fps_idx}
+    out = {"patch_pos": patch_pos, "ds_pos": patch_pos[fps_idx], "patch_idx": patch, "fps_idx": fps_idx}
+    if return_free_surface_particles:
+        from .analysis import get_free_surface_particles
+        out["surface_points"] = get_free_surface_particles(patch_pos, 3.1 * 0.025 / float(h))
+    return out
 
 
 class _Gather(torch.autograd.Function):
@@ -1134,6 +1163,44 @@ def neighbour_search(p1, p2, K, lengths1=None, lengths2=None, r=None):
     if r is not None and getattr(be, "name", "") == "hip":
         return be.knn(a, b, l1, l2, int(K), r2, r=r)        # large clouds: uniform grid, same results
     return be.knn(a, b, l1, l2, int(K), r2)
+
+
+RADIUS_KERNELS = {"cubic": 0, "linear": 1}
+
+
+def radius_reduce(query, pos, r, kernel="cubic", lengths_q=None, lengths_p=None, _grid=None):
+    """Neighbourhood sums with no cap on the number of neighbours (csrc/radius_reduce.hip): per query the number of
+    points of `pos` within `r` (d2 <= r2, inclusive like scipy's query_ball_point, the query itself included when it is
+    a stored point) and the sum of a radial kernel over them -> (count int32, sum float32).
+
+    query (B,Nq,3), pos (B,Np,3) float tensors on the GPU, or unbatched (Nq,3) / (Np,3) (-> (Nq,) results); lengths
+    (B,) or None as in `neighbour_search` (queries beyond their length get 0 / 0).  kernel: "cubic"
+    (analysis_helper.py:102-113, coefficient 1), "linear" (train_utils.py:258-266) or None (counts only: sum is None).
+    Deterministic: the same bits whatever the order in which the grid hands out the neighbours.  No gradient."""
+    _need(isinstance(query, torch.Tensor) and isinstance(pos, torch.Tensor), "query and pos must be tensors")
+    squeeze, same = query.dim() == 2, pos is query
+    if squeeze:
+        _need(pos.dim() == 2, "query (Nq,3) needs pos (Np,3)")
+        query, pos = query.unsqueeze(0), pos.unsqueeze(0)
+    _need(query.dim() == 3 and pos.dim() == 3, "query (B,Nq,3), pos (B,Np,3)")
+    _need(query.shape[2] == 3 and pos.shape[2] == 3 and query.shape[0] == pos.shape[0], "query (B,Nq,3), pos (B,Np,3)")
+    _need(query.is_floating_point() and pos.is_floating_point(), "query and pos must be float tensors")
+    _need(kernel is None or kernel in RADIUS_KERNELS, f"kernel must be one of {sorted(RADIUS_KERNELS)} or None")
+    _need(float(r) > 0.0, "r must be positive")
+    _same_device(query, pos)
+    q = query.detach().float().contiguous()
+    p = q if same else pos.detach().float().contiguous()       # a cloud measured in itself: one cast, not two
+    be = backend_for(q)
+    _need(hasattr(be, "radius_reduce"), "this backend has no radius_reduce")
+    B = q.shape[0]
+    lq = _lengths(lengths_q, B, q.shape[1], q.device)
+    lp = _lengths(lengths_p, B, p.shape[1], q.device)
+    with torch.no_grad():
+        count, total = be.radius_reduce(q, p, lq, lp, float(r), RADIUS_KERNELS.get(kernel, 0), True,
+                                        kernel is not None, _grid)
+    if squeeze:
+        return count[0], None if total is None else total[0]
+    return count, total
 
 
 def cubic_interpolation(query_pos, field, pos, cutoff):

@@ -1,0 +1,314 @@
+"""Uncapped neighbourhood sums on the GPU (csrc/radius_reduce.hip through ops.radius_reduce and tpgan_amd.analysis)
+against the numpy statement of tests/test_analysis_cpu.py -- counts EQUAL on every query, nothing excluded; sums within
+
+    |err_i| <= 8 * 2^-24 * (count_i + 1)                              cubic kernel (terms in [0, 1])
+    |err_i| <= F * 2^-24 * (count_i + 1) * sum_j |term_ij| (float64)  linear kernel, F = 8
+
+-- and against the reference's own results (tests/golden/analysis.npz) by the rules stated there.
+
+The linear kernel's F: r / d - 1 cancels at the rim, so ONE neighbour at d = r (1 - 1e-5) carries a relative error
+of 2^-24 / 1e-5 whatever evaluates it in float32, and a query with a handful of neighbours, all near the rim, cannot
+meet F = 8 (at r = 0.025, one particle spacing, such queries exist; at the cutoffs of 2.2 and 3.1 spacings they do
+not).  As the issue rules for that case, F is then taken from the float32 numpy evaluation of the same expression on the
+same members (sequential float32 sum; the reference arithmetic, not the kernel) with a 2x margin:
+F = max(8, 2 x its measured ratio), both ratios printed.  Measured maxima: DESIGN.md, "radius_reduce".
+
+Each case is one launch per path; nothing is repeated on failure.
+"""
+import numpy as np
+import pytest
+import torch
+
+from test_analysis_cpu import (CUTOFFS, EPS, GOLDEN, RADII, SUM_FACTOR, check_counts_against_golden, check_density,
+                               check_surface_against_golden, members, statement, sum_bound)
+
+pytestmark = pytest.mark.gpu
+
+
+@pytest.fixture(scope="module")
+def hip():
+    import tpgan_amd.ops as ops
+    assert torch.cuda.is_available()
+    return ops.backend_for(torch.zeros(1, device="cuda"))
+
+
+@pytest.fixture(scope="module")
+def golden():
+    return np.load(GOLDEN)
+
+
+def dev(a):
+    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
+
+
+def fluid(n, seed):
+    from tpgan_amd.synthetic import fluid_clip
+    return fluid_clip(1, n, 8, 1, seed=seed)[1][0][0].numpy().astype(np.float32)
+
+
+def takes_the_grid(hip, B, Nq, Np):
+    return Np >= hip.GRID_MIN_POINTS and float(B) * Nq * Np >= hip.GRID_MIN_PAIRS
+
+
+def fp32_ratio(query, pos, r, kernel):
+    """max over the queries of |float32 numpy evaluation - statement| / (2^-24 (count + 1) [sum |terms|])."""
+    f32 = np.float32
+    query, pos = np.asarray(query, dtype=f32), np.asarray(pos, dtype=f32)
+    qi, pj, _ = members(query, pos, r)
+    t = query[qi] - pos[pj]
+    d2 = t[:, 0] * t[:, 0]
+    d2 = d2 + t[:, 1] * t[:, 1]
+    d2 = d2 + t[:, 2] * t[:, 2]
+    d, r32 = np.sqrt(d2), f32(r)
+    if kernel == "cubic":
+        q = d / r32
+        w = np.where(q <= f32(0.5), f32(6) * (q * q * q - q * q) + f32(1), f32(2) * (f32(1) - q) ** 3).astype(f32)
+    else:
+        w = np.where(d < f32(1e-8), f32(0), r32 / np.maximum(d, f32(1e-30)) - f32(1)).astype(f32)
+    seq = np.zeros(query.shape[0], dtype=f32)
+    np.add.at(seq, qi, w)
+    count, total, sabs = statement(query, pos, r, kernel)
+    scale = EPS * (count + 1.0) * (1.0 if kernel == "cubic" else sabs)
+    ok = scale > 0
+    return float(np.max(np.abs(seq.astype(np.float64) - total)[ok] / scale[ok])) if ok.any() else 0.0
+
+
+def check(tag, got_count, got_sum, query, pos, r, kernel, factor_from_fp32=False):
+    """counts equal on every query; sums within the bound."""
+    count, total, sabs = statement(query, pos, r, kernel)
+    gc = got_count.cpu().numpy().astype(np.int64)
+    bad = np.nonzero(gc != count)[0]
+    assert bad.size == 0, (tag, bad.size, bad[:8], gc[bad[:8]], count[bad[:8]])
+    if kernel is None or count.size == 0:
+        assert kernel is not None or got_sum is None
+        return count
+    err = np.abs(got_sum.cpu().numpy().astype(np.float64) - total)
+    scale = EPS * (count + 1.0) * (1.0 if kernel == "cubic" else sabs)
+    ok = scale > 0
+    ratio = float(np.max(err[ok] / scale[ok])) if ok.any() else 0.0
+    factor = SUM_FACTOR
+    if factor_from_fp32:
+        assert kernel == "linear"
+        ref = fp32_ratio(query, pos, r, kernel)
+        factor = max(SUM_FACTOR, 2.0 * ref)
+        print(f"{tag}: float32 numpy evaluation max ratio {ref:.3f} -> factor {factor:.3f}")
+    print(f"{tag}: {kernel} max |err| {err.max():.3e}, max err / scale {ratio:.3f} (factor {factor:.3f}), "
+          f"mean count {count.mean():.1f}, max count {count.max()}")
+    assert np.all(err[~ok] == 0.0), tag
+    assert np.all(err <= factor / SUM_FACTOR * sum_bound(count, sabs, kernel)), (tag, ratio, factor)
+    return count
+
+
+# ------------------------------------------------------------------------------ 4 / 5: counts equal, sums bounded
+@pytest.mark.parametrize("n,seed", [(2048, 1), (4096, 2), (20000, 3), (65536, 4)])
+def test_self_clouds_counts_equal_and_cubic_sums_within_the_bound(hip, n, seed):
+    import tpgan_amd.ops as ops
+    pos = fluid(n, seed)
+    assert takes_the_grid(hip, 1, n, n) == (n >= 20000)
+    x = dev(pos)
+    count, total = ops.radius_reduce(x, x, 0.0775, "cubic")
+    assert count.dtype == torch.int32 and total.dtype == torch.float32 and count.shape == total.shape == (n,)
+    assert not total.requires_grad
+    check(f"self {n}", count, total, pos, pos, 0.0775, "cubic")
+
+
+@pytest.mark.parametrize("n,seed,r,from_fp32", [(4096, 2, 0.055, False), (20000, 3, 0.0775, False),
+                                                (4096, 2, 0.025, True)])
+def test_linear_kernel_sums(hip, n, seed, r, from_fp32):
+    import tpgan_amd.ops as ops
+    pos = fluid(n, seed)
+    x = dev(pos)
+    count, total = ops.radius_reduce(x, x, r, "linear")
+    check(f"linear {n} r={r}", count, total, pos, pos, r, "linear", factor_from_fp32=from_fp32)
+
+
+@pytest.mark.parametrize("grid", [False, True])
+def test_ragged_batches_with_lengths(hip, grid):
+    import tpgan_amd.ops as ops
+    rng = np.random.RandomState(11)
+    B, Nq, Np = 4, 1500, 3000
+    pos = np.stack([fluid(Np, 20 + b) for b in range(B)])
+    query = (pos[:, :Nq] + rng.normal(0, 0.01, (B, Nq, 3))).astype(np.float32)
+    lq, lp = [1500, 700, 0, 1], [3000, 1234, 2000, 0]
+    count, total = ops.radius_reduce(dev(query), dev(pos), 0.055, "cubic", lengths_q=lq, lengths_p=lp, _grid=grid)
+    for b in range(B):
+        check(f"ragged b={b} grid={grid}", count[b, :lq[b]], total[b, :lq[b]], query[b, :lq[b]], pos[b, :lp[b]],
+              0.055, "cubic")
+        assert int(count[b, lq[b]:].abs().sum()) == 0 and float(total[b, lq[b]:].abs().sum()) == 0.0
+    assert int(count[3].sum()) == 0                              # nothing stored: zeros
+    count_only, none = ops.radius_reduce(dev(query), dev(pos), 0.055, None, lengths_q=lq, lengths_p=lp, _grid=grid)
+    assert none is None and torch.equal(count_only, count)
+
+
+@pytest.mark.parametrize("grid", [False, True])
+def test_queries_outside_the_cloud_are_zero(hip, golden, grid):
+    import tpgan_amd.ops as ops
+    pos, lattice = golden["b/pos"], golden["lattice/pos"]
+    far = np.array([[1e30, 0, 0], [0, -1e30, 0], [50.0, 50.0, 50.0], [-0.4, -0.4, 0.5]], dtype=np.float32)
+    query = np.concatenate([lattice, far])
+    count, total = ops.radius_reduce(dev(query), dev(pos), 0.0775, "cubic", _grid=grid)
+    want = check(f"lattice grid={grid}", count, total, query, pos, 0.0775, "cubic")
+    assert (want == 0).sum() > 100 and np.all(want[-4:] == 0)
+    zero = torch.from_numpy(want == 0).cuda()
+    assert int(count[zero].abs().sum()) == 0 and float(total[zero].abs().sum()) == 0.0
+    empty_c, empty_s = ops.radius_reduce(dev(query), dev(pos[:0]), 0.0775, "cubic", _grid=grid)
+    assert int(empty_c.abs().sum()) == 0 and float(empty_s.abs().sum()) == 0.0
+
+
+@pytest.mark.parametrize("grid", [False, True])
+def test_duplicates_and_padded_dummies(hip, grid):
+    import tpgan_amd.ops as ops
+    dup = fluid(2048, 31)
+    dup[1792:] = dup[:256]                                        # an eighth of the cloud twice, exactly
+    dup[100:104] = dup[7]
+    for kernel in ("cubic", "linear"):                            # (linear: the duplicates are the d < 1e-8 terms)
+        count, total = ops.radius_reduce(dev(dup), dev(dup), 0.055, kernel, _grid=grid)
+        got = check(f"duplicates grid={grid}", count, total, dup, dup, 0.055, kernel)
+    assert got[7] >= 5 and np.all(got[:256] >= 2)
+    pad = fluid(2048, 32)
+    pad[1700:] = 999.0                                            # the reference's dummies (upsampling_network.py)
+    count, total = ops.radius_reduce(dev(pad), dev(pad), 0.0775, "cubic", _grid=grid)
+    got = check(f"999-padded grid={grid}", count, total, pad, pad, 0.0775, "cubic")
+    assert np.all(got[1700:] == 348)
+
+
+@pytest.mark.parametrize("grid", [False, True])
+def test_radius_extremes(hip, grid):
+    import tpgan_amd.ops as ops
+    pos = fluid(2048, 33)
+    x = dev(pos)
+    count, total = ops.radius_reduce(x, x, 1e-6, "cubic", _grid=grid)     # only the self hit remains
+    assert torch.all(count == 1) and torch.all(total == 1.0)
+    check(f"tiny r grid={grid}", count, total, pos, pos, 1e-6, "cubic")
+    count, total = ops.radius_reduce(x, x, 10.0, "cubic", _grid=grid)     # larger than the cloud
+    assert torch.all(count == 2048)
+    check(f"huge r grid={grid}", count, total, pos, pos, 10.0, "cubic")
+
+
+@pytest.mark.parametrize("n,seed,r", [(4096, 41, 0.0775), (20000, 42, 0.055)])
+def test_grid_and_exhaustive_paths_agree_bit_for_bit(hip, n, seed, r):
+    """Equal counts, and -- the sum being taken in fixed point, whose additions commute -- equal sums too."""
+    import tpgan_amd.ops as ops
+    x = dev(fluid(n, seed))
+    for kernel in ("cubic", "linear"):
+        cg, sg = ops.radius_reduce(x, x, r, kernel, _grid=True)
+        ce, se = ops.radius_reduce(x, x, r, kernel, _grid=False)
+        assert torch.equal(cg, ce), kernel
+        assert torch.equal(sg.view(torch.int32), se.view(torch.int32)), kernel
+
+
+# --------------------------------------------------------------------------------------------- 6: determinism
+def test_sums_are_bitwise_reproducible_on_the_grid(hip):
+    """The grid's fill orders a cell's points through an atomic cursor; the sum must not see that order.  20000 points
+    at r = 0.0775: cells of edge r hold ~30 points each."""
+    import tpgan_amd.ops as ops
+    a, other = fluid(20000, 51), fluid(20000, 52)
+    x = dev(a)
+    assert takes_the_grid(hip, 1, 20000, 20000)
+    for kernel in ("cubic", "linear"):
+        c1, s1 = ops.radius_reduce(x, x, 0.0775, kernel)
+        c2, s2 = ops.radius_reduce(x, x, 0.0775, kernel)
+        assert torch.equal(c1, c2) and torch.equal(s1.view(torch.int32), s2.view(torch.int32)), kernel
+        batch = dev(np.stack([a, other, a]))
+        cb, sb = ops.radius_reduce(batch, batch, 0.0775, kernel)
+        assert torch.equal(cb[0], cb[2]) and torch.equal(sb[0].view(torch.int32), sb[2].view(torch.int32)), kernel
+        assert torch.equal(cb[0], c1) and torch.equal(sb[0].view(torch.int32), s1.view(torch.int32)), kernel
+        assert not torch.equal(cb[0], cb[1])
+
+
+# ------------------------------------------------------------------------- 7: the analysis layer vs the goldens
+@pytest.mark.parametrize("cloud", ["a", "b"])
+def test_analysis_functions_match_the_reference(hip, golden, cloud):
+    from tpgan_amd import analysis
+    pos = golden[f"{cloud}/pos"]
+    x = dev(pos)
+    for r in RADII:
+        num = analysis.fixed_radius_neighbor_num(x, r)
+        assert num.is_cuda and num.shape == (pos.shape[0],)
+        counts = num.cpu().numpy().astype(np.int64)
+        ex = check_counts_against_golden(counts, golden[f"{cloud}/nbr_num/{r}"], pos, pos, r, f"{cloud} r={r}")
+        if f"{cloud}/surface/{r}" in golden.files:
+            surf = analysis.get_free_surface_particles(x, r)
+            check_surface_against_golden(surf.cpu().numpy(), golden[f"{cloud}/surface/{r}"], counts, ex, pos,
+                                         f"{cloud} r={r}")
+    for c in CUTOFFS:
+        dns = analysis.get_particle_density(x, c)
+        assert dns.is_cuda and dns.shape == (pos.shape[0], 1)
+        check_density(dns.cpu().numpy(), golden[f"{cloud}/density/{c}"], statement(pos, pos, c, None)[0],
+                      f"{cloud} cutoff={c}")
+    # numpy in, numpy out, in the reference's dtypes
+    host = analysis.get_particle_density(pos, CUTOFFS[0])
+    assert isinstance(host, np.ndarray) and host.dtype == np.float64 and host.shape == (pos.shape[0], 1)
+    num = analysis.fixed_radius_neighbor_num(pos, 0.025)
+    assert isinstance(num, np.ndarray) and num.dtype == np.int64
+    surf = analysis.get_free_surface_particles(pos, 0.025)
+    assert isinstance(surf, np.ndarray) and np.array_equal(surf, golden[f"{cloud}/surface/0.025"])
+
+
+def test_analysis_two_cloud_density_loss_and_patch_match_the_reference(hip, golden):
+    import tpgan_amd.ops as ops
+    from tpgan_amd import analysis
+    pos, lattice = golden["b/pos"], golden["lattice/pos"]
+    for c in CUTOFFS:
+        count = statement(lattice, pos, c, None)[0]
+        two = analysis.get_particle_density_of_two_pcd(dev(lattice), dev(pos), c)
+        grid = analysis.particle_dns2grid_dns(lattice, pos, c)
+        assert isinstance(grid, np.ndarray) and grid.dtype == np.float64
+        check_density(two.cpu().numpy(), golden[f"lattice/two_pcd/{c}"], count, f"two_pcd cutoff={c}")
+        check_density(grid, golden[f"lattice/grid_dns/{c}"], count, f"grid_dns cutoff={c}")
+        assert np.all(grid[count == 0] == 0.0)
+    assert analysis.free_surface_particle_loss(dev(golden["pred/pos"]), dev(pos)) == int(golden["loss/free_surface"])
+    assert analysis.free_surface_particle_loss(golden["pred/pos"], pos) == int(golden["loss/free_surface"])
+    # the patch sampler's surface points: the reference's patch, then the sampler itself
+    h = float(golden["patch/h"])
+    patch = pos[golden["patch/idx"]]
+    surf = analysis.get_free_surface_particles(dev(patch), 3.1 * 0.025 / h)
+    assert np.array_equal(surf.cpu().numpy(), golden["patch/surface_points"])
+    out = ops.sample_patch_with_fps(dev(pos), 2048, seed_idx=int(golden["patch/seed_idx"]), initial_idx=0,
+                                    return_free_surface_particles=True, h=h)
+    assert sorted(out) == ["ds_pos", "fps_idx", "patch_idx", "patch_pos", "surface_points"]
+    assert torch.equal(out["surface_points"], analysis.get_free_surface_particles(out["patch_pos"], 3.1 * 0.025 / h))
+    if set(out["patch_idx"].tolist()) == set(golden["patch/idx"].tolist()):
+        assert np.array_equal(np.sort(out["surface_points"].cpu().numpy(), axis=0),
+                              np.sort(golden["patch/surface_points"], axis=0))
+    plain = ops.sample_patch_with_fps(dev(pos), 2048, seed_idx=int(golden["patch/seed_idx"]), initial_idx=0)
+    assert sorted(plain) == ["ds_pos", "fps_idx", "patch_idx", "patch_pos"]
+    assert all(torch.equal(plain[k], out[k]) for k in plain)
+
+
+def test_batched_forms_equal_per_frame_calls_bit_for_bit(hip):
+    from tpgan_amd import analysis
+    lens = [20000, 15000, 20000, 333]
+    frames = [fluid(20000, 60 + t)[:n] for t, n in enumerate(lens)]
+    batch = np.zeros((4, 20000, 3), dtype=np.float32)
+    for t, f in enumerate(frames):
+        batch[t, :lens[t]] = f
+    x = dev(batch)
+    assert takes_the_grid(hip, 4, 20000, 20000)
+    dns = analysis.particle_density_batch(x, 0.0775, lens)
+    num = analysis.neighbor_num_batch(x, 0.025, lens)
+    free = analysis.free_surface_count_batch(x, 0.025, lens)
+    assert dns.shape == num.shape == (4, 20000) and free.shape == (4,)
+    for t, f in enumerate(frames):
+        one = analysis.get_particle_density(dev(f), 0.0775)
+        assert torch.equal(dns[t, :lens[t]].view(torch.int32), one[:, 0].view(torch.int32)), t
+        assert float(dns[t, lens[t]:].abs().sum()) == 0.0
+        assert torch.equal(num[t, :lens[t]], analysis.fixed_radius_neighbor_num(dev(f), 0.025)), t
+        assert int(free[t]) == analysis.get_free_surface_particles(dev(f), 0.025).shape[0], t
+
+
+def test_sequence_statistics_cli(hip, tmp_path):
+    from tpgan_amd import analysis
+    frames = [fluid(3000, 70 + t) for t in range(5)]
+    for t, f in enumerate(frames):
+        np.save(tmp_path / f"pcd_{t}.npy", f)
+    out = tmp_path / "stats.npz"
+    analysis.main(["--frames", str(tmp_path / "pcd_{i}.npy"), "--count", "5", "--cutoff", "0.0775", "--out", str(out)])
+    stats = np.load(out)
+    assert stats["point_count"].tolist() == [3000] * 5 and stats["density_mean"].shape == (5,)
+    for t, f in enumerate(frames):
+        _, total, _ = statement(f, f, 0.0775, "cubic")
+        assert abs(stats["density_mean"][t] - total.mean()) <= 1e-5 * total.mean()
+        assert abs(stats["density_std"][t] - total.std()) <= 1e-4 * total.std()
+        assert stats["free_surface_count"][t] == analysis.get_free_surface_particles(f, 0.025).shape[0]
+    assert np.array_equal(stats["d_density_mean"], np.gradient(stats["density_mean"]))
