@@ -164,7 +164,6 @@ class GraphedFluidStep:
         if mode in ("1", "heads") and hasattr(sr_net, "filter_block"):
             from .srnet import set_aux_stream
             set_aux_stream(sr_net, self.aux)
-        self.use_plans = True
         self.defer_inverses = os.environ.get("TPGAN_DEFER_INVERSES", "1") != "0"
         self.wgrad_side = os.environ.get("TPGAN_WGRAD_SIDE", "0") != "0"    # measured: 13.1 -> 14.5 ms with it (a cross-stream edge per weight costs ~40 us): off
         self._keep = {}
@@ -209,10 +208,6 @@ class GraphedFluidStep:
         FPS rounds then cost the latency of one.  -> join_fs, join_ft, plan_fs, plan_ft for the
         generator step; the update's clouds and plans go to self._keep."""
         Ds, Dt, opt, k = self.Ds, self.Dt, self.opt, self._keep
-        if not self.use_plans:
-            if update_D:
-                k["fake_s"], k["plan_s"], k["fakes"], k["plan_t"] = make_fake_s(), None, make_fake_t(), None
-            return (lambda: None), (lambda: None), None, None
         if not update_D:
             plan_fs, join_fs = run_index_plan(lambda: Ds.index_plan(fake_s_in), self.sides[1])
             plan_ft, join_ft = run_index_plan(lambda: Dt.merge_plans(Dt.index_plans([fake_t_in], opt.R)), self.sides[0])
@@ -263,10 +258,9 @@ class GraphedFluidStep:
         generator's forward on a side stream the replayed step gets 1.2-1.5 ms slower, and update
         weights made on a side stream put their autograd node there, on which hipStreamEndCapture
         segfaults (ROCm 7.2)."""
-        if self.use_plans:
-            sn_discard_prepared()
-            self.Ds.prepare_sn(1)
-            self.Dt.prepare_sn(self.T, 1)
+        sn_discard_prepared()
+        self.Ds.prepare_sn(1)
+        self.Dt.prepare_sn(self.T, 1)
 
     def _spatial_term(self, forward, join_plan, inputs, lab):
         """The generator step's spatial-discriminator term (train_step_final.py:120-122), issued FIRST (the heads'
@@ -294,7 +288,7 @@ class GraphedFluidStep:
         for sd in self.sides + [self.aux, self.aux2]:
             stream.wait_stream(sd)
 
-    def _seg_generator(self, update_D, defer_backward=False):
+    def _seg_generator(self, update_D):
         G, Ds, Dt, opt, k = self.G, self.Ds, self.Dt, self.opt, self._keep
         low, high, lab = self.low, self.high, self.lab
         others = [0] + list(range(2, self.T))
@@ -304,11 +298,11 @@ class GraphedFluidStep:
             # the real clouds exist already: their (rotated) copies and index plans start now
             def real_t():
                 trues = [torch.matmul(h, self.rot_true_t[f]) for f, h in enumerate(high)]
-                return trues, (Dt.index_plans([trues], opt.R)[0] if self.use_plans else None)
+                return trues, Dt.index_plans([trues], opt.R)[0]
 
             def real_s():
                 true_s = torch.bmm(high[1], self.rot_true_s)
-                return true_s, (Ds.index_plans([true_s])[0] if self.use_plans else None)
+                return true_s, Ds.index_plans([true_s])[0]
             (k["trues"], k["plan_true_t"]), _ = run_index_plan(real_t, self.sides[0])
             (k["true_s"], k["plan_true_s"]), _ = run_index_plan(real_s, self.sides[1])
         # The generator has no cross-sample coupling (no BatchNorm): its T per-frame calls
@@ -353,12 +347,7 @@ class GraphedFluidStep:
         sr_loss = tempo_loss + spatial_loss + opt.w * position_loss
         k.update(tempo_loss=tempo_loss.detach(), spatial_loss=spatial_loss.detach(), cd=cd.detach(), ml=ml.detach())
         self.viol.copy_(viol.float().reshape(1))
-        if defer_backward:
-            return sr_loss
-        self.og.zero_grad(set_to_none=True)
-        sr_loss.backward()
-        # every side-stream branch rejoins before this segment ends (required inside a capture)
-        self._join_sides()
+        return sr_loss
 
     def _phase_grads(self, update_D):
         """Forward and backward of the whole step: three backward-heavy parts side by side.
@@ -391,20 +380,16 @@ class GraphedFluidStep:
         return self._shadow
 
     def _grads_body(self, update_D):
-        sr_loss = self._seg_generator(update_D, defer_backward=True)
+        sr_loss = self._seg_generator(update_D)
         k, lab = self._keep, self.lab
         main = torch.cuda.current_stream(self.dev)
         if update_D:
             self.branch.wait_stream(main)
             self.branch2.wait_stream(main)
-            if self.use_plans:                          # the updates' clouds and index lists (their inverted indices: below)
-                with torch.cuda.stream(self.branch):
-                    k["join_plan_s"]()
-                with torch.cuda.stream(self.branch2):
-                    k["join_plan_t"]()
-            else:
-                self.branch.wait_stream(self.sides[1])
-                self.branch2.wait_stream(self.sides[0])
+            with torch.cuda.stream(self.branch):        # the updates' clouds and index lists (their inverted indices: below)
+                k["join_plan_s"]()
+            with torch.cuda.stream(self.branch2):
+                k["join_plan_t"]()
             # issue order = the eager step's (and the reference's, train_step_final.py:171-214): the
             # temporal update first.  The streams decide what runs where; the ISSUE order decides
             # which Philox offsets the heads' dropout draws get inside a captured graph.
@@ -689,16 +674,16 @@ class GraphedActionStep(GraphedFluidStep):
         self._host_f.copy_(torch.tensor([valid, invalid, lab_s, lab_t], dtype=torch.float32))
         self._host_i.copy_(torch.cat([perm_sg] + perms + [perm_sd]))
 
-    def _seg_generator(self, update_D, defer_backward=False):
+    def _seg_generator(self, update_D):
         G, Ds, Dt, opt, k = self.G, self.Ds, self.Dt, self.opt, self._keep
         low, high, lab = self.low, self.high, self.lab
         others = [0] + list(range(2, self.T))
         order = [1] + others
         if update_D:                       # the real clouds exist already: their index plans start now
             (k["trues"], k["plan_true_t"]), _ = run_index_plan(
-                lambda: (list(high), Dt.index_plans([list(high)], opt.R)[0] if self.use_plans else None), self.sides[0])
+                lambda: (list(high), Dt.index_plans([list(high)], opt.R)[0]), self.sides[0])
             (k["true_s"], k["plan_true_s"]), _ = run_index_plan(
-                lambda: (high[1], Ds.index_plans([high[1]])[0] if self.use_plans else None), self.sides[1])
+                lambda: (high[1], Ds.index_plans([high[1]])[0]), self.sides[1])
         with _frozen(Ds, Dt), _autocast(self.amp, self.dev):
             edge_all = G.body(torch.cat([low[f] for f in order], 0))
             edges = edge_all.reshape(len(order), self.B, *edge_all.shape[1:]).unbind(0)
@@ -722,11 +707,7 @@ class GraphedActionStep(GraphedFluidStep):
         k.update(tempo_loss=tempo_loss.detach(), spatial_loss=spatial_loss.detach(), cd=cd.detach(),
                  ml=torch.zeros((), device=self.dev))
         self.viol.zero_()
-        if defer_backward:
-            return sr_loss
-        self.og.zero_grad(set_to_none=True)
-        sr_loss.backward()
-        self._join_sides()
+        return sr_loss
 
     def _eager(self, low, high, n_iter, freeze_D):
         from .gan_step import tempo_gan_step_no_mask

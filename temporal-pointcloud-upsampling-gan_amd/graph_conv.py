@@ -331,7 +331,7 @@ class _EdgeFront(torch.autograd.Function):
     kernels, no gradient sum of the shared input -- 7 launches fewer per EdgeConv and step on a latency-bound chain."""
 
     @staticmethod
-    def forward(ctx, x, we, wn, idx, slope_a, slope_e, out_dtype, inverse):
+    def forward(ctx, x, we, wn, idx, slope_a, slope_e, out_dtype):
         B, N, cin = x.shape
         H = we.shape[0]
         P = B * N
@@ -340,7 +340,7 @@ class _EdgeFront(torch.autograd.Function):
         Y = ops.timed("gemm_fwd", 4 * P * (cin + 2 * H), 4 * P * cin * H, xr, lambda: xr @ wc.t()).view(B, N, 2 * H)
         h = ops.backend_for(x).rowcombine_edge_fwd(Y, idx, slope_a, slope_e, out_dtype)
         ctx.save_for_backward(xr, wc, Y, idx)
-        ctx.inverse, ctx.slopes, ctx.shape = inverse, (slope_a, slope_e), (B, N, cin, H)
+        ctx.slopes, ctx.shape = (slope_a, slope_e), (B, N, cin, H)
         return h
 
     @staticmethod
@@ -351,8 +351,7 @@ class _EdgeFront(torch.autograd.Function):
         gh = gh.contiguous()
         if gh.dtype not in (torch.float32, torch.bfloat16):
             gh = gh.float()
-        kw = {} if ctx.inverse is None else {"inverse": ctx.inverse}
-        gY = ops.backend_for(gh).rowcombine_edge_bwd(gh, idx, Y, ctx.slopes[0], ctx.slopes[1], **kw).view(P, 2 * H)
+        gY = ops.backend_for(gh).rowcombine_edge_bwd(gh, idx, Y, ctx.slopes[0], ctx.slopes[1]).view(P, 2 * H)
         dx = dwe = dwn = None
         if ctx.needs_input_grad[0]:
             dx = ops.timed("gemm_dgrad", 4 * P * (cin + 2 * H), 4 * P * cin * H, gY, lambda: gY @ wc).view(B, N, cin)
@@ -360,14 +359,14 @@ class _EdgeFront(torch.autograd.Function):
             with _wgrad_ctx(gY, xr):
                 dw = _tall_wgrad(gY, xr)
             dwe, dwn = dw[:H], dw[H:]
-        return dx, dwe, dwn, None, None, None, None, None
+        return dx, dwe, dwn, None, None, None, None
 
 
 def edge_front(x, we, wn, idx, slope_a, slope_e, out_dtype):
-    """x (B,N,Cin) fp32 rows, we / wn (H,Cin) the bare edge / node convolutions, idx (B,N,K) int32 -> (B,N,K,H)."""
-    inv = getattr(idx, "_tpg_inverse", None)
-    inverse = inv[1:] if inv is not None and inv[0] == x.shape[1] else None
-    return _EdgeFront.apply(x.contiguous(), we, wn, idx, float(slope_a), float(slope_e), out_dtype, inverse)
+    """x (B,N,Cin) fp32 rows, we / wn (H,Cin) the bare edge / node convolutions, idx (B,N,K) int32 or an
+    ops.NeighbourList into N rows -> (B,N,K,H).  (The generator's kNN lists come bare: the backward inverts them itself.)"""
+    idx = ops.neighbour_list(idx, x.shape[1]).idx
+    return _EdgeFront.apply(x.contiguous(), we, wn, idx, float(slope_a), float(slope_e), out_dtype)
 
 
 def _act(y, slope):

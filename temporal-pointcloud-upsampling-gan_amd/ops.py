@@ -1362,18 +1362,69 @@ class _RowCombine(torch.autograd.Function):
         return gU, (gQE if ctx.has_q else None), None, None, None, None, None
 
 
+_DEFERRED_INVERSES = []        # stack of lists: inside `deferred_inverses()` NeighbourList.with_inverse only notes the list
+
+
+class NeighbourList:
+    """A neighbour list as the row gathers take it: idx (B,S,K) contiguous int32 into `n_src` source rows per cloud,
+    and `inverse` = (offs, lst), the inverted index (tpg_invert_index) a row gather's BACKWARD reads, or None while
+    nobody has prepared it (the backward then launches the inversion itself)."""
+    __slots__ = ("idx", "n_src", "inverse")
+
+    def __init__(self, idx, n_src, inverse=None):
+        _need(idx.dtype == torch.int32 and idx.dim() == 3 and idx.is_contiguous(), "idx must be contiguous (B,S,K) int32")
+        self.idx, self.n_src, self.inverse = idx, int(n_src), inverse
+
+    def clouds(self, lo, hi):
+        """Clouds lo..hi (a view: the clouds are the leading, contiguous axis), without an inverse."""
+        return NeighbourList(self.idx[lo:hi], self.n_src)
+
+    @staticmethod
+    def cat(lists):
+        """Lists into the same number of source rows, stacked along the cloud axis (no inverse yet)."""
+        _need(all(l.n_src == lists[0].n_src for l in lists), "neighbour lists into different numbers of source rows")
+        return NeighbourList(torch.cat([l.idx for l in lists], 0), lists[0].n_src)
+
+    def with_inverse(self):
+        """Prepare the inverted index NOW (on the current stream) -- index-only work like FPS and the ball query, so an
+        index plan can take it off the critical path -- or, inside `deferred_inverses()`, note the list for
+        `run_inverses`.  Returns self."""
+        if _DEFERRED_INVERSES:
+            _DEFERRED_INVERSES[-1].append(self)
+            return self
+        be = backend_for(self.idx)
+        if hasattr(be, "invert_index"):
+            self.inverse = be.invert_index(self.idx, self.n_src)
+        return self
+
+    def tensors(self):
+        return [self.idx] + list(self.inverse or ())
+
+
+def neighbour_list(idx, n_src):
+    """What a row gather over `n_src` source rows was handed as its list -> NeighbourList: a bare (B,S,K) int32 tensor
+    is a list without a prepared inverse; a NeighbourList must be one into that many rows (its inverse would be the
+    inverse of another gather: a caller error, not a reason to invert again)."""
+    if isinstance(idx, NeighbourList):
+        _need(idx.n_src == n_src, f"neighbour list into {idx.n_src} source rows used on {n_src}")
+        return idx
+    _need(torch.is_tensor(idx) and idx.dim() == 3 and idx.dtype == torch.int32, "idx must be (B,S,K) int32")
+    return NeighbourList(idx.contiguous(), n_src)
+
+
 def row_combine(U, QE, idx, mode, slope=0.2, out_dtype=None):
     """Channels-last gather of first-layer rows (include/tpgan_ops.h, tpg_rowcombine_fwd).
 
-    U (B,N,C); QE (B,S,C) or None; idx (B,S,K) int32 -> (B,S,K,C).
+    U (B,N,C); QE (B,S,C) or None; idx (B,S,K) int32 or a NeighbourList into N rows -> (B,S,K,C).
       ROW_GATHER: U[idx]      ROW_SUB: U[idx] - QE[s]      ROW_EDGE: U[idx] + lrelu(QE[idx] - QE[s])
     U/QE fp32 or bf16; out_dtype defaults to U.dtype (fp32 in -> bf16 out is supported)."""
-    _need(U.dim() == 3 and idx.dim() == 3 and idx.dtype == torch.int32, "U (B,N,C), idx (B,S,K) int32")
+    _need(U.dim() == 3, "U (B,N,C), idx (B,S,K) int32")
+    nl = neighbour_list(idx, U.shape[1])
+    idx = nl.idx
     _need(U.dtype in _DTYPE_CODE, f"row_combine supports fp32/bf16, got {U.dtype}")
     _need(U.shape[0] == idx.shape[0], "batch mismatch")
     out_dtype = out_dtype or U.dtype
     U = U.contiguous()
-    idx = idx.contiguous()
     if mode == ROW_GATHER:
         QE = None
     else:
@@ -1383,19 +1434,14 @@ def row_combine(U, QE, idx, mode, slope=0.2, out_dtype=None):
             _need(idx.shape[1] == U.shape[1], "EDGE mode needs S == N")
     ne = 4 if (U.dtype == torch.float32 and out_dtype == torch.float32) else 8
     _need(U.shape[2] % ne == 0, f"channel count {U.shape[2]} must be a multiple of {ne}")
-    inv = getattr(idx, "_tpg_inverse", None)        # see attach_inverse
-    inverse = inv[1:] if inv is not None and inv[0] == U.shape[1] else None
-    return _RowCombine.apply(U, QE, idx, mode, float(slope), out_dtype, inverse)
-
-
-_DEFERRED_INVERSES = []        # stack of lists: inside `deferred_inverses()` attach_inverse only notes its arguments
+    return _RowCombine.apply(U, QE, idx, mode, float(slope), out_dtype, nl.inverse)
 
 
 class deferred_inverses:
-    """with deferred_inverses() as pending: ... -- `attach_inverse` calls inside launch nothing; `run_inverses(pending)`
-    launches them later (on the stream current then) and hangs the results on the index tensors.  The inverted index is
-    read by a row gather's BACKWARD only, so an index plan can hand its lists to the forward first and build the
-    inverses behind that (gan_step_graph: ~150 us earlier start of a discriminator update)."""
+    """with deferred_inverses() as pending: ... -- `NeighbourList.with_inverse` calls inside launch nothing;
+    `run_inverses(pending)` launches them later (on the stream current then).  The inverted index is read by a row
+    gather's BACKWARD only, so an index plan can hand its lists to the forward first and build the inverses behind
+    that (gan_step_graph: ~150 us earlier start of a discriminator update)."""
 
     def __enter__(self):
         self.pending = []
@@ -1408,25 +1454,16 @@ class deferred_inverses:
 
 
 def run_inverses(pending):
-    for idx, N in pending:
-        attach_inverse(idx, N)
+    for nl in pending:
+        nl.with_inverse()
     del pending[:]
 
 
 def attach_inverse(idx, N):
-    """Prepare the inverted index of a neighbour list idx (B,S,K) int32 into N source rows NOW
-    (on the current stream) and hang it on the tensor: `row_combine` hands it to its backward,
-    which then skips its own tpg_invert_index launch.  Index-only work like FPS and the ball
-    query, so an index plan can take it off the critical path.  Returns idx."""
-    _need(idx.dtype == torch.int32 and idx.dim() == 3 and idx.is_contiguous(), "idx must be contiguous (B,S,K) int32")
-    if _DEFERRED_INVERSES:
-        _DEFERRED_INVERSES[-1].append((idx, int(N)))
-        return idx
-    be = backend_for(idx)
-    if hasattr(be, "invert_index"):
-        offs, lst = be.invert_index(idx, int(N))
-        idx._tpg_inverse = (int(N), offs, lst)
-    return idx
+    """A bare neighbour list idx (B,S,K) contiguous int32 into N source rows -> the NeighbourList that carries its
+    inverted index (`NeighbourList.with_inverse`): `row_combine` hands it to its backward, which then skips its own
+    tpg_invert_index launch."""
+    return NeighbourList(idx, N).with_inverse()
 
 
 # ------------------------------------------------ head: BatchNorm1d + LeakyReLU + dropout mask

@@ -394,21 +394,18 @@ class _PointnetSAModuleBase(nn.Module):
             centres = replace_dummy_centres(xyz, centres)
         return centres
 
-    def index_level(self, xyz, inverse=True, prefix=None):
+    def index_level(self, xyz, prefix=None):
         """All index-only work of this level for detached clouds xyz (B,N,3):
-        -> (centres (B,S) int32, new_xyz (B,S,3) detached, idx (B,S,ns) int32).
+        -> (centres (B,S) int32, new_xyz (B,S,3) detached, the ball-query list (B,S,ns) as an ops.NeighbourList).
         It depends on coordinates only, so a caller may run it ahead of time / on another stream
         (see `index_plan` of the discriminators) and hand the result to `forward_rows`.
-        inverse=False leaves the inverted index to whoever regroups the lists (`merge_plans`).
+        The list's inverted index is left to whoever regroups the lists (`merge_plans`, `attach_plan_inverses`).
         prefix: see `sample_centres` (pass the same list to every level of a chain, [None] at the first)."""
         xyz = xyz.detach().float().contiguous()
         centres = self.sample_centres(xyz, prefix)
         new_xyz = _gather_centres(xyz, centres)
         g = self.groupers[0]
-        idx = _sources(ops.ball_query(g.radius, g.nsample, xyz, new_xyz), xyz.shape[1])
-        if inverse and rows_first():
-            ops.attach_inverse(idx, xyz.shape[1])       # for the backward of the row gather
-        return centres, new_xyz, idx
+        return centres, new_xyz, ops.NeighbourList(ops.ball_query(g.radius, g.nsample, xyz, new_xyz), xyz.shape[1])
 
     def _first_layer(self, grouper, mlp, xyz, new_xyz, feat_rows, idx=None):
         """Rows of the first conv's output for every grouped position: (B,S,ns,C1)."""
@@ -664,16 +661,13 @@ class FlowModule(nn.Module):
                 spec = (hidden_feat, [hidden_feat, hidden_feat // 2, hidden_feat])
             self.flow_emb_layers.append(FlowEmbedding(spec[0], spec[1], sn=sn))
 
-    def pair_indices(self, pos_rows_lst, cutoff, inverse=True):
-        """Neighbour lists of the frame pairs (l, l+1): positions only, shared by every depth."""
-        pairs = [_sources(ball_query_wrapper(cutoff, FlowEmbedding.NSAMPLE, pos_rows_lst[l].detach(),
-                                             pos_rows_lst[l + 1].detach()).to(torch.int32).contiguous(),
-                          pos_rows_lst[l + 1].shape[1])
-                 for l in range(len(pos_rows_lst) - 1)]
-        if inverse and rows_first():
-            for l, idx in enumerate(pairs):               # for the backward of the row gather
-                ops.attach_inverse(idx, pos_rows_lst[l + 1].shape[1])
-        return pairs
+    def pair_indices(self, pos_rows_lst, cutoff):
+        """Neighbour lists (ops.NeighbourList, no inverse yet) of the frame pairs (l, l+1): positions only, shared by
+        every depth."""
+        return [ops.NeighbourList(ball_query_wrapper(cutoff, FlowEmbedding.NSAMPLE, pos_rows_lst[l].detach(),
+                                                     pos_rows_lst[l + 1].detach()).to(torch.int32).contiguous(),
+                                  pos_rows_lst[l + 1].shape[1])
+                for l in range(len(pos_rows_lst) - 1)]
 
     def forward_rows(self, feat_rows_lst, pos_rows_lst, cutoff, pair_idx=None):
         """Lists of (B,N,C) / (B,N,3) rows -> (B,N,out) rows."""
@@ -681,6 +675,8 @@ class FlowModule(nn.Module):
         feats = list(feat_rows_lst)
         if pair_idx is None and rows_first():
             pair_idx = self.pair_indices(pos_rows_lst, cutoff)     # depth d re-uses pairs 0..T-2-d
+            for idx in pair_idx:                                   # for the backward of the row gather
+                idx.with_inverse()
         for depth in range(self.depth):
             layer = self.flow_emb_layers[depth]
             feats = [layer.forward_rows(pos_rows_lst[l], pos_rows_lst[l + 1], feats[l], feats[l + 1], cutoff,
@@ -689,15 +685,12 @@ class FlowModule(nn.Module):
         assert len(feats) == 1
         return feats[0]
 
-    def depth_indices(self, pair_idx_per_pass, n_src):
+    def depth_indices(self, pair_idx_per_pass):
         """Neighbour lists of `forward_rows_passes`: for depth d the pairs 0..T-2-d of every pass,
-        stacked pass-major along the cloud axis (with their inverted index, ops.attach_inverse)."""
+        stacked pass-major along the cloud axis (with their inverted index)."""
         T1 = len(pair_idx_per_pass[0])
-        out = []
-        for d in range(self.depth):
-            idx = torch.cat([pairs[l] for pairs in pair_idx_per_pass for l in range(T1 - d)], 0).contiguous()
-            out.append(ops.attach_inverse(idx, n_src))
-        return out
+        return [ops.NeighbourList.cat([pairs[l] for pairs in pair_idx_per_pass for l in range(T1 - d)]).with_inverse()
+                for d in range(self.depth)]
 
     def forward_rows_passes(self, feats, poss, depth_idx):
         """NP passes x T frames at once: feats (NP,T,B,N,C), poss (NP,T,B,N,3) -> (NP*B,N,out).
@@ -784,24 +777,28 @@ def _gather_centres(xyz, centres):
     return ops.gather_operation(xyz.transpose(1, 2).contiguous(), centres).transpose(1, 2).contiguous()
 
 
-def _sources(idx, n_src):
-    """Remember on a neighbour list how many source rows it indexes (merge_plans needs it)."""
-    idx._tpg_nsrc = int(n_src)
-    return idx
+def _sa_index_plans(levels, xyz, NP):
+    """The set-abstraction half of `index_plans`: FPS centres (the FPS-prefix chain from level to level) and ball-query
+    lists of `levels` for the clouds xyz (NP*n,N,3) of NP passes, stacked pass-major, every search launched once.
+    -> the last level's centre coordinates (NP*n,S,3), per pass the [(centres, list)] of the levels (views)."""
+    n, sa, chain = xyz.shape[0] // NP, [], [None]
+    for level in levels:
+        c, xyz, i = level.index_level(xyz, prefix=chain)
+        sa.append((c, i))
+    return xyz, [[(c[p * n:(p + 1) * n], i.clouds(p * n, (p + 1) * n)) for c, i in sa] for p in range(NP)]
 
 
-def _cut(idx, lo, hi):
-    """Clouds lo..hi of a neighbour list (a view: the clouds are the leading, contiguous axis)."""
-    return _sources(idx[lo:hi], idx._tpg_nsrc)
+def _merge_sa(plans):
+    """The "sa" part of `merge_plans`: per level the passes' centres and lists stacked along the cloud axis."""
+    return [(torch.cat([p["sa"][l][0] for p in plans], 0),
+             ops.NeighbourList.cat([p["sa"][l][1] for p in plans]).with_inverse()) for l in range(len(plans[0]["sa"]))]
 
 
 def attach_plan_inverses(plan):
     """Give every ball-query list of a per-pass plan of `index_plans` its inverted index, so the
     plan can go to `forward(..., plan=)` directly instead of through `merge_plans`."""
-    for _, idx in plan["sa"]:
-        ops.attach_inverse(idx, idx._tpg_nsrc)
-    for idx in plan.get("flow", []):
-        ops.attach_inverse(idx, idx._tpg_nsrc)
+    for idx in [i for _, i in plan["sa"]] + plan.get("flow", []):
+        idx.with_inverse()
     return plan
 
 
@@ -828,9 +825,10 @@ def run_index_plan(make_plan, stream):
 
 def _plan_tensors(obj):
     """Every tensor inside a (nested) plan / tuple / list / dict."""
+    if isinstance(obj, ops.NeighbourList):
+        return obj.tensors()
     if torch.is_tensor(obj):
-        inv = getattr(obj, "_tpg_inverse", None)         # ops.attach_inverse
-        return [obj] + ([inv[1], inv[2]] if inv is not None else [])
+        return [obj]
     if isinstance(obj, dict):
         obj = list(obj.values())
     if isinstance(obj, (list, tuple)):
@@ -847,14 +845,7 @@ class _TempoDis(nn.Module):
         """Every index of one forward over the frames `pos_lst` -- FPS centres and ball-query
         lists of both levels (frames stacked) and the flow-embedding neighbour lists.  Depends on
         coordinates only; see `run_index_plan` for running it on a side stream."""
-        T, B = len(pos_lst), pos_lst[0].shape[0]
-        xyz = torch.cat([p.detach().float() for p in pos_lst], 0)
-        chain = [None]                              # level 1 samples level 0's centres: FPS-prefix shortcut
-        c0, x1, i0 = self.coarse_graining_module[0].index_level(xyz, prefix=chain)
-        c1, x2, i1 = self.coarse_graining_module[1].index_level(x1, prefix=chain)
-        pairs = self.flow_module.pair_indices([x2[t * B:(t + 1) * B] for t in range(T)],
-                                              self.flow_radius_scale * cutoff)
-        return {"sa": [(c0, i0), (c1, i1)], "flow": pairs}
+        return attach_plan_inverses(self.index_plans([pos_lst], cutoff)[0])
 
     def index_plans(self, pos_lsts, cutoff):
         """[index_plan(p, cutoff) for p in pos_lsts] (same shapes) with every search launched ONCE
@@ -864,16 +855,11 @@ class _TempoDis(nn.Module):
         inverted indices: hand them to `merge_plans` (or `attach_plan_inverses`)."""
         NP, T, B = len(pos_lsts), len(pos_lsts[0]), pos_lsts[0][0].shape[0]
         xyz = torch.cat([p.detach().float() for pos_lst in pos_lsts for p in pos_lst], 0)   # pass-major
-        chain = [None]
-        c0, x1, i0 = self.coarse_graining_module[0].index_level(xyz, inverse=False, prefix=chain)
-        c1, x2, i1 = self.coarse_graining_module[1].index_level(x1, inverse=False, prefix=chain)
+        x2, sa = _sa_index_plans(self.coarse_graining_module, xyz, NP)
         frames = x2.view(NP, T, B, *x2.shape[1:])
         pairs = self.flow_module.pair_indices([frames[:, t].reshape(NP * B, *x2.shape[1:]) for t in range(T)],
-                                              self.flow_radius_scale * cutoff, inverse=False)
-        n = T * B
-        return [{"sa": [(c0[p * n:(p + 1) * n], _cut(i0, p * n, (p + 1) * n)),
-                        (c1[p * n:(p + 1) * n], _cut(i1, p * n, (p + 1) * n))],
-                 "flow": [_cut(pr, p * B, (p + 1) * B) for pr in pairs]} for p in range(NP)]
+                                              self.flow_radius_scale * cutoff)
+        return [{"sa": sa[p], "flow": [pr.clouds(p * B, (p + 1) * B) for pr in pairs]} for p in range(NP)]
 
     def _levels(self, pos_lst, feat_lst, plan=None):
         feats0 = list(feat_lst) if feat_lst is not None else list(pos_lst)
@@ -900,15 +886,7 @@ class _TempoDis(nn.Module):
 
     def merge_plans(self, plans):
         """Index plans of successive forwards (same shapes) -> the plan of `forward_passes`."""
-        n0 = plans[0]["sa"][0][1]._tpg_nsrc
-        n1 = plans[0]["sa"][1][1]._tpg_nsrc
-        sa = []
-        for l, n_src in ((0, n0), (1, n1)):
-            c = torch.cat([p["sa"][l][0] for p in plans], 0)
-            i = ops.attach_inverse(torch.cat([p["sa"][l][1] for p in plans], 0).contiguous(), n_src)
-            sa.append((c, i))
-        n2 = plans[0]["flow"][0]._tpg_nsrc
-        return {"sa": sa, "flow_depth": self.flow_module.depth_indices([p["flow"] for p in plans], n2)}
+        return {"sa": _merge_sa(plans), "flow_depth": self.flow_module.depth_indices([p["flow"] for p in plans])}
 
     def forward_passes(self, pos_lsts, cutoff, plan=None):
         """[forward(pos_lst, cutoff) for pos_lst in pos_lsts] -- the same module calls in the same
@@ -990,12 +968,7 @@ class _SpatialDis(nn.Module):
 
     def merge_plans(self, plans):
         """Index plans of successive forwards (same shapes) -> the plan of `forward_passes`."""
-        sa = []
-        for l in range(len(self.coarse_graining_module)):
-            n_src = plans[0]["sa"][l][1]._tpg_nsrc
-            c = torch.cat([p["sa"][l][0] for p in plans], 0)
-            sa.append((c, ops.attach_inverse(torch.cat([p["sa"][l][1] for p in plans], 0).contiguous(), n_src)))
-        return {"sa": sa}
+        return {"sa": _merge_sa(plans)}
 
     def forward_passes(self, pos_list, plan=None):
         """[forward(pos) for pos in pos_list] with the passes sharing their launches (see
@@ -1017,20 +990,15 @@ class _SpatialDis(nn.Module):
     def index_plans(self, pos_list):
         """[index_plan(p) for p in pos_list] with every search launched once for all passes (see
         _TempoDis.index_plans); per-pass plans without inverted indices."""
-        NP, B = len(pos_list), pos_list[0].shape[0]
-        xyz, levels, chain = torch.cat([p.detach().float() for p in pos_list], 0), [], [None]
-        for sa in self.coarse_graining_module:
-            c, xyz, i = sa.index_level(xyz, inverse=False, prefix=chain)
-            levels.append((c, i))
-        return [{"sa": [(c[p * B:(p + 1) * B], _cut(i, p * B, (p + 1) * B)) for c, i in levels]} for p in range(NP)]
+        return self._plans(torch.cat([p.detach().float() for p in pos_list], 0), len(pos_list))
 
     def index_plan(self, pos):
-        """FPS centres + ball-query lists of every level for the clouds `pos` (coordinates only)."""
-        xyz, levels, chain = pos.detach().float(), [], [None]
-        for sa in self.coarse_graining_module:
-            c, xyz, i = sa.index_level(xyz, prefix=chain)
-            levels.append((c, i))
-        return {"sa": levels}
+        """FPS centres + ball-query lists of every level for the clouds `pos` (coordinates only): `index_plans` of one
+        pass (without its stacking copy) plus the lists' inverted indices."""
+        return attach_plan_inverses(self._plans(pos.detach().float(), 1)[0])
+
+    def _plans(self, xyz, NP):
+        return [{"sa": sa} for sa in _sa_index_plans(self.coarse_graining_module, xyz, NP)[1]]
 
     def _forward(self, pos, width, plan=None):
         with sn_prefetch(self._sn_calls(), self.training):

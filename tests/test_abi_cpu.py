@@ -77,6 +77,27 @@ def test_validation_errors_match_upstream_style(oracle_cpu):
         ops.furthest_point_sample(torch.zeros(1, 8, 3, dtype=torch.float64), 4)
 
 
+def test_neighbour_list_for_other_source_rows_is_refused(oracle_cpu):
+    """A list that carries an inverted index prepared for n_src source rows is a caller error on a gather over another
+    number of rows: `row_combine` / `edge_front` raise instead of dropping the inverse and inverting again.  The same
+    list on its own rows, and a bare tensor ("no inverse prepared") on any rows, go through."""
+    import tpgan_amd.ops as ops
+    from tpgan_amd import graph_conv
+    idx = torch.tensor([[[0, 1], [2, 3], [4, 5], [6, 7]]], dtype=torch.int32)
+    prepared = (torch.arange(9, dtype=torch.int32).view(1, 9), torch.arange(8, dtype=torch.int32).view(1, 8))
+    nl = ops.NeighbourList(idx, 8, prepared)
+    U8, U10 = torch.randn(1, 8, 4), torch.randn(1, 10, 4)
+    assert torch.equal(ops.row_combine(U8, None, nl, ops.ROW_GATHER), ops.row_combine(U8, None, idx, ops.ROW_GATHER))
+    assert ops.row_combine(U10, None, idx, ops.ROW_GATHER).shape == (1, 4, 2, 4)
+    with pytest.raises(RuntimeError, match="source rows"):
+        ops.row_combine(U10, None, nl, ops.ROW_GATHER)
+    with pytest.raises(RuntimeError, match="source rows"):
+        graph_conv.edge_front(U10, torch.randn(4, 4), torch.randn(4, 4), nl, 0.2, 0.2, torch.float32)
+    with pytest.raises(RuntimeError, match="source rows"):
+        ops.NeighbourList.cat([nl, ops.NeighbourList(idx, 10)])
+    assert nl.clouds(0, 1).n_src == 8 and nl.clouds(0, 1).inverse is None and len(nl.tensors()) == 3
+
+
 def test_new_entries_reject_bad_arguments_before_any_launch(hip_lib):
     """Argument checks of the round-2 entries return their status codes without touching a device (no GPU here):
     unsupported shapes are TPG_ERR_UNSUPPORTED (-3), malformed calls TPG_ERR_ARG (-1), empty work TPG_OK."""

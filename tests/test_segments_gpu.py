@@ -279,3 +279,54 @@ def test_prepared_spectral_norm_weights_equal_the_forwards_own():
     for (n, a), (_, b) in zip(Da.named_buffers(), Db.named_buffers()):
         assert torch.allclose(a.float(), b.float(), rtol=1e-5, atol=1e-5), n
     sn_discard_prepared()
+
+
+def _map_lists(plan, fn):
+    """A (nested) plan with every ops.NeighbourList replaced by fn(list)."""
+    from tpgan_amd.ops import NeighbourList
+    if isinstance(plan, NeighbourList):
+        return fn(plan)
+    if isinstance(plan, dict):
+        return {k: _map_lists(v, fn) for k, v in plan.items()}
+    if isinstance(plan, (list, tuple)):
+        return type(plan)(_map_lists(v, fn) for v in plan)
+    return plan
+
+
+@pytest.mark.parametrize("which", ["spatial", "tempo"])
+def test_merged_plan_inverts_each_list_once_and_its_backward_never(which):
+    """What an index plan is for: `merge_plans` launches tpg_invert_index exactly once per neighbour list, and the
+    backward of a `forward_passes` driven by that plan launches it not at all (counted with ops.OpTimer).  The
+    counter's own control: the same lists handed over as bare tensors -- "no inverse prepared" -- make the backward
+    invert every one of them."""
+    from tpgan_amd import ops
+    from tpgan_amd.set_abstraction import FluidSpatialDis, FluidTempoDis
+    from tpgan_amd.synthetic import fluid_clip
+    torch.manual_seed(4)
+    dev = torch.device("cuda", 0)
+    D = _no_dropout(FluidSpatialDis() if which == "spatial" else FluidTempoDis(3)).to(dev).train()
+    clips = [fluid_clip(2, 2048, 8, 3, seed=s, device=dev)[1] for s in (1, 2)]
+    passes, args = ([c[1] for c in clips], ()) if which == "spatial" else (clips, (0.1,))
+    timer = ops.OpTimer()
+    prev = ops.set_timer(timer)
+
+    def inversions():
+        torch.cuda.synchronize()
+        return timer.summary().get("invert_index", {"launches": 0})["launches"]
+    try:
+        per_pass = D.index_plans(passes, *args)
+        assert inversions() == 0                                    # per-pass plans come without inverses
+        plan = D.merge_plans(per_pass)
+        lists = []
+        _map_lists(plan, lists.append)
+        assert len(lists) == (3 if which == "spatial" else 4)       # 3 levels | 2 levels + 2 flow depths
+        assert inversions() == len(lists) and all(l.inverse is not None for l in lists)
+        for p, expect in ((plan, 0), (_map_lists(plan, lambda l: l.idx), len(lists))):
+            fake = [x.clone().requires_grad_(True) for x in clips[0]] if which == "tempo" else clips[0][1].clone().requires_grad_(True)
+            outs = D.forward_passes([fake, passes[1]], *args, plan=p)
+            before = inversions()
+            (((outs[0] - 0.1) ** 2).mean() + ((outs[1] - 1.0) ** 2).mean()).backward()
+            assert inversions() - before == expect, (inversions() - before, expect)
+            assert all(bool(torch.isfinite(x.grad).all()) for x in (fake if which == "tempo" else [fake]))
+    finally:
+        ops.set_timer(prev)
