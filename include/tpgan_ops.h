@@ -496,6 +496,58 @@ int tpg_radius_reduce_exhaustive_f32(const float *query, const float *pos, const
                                      int B, int Nq, int Np, float r, int kernel, int32_t *count, float *sum,
                                      void *stream);
 
+/* ---- training clips from device-resident sequences (csrc/clip_sample.hip) -------------------------------------
+ * train_fluid/tempo_dataset.py:58-105 (SiamData.__getitem__) with train_utils.py:98-139 (sample_patch_with_fps) and
+ * :214-221 (normalize_point_cloud), which the reference runs per clip on host workers (np.load, a scipy KD-tree, a
+ * numba FPS, a pinned upload of 13 arrays).  Here every frame stays on the device and a batch is four calls:
+ * tpg_patch_select_f32, tpg_clip_gather_high_f32, tpg_fps_start_f32 on the centre frame's patch,
+ * tpg_clip_gather_low_f32.
+ * EXCEPTION to the pointer convention above: the arrays marked HOST below are small per-clip tables in HOST memory (the
+ * sampler draws them on the host); they are checked before anything is launched and travel as kernel arguments, so a
+ * bad clip is an error status with nothing written, and a batch costs no host-to-device copy.
+ *
+ * tpg_patch_select_f32: the K nearest stored points of ONE seed point per scene (KDTree(pos).query(pos[seed], K),
+ * train_utils.py:118-123), for B scenes of different sizes.  points (P,3) f32; scene b is points[first[b] ..
+ * first[b]+count[b]) and its seed point is row seed[b] of that slice (first, count, seed: HOST, B ints each).
+ * idx (B,K) int32, scene-local.  Rule: d2 = (dx*dx + dy*dy) + dz*dz in fp32, each operation rounded (no FMA); the
+ * result is the K candidates smallest in (d2, index), in ascending lexicographic (d2, index) order -- idx[b][0] is the
+ * seed or a lower-indexed exact duplicate of it.  A non-finite d2 ranks by its bit pattern (+inf after every finite
+ * value), a NaN d2 as the single pattern 0x7FC00000: after +inf, all NaNs tied, by index.  Bit-exact, identical from
+ * run to run and at every batch position (integer atomics and a final sort of unique keys only).
+ * K <= 0, K > count[b], seed[b] outside [0, count[b]), a slice outside [0, P): TPG_ERR_ARG;
+ * K > tpg_patch_select_max_k() (the K keys of a scene are ordered in LDS): TPG_ERR_UNSUPPORTED.
+ * ws: tpg_patch_select_workspace_bytes(B, max_b count[b], K) bytes, 8-byte aligned; zeroed by the call itself. */
+#define TPG_PATCH_SELECT_MAX_K 16384
+int tpg_patch_select_max_k(void);
+size_t tpg_patch_select_workspace_bytes(int B, int max_count, int K);
+int tpg_patch_select_f32(const float *points, long long P, const int32_t *first, const int32_t *count,
+                         const int32_t *seed, int B, int K, int32_t *idx, void *ws, void *stream);
+
+/* All high-resolution arrays of a batch of B clips of T <= 8 frames (tempo_dataset.py:69-87):
+ *     high_pos[t,b,k,:] = pos[frame_first[t,b] + patch[b,k], :] - centroids[centroid_row[b], :]     (one fp32 subtraction)
+ *     high_vel[t,b,k,:] = vel[frame_first[t,b] + patch[b,k], :]                                     (vel, high_vel: both or neither)
+ * pos / vel (P,3) f32: every frame back to back; frame_first (T,B) HOST: first point of clip b's frame t; count (B)
+ * HOST: particles of clip b's scene (patch entries are clamped into [0, count[b])); centroids (F,3) f32: one row per
+ * stored frame, centroid_row (B) HOST: the row of clip b's CENTRE frame (normalize_point_cloud of the centre frame, applied
+ * to all T frames; its scale is the constant 1).  patch (B,K) int32 from tpg_patch_select_f32.  Outputs are frame-major
+ * (T,B,K,3): frame t is the contiguous (B,K,3) cloud batch the networks and tpg_fps_start_f32 take. */
+int tpg_clip_gather_high_f32(const float *pos, const float *vel, long long P, const int32_t *frame_first,
+                             const int32_t *count, const float *centroids, int F, const int32_t *centroid_row,
+                             const int32_t *patch, int T, int B, int K, float *high_pos, float *high_vel, void *stream);
+
+/* All low-resolution arrays of the batch (tempo_dataset.py:89-100), fps (B,M) int32 = the centre patch's sampling:
+ *     low_pos[t,b,j,:] = high_pos[t,b,fps[b,j],:] + noise[t,b,j,:] * jitter     (multiply, then add: two roundings)
+ *     low_vel[t,b,j,:] = vel[frame_first[t,b] + fps[b,j], :]                    (vel, low_vel: both or neither)
+ * noise (T,B,M,3) f32 drawn by the caller, or NULL: low_pos is then the plain gather.  The velocities are the
+ * reference's, quirk included: tempo_dataset.py:98-100 indexes the WHOLE scene's velocities with the patch-local
+ * sampling (`vel_center[fps_idx]`, not `highres_vel[fps_idx]`), so low_vel are the velocities of scene particles
+ * fps[b,j], not of the low-resolution points; pos-only training (--in_node_feats 3) never reads them.  vel (P,3),
+ * frame_first (T,B) HOST, count (B) HOST as in tpg_clip_gather_high_f32 (unused when vel is NULL).  fps entries are
+ * clamped into [0, K) for the positions and into [0, count[b]) for the velocities. */
+int tpg_clip_gather_low_f32(const float *high_pos, const int32_t *fps, const float *noise, float jitter,
+                            const float *vel, long long P, const int32_t *frame_first, const int32_t *count, int T,
+                            int B, int K, int M, float *low_pos, float *low_vel, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -71,12 +71,16 @@ SIGNATURES = {
     "tpg_context_expand_f32": [_P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P],
     "tpg_radius_reduce_f32": [_P, _P, _P, _P, _I, _I, _I, _F, _I, _P, _P, _P, _P],
     "tpg_radius_reduce_exhaustive_f32": [_P, _P, _P, _P, _I, _I, _I, _F, _I, _P, _P, _P],
+    "tpg_patch_select_f32": [_P, _L, _P, _P, _P, _I, _I, _P, _P, _P],
+    "tpg_clip_gather_high_f32": [_P, _P, _L, _P, _P, _P, _I, _P, _P, _I, _I, _I, _P, _P, _P],
+    "tpg_clip_gather_low_f32": [_P, _P, _P, _F, _P, _L, _P, _P, _I, _I, _I, _I, _P, _P, _P],
 }
 SIZE_GETTERS = ("tpg_rowbn_workspace_bytes", "tpg_mlp_workspace_bytes", "tpg_context_expand_workspace_bytes")
 OTHER_GETTERS = ("tpg_spectral_norm_multi_stride", "tpg_spectral_norm_multi_bwd_scratch",
                  "tpg_mlp_wgrad_workspace_bytes", "tpg_frnn_grid_workspace_bytes", "tpg_small_tail_workspace_bytes",
                  "tpg_chamfer_bwd_workspace_bytes", "tpg_rowlinear_wgrad_workspace_bytes", "tpg_rowlinear_supported",
-                 "tpg_spectral_norm_split_rows", "tpg_spectral_norm_split_max_cn", "tpg_spectral_norm_split_max_rows")
+                 "tpg_spectral_norm_split_rows", "tpg_spectral_norm_split_max_cn", "tpg_spectral_norm_split_max_rows",
+                 "tpg_patch_select_workspace_bytes", "tpg_patch_select_max_k")
 STRING_GETTERS = ("tpg_version", "tpg_target_arch")
 
 STATUS = {0: "TPG_OK", -1: "TPG_ERR_ARG", -2: "TPG_ERR_LAUNCH", -3: "TPG_ERR_UNSUPPORTED"}
@@ -121,7 +125,10 @@ def load():
     lib.tpg_chamfer_bwd_workspace_bytes.restype = C.c_size_t
     lib.tpg_rowlinear_wgrad_workspace_bytes.argtypes = [C.c_longlong, C.c_int, C.c_int, C.c_int, C.c_int]
     lib.tpg_rowlinear_wgrad_workspace_bytes.restype = C.c_size_t
-    for name in ("tpg_spectral_norm_split_rows", "tpg_spectral_norm_split_max_cn", "tpg_spectral_norm_split_max_rows"):
+    lib.tpg_patch_select_workspace_bytes.argtypes = [C.c_int, C.c_int, C.c_int]
+    lib.tpg_patch_select_workspace_bytes.restype = C.c_size_t
+    for name in ("tpg_spectral_norm_split_rows", "tpg_spectral_norm_split_max_cn", "tpg_spectral_norm_split_max_rows",
+                 "tpg_patch_select_max_k"):
         getattr(lib, name).argtypes = []
         getattr(lib, name).restype = C.c_int
     lib.tpg_rowlinear_supported.argtypes = [C.c_int, C.c_int, C.c_int]

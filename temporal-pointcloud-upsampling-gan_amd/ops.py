@@ -291,6 +291,39 @@ class HipBackend:
                    _ptr(ws))
         return out, offsets
 
+    def patch_select(self, points, first, count, seed, K):
+        """tpg_patch_select_f32: first / count / seed are host int32 arrays (numpy); -> idx (B,K) int32."""
+        B = len(first)
+        idx = torch.empty((B, K), dtype=torch.int32, device=points.device)
+        need = self.lib.tpg_patch_select_workspace_bytes(B, int(count.max()) if B else 0, K)
+        ws = torch.empty((max(need, 8) + 7) // 8, dtype=torch.int64, device=points.device)
+        self._call("tpg_patch_select_f32", "patch_select", 12 * int(count.sum()) + 4 * B * K, points,
+                   _ptr(points), points.shape[0], first.ctypes.data, count.ctypes.data, seed.ctypes.data, B, K,
+                   _ptr(idx), _ptr(ws))
+        return idx
+
+    def clip_gather_high(self, pos, vel, frame_first, count, centroids, centroid_row, patch):
+        """tpg_clip_gather_high_f32: frame_first (T,B) / count (B) / centroid_row (B) are host int32 arrays (numpy)."""
+        T, B = frame_first.shape
+        K = patch.shape[1]
+        high_pos = torch.empty((T, B, K, 3), dtype=torch.float32, device=pos.device)
+        high_vel = torch.empty_like(high_pos) if vel is not None else None
+        self._call("tpg_clip_gather_high_f32", "clip_gather_high", (1 if vel is None else 2) * 24 * T * B * K, pos,
+                   _ptr(pos), _ptr(vel), pos.shape[0], frame_first.ctypes.data, count.ctypes.data, _ptr(centroids),
+                   centroids.shape[0], centroid_row.ctypes.data, _ptr(patch), T, B, K, _ptr(high_pos), _ptr(high_vel))
+        return high_pos, high_vel
+
+    def clip_gather_low(self, high_pos, fps_idx, noise, jitter, vel, frame_first, count):
+        T, B, K, _ = high_pos.shape
+        M = fps_idx.shape[1]
+        low_pos = torch.empty((T, B, M, 3), dtype=torch.float32, device=high_pos.device)
+        low_vel = torch.empty_like(low_pos) if vel is not None else None
+        self._call("tpg_clip_gather_low_f32", "clip_gather_low", (1 if vel is None else 2) * 24 * T * B * M, high_pos,
+                   _ptr(high_pos), _ptr(fps_idx), _ptr(noise), float(jitter), _ptr(vel),
+                   0 if vel is None else vel.shape[0], None if vel is None else frame_first.ctypes.data,
+                   None if vel is None else count.ctypes.data, T, B, K, M, _ptr(low_pos), _ptr(low_vel))
+        return low_pos, low_vel
+
     def fps(self, xyz, m, start=None, skip_origin=True):
         B, N, _ = xyz.shape
         idx = torch.empty((B, m), dtype=torch.int32, device=xyz.device)
@@ -983,6 +1016,144 @@ def context_expand(pos, edge, mask, state, t0):
         if hasattr(be, "context_expand"):
             return be.context_expand(pos.detach(), edge.detach(), mask.detach(), state, int(t0))
         return _context_expand_torch(pos.detach(), edge.detach(), mask.detach(), state, int(t0))
+
+
+# ------------------------------------------- training clips from device-resident sequences (csrc/clip_sample.hip)
+PATCH_SELECT_NAN_KEY = 0x7FC00000      # the bit pattern every NaN distance ranks as (after +inf)
+
+
+def _host_ints(a, name, shape):
+    """A small per-clip table kept on the HOST (list / numpy / CPU tensor) -> contiguous int32 numpy array."""
+    if isinstance(a, torch.Tensor):
+        _need(not a.is_cuda, f"{name} is a host table (the sampler draws it on the host): pass a CPU tensor or a list")
+        a = a.numpy()
+    a = np.asarray(a)
+    _need(a.dtype.kind in "iu", f"{name} must hold integers, got {a.dtype}")
+    _need(a.shape == tuple(shape), f"{name} must have shape {tuple(shape)}, got {a.shape}")
+    _need(a.size == 0 or (a.min() >= -2 ** 31 and a.max() < 2 ** 31), f"{name} does not fit int32")
+    return np.ascontiguousarray(a, dtype=np.int32)
+
+
+def _patch_select_torch(points, first, count, seed, K):
+    """`patch_select` composed of torch ops (backends without the kernel): the rule, scene by scene."""
+    out = []
+    for f, n, s in zip(first.tolist(), count.tolist(), seed.tolist()):
+        x = points[f:f + n]
+        d = x - x[s]
+        d2 = (d[:, 0] * d[:, 0] + d[:, 1] * d[:, 1]) + d[:, 2] * d[:, 2]
+        bits = d2.view(torch.int32).long()             # a non-negative fp32 orders like its bit pattern
+        bits = torch.where(torch.isnan(d2), torch.full_like(bits, PATCH_SELECT_NAN_KEY), bits)
+        key = (bits << 32) | torch.arange(n, device=points.device)
+        out.append((torch.sort(key).values[:K] & 0xFFFFFFFF).int())
+    return torch.stack(out)
+
+
+def patch_select(points, first, count, seed, K):
+    """The K nearest stored points of one seed point per scene, for a ragged batch of scenes: the reference's
+    `KDTree(input_pos).query(input_pos[seed], K)` (train_utils.py:118-123) on the device.
+
+    points (P,3) fp32: the scenes back to back; first / count / seed: (B,) HOST integers (list, numpy or CPU tensor) --
+    scene b is points[first[b] : first[b] + count[b]], its seed point is row seed[b] of that slice.
+    -> idx (B,K) int32 on points' device, scene-local, ascending in (d2, index) with the canonical fp32
+    d2 = (dx*dx + dy*dy) + dz*dz; a NaN d2 ranks after +inf (include/tpgan_ops.h)."""
+    _check_float(points, "points", 2)
+    _need(points.shape[1] == 3, "points must be (P,3)")
+    B = len(first)
+    first, count, seed = (_host_ints(a, n, (B,)) for a, n in ((first, "first"), (count, "count"), (seed, "seed")))
+    K = int(K)
+    _need(B > 0, "patch_select needs at least one scene")
+    _need(K > 0, "K must be positive")
+    _need(bool((first >= 0).all() and (count > 0).all() and (first.astype(np.int64) + count <= points.shape[0]).all()),
+          "every scene must be a non-empty slice of points")
+    _need(bool((count >= K).all()), f"K = {K} exceeds a scene's particle count ({int(count.min())})")
+    _need(bool(((seed >= 0) & (seed < count)).all()), "seed must index a point of its scene")
+    be = backend_for(points)
+    with torch.no_grad():
+        if hasattr(be, "patch_select"):
+            return be.patch_select(points.detach(), first, count, seed, K)
+        return _patch_select_torch(points.detach(), first, count, seed, K)
+
+
+def clip_gather_high(pos, vel, frame_first, count, centroids, centroid_row, patch):
+    """Every high-resolution array of a batch of clips at once (tempo_dataset.py:69-87):
+    high_pos[t,b,k] = pos[frame_first[t,b] + patch[b,k]] - centroids[centroid_row[b]], high_vel the plain gather of `vel`
+    (None: no velocities).  pos / vel (P,3) fp32: every frame back to back; frame_first (T,B), count (B), centroid_row (B):
+    HOST integers; centroids (F,3) fp32; patch (B,K) int32.  -> (high_pos (T,B,K,3), high_vel or None)."""
+    _check_float(pos, "pos", 2)
+    _check_float(centroids, "centroids", 2)
+    _check_int(patch, "patch", 2)
+    _same_device(pos, centroids, patch)
+    _need(pos.shape[1] == 3 and centroids.shape[1] == 3, "pos and centroids must hold 3-D points")
+    if vel is not None:
+        _check_float(vel, "vel", 2)
+        _same_device(pos, vel)
+        _need(vel.shape == pos.shape, "vel must have pos's shape")
+    B = patch.shape[0]
+    frame_first = np.asarray(frame_first.numpy() if isinstance(frame_first, torch.Tensor) else frame_first)
+    _need(frame_first.ndim == 2 and frame_first.shape[1] == B, "frame_first must be (T,B)")
+    T = frame_first.shape[0]
+    frame_first = _host_ints(frame_first, "frame_first", (T, B))
+    count = _host_ints(count, "count", (B,))
+    centroid_row = _host_ints(centroid_row, "centroid_row", (B,))
+    _need(1 <= T <= 8, "a clip has 1..8 frames")
+    _need(B > 0 and patch.shape[1] > 0, "patch must be (B,K) with B, K positive")
+    _need(bool((count > 0).all() and (frame_first >= 0).all()
+               and (frame_first.astype(np.int64) + count[None, :] <= pos.shape[0]).all()),
+          "every frame must be a non-empty slice of pos")
+    _need(bool(((centroid_row >= 0) & (centroid_row < centroids.shape[0])).all()), "centroid_row out of range")
+    be = backend_for(pos)
+    with torch.no_grad():
+        if hasattr(be, "clip_gather_high"):
+            return be.clip_gather_high(pos.detach(), None if vel is None else vel.detach(), frame_first, count,
+                                       centroids.detach(), centroid_row, patch)
+        rows = torch.as_tensor(frame_first, dtype=torch.long, device=pos.device).view(T, B, 1) + patch.long().view(1, B, -1)
+        c = centroids[torch.as_tensor(centroid_row, dtype=torch.long, device=pos.device)].view(1, B, 1, 3)
+        return pos[rows] - c, None if vel is None else vel[rows]
+
+
+def clip_gather_low(high_pos, fps_idx, noise=None, jitter=0.0, vel=None, frame_first=None, count=None):
+    """Every low-resolution array of the batch at once (tempo_dataset.py:89-100):
+    low_pos[t,b,j] = high_pos[t,b,fps_idx[b,j]] + noise[t,b,j] * jitter (noise None: the plain gather) and, if `vel` is
+    given, low_vel[t,b,j] = vel[frame_first[t,b] + fps_idx[b,j]] -- the reference's rows, quirk included: it indexes the
+    whole scene's velocities with the patch-local sampling (include/tpgan_ops.h).  high_pos (T,B,K,3) fp32, fps_idx (B,M)
+    int32, noise (T,B,M,3) fp32, vel (P,3) fp32, frame_first (T,B) / count (B) HOST integers as in `clip_gather_high`.
+    -> (low_pos (T,B,M,3), low_vel or None)."""
+    _check_float(high_pos, "high_pos", 4)
+    _check_int(fps_idx, "fps_idx", 2)
+    _same_device(high_pos, fps_idx)
+    T, B, K, _ = high_pos.shape
+    M = fps_idx.shape[1]
+    _need(high_pos.shape[3] == 3 and fps_idx.shape[0] == B and min(T, B, K, M) > 0, "high_pos (T,B,K,3), fps_idx (B,M)")
+    _need(T <= 8, "a clip has 1..8 frames")
+    if noise is not None:
+        _check_float(noise, "noise", 4)
+        _same_device(high_pos, noise)
+        _need(tuple(noise.shape) == (T, B, M, 3), "noise must be (T,B,M,3)")
+    if vel is not None:
+        _check_float(vel, "vel", 2)
+        _same_device(high_pos, vel)
+        _need(vel.shape[1] == 3, "vel must be (P,3)")
+        _need(frame_first is not None and count is not None, "low-resolution velocities need frame_first and count")
+        frame_first = _host_ints(frame_first, "frame_first", (T, B))
+        count = _host_ints(count, "count", (B,))
+        _need(bool((count > 0).all() and (frame_first >= 0).all()
+                   and (frame_first.astype(np.int64) + count[None, :] <= vel.shape[0]).all()),
+              "every frame must be a non-empty slice of vel")
+    be = backend_for(high_pos)
+    with torch.no_grad():
+        if hasattr(be, "clip_gather_low"):
+            return be.clip_gather_low(high_pos.detach(), fps_idx, noise, float(jitter),
+                                      None if vel is None else vel.detach(), frame_first, count)
+        sel = fps_idx.long().view(1, B, M, 1).expand(T, B, M, 3)
+        low = torch.gather(high_pos, 2, sel)
+        if noise is not None:
+            low = low + noise * float(np.float32(jitter))
+        if vel is None:
+            return low, None
+        lim = torch.as_tensor(count, dtype=torch.long, device=vel.device).view(1, B, 1) - 1
+        rows = torch.as_tensor(frame_first, dtype=torch.long, device=vel.device).view(T, B, 1) \
+            + torch.minimum(fps_idx.long().view(1, B, M), lim)
+        return low, vel[rows]
 
 
 def farthest_point_sampling(pts, k, initial_idx=None):

@@ -1,0 +1,183 @@
+"""Adversarial training of the fluid upsampler from sequences on disk (train_fluid/train_tempo.py).
+
+    python -m tpgan_amd.train --train_dataset_path DATA --train_sequence_num 20 --sequence_length 200 --log_dir runs/a
+
+Data layout: DATA/case{c}/data_{s}.npz for c = 1 .. train_sequence_num, s = 0 .. sequence_length - 1, each holding
+`pos` and `vel`, (N,3), the same particles in every frame of a case.  Every frame is loaded to the device once
+(data.FluidSequences); the batches come from data.ClipSampler through data.prefetch on a side stream.
+
+The loop is the reference's: SRNet + FluidTempoDis(3) + FluidSpatialDis, Adam(lr) and 2 x Adam(0.33 lr), StepLR(10000,
+0.7) x 3, the EAGER step gan_step.tempo_gan_step (the one with the reference's regimes: n_iter <= 10, closed gate,
+999-padding), a checkpoint when (n_iter - 1) % ckpt_every == 0 or at the end.  Instead of tensorboardX one JSON line
+per --log_every iterations goes to stdout.  Checkpoints hold the reference's ten keys plus `tpgan_amd`: the sampler's
+generator state and the numpy / torch RNG states, which make a resumed run repeat the uninterrupted one bit for bit.
+Under torch.distributed.run every rank samples its own clips (seed + 1000 * rank), gradients are averaged by
+ddp.GradSync and rank 0 writes the checkpoints.
+"""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+import torch
+
+from . import ddp
+from .data import ClipSampler, FluidSequences, prefetch
+from .gan_step import tempo_gan_step
+from .set_abstraction import FluidSpatialDis, FluidTempoDis
+from .srnet import SRNet
+
+CKPT_KEYS = ("sr_net", "tempo_dis", "spatial_dis", "n_iter", "sr_optim", "tempo_optim", "spatial_optim", "sr_sched",
+             "tempo_sched", "spatial_sched", "tpgan_amd")
+
+
+def parse_args(argv=None):
+    ap = argparse.ArgumentParser(prog="python -m tpgan_amd.train", description="Train the temporally coherent upsampler.")
+    ap.add_argument("--lr", type=float, default=3e-4)
+    ap.add_argument("--resume", action="store_true", help="resume from --path_to_resume")
+    ap.add_argument("--path_to_resume", type=str, help="checkpoint file, or a directory with latest_checkpoint.txt")
+    ap.add_argument("--iters", type=int, default=80000)
+    ap.add_argument("--log_dir", type=str, default="./")
+    ap.add_argument("--ckpt_every", type=int, default=5000)
+    ap.add_argument("--in_node_feats", type=int, default=3)
+    ap.add_argument("--R", type=float, default=0.10, help="radius of the temporal discriminator's flow embedding")
+    ap.add_argument("--train_dataset_path", type=str, default="../../data/train_data_0.025_fine")
+    ap.add_argument("--train_sequence_num", type=int, default=20)
+    ap.add_argument("--sequence_length", type=int, default=200)
+    ap.add_argument("--batch_size", type=int, default=4)
+    ap.add_argument("--small_batch", action="store_true")
+    ap.add_argument("--w", type=float, default=0.5, help="weight of the position loss")
+    ap.add_argument("--cutoff", type=float, default=0.025, help="cutoff distance of the masking loss")
+    ap.add_argument("--use_vel", action="store_true")
+    ap.add_argument("--freeze_D", action="store_true")
+    # not in the reference
+    ap.add_argument("--seed", type=int, default=1)
+    ap.add_argument("--amp", choices=("bf16", "none"), default="bf16")
+    ap.add_argument("--device", type=str, default="cuda")
+    ap.add_argument("--log_every", type=int, default=100)
+    ap.add_argument("--sample_num", type=int, default=None,
+                    help="patch size (default, as the reference: 9216 if batch_size <= 4 and not --small_batch, else 4096)")
+    return ap.parse_args(argv)
+
+
+def _rng_state(device, sampler_state):
+    """Everything a bit-exact resume needs beyond the reference's ten keys, in types torch.load(weights_only=True) takes."""
+    kind, keys, pos, has_gauss, gauss = np.random.get_state()
+    st = {"sampler_generator": sampler_state, "torch_rng": torch.get_rng_state(),
+          "numpy_rng": {"kind": kind, "keys": torch.from_numpy(keys.astype(np.int64)), "pos": int(pos),
+                        "has_gauss": int(has_gauss), "cached_gaussian": float(gauss)}}
+    if device.type == "cuda":
+        st["device_rng"] = torch.cuda.get_rng_state(device)
+    return st
+
+
+def _set_rng_state(st, device, generator):
+    generator.set_state(st["sampler_generator"])
+    torch.set_rng_state(st["torch_rng"])
+    n = st["numpy_rng"]
+    np.random.set_state((n["kind"], n["keys"].numpy().astype(np.uint32), n["pos"], n["has_gauss"], n["cached_gaussian"]))
+    if device.type == "cuda" and "device_rng" in st:
+        torch.cuda.set_rng_state(st["device_rng"], device)
+
+
+def save_checkpoint(state, path):
+    """torch.save + the newest name on top of latest_checkpoint.txt beside it (utils.py:7-30)."""
+    torch.save(state, path)
+    listing = os.path.join(os.path.dirname(path), "latest_checkpoint.txt")
+    old = open(listing).readlines() if os.path.exists(listing) else []
+    with open(listing, "w") as f:
+        f.writelines([os.path.basename(path) + "\n"] + old)
+
+
+def load_checkpoint(path):
+    if os.path.isdir(path):
+        with open(os.path.join(path, "latest_checkpoint.txt")) as f:
+            path = os.path.join(path, f.readline().strip())
+    return torch.load(path, map_location="cpu", weights_only=True)
+
+
+def main(argv=None):
+    opt = parse_args(argv)
+    rank, world, local = ddp.init_from_env(backend=os.environ.get("TPGAN_DDP_BACKEND"))
+    dev = torch.device(opt.device)
+    if dev.type == "cuda":
+        torch.backends.cudnn.enabled = False         # hipBLASLt GEMMs + native BatchNorm, as bench.py and the tests
+        if dev.index is None:
+            dev = torch.device("cuda", local)
+        torch.cuda.set_device(dev)
+    np.random.seed(opt.seed + 1000 * rank)
+    torch.manual_seed(opt.seed)                      # same initial weights on every rank; broadcast below anyway
+
+    sr_net = SRNet(opt.in_node_feats, 128).to(dev)
+    tempo_dis = FluidTempoDis(3).to(dev)
+    spatial_dis = FluidSpatialDis().to(dev)
+    sr_optim = torch.optim.Adam(sr_net.parameters(), lr=opt.lr)
+    tempo_optim = torch.optim.Adam(tempo_dis.parameters(), lr=0.33 * opt.lr)
+    spatial_optim = torch.optim.Adam(spatial_dis.parameters(), lr=0.33 * opt.lr)
+    scheds = [torch.optim.lr_scheduler.StepLR(o, 10000, gamma=0.7) for o in (sr_optim, tempo_optim, spatial_optim)]
+    sync = ddp.GradSync()
+    sync.broadcast_state(sr_net, tempo_dis, spatial_dis)
+    torch.manual_seed(opt.seed + 1000 * rank)
+
+    sequences = FluidSequences(opt.train_dataset_path, opt.train_sequence_num, opt.sequence_length, device=dev)
+    sample_num = opt.sample_num or (9216 if opt.batch_size <= 4 and not opt.small_batch else 4096)
+    generator = torch.Generator().manual_seed(opt.seed + 1000 * rank)
+    sampler = ClipSampler(sequences, opt.batch_size, sample_num, generator=generator)
+
+    n_iter = 0
+    if opt.resume:
+        ckpt = load_checkpoint(opt.path_to_resume)
+        sr_net.load_state_dict(ckpt["sr_net"])
+        tempo_dis.load_state_dict(ckpt["tempo_dis"])
+        spatial_dis.load_state_dict(ckpt["spatial_dis"])
+        sr_optim.load_state_dict(ckpt["sr_optim"])
+        tempo_optim.load_state_dict(ckpt["tempo_optim"])
+        spatial_optim.load_state_dict(ckpt["spatial_optim"])
+        for s, k in zip(scheds, ("sr_sched", "tempo_sched", "spatial_sched")):
+            s.load_state_dict(ckpt[k])
+        n_iter = int(ckpt["n_iter"])
+        if "tpgan_amd" in ckpt and world == 1:       # (the file holds rank 0's streams; other ranks keep their seeds)
+            _set_rng_state(ckpt["tpgan_amd"], dev, generator)
+
+    ckpt_dir = os.path.join(opt.log_dir, "model_ckpt")
+    if rank == 0:
+        os.makedirs(ckpt_dir, exist_ok=True)
+    amp_dtype = torch.bfloat16 if opt.amp == "bf16" else None
+    batches = prefetch(sampler)
+    sr_net.train(), tempo_dis.train(), spatial_dis.train()
+    window_start, window_iters = time.time(), 0
+    while n_iter < opt.iters:
+        data = next(batches)
+        high_pos, high_vel, low_pos, low_vel = list(data[0:3]), list(data[3:6]), list(data[6:9]), list(data[9:12])
+        n_iter += 1
+        losses = tempo_gan_step(sr_net, spatial_dis, tempo_dis, low_pos, low_vel, high_pos, high_vel, 1., opt, n_iter,
+                                sr_optim, tempo_optim, spatial_optim, freeze_D=opt.freeze_D, sync=sync,
+                                amp_dtype=amp_dtype)
+        for s in scheds:
+            s.step()
+        window_iters += 1
+        if rank == 0 and (n_iter % opt.log_every == 0 or n_iter >= opt.iters):
+            if dev.type == "cuda":
+                torch.cuda.synchronize(dev)
+            now = time.time()
+            print(json.dumps({"n_iter": n_iter, "steps_per_s": window_iters / max(now - window_start, 1e-9),
+                              **{k: float(v) for k, v in losses.items()}}), flush=True)
+            window_start, window_iters = now, 0
+        if rank == 0 and ((n_iter - 1) % opt.ckpt_every == 0 or n_iter >= opt.iters):
+            save_checkpoint({
+                "sr_net": sr_net.state_dict(), "tempo_dis": tempo_dis.state_dict(),
+                "spatial_dis": spatial_dis.state_dict(), "n_iter": n_iter,
+                "sr_optim": sr_optim.state_dict(), "tempo_optim": tempo_optim.state_dict(),
+                "spatial_optim": spatial_optim.state_dict(),
+                "sr_sched": scheds[0].state_dict(), "tempo_sched": scheds[1].state_dict(),
+                "spatial_sched": scheds[2].state_dict(),
+                "tpgan_amd": _rng_state(dev, batches.resume_state),
+            }, os.path.join(ckpt_dir, f"tpugan_checkpoint{n_iter}.ckpt"))
+    ddp.barrier()
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())
