@@ -32,9 +32,12 @@ def knn_points(p1, p2, lengths1=None, lengths2=None, K=1, version=-1, return_nn=
     if p1.shape[2] != p2.shape[2]:
         raise ValueError("pts1 and pts2 must have the same point dimension.")
     dists, idx = _ops.neighbour_search(p1, p2, K, lengths1, lengths2, r=None)
-    dists = _ops.attach_dist_grad(p1, p2, dists, idx)
+    dists = _ops.attach_dist_grad(p1, p2, dists, idx, lengths1, lengths2)
     nn = None
     if return_nn:
-        l2 = lengths2 if lengths2 is None else torch.as_tensor(lengths2, device=p1.device)
+        if lengths2 is None:            # (upstream's default: every cloud full -- K > P2 still leaves empty slots)
+            l2 = torch.full((p2.shape[0],), p2.shape[1], dtype=torch.int64, device=p1.device)
+        else:
+            l2 = torch.as_tensor(lengths2, device=p1.device)
         nn = knn_gather(p2, idx, l2)
     return _KNN(dists=dists, idx=idx, knn=nn)

@@ -1404,16 +1404,15 @@ class _KnnDists(torch.autograd.Function):
     """Attaches the analytic gradient of squared distances to searched dists."""
 
     @staticmethod
-    def forward(ctx, p1, p2, dists, idx):
-        ctx.save_for_backward(p1, p2, idx)
+    def forward(ctx, p1, p2, dists, idx, valid):
+        ctx.save_for_backward(p1, p2, idx, valid)
         return dists.clone()
 
     @staticmethod
     def backward(ctx, g):
-        p1, p2, idx = ctx.saved_tensors
+        p1, p2, idx, valid = ctx.saved_tensors
         B, P1, K = idx.shape
         D = p1.shape[2]
-        valid = (idx >= 0)
         safe = idx.clamp(min=0)
         nb = torch.gather(p2.unsqueeze(1).expand(B, P1, p2.shape[1], D), 2,
                           safe.unsqueeze(-1).expand(B, P1, K, D))
@@ -1421,12 +1420,25 @@ class _KnnDists(torch.autograd.Function):
         g1 = diff.sum(2)
         g2 = torch.zeros_like(p2)
         g2.scatter_add_(1, safe.reshape(B, P1 * K, 1).expand(B, P1 * K, D), -diff.reshape(B, P1 * K, D))
-        return g1, g2, None, None
+        return g1, g2, None, None, None
 
 
-def attach_dist_grad(p1, p2, dists, idx):
+def attach_dist_grad(p1, p2, dists, idx, lengths1=None, lengths2=None):
+    """dists (B,P1,K) of a search of p1 in p2 -> the same values with the gradient of |p1 - p2[idx]|^2 attached.
+    A slot the search did not fill is a constant and takes no gradient: the -1 / -1 slots of a radius search, and
+    the 0 / 0 slots of a kNN search (include/tpgan_ops.h: k >= the cloud's length, rows beyond lengths1) -- those
+    cannot be told from a hit by their index, so pass the lengths the search was given."""
     if torch.is_grad_enabled() and (p1.requires_grad or p2.requires_grad):
-        return _KnnDists.apply(p1.float(), p2.float(), dists, idx)
+        B, P1, K = idx.shape
+        valid = idx >= 0
+        if lengths2 is not None or K > p2.shape[1]:
+            n2 = (torch.full((B,), p2.shape[1], device=idx.device) if lengths2 is None
+                  else torch.as_tensor(lengths2, device=idx.device))
+            valid = valid & (torch.arange(K, device=idx.device)[None, None, :] < n2[:, None, None])
+        if lengths1 is not None:
+            n1 = torch.as_tensor(lengths1, device=idx.device)
+            valid = valid & (torch.arange(P1, device=idx.device)[None, :, None] < n1[:, None, None])
+        return _KnnDists.apply(p1.float(), p2.float(), dists, idx, valid)
     return dists
 
 

@@ -397,18 +397,28 @@ def test_out_of_range_indices_never_fault(hip):
 
 # ------------------------------------------------------------------ three_nn / interpolate
 def test_three_nn_and_interpolate(hip):
+    _three_nn_and_interpolate(hip, 2, 300, 500, 6)
+
+
+# n and m off the block sizes, the smallest legal m (every known point is a neighbour), one channel, an odd batch
+@pytest.mark.parametrize("B,n,m,C", [(3, 257, 777, 1), (2, 1000, 3, 6), (1, 513, 255, 1), (3, 1, 3, 1), (3, 4099, 1023, 5)])
+def test_three_nn_and_interpolate_shapes(hip, B, n, m, C):
+    _three_nn_and_interpolate(hip, B, n, m, C)
+
+
+def _three_nn_and_interpolate(hip, B, n, m, C):
     rng = np.random.default_rng(6)
-    u, k = fluid(rng, 2, 300), fluid(rng, 2, 500)
+    u, k = fluid(rng, B, n), fluid(rng, B, m)
     d2, idx = hip.three_nn(dev(u), dev(k))
     rd, ri = R.three_nn(u, k)
     assert np.array_equal(idx.cpu().numpy(), ri) and np.array_equal(d2.cpu().numpy(), rd)
-    f = rng.standard_normal((2, 6, 500)).astype(np.float32)
-    w = rng.uniform(0, 1, (2, 300, 3)).astype(np.float32)
+    f = rng.standard_normal((B, C, m)).astype(np.float32)
+    w = rng.uniform(0, 1, (B, n, 3)).astype(np.float32)
     out = hip.three_interp_fwd(dev(f), idx, dev(w)).cpu().numpy()
     assert np.array_equal(out, R.three_interp_fwd(f, ri, w))
     g = rng.standard_normal(out.shape).astype(np.float32)
-    ref = R.three_interp_bwd(g, ri, w, 500)
-    got = hip.three_interp_bwd(dev(g), idx, dev(w), 500).cpu().numpy()
+    ref = R.three_interp_bwd(g, ri, w, m)
+    got = hip.three_interp_bwd(dev(g), idx, dev(w), m).cpu().numpy()
     assert np.abs(got - ref).max() <= TOL * max(1.0, np.abs(ref).max())
 
 
