@@ -369,13 +369,7 @@ extern "C" int tpg_patch_select_f32(const float *points, long long P, const int3
     while (n2 < K) n2 <<= 1;
     const size_t smem = (size_t)n2 * sizeof(tpg_u64);
     hipStream_t st = tpg_stream(stream);
-    static bool raised = false;                          // (idempotent; a race would only set it twice)
-    if (!raised) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void *>(sel_sort_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)(TPG_PATCH_SELECT_MAX_K * sizeof(tpg_u64))) != hipSuccess)
-            return TPG_ERR_UNSUPPORTED;
-        raised = true;
-    }
+    if (!tpg_allow_dynamic_lds<&sel_sort_kernel>((int)(TPG_PATCH_SELECT_MAX_K * sizeof(tpg_u64)))) return TPG_ERR_UNSUPPORTED;
     const int chunks = sel_chunks(max_count);
     // histograms, slot counters (and the rest of the head) start at zero
     if (hipMemsetAsync(ws, 0, (size_t)B * sel_scene_bytes(chunks, K), st) != hipSuccess) return TPG_ERR_LAUNCH;

@@ -25,12 +25,6 @@ namespace {
 constexpr int CI_WAVES = 4;
 constexpr int CI_K = 32;
 
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
-
 // gcn_lib/interpolation.py:94-104, evaluated in fp32 in the reference's operation order
 __device__ __forceinline__ float bicubic_w(float r, float cutoff, float coeff) {
     const float q = r / cutoff;
@@ -76,11 +70,11 @@ __global__ __launch_bounds__(CI_WAVES * 64) void cubic_interp_kernel(
         w = bicubic_w(sqrtf(d2), cutoff, coeff);
     }
     const float wp = lane < 4 ? 2.0f * w : w;            // padding edges duplicate the 4 nearest hits
-    const float den = wave_sum(w), denp = wave_sum(wp);
+    const float den = tpg_wave_sum(w), denp = tpg_wave_sum(wp);
     const float *fb = field + (size_t)b * Np * F;
     for (int f = 0; f < F; ++f) {
         const float v = has ? fb[(size_t)j * F + f] : 0.0f;
-        const float num = wave_sum(w * v), nump = wave_sum(wp * v);
+        const float num = tpg_wave_sum(w * v), nump = tpg_wave_sum(wp * v);
         if (lane == 0) {
             out_plain[q * F + f] = num / (den + 1e-6f);
             out_pad[q * F + f] = nump / (denp + 1e-6f);

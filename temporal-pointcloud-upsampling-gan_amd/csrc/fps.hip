@@ -514,17 +514,10 @@ void fps_go(const float *xyz, int B, int N, int m, int32_t *idx, const int32_t *
 #endif
     size_t smem = 256 + 512 + (use_lds ? sizeof(float) * 3 * (size_t)N : 0);
     if (smem > 48 * 1024) {
-        // opt in to > 48 KiB of dynamic LDS once per instantiation (not a stream operation, so
-        // it must not happen inside a captured launch sequence): request the maximum this
-        // instantiation can ever need.
-        static int granted = -1;
-        if (granted < 0) {
-            const int want = 256 + 512 + (int)sizeof(float) * 3 * FPS_LDS_POINTS;
-            granted = hipFuncSetAttribute(reinterpret_cast<const void *>(&fps_kernel<BLOCK, PPT, true>),
-                                          hipFuncAttributeMaxDynamicSharedMemorySize, want) == hipSuccess;
-            if (!granted) (void)hipGetLastError();
-        }
-        if (!granted) {
+        // opt in to > 48 KiB of dynamic LDS (tpg_allow_dynamic_lds: once per instantiation and device, in warm-up,
+        // never inside a captured launch sequence): request the maximum this instantiation can ever need.
+        const int want = 256 + 512 + (int)sizeof(float) * 3 * FPS_LDS_POINTS;
+        if (!tpg_allow_dynamic_lds<&fps_kernel<BLOCK, PPT, true>>(want)) {
             use_lds = 0;  // read the selected point from L2 instead
             smem = 256 + 512;
         }
@@ -543,18 +536,13 @@ int fps_pruned_go(const float *xyz, int B, int N, int m, int32_t *idx, const int
     const int use_lds = N <= FPP_LDS_POINTS;
     const size_t fixed = sizeof(float) * (64 + 128 + 128) + sizeof(int) * (FPP_CELLS + 2 + 32 + (size_t)BLOCK * 16);
     const size_t smem = fixed + (use_lds ? sizeof(float) * 3 * (size_t)N : 0);
-    // > 48 KiB of dynamic LDS: opt in once per kernel (not a stream operation), with the most that kernel can need
-    static int granted[2] = {-1, -1};
-    if (granted[use_lds] < 0) {
-        const void *fn = use_lds ? reinterpret_cast<const void *>(&fps_pruned_kernel<BLOCK, true>)
-                                 : reinterpret_cast<const void *>(&fps_pruned_kernel<BLOCK, false>);
-        const int cap = BLOCK * 16 < FPP_LDS_POINTS ? BLOCK * 16 : FPP_LDS_POINTS;
-        const int want = (int)(fixed + (use_lds ? sizeof(float) * 3 * (size_t)cap : 0));
-        granted[use_lds] = want <= 160 * 1024 &&
-                           hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, want) == hipSuccess;
-        if (!granted[use_lds]) (void)hipGetLastError();
-    }
-    if (!granted[use_lds]) return 0;
+    // > 48 KiB of dynamic LDS: opt in (tpg_allow_dynamic_lds, outside any capture) with the most that kernel can need
+    const int cap = BLOCK * 16 < FPP_LDS_POINTS ? BLOCK * 16 : FPP_LDS_POINTS;
+    const int want = (int)(fixed + (use_lds ? sizeof(float) * 3 * (size_t)cap : 0));
+    if (want > 160 * 1024) return 0;
+    if (!(use_lds ? tpg_allow_dynamic_lds<&fps_pruned_kernel<BLOCK, true>>(want)
+                  : tpg_allow_dynamic_lds<&fps_pruned_kernel<BLOCK, false>>(want)))
+        return 0;
     if (use_lds)
         hipLaunchKernelGGL((fps_pruned_kernel<BLOCK, true>), dim3(B), dim3(BLOCK), smem, st, xyz, N, m, idx, start,
                            skip_origin, pin, pout);

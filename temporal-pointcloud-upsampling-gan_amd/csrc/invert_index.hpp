@@ -255,13 +255,7 @@ template <typename IdxT>
 inline int launch(const IdxT *idx, int B, int N, int SK, int32_t *offs, int32_t *list, int32_t *tmp, hipStream_t st) {
     const Plan p = plan(N, SK);
     if (p.passes > 1 && !tmp) return TPG_ERR_ARG;
-    static bool raised = false;                 // (idempotent; a race would only set it twice)
-    if (!raised) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void *>(invert_index_kernel<IdxT>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, kMaxLdsBytes) != hipSuccess)
-            return TPG_ERR_UNSUPPORTED;
-        raised = true;
-    }
+    if (!tpg_allow_dynamic_lds<&invert_index_kernel<IdxT>>(kMaxLdsBytes)) return TPG_ERR_UNSUPPORTED;
     hipLaunchKernelGGL((invert_index_kernel<IdxT>), dim3(B), dim3(kThreads), p.smem, st, idx, N, SK, p.bits, p.passes,
                        p.ebits, p.pack, p.use_cnt, offs, list, tmp);
     return TPG_OK;

@@ -288,13 +288,7 @@ __global__ __launch_bounds__(KNN_WAVES * 64) void knn_redo_kernel(
 template <int D_T, int M>
 int knn_mfma_launch_m(const float *p1, const float *p2, const int64_t *len1, const int64_t *len2, int B, int P1, int P2,
                       int K, float *dist, int64_t *idx, bool redo, hipStream_t st) {
-    static bool attr_set = false;
-    if (!attr_set) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void *>(&knn_mfma_kernel<D_T, M>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)km_smem_bytes<D_T>()) != hipSuccess)
-            return TPG_ERR_LAUNCH;
-        attr_set = true;
-    }
+    if (!tpg_allow_dynamic_lds<&knn_mfma_kernel<D_T, M>>((int)km_smem_bytes<D_T>())) return TPG_ERR_LAUNCH;
     const int gx = (P1 + KM_Q - 1) / KM_Q;
     const long long total = (long long)gx * B;
     if (total > (1ll << 30)) return TPG_ERR_ARG;

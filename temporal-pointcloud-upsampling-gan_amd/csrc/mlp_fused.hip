@@ -17,7 +17,7 @@
 //             mean / sigma ratio) are accumulated from the ROUNDED values -- the statistics of the
 //             tensor the next stage reads.
 // A small finalize launch turns the per-workgroup partials into mean / rstd (+ running statistics,
-// batch counter) exactly like rowbn_stats_finalize_kernel.  What this replaces per layer:
+// batch counter) with the shared pieces of csrc/tpg_bn_finalize.hpp, as rowbn.hip's does.  What this replaces per layer:
 // rowbn_apply (read + write of x_l), the hipBLASLt GEMM (read x_l, write x_{l+1}) and rowbn_stats
 // (read x_{l+1}): 2 C_l + 1 C_{l+1} of the 3 C_l + 2 C_{l+1} tensor widths moved.
 //
@@ -28,28 +28,17 @@
 // Arithmetic intensity: 2*Cin*Cout flops per 2*(Cin+Cout) bytes = 43 flop/B at 64 -> 128,
 // 128 flop/B at 256 -> 256, against a ridge of ~310 flop/B (2.5 PFLOP/s / 8 TB/s): HBM-bound by
 // design; the MFMA pipe runs at 10-40 % while the rows stream.
-#include <hip/hip_bf16.h>
-
-#include "tpg_common.hpp"
+#include "tpg_bn_finalize.hpp"
+#include "tpg_rows.hpp"
 
 namespace {
 
 typedef __attribute__((ext_vector_type(8))) short bf16x8;   // one MFMA A / B fragment (4 VGPRs)
-typedef __attribute__((ext_vector_type(4))) float f32x4;    // one 16x16 accumulator tile (4 VGPRs)
 
 constexpr int ML_THREADS = 256;
 constexpr int ML_WAVES = ML_THREADS / 64;
 constexpr int ML_MAX_BLOCKS = 512;    // most workgroups (= partial rows) per segment
 constexpr int ML_WPAD = 8;            // bf16 elements of padding per LDS weight row (16 B)
-
-__device__ __forceinline__ unsigned pack_bf16x2(float lo, float hi) {
-    // round-to-nearest-even, NaN stays NaN: the compiler emits v_cvt_pk_bf16_f32
-    const __hip_bfloat16 a = __float2bfloat16(lo), b = __float2bfloat16(hi);
-    return (unsigned)(*reinterpret_cast<const unsigned short *>(&a)) |
-           ((unsigned)(*reinterpret_cast<const unsigned short *>(&b)) << 16);
-}
-__device__ __forceinline__ float bf16_lo(unsigned w) { return __uint_as_float(w << 16); }
-__device__ __forceinline__ float bf16_hi(unsigned w) { return __uint_as_float(w & 0xffff0000u); }
 
 // LDS row of weight row n (output channel n): tile-major so that the 16 lanes of a fragment read
 // read 16 CONSECUTIVE padded rows (conflict-free ds_read_b128)
@@ -88,8 +77,8 @@ __global__ __launch_bounds__(ML_THREADS, 2) void mlp_fwd_kernel(
             const int n = e / (CIN / 4), k = (e - n * (CIN / 4)) * 4;
             const float4 w4 = *reinterpret_cast<const float4 *>(Ws + (size_t)n * CIN + k);
             uint2 p;
-            p.x = pack_bf16x2(w4.x, w4.y);
-            p.y = pack_bf16x2(w4.z, w4.w);
+            p.x = tpg_pack_bf16x2(w4.x, w4.y);
+            p.y = tpg_pack_bf16x2(w4.z, w4.w);
             *reinterpret_cast<uint2 *>(wl + (size_t)w_lds_row<COUT>(n) * WROW + k) = p;
         }
         for (int c = tid; c < 2 * CIN; c += ML_THREADS)
@@ -120,11 +109,11 @@ __global__ __launch_bounds__(ML_THREADS, 2) void mlp_fwd_kernel(
     if (tile < ntiles) load_tile(tile);
     for (; tile < ntiles; tile += gridDim.x) {
         const long long row_base = tile * BM + (long long)wave * STRIPS * 16;
-        f32x4 acc[STRIPS][T];
+        tpg_f32x4 acc[STRIPS][T];
 #pragma unroll
         for (int st = 0; st < STRIPS; ++st)
 #pragma unroll
-            for (int t = 0; t < T; ++t) acc[st][t] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+            for (int t = 0; t < T; ++t) acc[st][t] = tpg_f32x4{0.0f, 0.0f, 0.0f, 0.0f};
         // k-step by k-step: BatchNorm + LeakyReLU on this step's A fragments (registers), then the
         // step's T column tiles -- one A fragment per strip and a few B fragments live at a time
 #pragma unroll
@@ -143,11 +132,11 @@ __global__ __launch_bounds__(ML_THREADS, 2) void mlp_fwd_kernel(
                 union { unsigned u[4]; bf16x8 v; } cv;
 #pragma unroll
                 for (int i = 0; i < 4; ++i) {
-                    float a = __builtin_fmaf(bf16_lo(w[i]), sc[2 * i], sh[2 * i]);
-                    float b = __builtin_fmaf(bf16_hi(w[i]), sc[2 * i + 1], sh[2 * i + 1]);
+                    float a = __builtin_fmaf(tpg_bf16_lo(w[i]), sc[2 * i], sh[2 * i]);
+                    float b = __builtin_fmaf(tpg_bf16_hi(w[i]), sc[2 * i + 1], sh[2 * i + 1]);
                     a = fmaxf(a, a * slope);            // LeakyReLU for 0 <= slope <= 1
                     b = fmaxf(b, b * slope);
-                    cv.u[i] = pack_bf16x2(a, b);
+                    cv.u[i] = tpg_pack_bf16x2(a, b);
                 }
                 afrag[st] = cv.v;
             }
@@ -171,7 +160,7 @@ __global__ __launch_bounds__(ML_THREADS, 2) void mlp_fwd_kernel(
             // register 0), rounded like the stored value
 #pragma unroll
             for (int t = 0; t < T; ++t) {
-                const float v = bf16_lo(pack_bf16x2(acc[0][t][0], 0.0f));
+                const float v = tpg_bf16_lo(tpg_pack_bf16x2(acc[0][t][0], 0.0f));
                 piv[t] = __shfl(v, li, 64);
             }
             have_piv = true;
@@ -185,10 +174,10 @@ __global__ __launch_bounds__(ML_THREADS, 2) void mlp_fwd_kernel(
                 unsigned o[T / 2];
 #pragma unroll
                 for (int t = 0; t < T; t += 2) {
-                    const unsigned w = pack_bf16x2(acc[st][t][r], acc[st][t + 1][r]);
+                    const unsigned w = tpg_pack_bf16x2(acc[st][t][r], acc[st][t + 1][r]);
                     o[t / 2] = w;
-                    const float d0 = valid ? bf16_lo(w) - piv[t] : 0.0f;
-                    const float d1 = valid ? bf16_hi(w) - piv[t + 1] : 0.0f;
+                    const float d0 = valid ? tpg_bf16_lo(w) - piv[t] : 0.0f;
+                    const float d1 = valid ? tpg_bf16_hi(w) - piv[t + 1] : 0.0f;
                     s1[t] += d0;
                     s1[t + 1] += d1;
                     s2[t] = __builtin_fmaf(d0, d0, s2[t]);
@@ -252,60 +241,36 @@ __global__ __launch_bounds__(ML_THREADS, 2) void mlp_fwd_kernel(
 // counter, as nn.BatchNorm's forward does); grid = ceil(C / 4), 64 lanes per channel over the
 // partials, fp64, fixed order -> bitwise reproducible.  ss_next (nseg, 2, C), optional: scale | shift
 // of THIS BatchNorm (gamma * rstd | beta - mean * gamma * rstd) for the consumer's prologue.
-constexpr int MF_CH = 4;
-__device__ __forceinline__ double mf_wave_sum(double v) {
-#pragma unroll
-    for (int m = 32; m > 0; m >>= 1) v += __shfl_xor(v, m, 64);      // fixed butterfly: every lane ends with the same bits
-    return v;
-}
+using tpg_bn::FIN_CH;
+using tpg_bn::FIN_THREADS;
+using tpg_bn::FIN_R;         // here also: partials a lane keeps in registers between the two passes
 
-// The segments of a launch are independent except for the running statistics, and a segment has few partials
-// (segments x partials <= the resident workgroups of the producing launch), so a wave's lanes are split into GROUPS,
-// one per segment: SP = segments per sweep (a power of two), L = 64 / SP lanes per segment.
-struct MfSplit { int SP, L; };
-__device__ __forceinline__ MfSplit mf_split(int nseg) {
-    int sp = 1;
-    while (sp < nseg && sp < 64) sp <<= 1;
-    return {sp, 64 / sp};
-}
-__device__ __forceinline__ double mf_group_sum(double v, int L) {
-    for (int m = L >> 1; m > 0; m >>= 1) v += __shfl_xor(v, m, 64);      // fixed butterfly inside the group
-    return v;
-}
-__device__ __forceinline__ double mf_readlane(double v, int l) {          // l wave-uniform
-    const long long b = __double_as_longlong(v);
-    const int lo = __builtin_amdgcn_readlane((int)(unsigned)(b & 0xffffffffll), l);
-    const int hi = __builtin_amdgcn_readlane((int)(b >> 32), l);
-    return __longlong_as_double(((long long)hi << 32) | (long long)(unsigned)lo);
-}
-constexpr int MF_R = 8;      // partials a lane keeps in registers between the two passes
-
-// One WAVE per channel (MF_CH = 4 channels per workgroup), no LDS and no barrier.  All segments of a sweep are
-// reduced side by side (a lane group each): the launch waits for memory twice per sweep, not twice per segment
+// One WAVE per channel (FIN_CH = 4 channels per workgroup), no LDS and no barrier.  All segments of a sweep are reduced
+// side by side (a lane group each, tpg_bn::split): the launch waits for memory twice per sweep, not twice per segment
 // (segment after segment it was 2 x 16 dependent round trips at cfg4 = 20 us per launch, 42 launches per step).
 // Only the running statistics walk the segments in call order, from registers.
-__global__ __launch_bounds__(ML_THREADS) void mlp_stats_finalize_kernel(
+__global__ __launch_bounds__(FIN_THREADS) void mlp_stats_finalize_kernel(
     const float *__restrict__ part, int G, int C, int nseg, float eps, float momentum,
     float *__restrict__ running_mean, float *__restrict__ running_var, long long *__restrict__ num_batches_tracked,
     const float *__restrict__ mean_shift, const float *__restrict__ gamma, const float *__restrict__ beta,
     float *__restrict__ mean, float *__restrict__ rstd, float *__restrict__ ci_out) {
     const int lane = threadIdx.x & 63;
-    const int c = blockIdx.x * MF_CH + (threadIdx.x >> 6);
+    const int c = blockIdx.x * FIN_CH + (threadIdx.x >> 6);
     if (num_batches_tracked && blockIdx.x == 0 && threadIdx.x == 0) *num_batches_tracked += nseg;
     if (c >= C) return;                              // whole wave
-    const MfSplit sp = mf_split(nseg);
+    const tpg_bn::Split sp = tpg_bn::split(nseg);
     const int grp = lane / sp.L, sub = lane - grp * sp.L;
-    const bool fits = G <= sp.L * MF_R;              // the partials of a segment fit its lanes' registers
+    const bool fits = G <= sp.L * FIN_R;              // the partials of a segment fit its lanes' registers
     float rmean = running_mean ? running_mean[c] : 0.0f, rvar = running_mean ? running_var[c] : 0.0f;
     const double shift = mean_shift ? (double)mean_shift[c] : 0.0;
     for (int seg0 = 0; seg0 < nseg; seg0 += sp.SP) {
         const int seg = seg0 + grp;
         const bool live = seg < nseg;
         const float *ps = part + (size_t)(live ? seg : nseg - 1) * G * 3 * C + c;
-        float pn[MF_R], pm[MF_R], pq[MF_R];
+        float pn[FIN_R], pm[FIN_R], pq[FIN_R];
         auto fetch = [&](int g0) {                   // unconditional, clamped: all requests of a block in flight
 #pragma unroll
-            for (int i = 0; i < MF_R; ++i) {
+            for (int i = 0; i < FIN_R; ++i) {
                 const int g = g0 + sub + i * sp.L;
                 const bool ok = live && g < G;
                 const float *pg = ps + (size_t)(ok ? g : 0) * 3 * C;
@@ -317,27 +282,27 @@ __global__ __launch_bounds__(ML_THREADS) void mlp_stats_finalize_kernel(
         };
         // pass 1: N and the weighted mean
         double n = 0.0, sm = 0.0;
-        for (int g0 = 0; g0 < G; g0 += sp.L * MF_R) {
+        for (int g0 = 0; g0 < G; g0 += sp.L * FIN_R) {
             fetch(g0);
 #pragma unroll
-            for (int i = 0; i < MF_R; ++i) {
+            for (int i = 0; i < FIN_R; ++i) {
                 n += (double)pn[i];
                 sm += (double)pn[i] * (double)pm[i];
             }
         }
-        const double N = mf_group_sum(n, sp.L);
-        const double m = N > 0.0 ? mf_group_sum(sm, sp.L) / N : 0.0;
+        const double N = tpg_bn::group_sum(n, sp.L);
+        const double m = N > 0.0 ? tpg_bn::group_sum(sm, sp.L) / N : 0.0;
         // pass 2: M2 = sum M2_g + n_g (mean_g - mean)^2
         double q = 0.0;
-        for (int g0 = 0; g0 < G; g0 += sp.L * MF_R) {
+        for (int g0 = 0; g0 < G; g0 += sp.L * FIN_R) {
             if (!fits) fetch(g0);
 #pragma unroll
-            for (int i = 0; i < MF_R; ++i) {
+            for (int i = 0; i < FIN_R; ++i) {
                 const double d = (double)pm[i] - m;
                 q += pn[i] > 0.0f ? (double)pq[i] + (double)pn[i] * d * d : 0.0;
             }
         }
-        double var = N > 0.0 ? mf_group_sum(q, sp.L) / N : 0.0;          // biased
+        double var = N > 0.0 ? tpg_bn::group_sum(q, sp.L) / N : 0.0;          // biased
         var = var < 0.0 ? 0.0 : var;
         const float mu = (float)m, rs = (float)(1.0 / sqrt(var + (double)eps));
         if (live && sub == 0) {
@@ -345,14 +310,13 @@ __global__ __launch_bounds__(ML_THREADS) void mlp_stats_finalize_kernel(
             if (rstd) rstd[(size_t)seg * C + c] = rs;
             if (ci_out) {
                 const float a = (gamma ? gamma[c] : 1.0f) * rs;
-                float *o = ci_out + (size_t)seg * 4 * C + c;
-                o[0] = a; o[C] = (beta ? beta[c] : 0.0f) - mu * a; o[2 * C] = mu; o[3 * C] = rs;
+                tpg_bn::write_ci(ci_out + (size_t)seg * 4 * C + c, C, a, beta ? beta[c] : 0.0f, mu, rs);
             }
         }
         if (running_mean) {                          // in call order: the running statistics chain
             const int last = nseg - seg0 < sp.SP ? nseg - seg0 : sp.SP;
             for (int k = 0; k < last; ++k) {
-                const double Nk = mf_readlane(N, k * sp.L), mk = mf_readlane(m, k * sp.L), vk = mf_readlane(var, k * sp.L);
+                const double Nk = tpg_bn::readlane(N, k * sp.L), mk = tpg_bn::readlane(m, k * sp.L), vk = tpg_bn::readlane(var, k * sp.L);
                 const double unbiased = Nk > 1.0 ? vk * Nk / (Nk - 1.0) : vk;
                 rmean = (float)((1.0 - momentum) * rmean + momentum * (mk + shift));
                 rvar = (float)((1.0 - momentum) * rvar + momentum * unbiased);
@@ -399,8 +363,8 @@ __device__ __forceinline__ void d_out8(const uint4 xr, const uint4 gr, const uin
 #pragma unroll
         for (int h = 0; h < 2; ++h) {
             const int j = 2 * i + h;
-            const float x = h ? bf16_hi(xw[i]) : bf16_lo(xw[i]);
-            const float g = h ? bf16_hi(gw[i]) : bf16_lo(gw[i]);
+            const float x = h ? tpg_bf16_hi(xw[i]) : tpg_bf16_lo(xw[i]);
+            const float g = h ? tpg_bf16_hi(gw[i]) : tpg_bf16_lo(gw[i]);
             const float c = __builtin_fmaf(-f[j], x, fm[j]);          // -f * (x - mu)
             if (MODE == MODE_MAX) {
                 const int ak = (int)__builtin_amdgcn_ubfe(j < 4 ? ar.x : ar.y, 8 * (j & 3), 8);
@@ -409,7 +373,7 @@ __device__ __forceinline__ void d_out8(const uint4 xr, const uint4 gr, const uin
                 v[h] = __builtin_fmaf(a[j], g, c);
             }
         }
-        o[i] = pack_bf16x2(v[0], v[1]);
+        o[i] = tpg_pack_bf16x2(v[0], v[1]);
     }
 }
 
@@ -432,10 +396,10 @@ __global__ void mlp_max_prep_kernel(const __hip_bfloat16 *__restrict__ g, const 
         unsigned o[4];
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
-            const float g0 = bf16_lo(gw[q]), g1 = bf16_hi(gw[q]);
-            const float v0 = av[2 * q] * (bf16_lo(yw[q]) > 0.0f ? g0 : g0 * slope);
-            const float v1 = av[2 * q + 1] * (bf16_hi(yw[q]) > 0.0f ? g1 : g1 * slope);
-            o[q] = pack_bf16x2(v0, v1);
+            const float g0 = tpg_bf16_lo(gw[q]), g1 = tpg_bf16_hi(gw[q]);
+            const float v0 = av[2 * q] * (tpg_bf16_lo(yw[q]) > 0.0f ? g0 : g0 * slope);
+            const float v1 = av[2 * q + 1] * (tpg_bf16_hi(yw[q]) > 0.0f ? g1 : g1 * slope);
+            o[q] = tpg_pack_bf16x2(v0, v1);
         }
         *reinterpret_cast<uint4 *>(ag + off) = make_uint4(o[0], o[1], o[2], o[3]);
     }
@@ -477,10 +441,7 @@ __global__ __launch_bounds__(ML_THREADS, OCC) void mlp_dgrad_kernel(
             const float4 w4 = *reinterpret_cast<const float4 *>(Ws + (size_t)n * CIN + k);
             const float wv[4] = {w4.x, w4.y, w4.z, w4.w};
 #pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                const __hip_bfloat16 b = __float2bfloat16(wv[i]);
-                wl[(size_t)w_lds_row<CIN>(k + i) * WROW + n] = *reinterpret_cast<const unsigned short *>(&b);
-            }
+            for (int i = 0; i < 4; ++i) wl[(size_t)w_lds_row<CIN>(k + i) * WROW + n] = tpg_bf16_bits(wv[i]);
         }
         const float *cb = cbo + (size_t)seg * 4 * COUT;
         for (int c = tid; c < COUT; c += ML_THREADS) {
@@ -602,11 +563,11 @@ __global__ __launch_bounds__(ML_THREADS, OCC) void mlp_dgrad_kernel(
                     }
                 }
         };
-        f32x4 acc[STRIPS][TI];
+        tpg_f32x4 acc[STRIPS][TI];
 #pragma unroll
         for (int st = 0; st < STRIPS; ++st)
 #pragma unroll
-            for (int t = 0; t < TI; ++t) acc[st][t] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+            for (int t = 0; t < TI; ++t) acc[st][t] = tpg_f32x4{0.0f, 0.0f, 0.0f, 0.0f};
 #pragma unroll
         for (int s = 0; s < KS; ++s) {
             float ca[8], cf[8], cfm[8];
@@ -647,11 +608,11 @@ __global__ __launch_bounds__(ML_THREADS, OCC) void mlp_dgrad_kernel(
                 unsigned o[TI / 2];
 #pragma unroll
                 for (int t = 0; t < TI; t += 2) {
-                    const float x0 = bf16_lo(xin[st][r][t / 2]), x1 = bf16_hi(xin[st][r][t / 2]);
+                    const float x0 = tpg_bf16_lo(xin[st][r][t / 2]), x1 = tpg_bf16_hi(xin[st][r][t / 2]);
                     const float z0 = __builtin_fmaf(x0, sc[t], sh[t]), z1 = __builtin_fmaf(x1, sc[t + 1], sh[t + 1]);
                     const float g0 = (acc[st][t][r] + bi[t]) * (z0 > 0.0f ? vm : vm * slope_in);
                     const float g1 = (acc[st][t + 1][r] + bi[t + 1]) * (z1 > 0.0f ? vm : vm * slope_in);
-                    o[t / 2] = pack_bf16x2(g0, g1);
+                    o[t / 2] = tpg_pack_bf16x2(g0, g1);
                     sg[t] += g0;
                     sg[t + 1] += g1;
                     sgx[t] = __builtin_fmaf(g0, x0 - mu[t], sgx[t]);
@@ -727,7 +688,7 @@ __global__ __launch_bounds__(ML_THREADS, OCC) void mlp_dgrad_kernel(
 // partial sums of the data-gradient kernel (sum g | sum g (x - mu)) -> c12 (nseg,2,C) = (sum g / P |
 // rstd * sum g (x - mu) / P) per segment, dgamma = sum over segments of sum g xhat, dbeta = of sum g
 // (both optional); rstd of segment s at rstd + s*rstd_stride; cb (nseg,4,C), optional: see below; grid ceil(C/4)
-__global__ __launch_bounds__(ML_THREADS) void mlp_bwd_finalize_kernel(const float *__restrict__ part, int G, long long P,
+__global__ __launch_bounds__(FIN_THREADS) void mlp_bwd_finalize_kernel(const float *__restrict__ part, int G, long long P,
                                                                       int C, int nseg, const float *__restrict__ rstd,
                                                                       int rstd_stride, float *__restrict__ c12,
                                                                       float *__restrict__ dgamma,
@@ -736,9 +697,9 @@ __global__ __launch_bounds__(ML_THREADS) void mlp_bwd_finalize_kernel(const floa
                                                                       float *__restrict__ cb) {
     // one wave per channel, a lane group per segment (see mlp_stats_finalize_kernel)
     const int lane = threadIdx.x & 63;
-    const int c = blockIdx.x * MF_CH + (threadIdx.x >> 6);
+    const int c = blockIdx.x * FIN_CH + (threadIdx.x >> 6);
     if (c >= C) return;
-    const MfSplit sp = mf_split(nseg);
+    const tpg_bn::Split sp = tpg_bn::split(nseg);
     const int grp = lane / sp.L, sub = lane - grp * sp.L;
     double ts = 0.0, tsx = 0.0;
     for (int seg0 = 0; seg0 < nseg; seg0 += sp.SP) {
@@ -747,28 +708,12 @@ __global__ __launch_bounds__(ML_THREADS) void mlp_bwd_finalize_kernel(const floa
         const int segc = live ? seg : nseg - 1;
         const float *ps = part + (size_t)segc * G * 2 * C + c;
         const float rs = rstd[(size_t)segc * rstd_stride + c];
-        double a0 = 0.0, a1 = 0.0;
-        for (int g0 = 0; g0 < G; g0 += sp.L * MF_R) {
-            float v0[MF_R], v1[MF_R];
-#pragma unroll
-            for (int i = 0; i < MF_R; ++i) {         // unconditional, clamped: all requests of a block in flight
-                const int g = g0 + sub + i * sp.L;
-                const bool ok = live && g < G;
-                const float *pg = ps + (size_t)(ok ? g : 0) * 2 * C;
-                const float x0 = pg[0], x1 = pg[C];
-                v0[i] = ok ? x0 : 0.0f;
-                v1[i] = ok ? x1 : 0.0f;
-            }
-#pragma unroll
-            for (int i = 0; i < MF_R; ++i) {
-                a0 += (double)v0[i];
-                a1 += (double)v1[i];
-            }
-        }
-        const double s = mf_group_sum(a0, sp.L), sx = mf_group_sum(a1, sp.L) * (double)rs;
+        double s, sx;
+        tpg_bn::pair_sums(ps, C, sub, sp.L, G, live, s, sx);
+        sx *= (double)rs;
         const bool owner = live && sub == 0;
-        ts += mf_wave_sum(owner ? s : 0.0);          // fixed order over the segments of the sweep
-        tsx += mf_wave_sum(owner ? sx : 0.0);
+        ts += tpg_bn::wave_sum(owner ? s : 0.0);          // fixed order over the segments of the sweep
+        tsx += tpg_bn::wave_sum(owner ? sx : 0.0);
         if (owner) {
             const float c1 = (float)(s / (double)P), c2 = (float)(sx / (double)P);
             if (c12) {
@@ -779,9 +724,7 @@ __global__ __launch_bounds__(ML_THREADS) void mlp_bwd_finalize_kernel(const floa
                 // the folded constants of THIS BatchNorm's backward, for the kernels one layer down:
                 // a | f*mu | e | f  (ci = sc | sh | mu | rs of the same BatchNorm)
                 const float *ip = ci + (size_t)seg * 4 * C + c;
-                const float a = ip[0], mu = ip[2 * C], f = a * ip[3 * C] * c2;
-                float *o = cb + (size_t)seg * 4 * C + c;
-                o[0] = a; o[C] = f * mu; o[2 * C] = -a * c1; o[3 * C] = f;
+                tpg_bn::write_cb(cb + (size_t)seg * 4 * C + c, C, ip[0], ip[2 * C], ip[3 * C], c1, c2);
             }
         }
     }
@@ -803,16 +746,11 @@ __global__ void mlp_consts_kernel(const float *__restrict__ mean, const float *_
     const int seg = i / C, c = i - seg * C;
     const float mu = mean[i], rs = rstd[i];
     const float a = (gamma ? gamma[c] : 1.0f) * rs;
-    const float bz = (beta ? beta[c] : 0.0f) - mu * a;
-    if (ci) {
-        float *o = ci + (size_t)seg * 4 * C + c;
-        o[0] = a; o[C] = bz; o[2 * C] = mu; o[3 * C] = rs;
-    }
+    const float be = beta ? beta[c] : 0.0f;
+    if (ci) tpg_bn::write_ci(ci + (size_t)seg * 4 * C + c, C, a, be, mu, rs);
     if (cb) {
         const float c1 = c12[((size_t)seg * 2 + 0) * C + c], c2 = c12[((size_t)seg * 2 + 1) * C + c];
-        float *o = cb + (size_t)seg * 4 * C + c;
-        const float f = a * rs * c2;
-        o[0] = a; o[C] = f * mu; o[2 * C] = -a * c1; o[3 * C] = f;
+        tpg_bn::write_cb(cb + (size_t)seg * 4 * C + c, C, a, mu, rs, c1, c2);
     }
 }
 
@@ -877,11 +815,11 @@ __global__ __launch_bounds__(ML_THREADS, OCC) void mlp_wgrad_kernel(
     ld8(cbi + ((size_t)seg * 4 + 1) * CIN + 8 * ach, sh);
 #pragma unroll
     for (int i = 0; i < 8; ++i) asum[i] = 0.0f;
-    f32x4 acc[MT][NT];
+    tpg_f32x4 acc[MT][NT];
 #pragma unroll
     for (int m = 0; m < MT; ++m)
 #pragma unroll
-        for (int n = 0; n < NT; ++n) acc[m][n] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+        for (int n = 0; n < NT; ++n) acc[m][n] = tpg_f32x4{0.0f, 0.0f, 0.0f, 0.0f};
     const long long ntiles = (P + WG_ROWS - 1) / WG_ROWS;
     uint4 xr[DN], gr[DN], xi[AN];
     uint2 ar[DN];
@@ -925,13 +863,13 @@ __global__ __launch_bounds__(ML_THREADS, OCC) void mlp_wgrad_kernel(
             unsigned o[4];
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
-                float a = __builtin_fmaf(bf16_lo(xw[q]), sc[2 * q], sh[2 * q]);
-                float b = __builtin_fmaf(bf16_hi(xw[q]), sc[2 * q + 1], sh[2 * q + 1]);
+                float a = __builtin_fmaf(tpg_bf16_lo(xw[q]), sc[2 * q], sh[2 * q]);
+                float b = __builtin_fmaf(tpg_bf16_hi(xw[q]), sc[2 * q + 1], sh[2 * q + 1]);
                 a = fmaxf(a, a * slope_in);
                 b = fmaxf(b, b * slope_in);
-                o[q] = valid ? pack_bf16x2(a, b) : 0u;
-                asum[2 * q] += bf16_lo(o[q]);          // of the rounded operand the MFMA sees
-                asum[2 * q + 1] += bf16_hi(o[q]);
+                o[q] = valid ? tpg_pack_bf16x2(a, b) : 0u;
+                asum[2 * q] += tpg_bf16_lo(o[q]);          // of the rounded operand the MFMA sees
+                asum[2 * q + 1] += tpg_bf16_hi(o[q]);
             }
             *reinterpret_cast<uint4 *>(at + (size_t)r * AROW + 8 * ach) = make_uint4(o[0], o[1], o[2], o[3]);
         }
@@ -1044,9 +982,9 @@ __global__ __launch_bounds__(ML_THREADS) void mlp_bn_bwd_apply_kernel(
             unsigned o[4];
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
-                const float v0 = __builtin_fmaf(a[2 * i], bf16_lo(gw[i]), __builtin_fmaf(-f[2 * i], bf16_lo(xw[i]), e[2 * i]));
-                const float v1 = __builtin_fmaf(a[2 * i + 1], bf16_hi(gw[i]), __builtin_fmaf(-f[2 * i + 1], bf16_hi(xw[i]), e[2 * i + 1]));
-                o[i] = pack_bf16x2(v0, v1);
+                const float v0 = __builtin_fmaf(a[2 * i], tpg_bf16_lo(gw[i]), __builtin_fmaf(-f[2 * i], tpg_bf16_lo(xw[i]), e[2 * i]));
+                const float v1 = __builtin_fmaf(a[2 * i + 1], tpg_bf16_hi(gw[i]), __builtin_fmaf(-f[2 * i + 1], tpg_bf16_hi(xw[i]), e[2 * i + 1]));
+                o[i] = tpg_pack_bf16x2(v0, v1);
             }
             *reinterpret_cast<uint4 *>(dx + (size_t)(r + u * step) * C + col) = make_uint4(o[0], o[1], o[2], o[3]);
         }
@@ -1058,9 +996,9 @@ __global__ __launch_bounds__(ML_THREADS) void mlp_bn_bwd_apply_kernel(
         unsigned o[4];
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
-            const float v0 = __builtin_fmaf(a[2 * i], bf16_lo(gw[i]), __builtin_fmaf(-f[2 * i], bf16_lo(xw[i]), e[2 * i]));
-            const float v1 = __builtin_fmaf(a[2 * i + 1], bf16_hi(gw[i]), __builtin_fmaf(-f[2 * i + 1], bf16_hi(xw[i]), e[2 * i + 1]));
-            o[i] = pack_bf16x2(v0, v1);
+            const float v0 = __builtin_fmaf(a[2 * i], tpg_bf16_lo(gw[i]), __builtin_fmaf(-f[2 * i], tpg_bf16_lo(xw[i]), e[2 * i]));
+            const float v1 = __builtin_fmaf(a[2 * i + 1], tpg_bf16_hi(gw[i]), __builtin_fmaf(-f[2 * i + 1], tpg_bf16_hi(xw[i]), e[2 * i + 1]));
+            o[i] = tpg_pack_bf16x2(v0, v1);
         }
         *reinterpret_cast<uint4 *>(dx + (size_t)r * C + col) = make_uint4(o[0], o[1], o[2], o[3]);
     }
@@ -1105,11 +1043,11 @@ __global__ __launch_bounds__(ML_THREADS) void mlp_bn_bwd_apply_rowsum_kernel(
             unsigned o[4];
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
-                const float v0 = __builtin_fmaf(a[2 * i], bf16_lo(gw[i]), __builtin_fmaf(-f[2 * i], bf16_lo(xw[i]), e[2 * i]));
-                const float v1 = __builtin_fmaf(a[2 * i + 1], bf16_hi(gw[i]), __builtin_fmaf(-f[2 * i + 1], bf16_hi(xw[i]), e[2 * i + 1]));
-                o[i] = pack_bf16x2(v0, v1);
-                acc[2 * i] -= bf16_lo(o[i]);
-                acc[2 * i + 1] -= bf16_hi(o[i]);
+                const float v0 = __builtin_fmaf(a[2 * i], tpg_bf16_lo(gw[i]), __builtin_fmaf(-f[2 * i], tpg_bf16_lo(xw[i]), e[2 * i]));
+                const float v1 = __builtin_fmaf(a[2 * i + 1], tpg_bf16_hi(gw[i]), __builtin_fmaf(-f[2 * i + 1], tpg_bf16_hi(xw[i]), e[2 * i + 1]));
+                o[i] = tpg_pack_bf16x2(v0, v1);
+                acc[2 * i] -= tpg_bf16_lo(o[i]);
+                acc[2 * i + 1] -= tpg_bf16_hi(o[i]);
             }
             *reinterpret_cast<uint4 *>(dx + off) = make_uint4(o[0], o[1], o[2], o[3]);
         };
@@ -1160,16 +1098,8 @@ int fwd_launch(const void *x, long long P, int nseg, const float *ss, int ss_str
     constexpr int STRIPS = fwd_strips<CIN, COUT>();
     constexpr int BM = ML_WAVES * STRIPS * 16;
     constexpr size_t smem = fwd_smem<CIN, COUT>();
-    auto kern = mlp_fwd_kernel<CIN, COUT, STRIPS>;
-    if (smem > 64 * 1024) {
-        static bool raised = false;
-        if (!raised) {
-            if (hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                    (int)smem) != hipSuccess)
-                return TPG_ERR_UNSUPPORTED;
-            raised = true;
-        }
-    }
+    constexpr auto kern = mlp_fwd_kernel<CIN, COUT, STRIPS>;
+    if (smem > 64 * 1024 && !tpg_allow_dynamic_lds<kern>((int)smem)) return TPG_ERR_UNSUPPORTED;
     const int G = fwd_blocks(P, BM, nseg, 2 * smem > 160 * 1024 ? 256 : 512);
     *G_out = G;
     hipLaunchKernelGGL(kern, dim3(G, nseg), dim3(ML_THREADS), smem, st, static_cast<const __hip_bfloat16 *>(x), P, ss,
@@ -1188,15 +1118,6 @@ template <int CIN, int COUT> constexpr size_t wgrad_smem() {
     return (size_t)WG_ROWS * ((COUT + WG_PAD) + (CIN + WG_PAD)) * 2 + sizeof(float) * (ML_THREADS / (CIN / 8)) * CIN;
 }
 
-template <typename Kern> bool raise_lds(Kern kern, size_t smem, bool *raised) {
-    if (smem <= 64 * 1024 || *raised) return true;
-    if (hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem) !=
-        hipSuccess)
-        return false;
-    *raised = true;
-    return true;
-}
-
 template <int CIN, int COUT, int MODE>
 int dgrad_launch(const void *x_out, const void *g_out, const uint8_t *arg, int K, const float *cbo,
                  const void *x_in, const float *cbi, float slope_in, const float *W, int w_per_seg, long long P, int nseg,
@@ -1205,9 +1126,8 @@ int dgrad_launch(const void *x_out, const void *g_out, const uint8_t *arg, int K
     constexpr int BM = ML_WAVES * STRIPS * 16;
     constexpr size_t smem = dgrad_smem<CIN, COUT>();
     constexpr int OCC = (smem > 60 * 1024 || CIN == 256) ? 1 : 2;
-    auto kern = mlp_dgrad_kernel<CIN, COUT, MODE, STRIPS, OCC>;
-    static bool raised = false;
-    if (!raise_lds(kern, smem, &raised)) return TPG_ERR_UNSUPPORTED;
+    constexpr auto kern = mlp_dgrad_kernel<CIN, COUT, MODE, STRIPS, OCC>;
+    if (smem > 64 * 1024 && !tpg_allow_dynamic_lds<kern>((int)smem)) return TPG_ERR_UNSUPPORTED;
     const int G = fwd_blocks(P, BM, nseg, OCC == 1 ? 256 : 512);
     *G_out = G;
     hipLaunchKernelGGL(kern, dim3(G, nseg), dim3(ML_THREADS), smem, st, static_cast<const __hip_bfloat16 *>(x_out),
@@ -1242,9 +1162,8 @@ int wgrad_launch(const void *x_out, const void *g_out, const uint8_t *arg, int K
     constexpr size_t smem = wgrad_smem<CIN, COUT>();
     // accumulators: COUT*CIN/256 registers per lane; from 128 of them on a workgroup has its SIMDs alone
     constexpr int OCC = (COUT * CIN / ML_THREADS >= 128) ? 1 : 2;
-    auto kern = mlp_wgrad_kernel<CIN, COUT, MODE, OCC>;
-    static bool raised = false;
-    if (!raise_lds(kern, smem, &raised)) return TPG_ERR_UNSUPPORTED;
+    constexpr auto kern = mlp_wgrad_kernel<CIN, COUT, MODE, OCC>;
+    if (smem > 64 * 1024 && !tpg_allow_dynamic_lds<kern>((int)smem)) return TPG_ERR_UNSUPPORTED;
     hipLaunchKernelGGL(kern, dim3(G, nseg), dim3(ML_THREADS), smem, st, static_cast<const __hip_bfloat16 *>(x_out),
                        static_cast<const __hip_bfloat16 *>(g_out), arg, K, cbo,
                        static_cast<const __hip_bfloat16 *>(x_in), cbi, slope_in, P, slab);
@@ -1289,7 +1208,7 @@ extern "C" int tpg_mlp_fwd(const void *x, long long P, int Cin, int Cout, int ns
     if (rc) return rc;
     // no statistics wanted (a tail without BatchNorm: the generator's EdgeConv MLPs): no finalize launch
     if (mean_out || rstd_out || ci_out || running_mean)
-        hipLaunchKernelGGL(mlp_stats_finalize_kernel, dim3((Cout + MF_CH - 1) / MF_CH), dim3(ML_THREADS), 0, st, part, G,
+        hipLaunchKernelGGL(mlp_stats_finalize_kernel, dim3((Cout + FIN_CH - 1) / FIN_CH), dim3(FIN_THREADS), 0, st, part, G,
                            Cout, nseg, eps, momentum, running_mean, running_var, num_batches_tracked, mean_shift,
                            gamma_out, beta_out, mean_out, rstd_out, ci_out);
     TPG_RETURN_IF_LAUNCH_FAILED();
@@ -1351,7 +1270,7 @@ extern "C" int tpg_mlp_dgrad(const void *x_out, const void *g_out, const uint8_t
     // (ci_in = sc | sh | mu | rs per segment: the finalize reads rs with stride 4*Cin); nothing wanted
     // (an input without BatchNorm: the generator's EdgeConv MLPs): no finalize launch
     if (c12_in || dgamma_in || dbeta_in || cb_in)
-        hipLaunchKernelGGL(mlp_bwd_finalize_kernel, dim3((Cin + MF_CH - 1) / MF_CH), dim3(ML_THREADS), 0, st, part, G, P,
+        hipLaunchKernelGGL(mlp_bwd_finalize_kernel, dim3((Cin + FIN_CH - 1) / FIN_CH), dim3(FIN_THREADS), 0, st, part, G, P,
                            Cin, nseg, ci_in + 3 * Cin, 4 * Cin, c12_in, dgamma_in, dbeta_in, ci_in, cb_in);
     TPG_RETURN_IF_LAUNCH_FAILED();
     return TPG_OK;

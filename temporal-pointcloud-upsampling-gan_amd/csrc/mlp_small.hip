@@ -20,9 +20,7 @@
 //          the two weight gradients as edge-summed outer products (12, operands transposed through 5 KB of the
 //          wave's LDS), accumulated in registers across the launch (persistent waves, grid-stride tiles); one
 //          slab of 768 floats per wave at the end, summed in wave order by the reduce kernel (no atomics).
-#include <hip/hip_bf16.h>
-
-#include "tpg_common.hpp"
+#include "tpg_rows.hpp"
 
 namespace {
 
@@ -36,31 +34,6 @@ constexpr int SM_NW = SM_C1 * SM_H + SM_C2 * SM_C1;   // 768 weights
 // four k-steps (k-step s, k = q  <->  channel 4q + s: any one-to-one map of k works when A uses the same one), and gets
 // back output channels 4q .. 4q+3 of the same point -- the layout the NEXT product wants as its B operand.  The weights
 // sit in registers as A operands (lane: row e of W, columns 4q + s).  No transposes, no LDS in the forward.
-typedef float sm_f32x4 __attribute__((ext_vector_type(4)));
-
-template <typename T>
-__device__ __forceinline__ void sm_load4(const T *__restrict__ p, float (&v)[4]) {
-    if constexpr (sizeof(T) == 2) {
-        const uint2 a = *reinterpret_cast<const uint2 *>(p);
-        v[0] = __uint_as_float(a.x << 16); v[1] = __uint_as_float(a.x & 0xffff0000u);
-        v[2] = __uint_as_float(a.y << 16); v[3] = __uint_as_float(a.y & 0xffff0000u);
-    } else {
-        const float4 a = *reinterpret_cast<const float4 *>(p);
-        v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w;
-    }
-}
-template <typename T>
-__device__ __forceinline__ void sm_store4(T *__restrict__ p, const float (&v)[4]) {
-    if constexpr (sizeof(T) == 2) {
-        unsigned short b[4];
-#pragma unroll
-        for (int i = 0; i < 4; ++i) { const __hip_bfloat16 t = __float2bfloat16(v[i]); b[i] = *reinterpret_cast<const unsigned short *>(&t); }
-        *reinterpret_cast<uint2 *>(p) = make_uint2((unsigned)b[0] | ((unsigned)b[1] << 16), (unsigned)b[2] | ((unsigned)b[3] << 16));
-    } else {
-        *reinterpret_cast<float4 *>(p) = make_float4(v[0], v[1], v[2], v[3]);
-    }
-}
-
 #define SM_MFMA(a, b, c) __builtin_amdgcn_mfma_f32_16x16x4f32((a), (b), (c), 0, 0, 0)
 
 // ------------------------------------------------------------------------------------------- forward
@@ -75,9 +48,9 @@ __global__ __launch_bounds__(SF_WAVES * 64) void small_tail_fwd_kernel(
     if (tile * 16 >= P) return;                                   // whole wave
     const bool live = n < P;
     float w1a[4], w2a[2][4];
-    sm_load4(W1 + e * SM_H + 4 * q, w1a);
-    sm_load4(W2 + e * SM_C1 + 4 * q, w2a[0]);
-    sm_load4(W2 + (16 + e) * SM_C1 + 4 * q, w2a[1]);
+    tpg_load_row(W1 + e * SM_H + 4 * q, w1a);
+    tpg_load_row(W2 + e * SM_C1 + 4 * q, w2a[0]);
+    tpg_load_row(W2 + (16 + e) * SM_C1 + 4 * q, w2a[1]);
     float best[2][4];
     int barg[2][4];
 #pragma unroll
@@ -86,11 +59,11 @@ __global__ __launch_bounds__(SF_WAVES * 64) void small_tail_fwd_kernel(
         for (int r = 0; r < 4; ++r) { best[t][r] = -INFINITY; barg[t][r] = 0; }
     const T *hp = h + ((size_t)(live ? n : P - 1) * K) * SM_H + 4 * q;
     float hq[4];
-    sm_load4(hp, hq);
+    tpg_load_row(hp, hq);
     for (int j = 0; j < K; ++j) {
         float hn[4];
-        sm_load4(hp + (size_t)(j + 1 < K ? j + 1 : j) * SM_H, hn);      // the next edge travels during this one
-        sm_f32x4 z1 = {0.f, 0.f, 0.f, 0.f};
+        tpg_load_row(hp + (size_t)(j + 1 < K ? j + 1 : j) * SM_H, hn);      // the next edge travels during this one
+        tpg_f32x4 z1 = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
         for (int s = 0; s < 4; ++s) z1 = SM_MFMA(w1a[s], hq[s], z1);
         float a1[4];
@@ -98,7 +71,7 @@ __global__ __launch_bounds__(SF_WAVES * 64) void small_tail_fwd_kernel(
         for (int r = 0; r < 4; ++r) a1[r] = z1[r] > 0.0f ? z1[r] : z1[r] * s1;
 #pragma unroll
         for (int t = 0; t < 2; ++t) {
-            sm_f32x4 z2 = {0.f, 0.f, 0.f, 0.f};
+            tpg_f32x4 z2 = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
             for (int s = 0; s < 4; ++s) z2 = SM_MFMA(w2a[t][s], a1[s], z2);
 #pragma unroll
@@ -114,7 +87,7 @@ __global__ __launch_bounds__(SF_WAVES * 64) void small_tail_fwd_kernel(
             float o[4];
 #pragma unroll
             for (int r = 0; r < 4; ++r) o[r] = best[t][r] > 0.0f ? best[t][r] : best[t][r] * s2;
-            sm_store4(out + (size_t)n * SM_C2 + 16 * t + 4 * q, o);
+            tpg_store_row(out + (size_t)n * SM_C2 + 16 * t + 4 * q, o);
             *reinterpret_cast<unsigned *>(arg + (size_t)n * SM_C2 + 16 * t + 4 * q) =
                 (unsigned)barg[t][0] | ((unsigned)barg[t][1] << 8) | ((unsigned)barg[t][2] << 16) | ((unsigned)barg[t][3] << 24);
         }
@@ -140,14 +113,14 @@ __global__ __launch_bounds__(SB_WAVES * 64) void small_tail_bwd_kernel(
     const long long tiles = (P + 15) / 16;
     const long long gw = (long long)blockIdx.x * SB_WAVES + wave, nw = (long long)gridDim.x * SB_WAVES;
     float w1a[4], w1t[4], w2t[2][4];
-    sm_load4(W1 + e * SM_H + 4 * q, w1a);                         // A of z1 = W1 h:      W1[e][4q + s]
+    tpg_load_row(W1 + e * SM_H + 4 * q, w1a);                         // A of z1 = W1 h:      W1[e][4q + s]
 #pragma unroll
     for (int s = 0; s < 4; ++s) {
         w1t[s] = W1[(4 * q + s) * SM_H + e];                      // A of gh = W1^T gz1:  W1[4q + s][e]
         w2t[0][s] = W2[(4 * q + s) * SM_C1 + e];                  // A of ga1 = W2^T gz2: W2[16 t + 4q + s][e]
         w2t[1][s] = W2[(16 + 4 * q + s) * SM_C1 + e];
     }
-    sm_f32x4 dw1 = {0.f, 0.f, 0.f, 0.f}, dw2[2] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
+    tpg_f32x4 dw1 = {0.f, 0.f, 0.f, 0.f}, dw2[2] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
     for (long long tile = gw; tile < tiles; tile += nw) {
         const long long n = tile * 16 + e;
         const bool live = n < P;
@@ -158,8 +131,8 @@ __global__ __launch_bounds__(SB_WAVES * 64) void small_tail_bwd_kernel(
 #pragma unroll
         for (int t = 0; t < 2; ++t) {
             float go[4], oo[4];
-            sm_load4(gout + (size_t)nn * SM_C2 + 16 * t + 4 * q, go);
-            sm_load4(out + (size_t)nn * SM_C2 + 16 * t + 4 * q, oo);
+            tpg_load_row(gout + (size_t)nn * SM_C2 + 16 * t + 4 * q, go);
+            tpg_load_row(out + (size_t)nn * SM_C2 + 16 * t + 4 * q, oo);
             const unsigned b = *reinterpret_cast<const unsigned *>(arg + (size_t)nn * SM_C2 + 16 * t + 4 * q);
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
@@ -170,11 +143,11 @@ __global__ __launch_bounds__(SB_WAVES * 64) void small_tail_bwd_kernel(
         const T *hp = h + ((size_t)nn * K) * SM_H + 4 * q;
         T *gp_out = gh + ((size_t)nn * K) * SM_H + 4 * q;
         float hq[4];
-        sm_load4(hp, hq);
+        tpg_load_row(hp, hq);
         for (int j = 0; j < K; ++j) {
             float hn[4];
-            sm_load4(hp + (size_t)(j + 1 < K ? j + 1 : j) * SM_H, hn);
-            sm_f32x4 z1 = {0.f, 0.f, 0.f, 0.f};
+            tpg_load_row(hp + (size_t)(j + 1 < K ? j + 1 : j) * SM_H, hn);
+            tpg_f32x4 z1 = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
             for (int s = 0; s < 4; ++s) z1 = SM_MFMA(w1a[s], hq[s], z1);
             float a1[4], dz1[4], gz2[2][4];
@@ -183,7 +156,7 @@ __global__ __launch_bounds__(SB_WAVES * 64) void small_tail_bwd_kernel(
                 a1[r] = z1[r] > 0.0f ? z1[r] : z1[r] * s1;
                 dz1[r] = z1[r] > 0.0f ? 1.0f : s1;
             }
-            sm_f32x4 ga1 = {0.f, 0.f, 0.f, 0.f};
+            tpg_f32x4 ga1 = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
             for (int t = 0; t < 2; ++t)
 #pragma unroll
@@ -194,12 +167,12 @@ __global__ __launch_bounds__(SB_WAVES * 64) void small_tail_bwd_kernel(
             float gz1[4];
 #pragma unroll
             for (int r = 0; r < 4; ++r) gz1[r] = ga1[r] * dz1[r];
-            sm_f32x4 g = {0.f, 0.f, 0.f, 0.f};
+            tpg_f32x4 g = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
             for (int s = 0; s < 4; ++s) g = SM_MFMA(w1t[s], gz1[s], g);
             if (live) {
                 const float gv[4] = {g[0], g[1], g[2], g[3]};
-                sm_store4(gp_out + (size_t)j * SM_H, gv);
+                tpg_store_row(gp_out + (size_t)j * SM_H, gv);
             }
             // transposed read-back for the two outer-product sums (LDS operations of one wave complete in order)
             const float hz[4] = {live ? hq[0] : 0.0f, live ? hq[1] : 0.0f, live ? hq[2] : 0.0f, live ? hq[3] : 0.0f};

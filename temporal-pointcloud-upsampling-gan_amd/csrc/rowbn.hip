@@ -33,9 +33,8 @@
 // Rows are 16-byte vectors per lane (fp32 or bf16 storage, fp32 arithmetic); a thread owns one
 // column chunk, so per-channel constants stay in registers.  Sums are taken about a per-channel
 // pivot (the first row) to keep E[x^2]-E[x]^2 well conditioned.
-#include <hip/hip_bf16.h>
-
-#include "tpg_common.hpp"
+#include "tpg_bn_finalize.hpp"
+#include "tpg_rows.hpp"
 
 namespace {
 
@@ -78,54 +77,8 @@ __device__ __forceinline__ float lrelu_f(float z, float slope) { return z > 0.0f
 // pre-activation, written ONCE so that forward and backward see the same sign
 __device__ __forceinline__ float bn_z(float v, float mu, float a, float beta) { return (v - mu) * a + beta; }
 
-// ---- a row chunk of NE channels held as raw 16-byte registers until it is used --------------
-template <typename T, int NE> struct Chunk;
-template <int NE> struct Chunk<float, NE> {
-    float4 r[NE / 4];
-    __device__ __forceinline__ void load(const float *p) {
-#pragma unroll
-        for (int i = 0; i < NE / 4; ++i) r[i] = reinterpret_cast<const float4 *>(p)[i];
-    }
-    __device__ __forceinline__ void unpack(float (&v)[NE]) const {
-#pragma unroll
-        for (int i = 0; i < NE / 4; ++i) {
-            v[4 * i] = r[i].x; v[4 * i + 1] = r[i].y; v[4 * i + 2] = r[i].z; v[4 * i + 3] = r[i].w;
-        }
-    }
-    static __device__ __forceinline__ void store(float *p, const float (&v)[NE]) {
-#pragma unroll
-        for (int i = 0; i < NE / 4; ++i)
-            reinterpret_cast<float4 *>(p)[i] = make_float4(v[4 * i], v[4 * i + 1], v[4 * i + 2], v[4 * i + 3]);
-    }
-    static __device__ __forceinline__ float one(const float *p) { return *p; }
-};
-template <> struct Chunk<__hip_bfloat16, 8> {
-    uint4 r;
-    __device__ __forceinline__ void load(const __hip_bfloat16 *p) { r = *reinterpret_cast<const uint4 *>(p); }
-    __device__ __forceinline__ void unpack(float (&v)[8]) const {
-        const unsigned w[4] = {r.x, r.y, r.z, r.w};
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            v[2 * i] = __uint_as_float(w[i] << 16);
-            v[2 * i + 1] = __uint_as_float(w[i] & 0xffff0000u);
-        }
-    }
-    static __device__ __forceinline__ void store(__hip_bfloat16 *p, const float (&v)[8]) {
-        unsigned w[4];
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const __hip_bfloat16 lo = __float2bfloat16(v[2 * i]);
-            const __hip_bfloat16 hi = __float2bfloat16(v[2 * i + 1]);
-            w[i] = (unsigned)(*reinterpret_cast<const unsigned short *>(&lo)) |
-                   ((unsigned)(*reinterpret_cast<const unsigned short *>(&hi)) << 16);
-        }
-        *reinterpret_cast<uint4 *>(p) = make_uint4(w[0], w[1], w[2], w[3]);
-    }
-    static __device__ __forceinline__ float one(const __hip_bfloat16 *p) {
-        return __uint_as_float((unsigned)(*reinterpret_cast<const unsigned short *>(p)) << 16);
-    }
-};
-template <typename T> struct BnElems { static constexpr int NE = sizeof(T) == 2 ? 8 : 4; };
+using tpg_bn::FIN_CH;
+using tpg_bn::FIN_THREADS;
 
 // NE per-channel constants starting at channel `col` (a multiple of NE): vector loads when the
 // array is 16-byte aligned, `dflt` when the array is absent.  All branches are wave-uniform.
@@ -203,58 +156,10 @@ __device__ __forceinline__ void block_column_reduce(float (&acc)[NQ][NE], int cp
     }
 }
 
-// Sums of the per-workgroup partials of two quantities, for every segment of a launch: one WAVE per channel
-// (FIN_CH channels per workgroup), its lanes split into groups, one per segment (SP segments per sweep, a power
-// of two; L = 64 / SP lanes each), so that the segments' partials travel side by side and the launch waits for
-// memory once per sweep instead of once per segment.  fp64, fixed butterflies, no LDS and no barrier.
-constexpr int FIN_CH = 4;
-constexpr int FIN_THREADS = 64 * FIN_CH;
-constexpr int FIN_R = 8;                       // requests in flight per lane and quantity
-struct FinSplit { int SP, L; };
-__device__ __forceinline__ FinSplit fin_split(int nseg) {
-    int sp = 1;
-    while (sp < nseg && sp < 64) sp <<= 1;
-    return {sp, 64 / sp};
-}
-__device__ __forceinline__ double fin_group_sum(double v, int L) {
-    for (int m = L >> 1; m > 0; m >>= 1) v += __shfl_xor(v, m, 64);
-    return v;
-}
-__device__ __forceinline__ double fin_wave_sum(double v) {
-#pragma unroll
-    for (int m = 32; m > 0; m >>= 1) v += __shfl_xor(v, m, 64);
-    return v;
-}
-__device__ __forceinline__ double fin_readlane(double v, int l) {          // l wave-uniform
-    const long long b = __double_as_longlong(v);
-    const int lo = __builtin_amdgcn_readlane((int)(unsigned)(b & 0xffffffffll), l);
-    const int hi = __builtin_amdgcn_readlane((int)(b >> 32), l);
-    return __longlong_as_double(((long long)hi << 32) | (long long)(unsigned)lo);
-}
-// the two sums of segment `seg` (clamped when the group has none: live == false) in every lane of its group
+// the two sums of segment `seg` (see tpg_bn::pair_sums) from this file's workspace layout
 __device__ __forceinline__ void finalize_sums(const float *__restrict__ ws, int seg, bool live, int sub, int L, int G,
                                               int C, int c, double &s0, double &s1) {
-    const float *part = ws + WS_HEAD + (size_t)seg * BN_MAX_BLOCKS * 2 * C + c;
-    double a0 = 0.0, a1 = 0.0;
-    for (int g0 = 0; g0 < G; g0 += L * FIN_R) {
-        float v0[FIN_R], v1[FIN_R];
-#pragma unroll
-        for (int i = 0; i < FIN_R; ++i) {      // unconditional, clamped: all requests of a block in flight
-            const int g = g0 + sub + i * L;
-            const bool ok = live && g < G;
-            const float *pg = part + (size_t)(ok ? g : 0) * 2 * C;
-            const float x0 = pg[0], x1 = pg[C];
-            v0[i] = ok ? x0 : 0.0f;
-            v1[i] = ok ? x1 : 0.0f;
-        }
-#pragma unroll
-        for (int i = 0; i < FIN_R; ++i) {
-            a0 += (double)v0[i];
-            a1 += (double)v1[i];
-        }
-    }
-    s0 = fin_group_sum(a0, L);
-    s1 = fin_group_sum(a1, L);
+    tpg_bn::pair_sums(ws + WS_HEAD + (size_t)seg * BN_MAX_BLOCKS * 2 * C + c, C, sub, L, G, live, s0, s1);
 }
 
 // ------------------------------------------------------------------ forward statistics
@@ -262,7 +167,7 @@ __device__ __forceinline__ void finalize_sums(const float *__restrict__ ws, int 
 template <typename T>
 __global__ __launch_bounds__(BN_THREADS) void rowbn_stats_kernel(const T *__restrict__ x, long long P, int C,
                                                                  float *__restrict__ ws) {
-    constexpr int NE = BnElems<T>::NE;
+    constexpr int NE = tpg_elems<T>::NE;
     const int cpr = C / NE, rpi = BN_THREADS / cpr;  // chunks per row, rows per iteration
     const int tid = threadIdx.x;
     const int chunk = tid % cpr, rsub = tid / cpr;
@@ -274,11 +179,11 @@ __global__ __launch_bounds__(BN_THREADS) void rowbn_stats_kernel(const T *__rest
     if (rsub < rpi) {
         float piv[NE];
         {
-            Chunk<T, NE> p0;
+            tpg_chunk<T, NE> p0;
             p0.load(x + chunk * NE);  // pivot = first row
             p0.unpack(piv);
         }
-        struct Stage { Chunk<T, NE> v[TPG_BN_STATS_U]; };
+        struct Stage { tpg_chunk<T, NE> v[TPG_BN_STATS_U]; };
         const T *xc = x + chunk * NE;
         pipelined_rows<TPG_BN_STATS_U, Stage>(
             (long long)blockIdx.x * rpi + rsub, (long long)gridDim.x * rpi, P,
@@ -311,7 +216,7 @@ __global__ __launch_bounds__(FIN_THREADS) void rowbn_stats_finalize_kernel(
     const int lane = threadIdx.x & 63;
     const int c = blockIdx.x * FIN_CH + (threadIdx.x >> 6);
     if (c >= C) return;                        // whole wave
-    const FinSplit sp = fin_split(nseg);
+    const tpg_bn::Split sp = tpg_bn::split(nseg);
     const int grp = lane / sp.L, sub = lane - grp * sp.L;
     float rmean = running_mean ? running_mean[c] : 0.0f, rvar = running_mean ? running_var[c] : 0.0f;
     const double shift = mean_shift ? (double)mean_shift[c] : 0.0;   // see tpgan_ops.h
@@ -321,7 +226,7 @@ __global__ __launch_bounds__(FIN_THREADS) void rowbn_stats_finalize_kernel(
         const int segc = live ? seg : nseg - 1;
         double s, ss;
         finalize_sums(ws, segc, live, sub, sp.L, G, C, c, s, ss);
-        const double piv = Chunk<T, BnElems<T>::NE>::one(x + (size_t)segc * P * C + c);
+        const double piv = tpg_chunk<T, tpg_elems<T>::NE>::one(x + (size_t)segc * P * C + c);
         const double m = s / (double)P;
         double var = ss / (double)P - m * m;  // biased, about the pivot
         var = var < 0.0 ? 0.0 : var;
@@ -331,15 +236,14 @@ __global__ __launch_bounds__(FIN_THREADS) void rowbn_stats_finalize_kernel(
             rstd[(size_t)seg * C + c] = rs;
             if (ci_out) {
                 const float a = (gamma ? gamma[c] : 1.0f) * rs;
-                float *o = ci_out + (size_t)seg * 4 * C + c;
-                o[0] = a; o[C] = (beta ? beta[c] : 0.0f) - mu * a; o[2 * C] = mu; o[3 * C] = rs;
+                tpg_bn::write_ci(ci_out + (size_t)seg * 4 * C + c, C, a, beta ? beta[c] : 0.0f, mu, rs);
             }
         }
         if (running_mean) {                    // in call order: the running statistics chain
             const int last = nseg - seg0 < sp.SP ? nseg - seg0 : sp.SP;
             const double pm = piv + m;
             for (int k = 0; k < last; ++k) {
-                const double mk = fin_readlane(pm, k * sp.L), vk = fin_readlane(var, k * sp.L);
+                const double mk = tpg_bn::readlane(pm, k * sp.L), vk = tpg_bn::readlane(var, k * sp.L);
                 const double unbiased = P > 1 ? vk * (double)P / (double)(P - 1) : vk;
                 rmean = (float)((1.0 - momentum) * rmean + momentum * (mk + shift));
                 rvar = (float)((1.0 - momentum) * rvar + momentum * unbiased);
@@ -355,7 +259,7 @@ __global__ __launch_bounds__(BN_THREADS) void rowbn_apply_kernel(
     const TI *__restrict__ x, long long P, int C, const float *__restrict__ mean,
     const float *__restrict__ rstd, const float *__restrict__ gamma, const float *__restrict__ beta,
     float slope, TO *__restrict__ y) {
-    constexpr int NE = (sizeof(TI) == 2 || sizeof(TO) == 2) ? 8 : 4;
+    constexpr int NE = tpg_elems<TI, TO>::NE;
     const int cpr = C / NE, rpi = BN_THREADS / cpr;
     const int chunk = threadIdx.x % cpr, rsub = threadIdx.x / cpr, col = chunk * NE;
     if (rsub >= rpi) return;
@@ -372,7 +276,7 @@ __global__ __launch_bounds__(BN_THREADS) void rowbn_apply_kernel(
 #pragma unroll
         for (int i = 0; i < NE; ++i) a[i] = gm[i] * a[i];
     }
-    struct Stage { Chunk<TI, NE> v[BN_UNROLL]; };
+    struct Stage { tpg_chunk<TI, NE> v[BN_UNROLL]; };
     const TI *xc = x + col;
     TO *yc = y + col;
     pipelined_rows<BN_UNROLL, Stage>(
@@ -383,7 +287,7 @@ __global__ __launch_bounds__(BN_THREADS) void rowbn_apply_kernel(
             s.v[u].unpack(v);
 #pragma unroll
             for (int i = 0; i < NE; ++i) v[i] = lrelu_f(bn_z(v[i], mu[i], a[i], b[i]), slope);
-            Chunk<TO, NE>::store(yc + r * C, v);
+            tpg_chunk<TO, NE>::store(yc + r * C, v);
         });
 }
 
@@ -400,7 +304,7 @@ __global__ __launch_bounds__(BN_THREADS) void rowbn_apply_max_kernel(
     const float *__restrict__ rstd, const float *__restrict__ gamma, const float *__restrict__ beta,
     float slope, TO *__restrict__ y, uint8_t *__restrict__ arg, int L, float *__restrict__ part,
     uint8_t *__restrict__ parg) {
-    constexpr int NE = (sizeof(TI) == 2 || sizeof(TO) == 2) ? 8 : 4;
+    constexpr int NE = tpg_elems<TI, TO>::NE;
     const int cpr = C / NE, rpi = BN_THREADS / cpr;
     const int chunk = threadIdx.x % cpr, rsub = threadIdx.x / cpr, col = chunk * NE;
     if (rsub >= rpi) return;
@@ -428,7 +332,7 @@ __global__ __launch_bounds__(BN_THREADS) void rowbn_apply_max_kernel(
     long long grp = (long long)blockIdx.x * rpi + rsub;
     int k = 0;
     bool have = grp < Gp;
-    Chunk<TI, NE> cur[U], nxt[U];
+    tpg_chunk<TI, NE> cur[U], nxt[U];
     const TI *xc = x + col;
     if (have) {
 #pragma unroll
@@ -460,13 +364,13 @@ __global__ __launch_bounds__(BN_THREADS) void rowbn_apply_max_kernel(
         if (kn == 0) {   // group complete
             uint8_t *ab = arg;
             if (L > 1) {                                  // a run: fp32 maximum, k counted in the group
-                Chunk<float, NE>::store(part + grp * C + col, best);
+                tpg_chunk<float, NE>::store(part + grp * C + col, best);
                 const int kb = (int)(grp % L) * K;
 #pragma unroll
                 for (int i = 0; i < NE; ++i) bk[i] += kb;
                 ab = parg;
             } else {
-                Chunk<TO, NE>::store(y + grp * C + col, best);
+                tpg_chunk<TO, NE>::store(y + grp * C + col, best);
             }
             // NE arg-max bytes (8-byte aligned for NE = 8, 4-byte for NE = 4)
             if constexpr (NE == 8) {
@@ -509,7 +413,7 @@ __global__ __launch_bounds__(BN_THREADS) void rowbn_max_combine_kernel(
     for (int i = 0; i < NE; ++i) { best[i] = -INFINITY; run[i] = 0; }
 #pragma unroll 8
     for (int l = 0; l < L; ++l) {
-        Chunk<float, NE> c;
+        tpg_chunk<float, NE> c;
         c.load(part + (size_t)l * C);
         float v[NE];
         c.unpack(v);
@@ -517,7 +421,7 @@ __global__ __launch_bounds__(BN_THREADS) void rowbn_max_combine_kernel(
         for (int i = 0; i < NE; ++i)
             if (v[i] > best[i]) { best[i] = v[i]; run[i] = l; }        // strict: the first run wins a tie
     }
-    Chunk<TO, NE>::store(y, best);
+    tpg_chunk<TO, NE>::store(y, best);
 #pragma unroll
     for (int i = 0; i < NE; ++i) arg[i] = parg[(size_t)run[i] * C + i];
 }
@@ -538,7 +442,7 @@ __global__ __launch_bounds__(FIN_THREADS) void rowbn_bwd_finalize_kernel(const f
     const int lane = threadIdx.x & 63;
     const int c = blockIdx.x * FIN_CH + (threadIdx.x >> 6);
     if (c >= C) return;                        // whole wave
-    const FinSplit sp = fin_split(nseg);
+    const tpg_bn::Split sp = tpg_bn::split(nseg);
     const int grp = lane / sp.L, sub = lane - grp * sp.L;
     double ts = 0.0, tsx = 0.0;
     for (int seg0 = 0; seg0 < nseg; seg0 += sp.SP) {
@@ -547,8 +451,8 @@ __global__ __launch_bounds__(FIN_THREADS) void rowbn_bwd_finalize_kernel(const f
         double s, sx;
         finalize_sums(ws, live ? seg : nseg - 1, live, sub, sp.L, G, C, c, s, sx);
         const bool owner = live && sub == 0;
-        ts += fin_wave_sum(owner ? s : 0.0);   // fixed order over the segments of the sweep
-        tsx += fin_wave_sum(owner ? sx : 0.0);
+        ts += tpg_bn::wave_sum(owner ? s : 0.0);   // fixed order over the segments of the sweep
+        tsx += tpg_bn::wave_sum(owner ? sx : 0.0);
         if (owner) {
             float *cs = c12 + (size_t)seg * 2 * C;
             const float c1 = training ? (float)(s / (double)P) : 0.0f;       // eval-mode BN: no batch terms
@@ -557,9 +461,7 @@ __global__ __launch_bounds__(FIN_THREADS) void rowbn_bwd_finalize_kernel(const f
             cs[C + c] = c2;
             if (cb) {
                 const float mu = mean ? mean[(size_t)seg * C + c] : 0.0f, rs = rstd ? rstd[(size_t)seg * C + c] : 1.0f;
-                const float a = (gamma ? gamma[c] : 1.0f) * rs, f = a * rs * c2;
-                float *o = cb + (size_t)seg * 4 * C + c;
-                o[0] = a; o[C] = f * mu; o[2 * C] = -a * c1; o[3 * C] = f;
+                tpg_bn::write_cb(cb + (size_t)seg * 4 * C + c, C, (gamma ? gamma[c] : 1.0f) * rs, mu, rs, c1, c2);
             }
         }
     }
@@ -573,7 +475,7 @@ __global__ __launch_bounds__(BN_THREADS) void rowbn_bwd_reduce_kernel(
     const TG *__restrict__ gy, const TI *__restrict__ x, long long P, int C, const float *__restrict__ mean,
     const float *__restrict__ rstd, const float *__restrict__ gamma, const float *__restrict__ beta,
     float slope, float *__restrict__ ws) {
-    constexpr int NE = (sizeof(TI) == 2 || sizeof(TG) == 2) ? 8 : 4;
+    constexpr int NE = tpg_elems<TI, TG>::NE;
     const int cpr = C / NE, rpi = BN_THREADS / cpr;
     const int tid = threadIdx.x;
     const int chunk = tid % cpr, rsub = tid / cpr, col = chunk * NE;
@@ -592,7 +494,7 @@ __global__ __launch_bounds__(BN_THREADS) void rowbn_bwd_reduce_kernel(
         ld_consts<NE>(gamma, col, 1.0f, a);
 #pragma unroll
         for (int i = 0; i < NE; ++i) a[i] = a[i] * rs[i];
-        struct Stage { Chunk<TI, NE> v[BN_BWD_U]; Chunk<TG, NE> g[BN_BWD_U]; };
+        struct Stage { tpg_chunk<TI, NE> v[BN_BWD_U]; tpg_chunk<TG, NE> g[BN_BWD_U]; };
         const TI *xc = x + col;
         const TG *gc = gy + col;
         pipelined_rows<BN_BWD_U, Stage>(
@@ -626,7 +528,7 @@ __global__ __launch_bounds__(BN_THREADS) void rowbn_bwd_reduce_max_kernel(
     float slope, float *__restrict__ ws, TG *__restrict__ ag) {
     // ag (nseg*Gp, C), optional (needs y): gamma*rstd * lrelu'(y) * gy per (group, channel) -- the MODE_MAX operand of
     // the fused tail's gradient kernels (tpg_mlp_max_prep's output, same bits), a by-product of the rows read here
-    constexpr int NE = (sizeof(TI) == 2 || sizeof(TG) == 2) ? 8 : 4;
+    constexpr int NE = tpg_elems<TI, TG>::NE;
     const int cpr = C / NE, rpi = BN_THREADS / cpr;
     const int tid = threadIdx.x;
     const int chunk = tid % cpr, rsub = tid / cpr, col = chunk * NE;
@@ -656,7 +558,7 @@ __global__ __launch_bounds__(BN_THREADS) void rowbn_bwd_reduce_max_kernel(
         }
         for (long long r = (long long)blockIdx.x * rpi + rsub; r < Gp; r += (long long)gridDim.x * rpi) {
             float g[NE], yy[NE];
-            Chunk<TG, NE> cg, cy;
+            tpg_chunk<TG, NE> cg, cy;
             cg.load(gy + r * C + col);
             if (y != nullptr) cy.load(y + r * C + col);
             else cy = cg;
@@ -666,7 +568,7 @@ __global__ __launch_bounds__(BN_THREADS) void rowbn_bwd_reduce_max_kernel(
                 float av[NE];
 #pragma unroll
                 for (int i = 0; i < NE; ++i) av[i] = a[i] * (yy[i] > 0.0f ? g[i] : g[i] * slope);
-                Chunk<TG, NE>::store(ag + r * C + col, av);
+                tpg_chunk<TG, NE>::store(ag + r * C + col, av);
             }
 #pragma unroll
             for (int i = 0; i < NE; ++i) {
@@ -679,7 +581,7 @@ __global__ __launch_bounds__(BN_THREADS) void rowbn_bwd_reduce_max_kernel(
                 } else {
                     const int c = col + i;
                     const int k = arg[r * C + c];
-                    const float v = Chunk<TI, NE>::one(x + (r * K + k) * C + c);
+                    const float v = tpg_chunk<TI, NE>::one(x + (r * K + k) * C + c);
                     const float gg = bn_z(v, mu[i], a[i], b[i]) > 0.0f ? g[i] : g[i] * slope;
                     acc[0][i] += gg;
                     acc[1][i] += gg * ((v - mu[i]) * rs[i]);
@@ -696,7 +598,7 @@ __global__ __launch_bounds__(BN_THREADS) void rowbn_bwd_apply_kernel(
     const TG *__restrict__ gy, const TI *__restrict__ x, long long P, int C, const float *__restrict__ mean,
     const float *__restrict__ rstd, const float *__restrict__ gamma, const float *__restrict__ beta,
     float slope, const float *__restrict__ c12, TI *__restrict__ dx) {
-    constexpr int NE = (sizeof(TI) == 2 || sizeof(TG) == 2) ? 8 : 4;
+    constexpr int NE = tpg_elems<TI, TG>::NE;
     const int cpr = C / NE, rpi = BN_THREADS / cpr;
     const int chunk = threadIdx.x % cpr, rsub = threadIdx.x / cpr, col = chunk * NE;
     if (rsub >= rpi) return;
@@ -714,7 +616,7 @@ __global__ __launch_bounds__(BN_THREADS) void rowbn_bwd_apply_kernel(
     ld_consts<NE>(c12 ? c12 + C : nullptr, col, 0.0f, c2);
 #pragma unroll
     for (int i = 0; i < NE; ++i) a[i] = a[i] * rs[i];
-    struct Stage { Chunk<TI, NE> v[BN_BWD_U]; Chunk<TG, NE> g[BN_BWD_U]; };
+    struct Stage { tpg_chunk<TI, NE> v[BN_BWD_U]; tpg_chunk<TG, NE> g[BN_BWD_U]; };
     const TI *xc = x + col;
     const TG *gc = gy + col;
     TI *dc = dx + col;
@@ -730,7 +632,7 @@ __global__ __launch_bounds__(BN_THREADS) void rowbn_bwd_apply_kernel(
                 const float gg = bn_z(v[i], mu[i], a[i], b[i]) > 0.0f ? g[i] : g[i] * slope;
                 v[i] = a[i] * (gg - c1[i] - (v[i] - mu[i]) * rs[i] * c2[i]);
             }
-            Chunk<TI, NE>::store(dc + r * C, v);
+            tpg_chunk<TI, NE>::store(dc + r * C, v);
         });
 }
 
@@ -742,7 +644,7 @@ __global__ __launch_bounds__(BN_THREADS) void rowbn_bwd_apply_max_kernel(
     const TG *__restrict__ gy, const TI *__restrict__ x, const uint8_t *__restrict__ arg, long long Gp, int K,
     int C, const float *__restrict__ mean, const float *__restrict__ rstd, const float *__restrict__ gamma,
     const float *__restrict__ beta, float slope, const float *__restrict__ c12, TI *__restrict__ dx, int L) {
-    constexpr int NE = (sizeof(TI) == 2 || sizeof(TG) == 2) ? 8 : 4;
+    constexpr int NE = tpg_elems<TI, TG>::NE;
     const int cpr = C / NE, rpi = BN_THREADS / cpr;
     const int chunk = threadIdx.x % cpr, rsub = threadIdx.x / cpr, col = chunk * NE;
     if (rsub >= rpi) return;
@@ -767,11 +669,11 @@ __global__ __launch_bounds__(BN_THREADS) void rowbn_bwd_apply_max_kernel(
     long long grp = (long long)blockIdx.x * rpi + rsub;
     int k = 0;
     bool have = grp < Gp;
-    Chunk<TI, NE> cur[U], nxt[U];
-    Chunk<TG, NE> cgy, ngy;
+    tpg_chunk<TI, NE> cur[U], nxt[U];
+    tpg_chunk<TG, NE> cgy, ngy;
     unsigned ak_lo = 0, ak_hi = 0, nk_lo = 0, nk_hi = 0;     // NE arg-max bytes
     const TI *xc = x + col;
-    auto load_group = [&](long long r_, Chunk<TG, NE> &cg, unsigned &lo, unsigned &hi) {
+    auto load_group = [&](long long r_, tpg_chunk<TG, NE> &cg, unsigned &lo, unsigned &hi) {
         const long long g_ = r_ / L;
         cg.load(gy + g_ * C + col);
         if constexpr (NE == 8) {
@@ -812,7 +714,7 @@ __global__ __launch_bounds__(BN_THREADS) void rowbn_bwd_apply_max_kernel(
                 if (ak == kb + k + u) gg = bn_z(v[i], mu[i], a[i], b[i]) > 0.0f ? g[i] : g[i] * slope;
                 v[i] = a[i] * (gg - c1[i] - (v[i] - mu[i]) * rs[i] * c2[i]);
             }
-            Chunk<TI, NE>::store(dx + (grp * K + k + u) * C + col, v);
+            tpg_chunk<TI, NE>::store(dx + (grp * K + k + u) * C + col, v);
         }
         if (kn == 0) { cgy = ngy; ak_lo = nk_lo; ak_hi = nk_hi; }
 #pragma unroll
@@ -957,7 +859,7 @@ extern "C" int tpg_rowbn_fwd(const void *x, int dtype_in, long long P, int K, in
                            rows_out, K, C, mean, rstd, gamma, beta, slope, static_cast<TO *>(y), argmax, L, part, \
                            parg);                                                                         \
         if (L > 1) {                                                                                      \
-            constexpr int NE_ = (sizeof(TI) == 2 || sizeof(TO) == 2) ? 8 : 4;                             \
+            constexpr int NE_ = tpg_elems<TI, TO>::NE;                                                \
             const long long thr = rows_out * (C / NE_);                                                   \
             hipLaunchKernelGGL((rowbn_max_combine_kernel<TO, NE_>), dim3((unsigned)((thr + BN_THREADS - 1) / BN_THREADS), nseg), \
                                blk, 0, st, part, parg, rows_out, L, C, static_cast<TO *>(y), argmax);     \

@@ -19,87 +19,21 @@
 // where each destination row is summed by one group of lanes and written exactly once.
 // Element types: fp32 and bf16 (bf16 halves the bytes of the largest tensors; arithmetic is
 // fp32 in registers, one rounding on store).
-#include <hip/hip_bf16.h>
-
 #include <cstdlib>
 
 #include "invert_index.hpp"
-#include "tpg_common.hpp"
+#include "tpg_rows.hpp"
 
 namespace {
 
 enum { MODE_GATHER = 0, MODE_SUB = 1, MODE_EDGE = 2 };
 
-typedef unsigned int rc_u32x4 __attribute__((ext_vector_type(4)));
-typedef float rc_f32x4 __attribute__((ext_vector_type(4)));
 #ifndef TPG_RC_NT_STORE
 #define TPG_RC_NT_STORE 0        // 1: non-temporal stores for the forward's output rows.  Round 3: with two chains per thread
                                  // 46.7 -> 20.8 us ALONE on cache-resident operands (tools/tune_rowcombine.py), but in the
                                  // step 24.0 instead of 19.2 us per launch and +5 % step time (tools/ab_rowcombine.sh): the
                                  // consumer reads these rows next and wants them in L2.  Off.
 #endif
-
-// NE consecutive elements of T <-> NE floats (16-byte vector accesses).
-template <typename T, int NE> struct RowIO;
-template <int NE> struct RowIO<float, NE> {
-    static __device__ __forceinline__ void load(const float *p, float (&v)[NE]) {
-#pragma unroll
-        for (int i = 0; i < NE / 4; ++i) {
-            const float4 x = reinterpret_cast<const float4 *>(p)[i];
-            v[4 * i] = x.x; v[4 * i + 1] = x.y; v[4 * i + 2] = x.z; v[4 * i + 3] = x.w;
-        }
-    }
-    static __device__ __forceinline__ void store(float *p, const float (&v)[NE]) {
-#pragma unroll
-        for (int i = 0; i < NE / 4; ++i)
-            reinterpret_cast<float4 *>(p)[i] = make_float4(v[4 * i], v[4 * i + 1], v[4 * i + 2], v[4 * i + 3]);
-    }
-    static __device__ __forceinline__ void store_stream(float *p, const float (&v)[NE]) {
-#pragma unroll
-        for (int i = 0; i < NE / 4; ++i) {
-            const rc_f32x4 w = {v[4 * i], v[4 * i + 1], v[4 * i + 2], v[4 * i + 3]};
-            __builtin_nontemporal_store(w, reinterpret_cast<rc_f32x4 *>(p) + i);
-        }
-    }
-};
-template <> struct RowIO<__hip_bfloat16, 8> {
-    static __device__ __forceinline__ void load(const __hip_bfloat16 *p, float (&v)[8]) {
-        const uint4 x = *reinterpret_cast<const uint4 *>(p);
-        const unsigned w[4] = {x.x, x.y, x.z, x.w};
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            v[2 * i] = __uint_as_float(w[i] << 16);
-            v[2 * i + 1] = __uint_as_float(w[i] & 0xffff0000u);
-        }
-    }
-    static __device__ __forceinline__ void store(__hip_bfloat16 *p, const float (&v)[8]) {
-        unsigned w[4];
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const __hip_bfloat16 lo = __float2bfloat16(v[2 * i]);       // round-to-nearest-even
-            const __hip_bfloat16 hi = __float2bfloat16(v[2 * i + 1]);
-            w[i] = (unsigned)(*reinterpret_cast<const unsigned short *>(&lo)) |
-                   ((unsigned)(*reinterpret_cast<const unsigned short *>(&hi)) << 16);
-        }
-        *reinterpret_cast<uint4 *>(p) = make_uint4(w[0], w[1], w[2], w[3]);
-    }
-    static __device__ __forceinline__ void store_stream(__hip_bfloat16 *p, const float (&v)[8]) {
-        unsigned w[4];
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const __hip_bfloat16 lo = __float2bfloat16(v[2 * i]);
-            const __hip_bfloat16 hi = __float2bfloat16(v[2 * i + 1]);
-            w[i] = (unsigned)(*reinterpret_cast<const unsigned short *>(&lo)) |
-                   ((unsigned)(*reinterpret_cast<const unsigned short *>(&hi)) << 16);
-        }
-        const rc_u32x4 x = {w[0], w[1], w[2], w[3]};
-        __builtin_nontemporal_store(x, reinterpret_cast<rc_u32x4 *>(p));
-    }
-};
-// elements per thread: 8 as soon as one side is bf16 (16-byte bf16 vectors), else 4
-template <typename TA, typename TB> struct Elems {
-    static constexpr int NE = (sizeof(TA) == 2 || sizeof(TB) == 2) ? 8 : 4;
-};
 
 // ------------------------------------------------------------------ forward
 // Tunables (tools/tune_rowcombine.py)
@@ -128,10 +62,8 @@ __global__ __launch_bounds__(256) void rowcombine_fwd_kernel(
     int K, int C, float slope, TO *__restrict__ out, unsigned total, int xcd_order, int ld, float slope_u) {
     // ld = row stride of U / QE in elements (C, or 2C when both are column halves of ONE product: the EdgeConv
     // front end, tpg_rowcombine_edge_fwd); slope_u: EDGE only, LeakyReLU applied to the gathered U row (1 = none)
-    constexpr int NE = Elems<TI, TO>::NE;
+    constexpr int NE = tpg_elems<TI, TO>::NE;
     constexpr int UF = TPG_RC_FWD_U;
-    using In = RowIO<TI, NE>;
-    using Out = RowIO<TO, NE>;
     const unsigned cpr = (unsigned)C / NE;  // 16-byte chunks per row
     const unsigned stride = gridDim.x * 256u;
     // consecutive workgroup ids land on the 8 XCDs in turn: with the plain order every XCD's L2 fetches every
@@ -146,16 +78,16 @@ __global__ __launch_bounds__(256) void rowcombine_fwd_kernel(
         const unsigned b = bs / (unsigned)S;
         const int n = tpg_clamp_idx(idx[row], N);
         float u[NE];
-        In::load(U + ((size_t)b * N + n) * ld + col, u);
+        tpg_load_row(U + ((size_t)b * N + n) * ld + col, u);
         if (MODE == MODE_SUB) {
             float q[NE];
-            In::load(QE + (size_t)bs * ld + col, q);
+            tpg_load_row(QE + (size_t)bs * ld + col, q);
 #pragma unroll
             for (int i = 0; i < NE; ++i) u[i] = u[i] - q[i];
         } else if (MODE == MODE_EDGE) {
             float en[NE], es[NE];
-            In::load(QE + ((size_t)b * N + n) * ld + col, en);
-            In::load(QE + (size_t)bs * ld + col, es);   // S == N: centre row of E
+            tpg_load_row(QE + ((size_t)b * N + n) * ld + col, en);
+            tpg_load_row(QE + (size_t)bs * ld + col, es);   // S == N: centre row of E
 #pragma unroll
             for (int i = 0; i < NE; ++i) {
                 const float d = en[i] - es[i];
@@ -163,8 +95,8 @@ __global__ __launch_bounds__(256) void rowcombine_fwd_kernel(
                 u[i] = a + (d > 0.0f ? d : d * slope);
             }
         }
-        if (TPG_RC_NT_STORE) Out::store_stream(out + (size_t)row * C + col, u);
-        else Out::store(out + (size_t)row * C + col, u);
+        if (TPG_RC_NT_STORE) tpg_chunk<TO, NE>::store_stream(out + (size_t)row * C + col, u);
+        else tpg_store_row(out + (size_t)row * C + col, u);
     };
     for (; (unsigned long long)t + (unsigned long long)(UF - 1) * stride < total; t += UF * stride) {
         unsigned row[UF], col[UF], bs[UF], b[UF];
@@ -182,9 +114,9 @@ __global__ __launch_bounds__(256) void rowcombine_fwd_kernel(
 #pragma unroll
         for (int j = 0; j < UF; ++j) {
             n[j] = tpg_clamp_idx(n[j], N);
-            In::load(U + ((size_t)b[j] * N + n[j]) * ld + col[j], u[j]);
-            if (MODE != MODE_GATHER) In::load(QE + (size_t)bs[j] * ld + col[j], q[j]);      // centre row
-            if (MODE == MODE_EDGE) In::load(QE + ((size_t)b[j] * N + n[j]) * ld + col[j], en[j]);
+            tpg_load_row(U + ((size_t)b[j] * N + n[j]) * ld + col[j], u[j]);
+            if (MODE != MODE_GATHER) tpg_load_row(QE + (size_t)bs[j] * ld + col[j], q[j]);      // centre row
+            if (MODE == MODE_EDGE) tpg_load_row(QE + ((size_t)b[j] * N + n[j]) * ld + col[j], en[j]);
         }
 #pragma unroll
         for (int j = 0; j < UF; ++j) {
@@ -199,8 +131,8 @@ __global__ __launch_bounds__(256) void rowcombine_fwd_kernel(
                     u[j][i] = a + (d > 0.0f ? d : d * slope);
                 }
             }
-            if (TPG_RC_NT_STORE) Out::store_stream(out + (size_t)row[j] * C + col[j], u[j]);
-            else Out::store(out + (size_t)row[j] * C + col[j], u[j]);
+            if (TPG_RC_NT_STORE) tpg_chunk<TO, NE>::store_stream(out + (size_t)row[j] * C + col[j], u[j]);
+            else tpg_store_row(out + (size_t)row[j] * C + col[j], u[j]);
         }
     }
     for (; t < total; t += stride) one(t);
@@ -217,9 +149,7 @@ __global__ __launch_bounds__(256) void rowcombine_bwd_kernel(
     TI *__restrict__ gU, TI *__restrict__ gE, unsigned total, int ld, const TI *__restrict__ Uraw, float slope_u) {
     // ld: row stride of E / gU / gE (and Uraw) in elements; Uraw (EDGE, may be NULL): the forward's U rows before
     // their LeakyReLU(slope_u) -- gU is then the gradient of those raw rows
-    constexpr int NE = Elems<TI, TG>::NE;
-    using In = RowIO<TI, NE>;
-    using Gr = RowIO<TG, NE>;
+    constexpr int NE = tpg_elems<TI, TG>::NE;
     const unsigned cpr = (unsigned)C / NE;
     const size_t SK = (size_t)S * K;
     for (unsigned t = blockIdx.x * 256u + threadIdx.x; t < total; t += gridDim.x * 256u) {
@@ -233,7 +163,7 @@ __global__ __launch_bounds__(256) void rowcombine_bwd_kernel(
         float acc[NE], accE[NE], en[NE];
 #pragma unroll
         for (int i = 0; i < NE; ++i) { acc[i] = 0.0f; accE[i] = 0.0f; }
-        if (MODE == MODE_EDGE) In::load(E + (size_t)drow * ld + col, en);
+        if (MODE == MODE_EDGE) tpg_load_row(E + (size_t)drow * ld + col, en);
         const int p1 = of[n + 1];
         int p = of[n];
         // entries four at a time: the 4 list reads, then the 4 (+4) row reads are independent
@@ -245,8 +175,8 @@ __global__ __launch_bounds__(256) void rowcombine_bwd_kernel(
             float g[4][NE], es[4][NE];
 #pragma unroll
             for (int u = 0; u < 4; ++u) {
-                Gr::load(go + (size_t)e[u] * C, g[u]);
-                if (MODE == MODE_EDGE) In::load(E + ((size_t)b * N + (unsigned)e[u] / (unsigned)K) * ld + col, es[u]);
+                tpg_load_row(go + (size_t)e[u] * C, g[u]);
+                if (MODE == MODE_EDGE) tpg_load_row(E + ((size_t)b * N + (unsigned)e[u] / (unsigned)K) * ld + col, es[u]);
             }
 #pragma unroll
             for (int u = 0; u < 4; ++u) {
@@ -261,12 +191,12 @@ __global__ __launch_bounds__(256) void rowcombine_bwd_kernel(
         for (; p < p1; ++p) {
             const int e = ls[p];
             float g[NE];
-            Gr::load(go + (size_t)e * C, g);
+            tpg_load_row(go + (size_t)e * C, g);
 #pragma unroll
             for (int i = 0; i < NE; ++i) acc[i] += g[i];
             if (MODE == MODE_EDGE) {
                 float es[NE];
-                In::load(E + ((size_t)b * N + (unsigned)e / (unsigned)K) * ld + col, es);
+                tpg_load_row(E + ((size_t)b * N + (unsigned)e / (unsigned)K) * ld + col, es);
 #pragma unroll
                 for (int i = 0; i < NE; ++i) accE[i] += (en[i] - es[i] > 0.0f) ? g[i] : g[i] * slope;
             }
@@ -281,8 +211,8 @@ __global__ __launch_bounds__(256) void rowcombine_bwd_kernel(
                 float g[4][NE], eb[4][NE];
 #pragma unroll
                 for (int u = 0; u < 4; ++u) {
-                    Gr::load(go + ((size_t)n * K + k + u) * C, g[u]);
-                    In::load(E + ((size_t)b * N + nb[u]) * ld + col, eb[u]);
+                    tpg_load_row(go + ((size_t)n * K + k + u) * C, g[u]);
+                    tpg_load_row(E + ((size_t)b * N + nb[u]) * ld + col, eb[u]);
                 }
 #pragma unroll
                 for (int u = 0; u < 4; ++u)
@@ -293,20 +223,20 @@ __global__ __launch_bounds__(256) void rowcombine_bwd_kernel(
                 const size_t e = (size_t)n * K + k;
                 const int nb = tpg_clamp_idx(idx[(size_t)b * SK + e], N);
                 float g[NE], eb[NE];
-                Gr::load(go + e * C, g);
-                In::load(E + ((size_t)b * N + nb) * ld + col, eb);
+                tpg_load_row(go + e * C, g);
+                tpg_load_row(E + ((size_t)b * N + nb) * ld + col, eb);
 #pragma unroll
                 for (int i = 0; i < NE; ++i) accE[i] -= (eb[i] - en[i] > 0.0f) ? g[i] : g[i] * slope;
             }
-            In::store(gE + (size_t)drow * ld + col, accE);
+            tpg_store_row(gE + (size_t)drow * ld + col, accE);
             if (Uraw) {
                 float a[NE];
-                In::load(Uraw + (size_t)drow * ld + col, a);
+                tpg_load_row(Uraw + (size_t)drow * ld + col, a);
 #pragma unroll
                 for (int i = 0; i < NE; ++i) acc[i] = a[i] > 0.0f ? acc[i] : acc[i] * slope_u;
             }
         }
-        In::store(gU + (size_t)drow * ld + col, acc);
+        tpg_store_row(gU + (size_t)drow * ld + col, acc);
     }
 }
 
@@ -324,9 +254,7 @@ __global__ __launch_bounds__(256) void rowcombine_bwd_wave_kernel(
     const TG *__restrict__ gout, const int32_t *__restrict__ idx, const int32_t *__restrict__ offs,
     const int32_t *__restrict__ list, const TI *__restrict__ E, int N, int S, int K, int C, float slope,
     TI *__restrict__ gU, TI *__restrict__ gE, unsigned rows, int ld, const TI *__restrict__ Uraw, float slope_u) {
-    constexpr int NE = Elems<TI, TG>::NE;
-    using In = RowIO<TI, NE>;
-    using Gr = RowIO<TG, NE>;
+    constexpr int NE = tpg_elems<TI, TG>::NE;
     const unsigned cpr = (unsigned)C / NE;          // 1, 2, 4 .. 64
     const unsigned G = 64u / cpr;                   // entries in flight per step
     const unsigned lane = threadIdx.x & 63u;
@@ -343,19 +271,19 @@ __global__ __launch_bounds__(256) void rowcombine_bwd_wave_kernel(
         float acc[NE], accE[NE], en[NE];
 #pragma unroll
         for (int i = 0; i < NE; ++i) { acc[i] = 0.0f; accE[i] = 0.0f; }
-        if (MODE == MODE_EDGE) In::load(E + (size_t)drow * ld + col, en);
+        if (MODE == MODE_EDGE) tpg_load_row(E + (size_t)drow * ld + col, en);
         const int p1 = of[n + 1];
         int p = of[n] + (int)grp;
         // two entries per lane group in flight
         for (; p + (int)G < p1; p += 2 * (int)G) {
             const int e0 = ls[p], e1 = ls[p + G];
             float g0[NE], g1[NE];
-            Gr::load(go + (size_t)e0 * C, g0);
-            Gr::load(go + (size_t)e1 * C, g1);
+            tpg_load_row(go + (size_t)e0 * C, g0);
+            tpg_load_row(go + (size_t)e1 * C, g1);
             if (MODE == MODE_EDGE) {
                 float s0[NE], s1[NE];
-                In::load(E + ((size_t)b * N + (unsigned)e0 / (unsigned)K) * ld + col, s0);
-                In::load(E + ((size_t)b * N + (unsigned)e1 / (unsigned)K) * ld + col, s1);
+                tpg_load_row(E + ((size_t)b * N + (unsigned)e0 / (unsigned)K) * ld + col, s0);
+                tpg_load_row(E + ((size_t)b * N + (unsigned)e1 / (unsigned)K) * ld + col, s1);
 #pragma unroll
                 for (int i = 0; i < NE; ++i) {
                     accE[i] += (en[i] - s0[i] > 0.0f) ? g0[i] : g0[i] * slope;
@@ -368,12 +296,12 @@ __global__ __launch_bounds__(256) void rowcombine_bwd_wave_kernel(
         if (p < p1) {
             const int e0 = ls[p];
             float g0[NE];
-            Gr::load(go + (size_t)e0 * C, g0);
+            tpg_load_row(go + (size_t)e0 * C, g0);
 #pragma unroll
             for (int i = 0; i < NE; ++i) acc[i] += g0[i];
             if (MODE == MODE_EDGE) {
                 float s0[NE];
-                In::load(E + ((size_t)b * N + (unsigned)e0 / (unsigned)K) * ld + col, s0);
+                tpg_load_row(E + ((size_t)b * N + (unsigned)e0 / (unsigned)K) * ld + col, s0);
 #pragma unroll
                 for (int i = 0; i < NE; ++i) accE[i] += (en[i] - s0[i] > 0.0f) ? g0[i] : g0[i] * slope;
             }
@@ -384,8 +312,8 @@ __global__ __launch_bounds__(256) void rowcombine_bwd_wave_kernel(
                 const size_t e = (size_t)n * K + k;
                 const int nb = tpg_clamp_idx(idx[(size_t)b * SK + e], N);
                 float g0[NE], eb[NE];
-                Gr::load(go + e * C, g0);
-                In::load(E + ((size_t)b * N + nb) * ld + col, eb);
+                tpg_load_row(go + e * C, g0);
+                tpg_load_row(E + ((size_t)b * N + nb) * ld + col, eb);
 #pragma unroll
                 for (int i = 0; i < NE; ++i) accE[i] -= (eb[i] - en[i] > 0.0f) ? g0[i] : g0[i] * slope;
             }
@@ -400,15 +328,15 @@ __global__ __launch_bounds__(256) void rowcombine_bwd_wave_kernel(
         }
         if (grp == 0) {
             if (MODE == MODE_EDGE) {
-                In::store(gE + (size_t)drow * ld + col, accE);
+                tpg_store_row(gE + (size_t)drow * ld + col, accE);
                 if (Uraw) {
                     float a[NE];
-                    In::load(Uraw + (size_t)drow * ld + col, a);
+                    tpg_load_row(Uraw + (size_t)drow * ld + col, a);
 #pragma unroll
                     for (int i = 0; i < NE; ++i) acc[i] = a[i] > 0.0f ? acc[i] : acc[i] * slope_u;
                 }
             }
-            In::store(gU + (size_t)drow * ld + col, acc);
+            tpg_store_row(gU + (size_t)drow * ld + col, acc);
         }
     }
 }
@@ -417,7 +345,7 @@ __global__ __launch_bounds__(256) void rowcombine_bwd_wave_kernel(
 template <typename TI, typename TG>
 __global__ __launch_bounds__(256) void rowsum_neg_kernel(const TG *__restrict__ gout, int K, int C,
                                                          TI *__restrict__ gQ, unsigned total) {
-    constexpr int NE = Elems<TI, TG>::NE;
+    constexpr int NE = tpg_elems<TI, TG>::NE;
     const unsigned cpr = (unsigned)C / NE;
     for (unsigned t = blockIdx.x * 256u + threadIdx.x; t < total; t += gridDim.x * 256u) {
         const unsigned bs = t / cpr;
@@ -429,7 +357,7 @@ __global__ __launch_bounds__(256) void rowsum_neg_kernel(const TG *__restrict__ 
         for (; k + 4 <= K; k += 4) {           // four independent row reads in flight, sequential sums
             float g[4][NE];
 #pragma unroll
-            for (int u = 0; u < 4; ++u) RowIO<TG, NE>::load(gout + ((size_t)bs * K + k + u) * C + col, g[u]);
+            for (int u = 0; u < 4; ++u) tpg_load_row(gout + ((size_t)bs * K + k + u) * C + col, g[u]);
 #pragma unroll
             for (int u = 0; u < 4; ++u)
 #pragma unroll
@@ -437,11 +365,11 @@ __global__ __launch_bounds__(256) void rowsum_neg_kernel(const TG *__restrict__ 
         }
         for (; k < K; ++k) {
             float g[NE];
-            RowIO<TG, NE>::load(gout + ((size_t)bs * K + k) * C + col, g);
+            tpg_load_row(gout + ((size_t)bs * K + k) * C + col, g);
 #pragma unroll
             for (int i = 0; i < NE; ++i) acc[i] -= g[i];
         }
-        RowIO<TI, NE>::store(gQ + (size_t)bs * C + col, acc);
+        tpg_store_row(gQ + (size_t)bs * C + col, acc);
     }
 }
 
@@ -459,7 +387,7 @@ bool dtype_ok(int d) { return d == TPG_DTYPE_F32 || d == TPG_DTYPE_BF16; }
 template <typename TI, typename TO>
 int fwd_go(const void *U, const void *QE, const int32_t *idx, int mode, int B, int N, int S, int K,
            int C, float slope, void *out, hipStream_t st, int ld, float slope_u) {
-    constexpr int NE = Elems<TI, TO>::NE;
+    constexpr int NE = tpg_elems<TI, TO>::NE;
     if (C % NE) return TPG_ERR_UNSUPPORTED;
     const unsigned long long total64 = (unsigned long long)B * S * K * (C / NE);
     if (total64 >= 0x7fffffffULL) return TPG_ERR_ARG;
@@ -484,7 +412,7 @@ template <typename TI, typename TG>
 int bwd_go(const void *gout, const int32_t *idx, const int32_t *offs, const int32_t *list, const void *E,
            int mode, int B, int N, int S, int K, int C, float slope, void *gU, void *gQE, hipStream_t st, int ld,
            const void *Uraw, float slope_u) {
-    constexpr int NE = Elems<TI, TG>::NE;
+    constexpr int NE = tpg_elems<TI, TG>::NE;
     if (C % NE) return TPG_ERR_UNSUPPORTED;
     const unsigned long long total64 = (unsigned long long)B * N * (C / NE);
     const unsigned long long totq64 = (unsigned long long)B * S * (C / NE);

@@ -28,23 +28,13 @@
 //   wgrad     dW = (gy * lrelu'(y))^T . x, db = column sums: row slabs, each walked in LDS-staged chunks -> fp32
 //             partial tiles -> a reduce launch that sums the slabs in a fixed order (bitwise reproducible; the bias
 //             is the weight of a constant-one input).
-#include <hip/hip_bf16.h>
-
-#include "tpg_common.hpp"
+#include "tpg_rows.hpp"
 
 namespace {
 
-using f4 = __attribute__((__vector_size__(4 * sizeof(float)))) float;
 #define RL_MFMA(a, b, c) __builtin_amdgcn_mfma_f32_16x16x4f32((a), (b), (c), 0, 0, 0)
 
 constexpr int RL_WG_CT = 16;         // wgrad: tiles per group (64 accumulator registers)
-
-__device__ __forceinline__ float rl_ld(const float *p) { return *p; }
-__device__ __forceinline__ float rl_ld(const __hip_bfloat16 *p) {
-    return __uint_as_float((unsigned)(*reinterpret_cast<const unsigned short *>(p)) << 16);
-}
-__device__ __forceinline__ void rl_st(float *p, float v) { *p = v; }
-__device__ __forceinline__ void rl_st(__hip_bfloat16 *p, float v) { *p = __float2bfloat16(v); }
 
 // f[s] = M[r][k + s], s = 0..3 (row-major, leading dimension ld = K): zero beyond K or when !ok.
 template <typename T>
@@ -53,26 +43,19 @@ __device__ __forceinline__ void rl_load_k4(const T *M, long long r, bool ok, int
     if (!ok || k >= K) return;
     const T *p = M + r * (long long)K + k;
     if (vec && k + 3 < K) {
-        if constexpr (sizeof(T) == 4) {
-            const float4 v = *reinterpret_cast<const float4 *>(p);
-            f[0] = v.x; f[1] = v.y; f[2] = v.z; f[3] = v.w;
-        } else {
-            const uint2 v = *reinterpret_cast<const uint2 *>(p);
-            f[0] = __uint_as_float(v.x << 16); f[1] = __uint_as_float(v.x & 0xffff0000u);
-            f[2] = __uint_as_float(v.y << 16); f[3] = __uint_as_float(v.y & 0xffff0000u);
-        }
+        tpg_load_row(p, f);
         return;
     }
 #pragma unroll
     for (int s = 0; s < 4; ++s)
-        if (k + s < K) f[s] = rl_ld(p + s);
+        if (k + s < K) f[s] = tpg_load_one(p + s);
 }
 
 // f[s] = M[k + s][c], s = 0..3 (rows k .. k+3 of a row-major (Krows x ld) matrix): zero beyond Krows or when !ok.
 template <typename T>
 __device__ __forceinline__ void rl_load_r4(const T *M, long long k, long long Krows, int ld, int c, bool ok, float (&f)[4]) {
 #pragma unroll
-    for (int s = 0; s < 4; ++s) f[s] = (ok && k + s < Krows) ? rl_ld(M + (k + s) * (long long)ld + c) : 0.0f;
+    for (int s = 0; s < 4; ++s) f[s] = (ok && k + s < Krows) ? tpg_load_one(M + (k + s) * (long long)ld + c) : 0.0f;
 }
 
 // ---- forward / dgrad ---------------------------------------------------------------------------------------------
@@ -167,9 +150,9 @@ __global__ __launch_bounds__(RL_THREADS) void rowlin_kernel(const TA *__restrict
         }
         __syncthreads();
         if (r0 >= P) continue;                                        // (the wave still takes part in the barriers)
-        f4 acc[RL_NP_MAX / 16];
+        tpg_f32x4 acc[RL_NP_MAX / 16];
 #pragma unroll
-        for (int c = 0; c < RL_NP_MAX / 16; ++c) acc[c] = f4{0.0f, 0.0f, 0.0f, 0.0f};
+        for (int c = 0; c < RL_NP_MAX / 16; ++c) acc[c] = tpg_f32x4{0.0f, 0.0f, 0.0f, 0.0f};
         // software-pipelined k loop (NOT unrolled: ~90 live registers, several waves per SIMD): the A fragment of the
         // next 16 k's is in flight while this one meets its <= 8 B fragments
         float a[4], an[4];
@@ -215,7 +198,7 @@ __global__ __launch_bounds__(RL_THREADS) void rowlin_kernel(const TA *__restrict
                 if (p < P) {
                     float v = acc[c][i] + bv;
                     if (!BT) v = v > 0.0f ? v : v * slope_out;
-                    rl_st(out + p * (long long)N + n, v);
+                    tpg_store_one(out + p * (long long)N + n, v);
                 }
             }
         }
@@ -248,11 +231,11 @@ __global__ __launch_bounds__(256) void rowlin_wgrad_kernel(const TX *__restrict_
     // a wave keeps the accumulators of two tile groups across the chunks; more than 8 groups (Cout * Cin beyond
     // ~128 x 256) take further rounds over the slab
     for (int gb = 0; gb < ngroups; gb += 8) {
-        f4 acc[2][RL_WG_CT];
+        tpg_f32x4 acc[2][RL_WG_CT];
 #pragma unroll
         for (int u = 0; u < 2; ++u)
 #pragma unroll
-            for (int c = 0; c < RL_WG_CT; ++c) acc[u][c] = f4{0.0f, 0.0f, 0.0f, 0.0f};
+            for (int c = 0; c < RL_WG_CT; ++c) acc[u][c] = tpg_f32x4{0.0f, 0.0f, 0.0f, 0.0f};
         for (long long c0r = p0; c0r < p1; c0r += RC) {
             const int rows = (int)min((long long)RC, p1 - c0r);
             __syncthreads();
@@ -268,8 +251,8 @@ __global__ __launch_bounds__(256) void rowlin_wgrad_kernel(const TX *__restrict_
 #pragma unroll
                         for (int j = 0; j < 4; ++j)
                             if (rin && o + j < Cout) {
-                                v[j] = rl_ld(gsrc + o + j);
-                                if (ysrc != nullptr) v[j] = rl_ld(ysrc + o + j) > 0.0f ? v[j] : v[j] * slope;
+                                v[j] = tpg_load_one(gsrc + o + j);
+                                if (ysrc != nullptr) v[j] = tpg_load_one(ysrc + o + j) > 0.0f ? v[j] : v[j] * slope;
                             }
                         *reinterpret_cast<float4 *>(Gl + pr * GS + o) = make_float4(v[0], v[1], v[2], v[3]);
                     }
@@ -278,7 +261,7 @@ __global__ __launch_bounds__(256) void rowlin_wgrad_kernel(const TX *__restrict_
                         float v[4] = {0.0f, 0.0f, 0.0f, 0.0f};
 #pragma unroll
                         for (int j = 0; j < 4; ++j)
-                            if (rin) v[j] = c + j < Cin ? rl_ld(xsrc + c + j) : ((c + j == Cin && has_bias) ? 1.0f : 0.0f);
+                            if (rin) v[j] = c + j < Cin ? tpg_load_one(xsrc + c + j) : ((c + j == Cin && has_bias) ? 1.0f : 0.0f);
                         *reinterpret_cast<float4 *>(Xl + pr * XS + c) = make_float4(v[0], v[1], v[2], v[3]);
                     }
                 }

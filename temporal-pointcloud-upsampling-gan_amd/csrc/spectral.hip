@@ -18,21 +18,15 @@ namespace {
 
 constexpr int SN_THREADS = 1024;
 
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) v += __shfl_xor(v, d);
-    return v;
-}
-
 // sum over the workgroup, result broadcast to every thread (scratch: 16 floats)
 __device__ __forceinline__ float block_sum(float v, float *scratch) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    v = wave_sum(v);
+    v = tpg_wave_sum(v);
     __syncthreads();
     if (lane == 0) scratch[wave] = v;
     __syncthreads();
     float t = lane < (SN_THREADS / 64) ? scratch[lane] : 0.0f;
-    return wave_sum(t);
+    return tpg_wave_sum(t);
 }
 
 __global__ __launch_bounds__(SN_THREADS) void spectral_norm_fwd_kernel(
@@ -62,7 +56,7 @@ __global__ __launch_bounds__(SN_THREADS) void spectral_norm_fwd_kernel(
     for (int i = wave; i < R; i += SN_THREADS / 64) {
         float s = 0.0f;
         for (int j = lane; j < Cn; j += 64) s += W[(size_t)i * Cn + j] * sv[j];
-        s = wave_sum(s);
+        s = tpg_wave_sum(s);
         if (lane == 0) su[i] = s;   // su now holds s = W v (the old u was consumed above)
     }
     __syncthreads();
@@ -180,7 +174,7 @@ __global__ __launch_bounds__(SN_THREADS) void spectral_norm_multi_fwd_kernel(con
         for (int i = wave; i < R; i += SN_THREADS / 64) {  // s = W v, wave per row
             float sacc = 0.0f;
             for (int j = lane; j < Cn; j += 64) sacc += W[(size_t)i * Cn + j] * sv[j];
-            sacc = wave_sum(sacc);
+            sacc = tpg_wave_sum(sacc);
             if (lane == 0) {
                 ou[i] = sacc;               // raw s = W v (eval mode reads it for sigma below)
                 if (iterate) su[i] = sacc;  // training: u <- s, normalised below
@@ -246,7 +240,7 @@ struct SnSplitDesc {
 
 __device__ __forceinline__ float sns_block_sum(float v, float *scratch) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    v = wave_sum(v);
+    v = tpg_wave_sum(v);
     __syncthreads();
     if (lane == 0) scratch[wave] = v;
     __syncthreads();
@@ -460,7 +454,7 @@ __global__ __launch_bounds__(SNS_THREADS) void spectral_norm_split_kernel(const 
             float a = 0.0f;
 #pragma unroll
             for (int c = 0; c < SN_CB; ++c) a += w[r][c] * vloc[c];
-            a = wave_sum(a);
+            a = tpg_wave_sum(a);
             if (lane == 0) ss[wave * SNS_RW + r] = a;
         }
         __syncthreads();

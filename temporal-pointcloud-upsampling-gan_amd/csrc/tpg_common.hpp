@@ -1,4 +1,5 @@
-// Shared device helpers for the gfx950 kernels.  wave = 64 lanes everywhere.
+// Shared helpers for the gfx950 kernels: launch plumbing, cross-lane moves, wave reductions.  wave = 64 lanes
+// everywhere.  (Row chunks and bf16 conversion: tpg_rows.hpp; the BatchNorm finalize pieces: tpg_bn_finalize.hpp.)
 //
 // Every translation unit is compiled with -ffp-contract=off: the canonical
 // distance sum_d (a_d-b_d)^2 must round each mul and add separately so that
@@ -19,6 +20,28 @@
 typedef unsigned long long tpg_u64;
 
 static inline hipStream_t tpg_stream(void *s) { return reinterpret_cast<hipStream_t>(s); }
+
+// Opt kernel `Kern` in to `bytes` of dynamic LDS (launches asking for more than the default limit fail without it).
+// hipFuncSetAttribute is PER DEVICE and not a stream operation: it must stay outside captured launch sequences, so
+// the device's answer, yes or no, is remembered per device and the warm-up call is the only one that reaches the
+// runtime.  Pass the most the kernel can ever ask for.  false: the device refuses (the sticky error is cleared; the
+// caller decides), or its index is beyond the TPG_MAX_DEVICES answers kept here.
+constexpr int TPG_MAX_DEVICES = 64;
+template <auto Kern> inline bool tpg_allow_dynamic_lds(int bytes) {
+    static signed char answer[TPG_MAX_DEVICES] = {};     // 0 not asked, 1 granted, -1 refused (a race only asks twice)
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= TPG_MAX_DEVICES) {
+        (void)hipGetLastError();
+        return false;
+    }
+    if (answer[dev] == 0) {
+        const bool ok = hipFuncSetAttribute(reinterpret_cast<const void *>(Kern),
+                                            hipFuncAttributeMaxDynamicSharedMemorySize, bytes) == hipSuccess;
+        if (!ok) (void)hipGetLastError();
+        answer[dev] = ok ? 1 : -1;
+    }
+    return answer[dev] > 0;
+}
 
 __device__ __forceinline__ float tpg_sq3(float ax, float ay, float az, float bx, float by,
                                          float bz) {
@@ -123,6 +146,13 @@ __device__ __forceinline__ unsigned tpg_row16_min_u32(unsigned v) {
     v = min(v, (unsigned)tpg_dpp_full<0x124>((int)v));
     v = min(v, (unsigned)tpg_dpp_full<0x128>((int)v));
     return (unsigned)__builtin_amdgcn_readlane((int)v, 0);
+}
+
+// sum over the wave in every lane (xor butterfly: every lane ends with the same bits)
+__device__ __forceinline__ float tpg_wave_sum(float v) {
+#pragma unroll
+    for (int d = 32; d > 0; d >>= 1) v += __shfl_xor(v, d);
+    return v;
 }
 
 // clamp an index into [0, n) -- invalid indices are undefined behaviour upstream;

@@ -140,6 +140,18 @@ class HipBackend:
         if ws is not None:
             self._ws_retired.append(ws)
 
+    def _workspace(self, kind, ref, need, dtype=torch.float32, zeroed=False):
+        """The grow-only scratch buffer of `kind` (>= need elements of dtype) on ref's device and current stream.
+        One buffer per (kind, device, stream), reused by every call: launches on a stream are ordered, so the next
+        call cannot start before the previous one has consumed it.  zeroed: filled with zeros when it is created."""
+        key = (kind, ref.device, torch.cuda.current_stream(ref.device).cuda_stream)
+        ws = self._ws.get(key)
+        if ws is None or ws.numel() < need:
+            self._retire(ws)
+            ws = (torch.zeros if zeroed else torch.empty)(need, dtype=dtype, device=ref.device)
+            self._ws[key] = ws
+        return ws
+
     def _call(self, symbol, op, nbytes, ref, *args, flops=0):
         fn = getattr(self.lib, symbol)
         with _DeviceGuard(ref):
@@ -157,14 +169,7 @@ class HipBackend:
     CHAMFER_GRID_MIN_POINTS = 8192
 
     def _grid_ws(self, ref, B, P2):
-        need = self.lib.tpg_frnn_grid_workspace_bytes(B, P2)
-        key = ("frnn", ref.device, torch.cuda.current_stream(ref.device).cuda_stream)
-        ws = self._ws.get(key)
-        if ws is None or ws.numel() < need:
-            self._retire(ws)
-            ws = torch.empty(need, dtype=torch.uint8, device=ref.device)
-            self._ws[key] = ws
-        return ws
+        return self._workspace("frnn", ref, self.lib.tpg_frnn_grid_workspace_bytes(B, P2), dtype=torch.uint8)
 
     def knn(self, p1, p2, len1, len2, K, r2, r=None):
         B, P1, D = p1.shape
@@ -495,16 +500,8 @@ class HipBackend:
 
     # ---- fused BatchNorm + LeakyReLU (+ max over K) on rows (csrc/rowbn.hip) -------------
     def _bn_ws(self, x, C_, nseg=1):
-        # one scratch buffer per (device, stream), reused by every call: launches on a stream are
-        # ordered, so the next call cannot start before the previous one has consumed it
-        key = (x.device, torch.cuda.current_stream(x.device).cuda_stream)
-        ws = self._ws.get(key)
         need = self.lib.tpg_rowbn_workspace_bytes(max(C_, 256), max(nseg, 1)) // 4
-        if ws is None or ws.numel() < need:
-            self._retire(ws)
-            ws = torch.zeros(need, dtype=torch.float32, device=x.device)
-            self._ws[key] = ws
-        return ws
+        return self._workspace("rowbn", x, need, zeroed=True)
 
     def rowbn_fwd(self, x, K, eps, momentum, training, running_mean, running_var, gamma, beta, slope,
                   mean, rstd, out_dtype, num_batches_tracked=None, nseg=1, mean_shift=None):
@@ -554,14 +551,8 @@ class HipBackend:
 
     # ---- fused MLP tail layer on MFMA tiles (csrc/mlp_fused.hip) ---------------------------
     def _mlp_ws(self, x, C_, nseg):
-        key = ("mlp", x.device, torch.cuda.current_stream(x.device).cuda_stream)
-        ws = self._ws.get(key)
         need = self.lib.tpg_mlp_workspace_bytes(max(C_, 256), max(nseg, 1)) // 4
-        if ws is None or ws.numel() < need:
-            self._retire(ws)
-            ws = torch.zeros(need, dtype=torch.float32, device=x.device)
-            self._ws[key] = ws
-        return ws
+        return self._workspace("mlp", x, need, zeroed=True)
 
     def mlp_fwd(self, x, ss_in, slope_in, W, nseg, eps=0.0, momentum=0.0, running_mean=None, running_var=None,
                 num_batches_tracked=None, mean_shift=None, gamma_out=None, beta_out=None, stats=True, mean_rstd=False):
@@ -689,13 +680,7 @@ class HipBackend:
         Cin = x_in.shape[1]
         mode = 1 if arg is not None else 0
         dW = torch.empty((nseg, Cout, Cin), dtype=torch.float32, device=x_out.device)
-        need = self.lib.tpg_mlp_wgrad_workspace_bytes(P, Cin, Cout, nseg) // 4
-        key = ("wgrad", x_out.device, torch.cuda.current_stream(x_out.device).cuda_stream)
-        ws = self._ws.get(key)
-        if ws is None or ws.numel() < need:
-            self._retire(ws)
-            ws = torch.empty(need, dtype=torch.float32, device=x_out.device)
-            self._ws[key] = ws
+        ws = self._workspace("wgrad", x_out, self.lib.tpg_mlp_wgrad_workspace_bytes(P, Cin, Cout, nseg) // 4)
         self._call("tpg_mlp_wgrad", "mlp_wgrad", 2 * P * (Cout + Cin) + (0 if mode else 2 * P * Cout), x_out,
                    _ptr(x_out), _ptr(g_out), _ptr(arg), int(K), _ptr(cb_out), _ptr(x_in), _ptr(ci_in),
                    float(slope_in), P, Cin, Cout, nseg, mode, _ptr(dW), _ptr(ws), flops=2 * P * Cin * Cout)
@@ -721,13 +706,7 @@ class HipBackend:
         gh = torch.empty_like(h)
         dW1 = torch.empty((C1, H), dtype=torch.float32, device=h.device)
         dW2 = torch.empty((C2, C1), dtype=torch.float32, device=h.device)
-        need = max(16, self.lib.tpg_small_tail_workspace_bytes(P, int(K)) // 4)
-        key = ("small_tail", h.device, torch.cuda.current_stream(h.device).cuda_stream)
-        ws = self._ws.get(key)
-        if ws is None or ws.numel() < need:
-            self._retire(ws)
-            ws = torch.empty(need, dtype=torch.float32, device=h.device)
-            self._ws[key] = ws
+        ws = self._workspace("small_tail", h, max(16, self.lib.tpg_small_tail_workspace_bytes(P, int(K)) // 4))
         self._call("tpg_small_tail_bwd", "small_tail_bwd", h.element_size() * (2 * E * H + 2 * P * C2) + P * C2, h,
                    _ptr(h), _ptr(out), _ptr(gout), _ptr(arg), 1 if h.dtype == torch.bfloat16 else 0, _ptr(W1), _ptr(W2),
                    float(s1), float(s2), P, int(K), H, C1, C2, _ptr(gh), _ptr(dW1), _ptr(dW2), _ptr(ws),
@@ -838,12 +817,7 @@ class HipBackend:
         dW = torch.empty((nseg, Cout, Cin), dtype=torch.float32, device=x.device)
         db = torch.empty(Cout, dtype=torch.float32, device=x.device) if need_bias else None
         need = self.lib.tpg_rowlinear_wgrad_workspace_bytes(P, int(nseg), Cin, Cout, int(bool(need_bias))) // 4 + 4
-        key = ("rowlinear", x.device, torch.cuda.current_stream(x.device).cuda_stream)
-        ws = self._ws.get(key)
-        if ws is None or ws.numel() < need:
-            self._retire(ws)
-            ws = torch.empty(need, dtype=torch.float32, device=x.device)
-            self._ws[key] = ws
+        ws = self._workspace("rowlinear", x, need)
         self._call("tpg_rowlinear_wgrad", "rowlinear_wgrad", x.element_size() * P * Cin + gy.element_size() * P * Cout
                    * (2 if y is not None else 1), x,
                    _ptr(x), _DTYPE_CODE[x.dtype], _ptr(gy), _ptr(y), _DTYPE_CODE[gy.dtype], P, int(nseg), Cin, Cout,
