@@ -548,6 +548,44 @@ int tpg_clip_gather_low_f32(const float *high_pos, const int32_t *fps, const flo
                             const float *vel, long long P, const int32_t *frame_first, const int32_t *count, int T,
                             int B, int K, int M, float *low_pos, float *low_vel, void *stream);
 
+/* ---- action clips from device-resident depth videos (csrc/action_sample.hip) ----------------------------------
+ * train_action/msr_dataset.py:60-135 (MSRAction3D.__getitem__), which the reference runs per clip on host workers (per
+ * frame an np.random.choice, a numpy gather and a numba FPS from 2048 down to 128 points).  The frames of a depth video
+ * are RAGGED: every frame has its own point count.  Here every frame stays on the device and a batch is four calls:
+ * tpg_frame_subset, tpg_action_gather_f32, ONE tpg_fps_start_f32 over all T*B clouds, tpg_clip_gather_low_f32 with the
+ * batch viewed as (1, T*B, K, 3).  The arrays marked HOST follow the exception stated for the clip sampler above.
+ *
+ * tpg_frame_subset: a uniformly random ordered subset of K points of each of F frames (np.random.choice(n, K,
+ * replace=False), msr_dataset.py:69-74).  count (F) HOST: points per frame; seed (F) HOST: one 64-bit seed per frame,
+ * seed_lo / seed_hi its low / high 32 bits.  idx (F,K) int32, frame-local.  Key of point j, uint32 arithmetic, wrapping:
+ *     mix(h):  h ^= h>>16; h *= 0x7FEB352D; h ^= h>>15; h *= 0x846CA68B; h ^= h>>16
+ *     key(j) = mix( mix(j * 0x9E3779B1 + seed_lo) ^ seed_hi )
+ * (a bijection of uint32: the keys of a frame are distinct).  Candidates are ordered by ascending (key, j).
+ *     n >  K: the K smallest, in that order;
+ *     n <= K: 0..n-1 repeated K / n times, then the K % n smallest in that order (n = K: the identity).
+ * A pure function of (count, seed, K): bit-identical from run to run and at every batch position (integer atomics on LDS
+ * histograms and a final sort of unique keys only).  One workgroup per frame selects and orders in LDS, so there is
+ * no workspace; the frame's keys are recomputed in each of its four passes, which suits depth frames (10^3..10^5 points).
+ * count[f] < 1 or K < 1: TPG_ERR_ARG, nothing written; K > TPG_PATCH_SELECT_MAX_K: TPG_ERR_UNSUPPORTED. */
+int tpg_frame_subset(const int32_t *count, const uint64_t *seed, int F, int K, int32_t *idx, void *stream);
+
+/* All high-resolution clouds of a batch of B clips of T <= 8 frames (msr_dataset.py:67-91 train, :105-127 test).
+ * points (P,3) f32: every stored frame back to back; frame_first (T,B) HOST, count (T,B) HOST: clip b's frame t is
+ * points[frame_first[t,b] .. + count[t,b]); idx (T,B,K) int32 from tpg_frame_subset (entries are clamped into the
+ * frame); scale (B,3) f64 HOST or NULL (= ones).  With q = (double)p, y negated, and v = (q * scale[b]) / 300.0 in
+ * fp64, in this operation order:
+ *     TPG_ACTION_TRAIN  c[b] = fp64 mean of v over the K rows of frame T/2;  high[t,b,k,:] = (float)(v - c[b]);
+ *                       centre must be NULL
+ *     TPG_ACTION_TEST   c[t,b] = fp64 mean of v over the K rows of frame t;  high[t,b,k,:] = (float)(v - c[t,b]);
+ *                       scale must be NULL; centre (T,B,3) f32 receives (float)c
+ * The mean is summed in a fixed order (no floating-point atomics): bit-identical from run to run.  high (T,B,K,3) is
+ * frame-major like tpg_clip_gather_high_f32's.  A frame outside [0, P), count < 1, a non-finite scale: TPG_ERR_ARG. */
+#define TPG_ACTION_TRAIN 0
+#define TPG_ACTION_TEST 1
+int tpg_action_gather_f32(const float *points, long long P, const int32_t *frame_first, const int32_t *count,
+                          const int32_t *idx, const double *scale, int mode, int T, int B, int K, float *high,
+                          float *centre, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

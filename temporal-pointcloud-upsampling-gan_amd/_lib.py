@@ -74,6 +74,8 @@ SIGNATURES = {
     "tpg_patch_select_f32": [_P, _L, _P, _P, _P, _I, _I, _P, _P, _P],
     "tpg_clip_gather_high_f32": [_P, _P, _L, _P, _P, _P, _I, _P, _P, _I, _I, _I, _P, _P, _P],
     "tpg_clip_gather_low_f32": [_P, _P, _P, _F, _P, _L, _P, _P, _I, _I, _I, _I, _P, _P, _P],
+    "tpg_frame_subset": [_P, _P, _I, _I, _P, _P],
+    "tpg_action_gather_f32": [_P, _L, _P, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P],
 }
 SIZE_GETTERS = ("tpg_rowbn_workspace_bytes", "tpg_mlp_workspace_bytes", "tpg_context_expand_workspace_bytes")
 OTHER_GETTERS = ("tpg_spectral_norm_multi_stride", "tpg_spectral_norm_multi_bwd_scratch",

@@ -6,8 +6,13 @@ in HBM many times over, so here every frame is loaded ONCE (`FluidSequences`) an
 size (`ClipSampler`): ops.patch_select, ops.clip_gather_high, the dataset-side FPS on the centre frame's patch,
 ops.clip_gather_low -- plus the draw of the jitter noise.  `prefetch` prepares batch n+1 on a side stream while the
 step consumes batch n.
+
+The action upsampler's clips (train_action/msr_dataset.py) come the same way from depth videos whose frames are ragged:
+`ActionSequences` and `ActionClipSampler` (ops.frame_subset, ops.action_gather, one FPS over all frames,
+ops.clip_gather_low), under the same `prefetch`.
 """
 import os
+import re
 
 import numpy as np
 import torch
@@ -152,6 +157,144 @@ class ClipSampler:
         self.last = {"patch_idx": patch, "fps_idx": fps_idx, "indices": [int(indices[i]) for i in keep]}
         return (*high_pos.unbind(0), *high_vel.unbind(0), *low_pos.unbind(0), *low_vel.unbind(0),
                 torch.ones(B, dtype=torch.float32))
+
+    def __iter__(self):
+        while True:
+            yield self.sample()
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# Action clips from depth videos (train_action/msr_dataset.py on the GPU)
+_ACTION_FILE = re.compile(r"^a(\d+)_s(\d+)_e(\d+)_sdepth\.npz$")
+
+
+class ActionSequences:
+    """Depth videos `a{label}_s{subject}_e{..}_sdepth.npz` under `root` (key `point_clouds`: an object array of (n_i,3)
+    frames, every frame with its own point count), loaded once: all frames cast to fp32 and stored back to back on
+    `device`, with per-frame `first` / `count` (host int64) and per-video `video_first` (index of its first frame).
+
+    The split, the labels, `num_classes` and `index_map` are MSRAction3D's (msr_dataset.py:26-52): train = subject <= 5,
+    test = subject > 5, label = the file's action number - 1, one clip per start frame t in
+    range(0, nframes - step_between_clips * (frames_per_clip - 1), step_between_clips).  DEVIATION: the files are read
+    in SORTED name order (the reference's `os.listdir` order is the file system's), so a video's index does not depend on
+    the machine.  Other files in the directory are ignored."""
+
+    def __init__(self, root, train=True, frames_per_clip=3, step_between_clips=1, device="cuda"):
+        if frames_per_clip < 1 or step_between_clips < 1:
+            raise ValueError("frames_per_clip and step_between_clips must be positive")
+        self.root, self.train = root, bool(train)
+        self.frames_per_clip, self.step_between_clips = int(frames_per_clip), int(step_between_clips)
+        self.device = torch.device(device)
+        self.names, self.labels, self.index_map = [], [], []
+        frames, counts, video_first = [], [], []
+        for name in sorted(os.listdir(root)):
+            m = _ACTION_FILE.match(name)
+            if m is None or (int(m.group(2)) <= 5) != self.train:
+                continue
+            with np.load(os.path.join(root, name), allow_pickle=True) as f:
+                video = f["point_clouds"]
+            index = len(self.names)
+            self.names.append(name)
+            self.labels.append(int(m.group(1)) - 1)
+            video_first.append(len(frames))
+            for i, p in enumerate(video):
+                p = np.asarray(p)
+                if p.ndim != 2 or p.shape[1] != 3:
+                    raise ValueError(f"{os.path.join(root, name)}: frame {i} must be an (n,3) array, got {p.shape}")
+                if p.shape[0] == 0:
+                    raise ValueError(f"{os.path.join(root, name)}: frame {i} is empty: a clip cannot sample from it")
+                frames.append(p.astype(np.float32))
+                counts.append(p.shape[0])
+            span = self.step_between_clips * (self.frames_per_clip - 1)
+            for t in range(0, len(video) - span, self.step_between_clips):
+                self.index_map.append((index, t))
+        if not self.names:
+            raise ValueError(f"{root}: no {'train' if self.train else 'test'} video (a*_s*_e*_sdepth.npz)")
+        self.count = np.array(counts, np.int64)
+        self.first = np.concatenate([[0], np.cumsum(self.count)[:-1]]).astype(np.int64)
+        self.video_first = np.array(video_first, np.int64)
+        total = int(self.count.sum())
+        if total >= 2 ** 31:
+            raise ValueError(f"{total} points: frame offsets must fit int32")
+        self.points = torch.from_numpy(np.concatenate(frames)).to(self.device)
+        self.num_classes = max(self.labels) + 1
+
+    def __len__(self):
+        return len(self.index_map)
+
+    def clip(self, idx):
+        """Clip index -> (video, first frame); the clip is frames t, t + step, ... of that video."""
+        if not 0 <= idx < len(self):
+            raise IndexError(idx)
+        return self.index_map[idx]
+
+    def frame_rows(self, idx):
+        """Rows of the clip's frames in `first` / `count`."""
+        video, t = self.clip(idx)
+        return self.video_first[video] + t + self.step_between_clips * np.arange(self.frames_per_clip)
+
+
+class ActionClipSampler:
+    """Batches of action clips in the reference's layout (msr_dataset.py:98,133-135, default collate): a flat tuple of
+    T high-resolution (B,K,3) and T low-resolution (B,K/16,3) tensors on the sequences' device and `label` (B,) int64 on
+    the host; for test sequences additionally the T per-frame centres (B,3) before the label and the video index (B,)
+    int64 on the host after it.
+
+    Per frame the high-resolution cloud is a uniformly random ordered subset of `num_points` points (a frame with no
+    more points than that is repeated and padded with a random residue), y negated, scaled per clip (train) and divided
+    by 300, centred on the middle frame's mean (train) or its own (test); every frame gets its own FPS down to K / 16.
+    A batch is four launches whatever its size: ops.frame_subset, ops.action_gather, ONE FPS over all T * B clouds,
+    ops.clip_gather_low.  All randomness -- clip indices, one 64-bit subset seed per frame, the scales ~ U(0.9, 1.1) in
+    float64 per clip (train only), one FPS start per frame -- comes from ONE host torch.Generator, in that order."""
+
+    def __init__(self, sequences, batch_size, num_points=2048, generator=None):
+        if num_points < 16 or num_points % 16:
+            raise ValueError("num_points must be a positive multiple of 16 (the low resolution is num_points / 16)")
+        self.seq, self.batch_size, self.num_points = sequences, int(batch_size), int(num_points)
+        self.frames = sequences.frames_per_clip
+        self.generator = generator if generator is not None else torch.Generator().manual_seed(0)
+        self.device = sequences.device
+
+    def sample(self, indices=None, subset_idx=None, scales=None, initial_idx=None):
+        """One batch.  indices: clip indices (default: batch_size draws); scales: (B,3) float64 per clip (train only;
+        default: drawn); initial_idx: (T,B) the FPS' first pick per frame, a position in the subset (default: drawn).
+        Given values replace the draws (the generator advances as if they had been drawn).  subset_idx (T,B,K) int32 on the device: frame-local point lists that replace
+        the selection itself (a comparison with another implementation's subsets)."""
+        seq, K, T, g = self.seq, self.num_points, self.frames, self.generator
+        if indices is None:
+            indices = torch.randint(len(seq), (self.batch_size,), generator=g).tolist()
+        indices = [int(i) for i in indices]
+        B = len(indices)
+        rows = np.stack([seq.frame_rows(i) for i in indices], 1)                                 # (T,B)
+        frame_first, count = seq.first[rows], seq.count[rows]
+        halves = torch.randint(2 ** 32, (T * B, 2), generator=g).numpy().astype(np.uint64)
+        if seq.train:
+            drawn = 0.9 + 0.2 * torch.rand((B, 3), dtype=torch.float64, generator=g).numpy()
+            scales = drawn if scales is None else np.asarray(scales, np.float64).reshape(B, 3)
+        elif scales is not None:
+            raise ValueError("the test split has no scales")
+        starts = torch.randint(K, (T, B), generator=g)
+        if initial_idx is not None:
+            starts = torch.as_tensor(np.asarray(initial_idx)).reshape(T, B)
+        if subset_idx is None:
+            subset = ops.frame_subset(count.reshape(-1), (halves[:, 1] << np.uint64(32)) | halves[:, 0], K,
+                                      device=self.device).view(T, B, K)
+        else:
+            if tuple(subset_idx.shape) != (T, B, K):
+                raise ValueError(f"subset_idx must be ({T}, {B}, {K})")
+            subset = subset_idx
+        high, centres = ops.action_gather(seq.points, frame_first, count, subset, scales,
+                                          "train" if seq.train else "test")
+        start = starts.to(torch.int32).reshape(T * B).to(self.device, non_blocking=True)
+        fps_idx = ops.backend_for(high).fps(high.view(T * B, K, 3), K // 16, start, False)
+        low, _ = ops.clip_gather_low(high.view(1, T * B, K, 3), fps_idx)
+        low = low.view(T, B, K // 16, 3)
+        self.last = {"subset_idx": subset, "fps_idx": fps_idx.view(T, B, K // 16), "indices": indices, "scales": scales}
+        label = torch.tensor([seq.labels[seq.clip(i)[0]] for i in indices], dtype=torch.int64)
+        if seq.train:
+            return (*high.unbind(0), *low.unbind(0), label)
+        video = torch.tensor([seq.clip(i)[0] for i in indices], dtype=torch.int64)
+        return (*high.unbind(0), *low.unbind(0), *centres.unbind(0), label, video)
 
     def __iter__(self):
         while True:

@@ -329,6 +329,24 @@ class HipBackend:
                    None if vel is None else count.ctypes.data, T, B, K, M, _ptr(low_pos), _ptr(low_vel))
         return low_pos, low_vel
 
+    def frame_subset(self, count, seed, K, device):
+        """tpg_frame_subset: count (F,) int32 / seed (F,) uint64 are host arrays (numpy); -> idx (F,K) int32 on `device`."""
+        F = len(count)
+        idx = torch.empty((F, K), dtype=torch.int32, device=device)
+        self._call("tpg_frame_subset", "frame_subset", 4 * F * K, idx, count.ctypes.data, seed.ctypes.data, F, K, _ptr(idx))
+        return idx
+
+    def action_gather(self, points, frame_first, count, idx, scale, per_frame):
+        """tpg_action_gather_f32: frame_first / count (T,B) int32 and scale (B,3) float64 (or None) are host arrays
+        (numpy); per_frame selects the test split.  -> (high (T,B,K,3), centre (T,B,3) or None)."""
+        T, B, K = idx.shape
+        high = torch.empty((T, B, K, 3), dtype=torch.float32, device=points.device)
+        centre = torch.empty((T, B, 3), dtype=torch.float32, device=points.device) if per_frame else None
+        self._call("tpg_action_gather_f32", "action_gather", 28 * T * B * K, points,
+                   _ptr(points), points.shape[0], frame_first.ctypes.data, count.ctypes.data, _ptr(idx),
+                   None if scale is None else scale.ctypes.data, 1 if per_frame else 0, T, B, K, _ptr(high), _ptr(centre))
+        return high, centre
+
     def fps(self, xyz, m, start=None, skip_origin=True):
         B, N, _ = xyz.shape
         idx = torch.empty((B, m), dtype=torch.int32, device=xyz.device)
@@ -1128,6 +1146,73 @@ def clip_gather_low(high_pos, fps_idx, noise=None, jitter=0.0, vel=None, frame_f
         rows = torch.as_tensor(frame_first, dtype=torch.long, device=vel.device).view(T, B, 1) \
             + torch.minimum(fps_idx.long().view(1, B, M), lim)
         return low, vel[rows]
+
+
+# --------------------------------------------- action clips from device-resident depth videos (csrc/action_sample.hip)
+def frame_subset_max_k():
+    return _lib.load().tpg_patch_select_max_k()
+
+
+def frame_subset(count, seeds, K, device="cuda"):
+    """A uniformly random ordered subset of K points of every frame of a ragged batch: the reference's
+    `np.random.choice(n, K, replace=False)` per frame (msr_dataset.py:69-74) on the device.
+
+    count / seeds: (F,) HOST integers (list, numpy or CPU tensor): points per frame, and one 64-bit seed per frame
+    (0 <= seed < 2^64).  -> idx (F,K) int32 on `device`, frame-local: by ascending (key, j) with the hash key of
+    include/tpgan_ops.h, the K smallest if a frame has more than K points, else 0..n-1 repeated K // n times followed by
+    the K % n smallest.  A pure function of (count, seeds, K)."""
+    F = len(count)
+    count = _host_ints(count, "count", (F,))
+    if isinstance(seeds, torch.Tensor):
+        _need(not seeds.is_cuda, "seeds is a host table (the sampler draws it on the host): pass a CPU tensor or a list")
+        seeds = seeds.numpy()
+    seeds = np.asarray(seeds, dtype=object)              # Python ints: a list may hold values above 2^63
+    _need(seeds.shape == (F,), f"seeds must have shape {(F,)}, got {seeds.shape}")
+    _need(all(isinstance(s, (int, np.integer)) and 0 <= s < 2 ** 64 for s in seeds),
+          "seeds must hold integers in [0, 2^64)")
+    seeds = np.array([int(s) for s in seeds], dtype=np.uint64)
+    K = int(K)
+    _need(F > 0, "frame_subset needs at least one frame")
+    _need(K > 0, "K must be positive")
+    _need(bool((count > 0).all()), "every frame must hold at least one point")
+    device = torch.device(device)
+    be = backend_for(torch.empty(0, device=device))
+    _need(hasattr(be, "frame_subset"), f"the {device.type} backend has no frame_subset")
+    if device.type == "cuda":
+        _need(K <= frame_subset_max_k(), f"K = {K} exceeds the selection's capacity ({frame_subset_max_k()})")
+    with torch.no_grad():
+        return be.frame_subset(count, seeds, K, device)
+
+
+def action_gather(points, frame_first, count, idx, scale=None, mode="train"):
+    """Every high-resolution cloud of a batch of action clips at once (msr_dataset.py:67-91 / :105-127): with
+    q = (double)points[frame_first[t,b] + idx[t,b,k]], y negated, and v = (q * scale[b]) / 300.0 in fp64,
+        mode "train": high[t,b,k] = (float)(v - c[b]), c[b] the fp64 mean of v over frame T // 2's K rows;
+        mode "test":  high[t,b,k] = (float)(v - c[t,b]), c[t,b] the mean per frame, also returned; no scale.
+    points (P,3) fp32: every stored frame back to back; frame_first / count (T,B): HOST integers; idx (T,B,K) int32
+    (`frame_subset`; entries are clamped into the frame); scale (B,3) HOST float64 or None (ones).
+    -> (high (T,B,K,3) fp32, centres (T,B,3) fp32 in test mode, else None)."""
+    _check_float(points, "points", 2)
+    _check_int(idx, "idx", 3)
+    _same_device(points, idx)
+    _need(points.shape[1] == 3, "points must be (P,3)")
+    _need(mode in ("train", "test"), 'mode must be "train" or "test"')
+    T, B, K = idx.shape
+    _need(1 <= T <= 8, "a clip has 1..8 frames")
+    _need(B > 0 and K > 0, "idx must be (T,B,K) with B, K positive")
+    frame_first = _host_ints(frame_first, "frame_first", (T, B))
+    count = _host_ints(count, "count", (T, B))
+    _need(bool((count > 0).all() and (frame_first >= 0).all()
+               and (frame_first.astype(np.int64) + count <= points.shape[0]).all()),
+          "every frame must be a non-empty slice of points")
+    if scale is not None:
+        _need(mode == "train", "the test split has no scale")
+        scale = np.ascontiguousarray(scale.numpy() if isinstance(scale, torch.Tensor) else scale, dtype=np.float64)
+        _need(scale.shape == (B, 3) and bool(np.isfinite(scale).all()), "scale must be (B,3) finite float64 values")
+    be = backend_for(points)
+    _need(hasattr(be, "action_gather"), f"the {points.device.type} backend has no action_gather")
+    with torch.no_grad():
+        return be.action_gather(points.detach(), frame_first, count, idx, scale, mode == "test")
 
 
 def farthest_point_sampling(pts, k, initial_idx=None):
