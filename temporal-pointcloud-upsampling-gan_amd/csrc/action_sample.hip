@@ -13,8 +13,10 @@
 // ONE workgroup per frame does the whole selection: a depth frame has 10^3..10^5 points and a key costs a dozen integer
 // instructions, so the frame's keys are simply recomputed in each of the four passes (three 11 + 11 + 10-bit histogram
 // passes of a radix select in LDS for the ksel-th smallest key, one pass that collects the keys up to it) and the
-// survivors are ordered by a bitonic sort in LDS, as sel_sort_kernel orders a patch.  LDS atomics on integers and a sort
-// of unique keys only: the result is a pure function of (count, seed, K), and nothing but idx is written to memory.
+// survivors are ordered by a bitonic sort in LDS, as sel_sort_kernel orders a patch (digits, block scan and sort are
+// tpg_select.hpp's, shared with clip_sample.hip; the two-bin resolve is written out here).  LDS atomics on integers
+// and a sort of unique keys only: the result is a pure function of (count, seed, K), and nothing but idx is written to
+// memory.
 //
 // tpg_action_gather_f32: all high-resolution clouds of the batch and their centroid in one launch, one workgroup per
 // frame.  The centroid is an fp64 sum in a FIXED order (thread t adds rows t, t + 256, ... in that order; the 256
@@ -22,13 +24,11 @@
 // workspace, no second launch, the same bits wherever and whenever it runs.
 #include <math.h>
 
-#include "tpg_common.hpp"
+#include "tpg_select.hpp"
 
 namespace {
 
 constexpr int FS_THREADS = 1024;
-constexpr int FS_BINS = 2048;
-constexpr int FS_SHIFT0 = 21, FS_SHIFT1 = 10;            // digits: bits 31..21, 20..10, 9..0
 constexpr int FS_GROUP = 32;                             // frames per launch (their rows travel as kernel arguments)
 
 struct FsFrames {                                        // host arrays of one group of frames, passed by value
@@ -48,29 +48,40 @@ __host__ __device__ inline unsigned fs_key(unsigned j, unsigned seed_lo, unsigne
     return fs_mix(fs_mix(j * 0x9E3779B1u + seed_lo) ^ seed_hi);
 }
 
-// Inclusive scan of one value per thread over the workgroup (FS_THREADS), through `s` (FS_THREADS words).
-__device__ __forceinline__ unsigned fs_block_incl_scan(unsigned v, unsigned *s) {
-    const int t = threadIdx.x;
-    s[t] = v;
-    __syncthreads();
-    for (int d = 1; d < FS_THREADS; d <<= 1) {
-        const unsigned add = t >= d ? s[t - d] : 0u;
-        __syncthreads();
-        s[t] += add;
-        __syncthreads();
-    }
-    const unsigned incl = s[t];
-    __syncthreads();
-    return incl;
-}
-
 // Points of the frame selected by the K % n (n <= K) or K (n > K) smallest keys.
 __host__ __device__ inline int fs_selected(int n, int K) { return n > K ? K : K % n; }
+
+// Digit PASS of the ksel-th smallest key of the frame: prefix = the digits found so far, krem = the rank left.
+template <int PASS>
+__device__ __forceinline__ void fs_digit(int n, unsigned lo, unsigned hi, unsigned *h, unsigned *s_scan, unsigned *s_out,
+                                         unsigned *prefix, unsigned *krem) {
+    const int t = threadIdx.x;
+    for (int i = t; i < TPG_SEL_BINS; i += FS_THREADS) h[i] = 0;
+    __syncthreads();
+    for (int j = t; j < n; j += FS_THREADS) {
+        const unsigned key = fs_key((unsigned)j, lo, hi);
+        if (tpg_sel_matches<PASS>(key, *prefix)) atomicAdd(&h[tpg_sel_digit<PASS>(key)], 1u);
+    }
+    __syncthreads();
+    // the bin that holds the krem-th smallest entry (the histogram's total is >= krem >= 1): two bins per thread,
+    // written out by hand -- tpg_sel_resolve<FS_THREADS> gives the same bin but other code, not yet timed in this kernel
+    const unsigned v0 = h[2 * t], v1 = h[2 * t + 1];
+    const unsigned excl = tpg_block_excl_scan<FS_THREADS>(v0 + v1, s_scan, nullptr);
+    if (excl < *krem && *krem <= excl + (v0 + v1)) {     // exactly one thread
+        const bool first = *krem <= excl + v0;
+        s_out[0] = (unsigned)(2 * t) + (first ? 0u : 1u);
+        s_out[1] = *krem - excl - (first ? 0u : v0);
+    }
+    __syncthreads();
+    *prefix |= tpg_sel_place<PASS>(s_out[0]);
+    *krem = s_out[1];
+    __syncthreads();
+}
 
 __global__ __launch_bounds__(FS_THREADS) void frame_subset_kernel(FsFrames fr, int f0, int K, int n2,
                                                                  int32_t *__restrict__ idx) {
     extern __shared__ __attribute__((aligned(16))) tpg_u64 fs_keys[];    // n2 slots
-    __shared__ unsigned h[FS_BINS];
+    __shared__ unsigned h[TPG_SEL_BINS];
     __shared__ unsigned s_scan[FS_THREADS];
     __shared__ unsigned s_out[3];                                        // bin, rank left, slot counter
     const int g = blockIdx.x, t = threadIdx.x;
@@ -84,35 +95,9 @@ __global__ __launch_bounds__(FS_THREADS) void frame_subset_kernel(FsFrames fr, i
 
     // the ksel-th smallest key, digit by digit
     unsigned prefix = 0, krem = (unsigned)ksel;
-#pragma unroll
-    for (int pass = 0; pass < 3; ++pass) {
-        for (int i = t; i < FS_BINS; i += FS_THREADS) h[i] = 0;
-        __syncthreads();
-        for (int j = t; j < n; j += FS_THREADS) {
-            const unsigned key = fs_key((unsigned)j, lo, hi);
-            if (pass == 0) {
-                atomicAdd(&h[key >> FS_SHIFT0], 1u);
-            } else if (pass == 1) {
-                if ((key >> FS_SHIFT0) == (prefix >> FS_SHIFT0)) atomicAdd(&h[(key >> FS_SHIFT1) & (FS_BINS - 1)], 1u);
-            } else {
-                if ((key >> FS_SHIFT1) == (prefix >> FS_SHIFT1)) atomicAdd(&h[key & ((1u << FS_SHIFT1) - 1)], 1u);
-            }
-        }
-        __syncthreads();
-        // the bin that holds the krem-th smallest entry (the histogram's total is >= krem >= 1): two bins per thread
-        const unsigned v0 = h[2 * t], v1 = h[2 * t + 1];
-        const unsigned incl = fs_block_incl_scan(v0 + v1, s_scan);
-        const unsigned excl = incl - (v0 + v1);
-        if (excl < krem && krem <= incl) {               // exactly one thread
-            const bool first = krem <= excl + v0;
-            s_out[0] = (unsigned)(2 * t) + (first ? 0u : 1u);
-            s_out[1] = krem - excl - (first ? 0u : v0);
-        }
-        __syncthreads();
-        prefix |= s_out[0] << (pass == 0 ? FS_SHIFT0 : pass == 1 ? FS_SHIFT1 : 0);
-        krem = s_out[1];
-        __syncthreads();
-    }
+    fs_digit<0>(n, lo, hi, h, s_scan, s_out, &prefix, &krem);
+    fs_digit<1>(n, lo, hi, h, s_scan, s_out, &prefix, &krem);
+    fs_digit<2>(n, lo, hi, h, s_scan, s_out, &prefix, &krem);
     const unsigned kth = prefix;                         // keys are distinct: exactly ksel of them are <= kth
 
     if (t == 0) s_out[2] = 0;
@@ -126,33 +111,14 @@ __global__ __launch_bounds__(FS_THREADS) void frame_subset_kernel(FsFrames fr, i
         }
     }
     __syncthreads();
-    for (int k = 2; k <= n2; k <<= 1) {
-        for (int j = k >> 1; j > 0; j >>= 1) {
-            for (int i = t; i < n2; i += FS_THREADS) {
-                const int p = i ^ j;
-                if (p > i) {
-                    const tpg_u64 a = fs_keys[i], c = fs_keys[p];
-                    if ((a > c) == ((i & k) == 0)) {
-                        fs_keys[i] = c;
-                        fs_keys[p] = a;
-                    }
-                }
-            }
-            __syncthreads();
-        }
-    }
+    tpg_lds_bitonic_sort<FS_THREADS>(fs_keys, n2);
     for (int i = t; i < ksel; i += FS_THREADS) out[lead + i] = tpg_clamp_idx((int32_t)(unsigned)fs_keys[i], n);
 }
 
 // ---- gather + scale + centre ------------------------------------------------------------------------------------------
-constexpr int AG_MAX_T = 8;
-constexpr int AG_GROUP = 32;
-constexpr int AG_THREADS = 256;
-
 struct AgFrames {                                        // host arrays of one group of clips, passed by value
-    int first[AG_MAX_T * AG_GROUP];                      // [t * AG_GROUP + g]: first point of clip g's frame t
-    int count[AG_MAX_T * AG_GROUP];                      // its point count
-    double scale[AG_GROUP * 3];
+    TpgClipTable first, count;                           // first point of clip g's frame t, and its point count
+    double scale[TPG_CLIP_GROUP * 3];
 };
 
 // Row k of frame (t,b): the stored point, y negated, times the clip's scale, over 300 -- fp64, in this order.
@@ -164,20 +130,21 @@ __device__ __forceinline__ void ag_row(const float *__restrict__ points, const i
     v[2] = ((double)points[src + 2] * sz) / 300.0;
 }
 
-__global__ __launch_bounds__(AG_THREADS) void action_gather_kernel(const float *__restrict__ points, AgFrames fr,
-                                                                  const int32_t *__restrict__ idx, int b0, int T, int B,
-                                                                  int K, int per_frame, float *__restrict__ high,
-                                                                  float *__restrict__ centre) {
-    __shared__ double s_sum[3][AG_THREADS];
+__global__ __launch_bounds__(TPG_CLIP_THREADS) void action_gather_kernel(const float *__restrict__ points, AgFrames fr,
+                                                                        const int32_t *__restrict__ idx, int b0, int T,
+                                                                        int B, int K, int per_frame,
+                                                                        float *__restrict__ high,
+                                                                        float *__restrict__ centre) {
+    __shared__ double s_sum[3][TPG_CLIP_THREADS];
     const int g = blockIdx.x, t = blockIdx.y, b = b0 + g, tid = threadIdx.x;
     const double sx = fr.scale[g * 3], sy = fr.scale[g * 3 + 1], sz = fr.scale[g * 3 + 2];
     // the centroid: of this frame (test split) or of the clip's middle frame (train split)
     const int tc = per_frame ? t : T / 2;
     {
         const int32_t *ci = idx + ((size_t)tc * B + b) * K;
-        const int cfirst = fr.first[tc * AG_GROUP + g], ccount = fr.count[tc * AG_GROUP + g];
+        const int cfirst = fr.first.at[tc * TPG_CLIP_GROUP + g], ccount = fr.count.at[tc * TPG_CLIP_GROUP + g];
         double a0 = 0.0, a1 = 0.0, a2 = 0.0, v[3];
-        for (int k = tid; k < K; k += AG_THREADS) {
+        for (int k = tid; k < K; k += TPG_CLIP_THREADS) {
             ag_row(points, ci, cfirst, ccount, k, sx, sy, sz, v);
             a0 += v[0];
             a1 += v[1];
@@ -187,7 +154,7 @@ __global__ __launch_bounds__(AG_THREADS) void action_gather_kernel(const float *
         s_sum[1][tid] = a1;
         s_sum[2][tid] = a2;
         __syncthreads();
-        for (int d = AG_THREADS / 2; d > 0; d >>= 1) {
+        for (int d = TPG_CLIP_THREADS / 2; d > 0; d >>= 1) {
             if (tid < d) {
                 s_sum[0][tid] += s_sum[0][tid + d];
                 s_sum[1][tid] += s_sum[1][tid + d];
@@ -204,9 +171,9 @@ __global__ __launch_bounds__(AG_THREADS) void action_gather_kernel(const float *
         c[2] = (float)c2;
     }
     const int32_t *fi = idx + ((size_t)t * B + b) * K;
-    const int first = fr.first[t * AG_GROUP + g], count = fr.count[t * AG_GROUP + g];
+    const int first = fr.first.at[t * TPG_CLIP_GROUP + g], count = fr.count.at[t * TPG_CLIP_GROUP + g];
     float *dst = high + ((size_t)t * B + b) * K * 3;
-    for (int k = tid; k < K; k += AG_THREADS) {
+    for (int k = tid; k < K; k += TPG_CLIP_THREADS) {
         double v[3];
         ag_row(points, fi, first, count, k, sx, sy, sz, v);
         dst[(size_t)k * 3] = (float)(v[0] - c0);
@@ -251,7 +218,7 @@ extern "C" int tpg_action_gather_f32(const float *points, long long P, const int
     if (T < 0 || B < 0 || K < 0 || P < 0) return TPG_ERR_ARG;
     if (mode != TPG_ACTION_TRAIN && mode != TPG_ACTION_TEST) return TPG_ERR_ARG;
     if (T == 0 || B == 0 || K == 0) return TPG_OK;
-    if (T > AG_MAX_T) return TPG_ERR_UNSUPPORTED;
+    if (T > TPG_CLIP_MAX_T) return TPG_ERR_UNSUPPORTED;
     if (!points || !frame_first || !count || !idx || !high) return TPG_ERR_ARG;
     if (mode == TPG_ACTION_TEST ? (scale != nullptr || centre == nullptr) : centre != nullptr) return TPG_ERR_ARG;
     for (int i = 0; i < T * B; ++i)
@@ -260,19 +227,14 @@ extern "C" int tpg_action_gather_f32(const float *points, long long P, const int
         for (int i = 0; i < B * 3; ++i)
             if (!isfinite(scale[i])) return TPG_ERR_ARG;
     hipStream_t st = tpg_stream(stream);
-    for (int b0 = 0; b0 < B; b0 += AG_GROUP) {
-        const int nb = B - b0 < AG_GROUP ? B - b0 : AG_GROUP;
+    for (int b0 = 0; b0 < B; b0 += TPG_CLIP_GROUP) {
+        const int nb = B - b0 < TPG_CLIP_GROUP ? B - b0 : TPG_CLIP_GROUP;
         AgFrames fr;
-        for (int g = 0; g < AG_GROUP; ++g) {
-            for (int d = 0; d < 3; ++d) fr.scale[g * 3 + d] = (scale && g < nb) ? scale[(b0 + g) * 3 + d] : 1.0;
-            for (int t = 0; t < AG_MAX_T; ++t) {
-                const bool live = g < nb && t < T;
-                fr.first[t * AG_GROUP + g] = live ? frame_first[t * B + b0 + g] : 0;
-                fr.count[t * AG_GROUP + g] = live ? count[t * B + b0 + g] : 1;
-            }
-        }
-        hipLaunchKernelGGL(action_gather_kernel, dim3(nb, T), dim3(AG_THREADS), 0, st, points, fr, idx, b0, T, B, K,
-                           mode == TPG_ACTION_TEST ? 1 : 0, high, centre);
+        fr.first = tpg_clip_table(frame_first, T, B, b0, 0);
+        fr.count = tpg_clip_table(count, T, B, b0, 1);
+        for (int i = 0; i < TPG_CLIP_GROUP * 3; ++i) fr.scale[i] = (scale && i < nb * 3) ? scale[b0 * 3 + i] : 1.0;
+        hipLaunchKernelGGL(action_gather_kernel, dim3(nb, T), dim3(TPG_CLIP_THREADS), 0, st, points, fr, idx, b0, T, B,
+                           K, mode == TPG_ACTION_TEST ? 1 : 0, high, centre);
         TPG_RETURN_IF_LAUNCH_FAILED();
     }
     return TPG_OK;

@@ -4,7 +4,8 @@
 // of scenes -- what the reference asks a KD-tree for.  Selection key of candidate j: (bits of d2_j, j) with the canonical
 // d2 = (dx*dx + dy*dy) + dz*dz in fp32 (tpg_sq3); a non-negative fp32 orders like its bit pattern, a NaN d2 counts as
 // 0x7FC00000 (after +inf).  Result = the K smallest keys in ascending order.  A radix select on the 32 distance bits
-// (11 + 11 + 10) finds the K-th key, the survivors are compacted and one workgroup per scene orders them in LDS:
+// (11 + 11 + 10) finds the K-th key, the survivors are compacted and one workgroup per scene orders them in LDS (digits,
+// block scan, resolve and bitonic sort: tpg_select.hpp, shared with action_sample.hip):
 //
 //   sel_hist<0,1,2>  (chunks, scenes) workgroups of SEL_CHUNK candidates: LDS histogram of the pass's digit over the
 //                    candidates that match the digits found so far, added to the scene's global histogram (integer
@@ -18,15 +19,13 @@
 // The result is therefore a pure function of the input: bit-identical from run to run and at every batch position.
 //
 // tpg_clip_gather_high_f32 / tpg_clip_gather_low_f32: every high- / low-resolution array of a batch in one launch each.
-#include "tpg_common.hpp"
+#include "tpg_select.hpp"
 
 namespace {
 
 constexpr int SEL_THREADS = 256;
 constexpr int SEL_PER_THREAD = 4;                        // consecutive candidates per thread (index order = thread order)
 constexpr int SEL_CHUNK = SEL_THREADS * SEL_PER_THREAD;  // candidates per workgroup
-constexpr int SEL_BINS = 2048;
-constexpr int SEL_SHIFT0 = 21, SEL_SHIFT1 = 10;          // digits: bits 31..21, 20..10, 9..0
 constexpr int SEL_SORT_THREADS = 1024;
 constexpr int SEL_GROUP = 32;                            // scenes per launch (their slices travel as kernel arguments)
 constexpr unsigned SEL_NAN_KEY = 0x7FC00000u;
@@ -37,14 +36,14 @@ struct SelScenes {                                       // host arrays of one g
 
 // per-scene workspace: 3 histograms | slot counter (+ 3 pad words) | tie count per chunk | K keys
 struct SelWs {
-    unsigned *hist;     // [3][SEL_BINS]
+    unsigned *hist;     // [3][TPG_SEL_BINS]
     unsigned *counter;  // [4]
     unsigned *ties;     // [chunks]
     tpg_u64 *keys;      // [K]
 };
 
 __host__ __device__ inline size_t sel_head_words(int chunks) {
-    const size_t w = 3 * (size_t)SEL_BINS + 4 + (size_t)chunks;
+    const size_t w = 3 * (size_t)TPG_SEL_BINS + 4 + (size_t)chunks;
     return (w + 1) & ~(size_t)1;                         // keys start 8-byte aligned
 }
 __host__ __device__ inline size_t sel_scene_bytes(int chunks, int K) { return sel_head_words(chunks) * 4 + (size_t)K * 8; }
@@ -53,7 +52,7 @@ __device__ __forceinline__ SelWs sel_ws(void *ws, int scene, int chunks, int K) 
     unsigned char *base = reinterpret_cast<unsigned char *>(ws) + (size_t)scene * sel_scene_bytes(chunks, K);
     SelWs w;
     w.hist = reinterpret_cast<unsigned *>(base);
-    w.counter = w.hist + 3 * SEL_BINS;
+    w.counter = w.hist + 3 * TPG_SEL_BINS;
     w.ties = w.counter + 4;
     w.keys = reinterpret_cast<tpg_u64 *>(base + sel_head_words(chunks) * 4);
     return w;
@@ -64,99 +63,38 @@ __device__ __forceinline__ unsigned sel_key(const float *__restrict__ pts, size_
     return d2 != d2 ? SEL_NAN_KEY : __float_as_uint(d2);
 }
 
-// Exclusive scan of one value per thread over the workgroup (SEL_THREADS), through `s` (SEL_THREADS words).
-__device__ __forceinline__ unsigned sel_block_excl_scan(unsigned v, unsigned *s, unsigned *total) {
-    const int t = threadIdx.x;
-    s[t] = v;
-    __syncthreads();
-    for (int d = 1; d < SEL_THREADS; d <<= 1) {
-        const unsigned add = t >= d ? s[t - d] : 0u;
-        __syncthreads();
-        s[t] += add;
-        __syncthreads();
-    }
-    const unsigned incl = s[t];
-    if (total) *total = s[SEL_THREADS - 1];
-    __syncthreads();
-    return incl - v;
-}
-
-// The bin of a finished histogram (SEL_BINS bins, total >= krem >= 1) that holds the krem-th smallest entry, and the
-// rank (1-based) of that entry inside the bin.  Uniform over the workgroup.
-__device__ __forceinline__ void sel_resolve(const unsigned *__restrict__ hist, unsigned krem, unsigned *s_scan,
-                                            unsigned *s_out, unsigned *bin, unsigned *krem_out) {
-    constexpr int PER = SEL_BINS / SEL_THREADS;
-    const int t = threadIdx.x;
-    unsigned v[PER], sum = 0;
-#pragma unroll
-    for (int i = 0; i < PER; ++i) {
-        v[i] = hist[t * PER + i];
-        sum += v[i];
-    }
-    const unsigned excl = sel_block_excl_scan(sum, s_scan, nullptr);
-    if (excl < krem && krem <= excl + sum) {             // exactly one thread
-        unsigned run = excl;
-#pragma unroll
-        for (int i = 0; i < PER; ++i) {
-            if (krem <= run + v[i]) {
-                s_out[0] = (unsigned)(t * PER + i);
-                s_out[1] = krem - run;
-                break;
-            }
-            run += v[i];
-        }
-    }
-    __syncthreads();
-    *bin = s_out[0];
-    *krem_out = s_out[1];
-    __syncthreads();
-}
-
 // Digits 0 .. NP-1 of the K-th key from the finished histograms: prefix = those digits in place, krem = rank left.
 template <int NP>
 __device__ __forceinline__ void sel_prefix(const SelWs &w, int K, unsigned *s_scan, unsigned *s_out, unsigned *prefix,
                                            unsigned *krem) {
     unsigned p = 0, k = (unsigned)K, bin;
     if (NP >= 1) {
-        sel_resolve(w.hist, k, s_scan, s_out, &bin, &k);
-        p = bin << SEL_SHIFT0;
+        tpg_sel_resolve<SEL_THREADS>(w.hist, k, s_scan, s_out, &bin, &k);
+        p = tpg_sel_place<0>(bin);
     }
     if (NP >= 2) {
-        sel_resolve(w.hist + SEL_BINS, k, s_scan, s_out, &bin, &k);
-        p |= bin << SEL_SHIFT1;
+        tpg_sel_resolve<SEL_THREADS>(w.hist + TPG_SEL_BINS, k, s_scan, s_out, &bin, &k);
+        p |= tpg_sel_place<1>(bin);
     }
     if (NP >= 3) {
-        sel_resolve(w.hist + 2 * SEL_BINS, k, s_scan, s_out, &bin, &k);
-        p |= bin;
+        tpg_sel_resolve<SEL_THREADS>(w.hist + 2 * TPG_SEL_BINS, k, s_scan, s_out, &bin, &k);
+        p |= tpg_sel_place<2>(bin);
     }
     *prefix = p;
     *krem = k;
 }
 
 template <int PASS>
-__device__ __forceinline__ bool sel_match(unsigned key, unsigned prefix) {
-    if (PASS == 0) return true;
-    if (PASS == 1) return (key >> SEL_SHIFT0) == (prefix >> SEL_SHIFT0);
-    return (key >> SEL_SHIFT1) == (prefix >> SEL_SHIFT1);
-}
-template <int PASS>
-__device__ __forceinline__ unsigned sel_digit(unsigned key) {
-    if (PASS == 0) return key >> SEL_SHIFT0;
-    if (PASS == 1) return (key >> SEL_SHIFT1) & (SEL_BINS - 1);
-    return key & ((1u << SEL_SHIFT1) - 1);
-}
-
-template <int PASS>
 __global__ __launch_bounds__(SEL_THREADS) void sel_hist_kernel(const float *__restrict__ points, SelScenes sc, int b0,
                                                               int K, int chunks, void *ws) {
-    __shared__ unsigned h[SEL_BINS];
+    __shared__ unsigned h[TPG_SEL_BINS];
     __shared__ unsigned s_scan[SEL_THREADS];
     __shared__ unsigned s_out[2];
     const int g = blockIdx.y, n = sc.count[g];
     const int base = blockIdx.x * SEL_CHUNK;
     if (base >= n) return;
     const SelWs w = sel_ws(ws, b0 + g, chunks, K);
-    for (int i = threadIdx.x; i < SEL_BINS; i += SEL_THREADS) h[i] = 0;
+    for (int i = threadIdx.x; i < TPG_SEL_BINS; i += SEL_THREADS) h[i] = 0;
     unsigned prefix, krem;
     sel_prefix<PASS>(w, K, s_scan, s_out, &prefix, &krem);
     __syncthreads();
@@ -167,12 +105,12 @@ __global__ __launch_bounds__(SEL_THREADS) void sel_hist_kernel(const float *__re
         const int j = base + threadIdx.x * SEL_PER_THREAD + i;
         if (j < n) {
             const unsigned key = sel_key(pts, (size_t)j, sx, sy, sz);
-            if (sel_match<PASS>(key, prefix)) atomicAdd(&h[sel_digit<PASS>(key)], 1u);
+            if (tpg_sel_matches<PASS>(key, prefix)) atomicAdd(&h[tpg_sel_digit<PASS>(key)], 1u);
         }
     }
     __syncthreads();
-    unsigned *gh = w.hist + PASS * SEL_BINS;
-    for (int i = threadIdx.x; i < SEL_BINS; i += SEL_THREADS)
+    unsigned *gh = w.hist + PASS * TPG_SEL_BINS;
+    for (int i = threadIdx.x; i < TPG_SEL_BINS; i += SEL_THREADS)
         if (h[i]) atomicAdd(&gh[i], h[i]);
 }
 
@@ -195,7 +133,7 @@ __global__ __launch_bounds__(SEL_THREADS) void sel_ties_kernel(const float *__re
         if (j < n && sel_key(pts, (size_t)j, sx, sy, sz) == kth) ++c;
     }
     unsigned total;
-    sel_block_excl_scan(c, s_scan, &total);
+    tpg_block_excl_scan<SEL_THREADS>(c, s_scan, &total);
     if (threadIdx.x == 0) w.ties[blockIdx.x] = total;
 }
 
@@ -213,7 +151,7 @@ __global__ __launch_bounds__(SEL_THREADS) void sel_compact_kernel(const float *_
     // ties in the chunks before this one
     unsigned part = 0, ties_before;
     for (int cidx = threadIdx.x; cidx < (int)blockIdx.x; cidx += SEL_THREADS) part += w.ties[cidx];
-    sel_block_excl_scan(part, s_scan, &ties_before);
+    tpg_block_excl_scan<SEL_THREADS>(part, s_scan, &ties_before);
 
     const float *pts = points + (size_t)sc.first[g] * 3;
     const float sx = pts[(size_t)sc.seed[g] * 3], sy = pts[(size_t)sc.seed[g] * 3 + 1], sz = pts[(size_t)sc.seed[g] * 3 + 2];
@@ -230,12 +168,12 @@ __global__ __launch_bounds__(SEL_THREADS) void sel_compact_kernel(const float *_
     }
     // slots of the keys below: one counter bump per workgroup, order inside by thread (any order would do)
     unsigned less_total;
-    const unsigned less_excl = sel_block_excl_scan(nless, s_scan, &less_total);
+    const unsigned less_excl = tpg_block_excl_scan<SEL_THREADS>(nless, s_scan, &less_total);
     if (threadIdx.x == 0) s_out[0] = less_total ? atomicAdd(w.counter, less_total) : 0u;
     __syncthreads();
     unsigned slot = s_out[0] + less_excl;
     __syncthreads();
-    unsigned rank = ties_before + sel_block_excl_scan(ntie, s_scan, nullptr);
+    unsigned rank = ties_before + tpg_block_excl_scan<SEL_THREADS>(ntie, s_scan, nullptr);
 #pragma unroll
     for (int i = 0; i < SEL_PER_THREAD; ++i) {
         const int j = base + threadIdx.x * SEL_PER_THREAD + i;
@@ -258,49 +196,31 @@ __global__ __launch_bounds__(SEL_SORT_THREADS) void sel_sort_kernel(int b0, int 
     const SelWs w = sel_ws(ws, b, chunks, K);
     for (int i = threadIdx.x; i < n2; i += SEL_SORT_THREADS) sel_keys[i] = i < K ? w.keys[i] : ~0ull;
     __syncthreads();
-    for (int k = 2; k <= n2; k <<= 1) {
-        for (int j = k >> 1; j > 0; j >>= 1) {
-            for (int i = threadIdx.x; i < n2; i += SEL_SORT_THREADS) {
-                const int p = i ^ j;
-                if (p > i) {
-                    const tpg_u64 a = sel_keys[i], c = sel_keys[p];
-                    if ((a > c) == ((i & k) == 0)) {
-                        sel_keys[i] = c;
-                        sel_keys[p] = a;
-                    }
-                }
-            }
-            __syncthreads();
-        }
-    }
+    tpg_lds_bitonic_sort<SEL_SORT_THREADS>(sel_keys, n2);
     for (int i = threadIdx.x; i < K; i += SEL_SORT_THREADS) idx[(size_t)b * K + i] = (int32_t)(unsigned)sel_keys[i];
 }
 
 int sel_chunks(int max_count) { return (max_count + SEL_CHUNK - 1) / SEL_CHUNK; }
 
 // ---- gathers ------------------------------------------------------------------------------------------------------
-constexpr int CG_MAX_T = 8;
-constexpr int CG_GROUP = 32;
-constexpr int CG_THREADS = 256;
-
 struct ClipFrames {                                      // host arrays of one group of clips, passed by value
-    int first[CG_MAX_T * CG_GROUP];                      // [t * CG_GROUP + g]: first point of clip g's frame t
-    int count[CG_GROUP];                                 // particles of the clip's scene
-    int crow[CG_GROUP];                                  // row of the centre frame's centroid
+    TpgClipTable first;                                  // first point of clip g's frame t
+    int count[TPG_CLIP_GROUP];                           // particles of the clip's scene
+    int crow[TPG_CLIP_GROUP];                            // row of the centre frame's centroid
 };
 
-__global__ __launch_bounds__(CG_THREADS) void clip_gather_high_kernel(const float *__restrict__ pos,
-                                                                     const float *__restrict__ vel, ClipFrames cf,
-                                                                     const float *__restrict__ centroids,
-                                                                     const int32_t *__restrict__ patch, int b0, int B,
-                                                                     int K, float *__restrict__ high_pos,
-                                                                     float *__restrict__ high_vel) {
-    const int k = blockIdx.x * CG_THREADS + threadIdx.x;
+__global__ __launch_bounds__(TPG_CLIP_THREADS) void clip_gather_high_kernel(const float *__restrict__ pos,
+                                                                           const float *__restrict__ vel, ClipFrames cf,
+                                                                           const float *__restrict__ centroids,
+                                                                           const int32_t *__restrict__ patch, int b0,
+                                                                           int B, int K, float *__restrict__ high_pos,
+                                                                           float *__restrict__ high_vel) {
+    const int k = blockIdx.x * TPG_CLIP_THREADS + threadIdx.x;
     const int g = blockIdx.y, t = blockIdx.z;
     if (k >= K) return;
     const int b = b0 + g;
     const int p = tpg_clamp_idx(patch[(size_t)b * K + k], cf.count[g]);
-    const size_t src = ((size_t)cf.first[t * CG_GROUP + g] + (size_t)p) * 3;
+    const size_t src = ((size_t)cf.first.at[t * TPG_CLIP_GROUP + g] + (size_t)p) * 3;
     const size_t dst = (((size_t)t * B + b) * K + k) * 3;
     const float *c = centroids + (size_t)cf.crow[g] * 3;
     high_pos[dst] = pos[src] - c[0];
@@ -313,13 +233,14 @@ __global__ __launch_bounds__(CG_THREADS) void clip_gather_high_kernel(const floa
     }
 }
 
-__global__ __launch_bounds__(CG_THREADS) void clip_gather_low_kernel(const float *__restrict__ high_pos,
-                                                                    const float *__restrict__ vel, ClipFrames cf,
-                                                                    const int32_t *__restrict__ fps,
-                                                                    const float *__restrict__ noise, float jitter, int b0,
-                                                                    int B, int K, int M, float *__restrict__ low_pos,
-                                                                    float *__restrict__ low_vel) {
-    const int j = blockIdx.x * CG_THREADS + threadIdx.x;
+__global__ __launch_bounds__(TPG_CLIP_THREADS) void clip_gather_low_kernel(const float *__restrict__ high_pos,
+                                                                          const float *__restrict__ vel, ClipFrames cf,
+                                                                          const int32_t *__restrict__ fps,
+                                                                          const float *__restrict__ noise, float jitter,
+                                                                          int b0, int B, int K, int M,
+                                                                          float *__restrict__ low_pos,
+                                                                          float *__restrict__ low_vel) {
+    const int j = blockIdx.x * TPG_CLIP_THREADS + threadIdx.x;
     const int g = blockIdx.y, t = blockIdx.z;
     if (j >= M) return;
     const int b = b0 + g;
@@ -336,7 +257,7 @@ __global__ __launch_bounds__(CG_THREADS) void clip_gather_low_kernel(const float
         low_pos[dst + 2] = high_pos[src + 2];
     }
     if (vel) {                                           // the reference's rows: fps[b,j] taken as a SCENE index
-        const size_t v = ((size_t)cf.first[t * CG_GROUP + g] + (size_t)tpg_clamp_idx(f, cf.count[g])) * 3;
+        const size_t v = ((size_t)cf.first.at[t * TPG_CLIP_GROUP + g] + (size_t)tpg_clamp_idx(f, cf.count[g])) * 3;
         low_vel[dst] = vel[v];
         low_vel[dst + 1] = vel[v + 1];
         low_vel[dst + 2] = vel[v + 2];
@@ -406,7 +327,7 @@ extern "C" int tpg_clip_gather_high_f32(const float *pos, const float *vel, long
                                         void *stream) {
     if (T < 0 || B < 0 || K < 0 || P < 0 || F < 0) return TPG_ERR_ARG;
     if (T == 0 || B == 0 || K == 0) return TPG_OK;
-    if (T > CG_MAX_T) return TPG_ERR_UNSUPPORTED;
+    if (T > TPG_CLIP_MAX_T) return TPG_ERR_UNSUPPORTED;
     if (!pos || !frame_first || !count || !centroids || !centroid_row || !patch || !high_pos) return TPG_ERR_ARG;
     if ((vel != nullptr) != (high_vel != nullptr)) return TPG_ERR_ARG;
     for (int b = 0; b < B; ++b) {
@@ -415,16 +336,17 @@ extern "C" int tpg_clip_gather_high_f32(const float *pos, const float *vel, long
             if (frame_first[t * B + b] < 0 || (long long)frame_first[t * B + b] + count[b] > P) return TPG_ERR_ARG;
     }
     hipStream_t st = tpg_stream(stream);
-    for (int b0 = 0; b0 < B; b0 += CG_GROUP) {
-        const int nb = B - b0 < CG_GROUP ? B - b0 : CG_GROUP;
+    for (int b0 = 0; b0 < B; b0 += TPG_CLIP_GROUP) {
+        const int nb = B - b0 < TPG_CLIP_GROUP ? B - b0 : TPG_CLIP_GROUP;
         ClipFrames cf;
-        for (int g = 0; g < CG_GROUP; ++g) {
+        cf.first = tpg_clip_table(frame_first, T, B, b0, 0);
+        for (int g = 0; g < TPG_CLIP_GROUP; ++g) {
             cf.count[g] = g < nb ? count[b0 + g] : 1;
             cf.crow[g] = g < nb ? centroid_row[b0 + g] : 0;
-            for (int t = 0; t < CG_MAX_T; ++t) cf.first[t * CG_GROUP + g] = (g < nb && t < T) ? frame_first[t * B + b0 + g] : 0;
         }
-        hipLaunchKernelGGL(clip_gather_high_kernel, dim3((K + CG_THREADS - 1) / CG_THREADS, nb, T), dim3(CG_THREADS), 0, st,
-                           pos, vel, cf, centroids, patch, b0, B, K, high_pos, high_vel);
+        const dim3 grid((K + TPG_CLIP_THREADS - 1) / TPG_CLIP_THREADS, nb, T);
+        hipLaunchKernelGGL(clip_gather_high_kernel, grid, dim3(TPG_CLIP_THREADS), 0, st, pos, vel, cf, centroids, patch, b0,
+                           B, K, high_pos, high_vel);
         TPG_RETURN_IF_LAUNCH_FAILED();
     }
     return TPG_OK;
@@ -435,7 +357,7 @@ extern "C" int tpg_clip_gather_low_f32(const float *high_pos, const int32_t *fps
                                        int T, int B, int K, int M, float *low_pos, float *low_vel, void *stream) {
     if (T < 0 || B < 0 || K < 0 || M < 0 || P < 0) return TPG_ERR_ARG;
     if (T == 0 || B == 0 || M == 0) return TPG_OK;
-    if (T > CG_MAX_T) return TPG_ERR_UNSUPPORTED;
+    if (T > TPG_CLIP_MAX_T) return TPG_ERR_UNSUPPORTED;
     if (K == 0 || !high_pos || !fps || !low_pos) return TPG_ERR_ARG;
     if ((vel != nullptr) != (low_vel != nullptr)) return TPG_ERR_ARG;
     if (vel) {
@@ -447,17 +369,17 @@ extern "C" int tpg_clip_gather_low_f32(const float *high_pos, const int32_t *fps
         }
     }
     hipStream_t st = tpg_stream(stream);
-    for (int b0 = 0; b0 < B; b0 += CG_GROUP) {
-        const int nb = B - b0 < CG_GROUP ? B - b0 : CG_GROUP;
+    for (int b0 = 0; b0 < B; b0 += TPG_CLIP_GROUP) {
+        const int nb = B - b0 < TPG_CLIP_GROUP ? B - b0 : TPG_CLIP_GROUP;
         ClipFrames cf;
-        for (int g = 0; g < CG_GROUP; ++g) {
+        cf.first = tpg_clip_table(vel ? frame_first : nullptr, T, B, b0, 0);
+        for (int g = 0; g < TPG_CLIP_GROUP; ++g) {
             cf.count[g] = (vel && g < nb) ? count[b0 + g] : 1;
             cf.crow[g] = 0;
-            for (int t = 0; t < CG_MAX_T; ++t)
-                cf.first[t * CG_GROUP + g] = (vel && g < nb && t < T) ? frame_first[t * B + b0 + g] : 0;
         }
-        hipLaunchKernelGGL(clip_gather_low_kernel, dim3((M + CG_THREADS - 1) / CG_THREADS, nb, T), dim3(CG_THREADS), 0, st,
-                           high_pos, vel, cf, fps, noise, jitter, b0, B, K, M, low_pos, low_vel);
+        const dim3 grid((M + TPG_CLIP_THREADS - 1) / TPG_CLIP_THREADS, nb, T);
+        hipLaunchKernelGGL(clip_gather_low_kernel, grid, dim3(TPG_CLIP_THREADS), 0, st, high_pos, vel, cf, fps, noise,
+                           jitter, b0, B, K, M, low_pos, low_vel);
         TPG_RETURN_IF_LAUNCH_FAILED();
     }
     return TPG_OK;

@@ -1,5 +1,6 @@
 // Shared helpers for the gfx950 kernels: launch plumbing, cross-lane moves, wave reductions.  wave = 64 lanes
-// everywhere.  (Row chunks and bf16 conversion: tpg_rows.hpp; the BatchNorm finalize pieces: tpg_bn_finalize.hpp.)
+// everywhere.  (Row chunks and bf16 conversion: tpg_rows.hpp; the BatchNorm finalize pieces: tpg_bn_finalize.hpp; the
+// samplers' radix select, LDS sort and clip tables: tpg_select.hpp.)
 //
 // Every translation unit is compiled with -ffp-contract=off: the canonical
 // distance sum_d (a_d-b_d)^2 must round each mul and add separately so that

@@ -1012,6 +1012,7 @@ def context_expand(pos, edge, mask, state, t0):
 
 # ------------------------------------------- training clips from device-resident sequences (csrc/clip_sample.hip)
 PATCH_SELECT_NAN_KEY = 0x7FC00000      # the bit pattern every NaN distance ranks as (after +inf)
+CLIP_MAX_T = 8                         # frames per clip the gathers take: csrc/tpg_select.hpp's TPG_CLIP_MAX_T says the same
 
 
 def _host_ints(a, name, shape):
@@ -1021,9 +1022,16 @@ def _host_ints(a, name, shape):
         a = a.numpy()
     a = np.asarray(a)
     _need(a.dtype.kind in "iu", f"{name} must hold integers, got {a.dtype}")
-    _need(a.shape == tuple(shape), f"{name} must have shape {tuple(shape)}, got {a.shape}")
+    _need(a.ndim == len(shape) and all(s in (None, n) for s, n in zip(shape, a.shape)),    # None: any extent, the table's
+          f"{name} must have shape {tuple(shape)}, got {a.shape}")
     _need(a.size == 0 or (a.min() >= -2 ** 31 and a.max() < 2 ** 31), f"{name} does not fit int32")
     return np.ascontiguousarray(a, dtype=np.int32)
+
+
+def _check_frames(first, count, rows, what):
+    """Every frame (scene) is a non-empty slice of the `rows` stored rows of `what`; count broadcasts over first."""
+    _need(bool((count > 0).all() and (first >= 0).all() and (first.astype(np.int64) + count <= rows).all()),
+          f"every frame must be a non-empty slice of {what}")
 
 
 def _patch_select_torch(points, first, count, seed, K):
@@ -1055,8 +1063,7 @@ def patch_select(points, first, count, seed, K):
     K = int(K)
     _need(B > 0, "patch_select needs at least one scene")
     _need(K > 0, "K must be positive")
-    _need(bool((first >= 0).all() and (count > 0).all() and (first.astype(np.int64) + count <= points.shape[0]).all()),
-          "every scene must be a non-empty slice of points")
+    _check_frames(first, count, points.shape[0], "points")
     _need(bool((count >= K).all()), f"K = {K} exceeds a scene's particle count ({int(count.min())})")
     _need(bool(((seed >= 0) & (seed < count)).all()), "seed must index a point of its scene")
     be = backend_for(points)
@@ -1081,17 +1088,13 @@ def clip_gather_high(pos, vel, frame_first, count, centroids, centroid_row, patc
         _same_device(pos, vel)
         _need(vel.shape == pos.shape, "vel must have pos's shape")
     B = patch.shape[0]
-    frame_first = np.asarray(frame_first.numpy() if isinstance(frame_first, torch.Tensor) else frame_first)
-    _need(frame_first.ndim == 2 and frame_first.shape[1] == B, "frame_first must be (T,B)")
+    frame_first = _host_ints(frame_first, "frame_first", (None, B))
     T = frame_first.shape[0]
-    frame_first = _host_ints(frame_first, "frame_first", (T, B))
     count = _host_ints(count, "count", (B,))
     centroid_row = _host_ints(centroid_row, "centroid_row", (B,))
-    _need(1 <= T <= 8, "a clip has 1..8 frames")
+    _need(1 <= T <= CLIP_MAX_T, f"a clip has 1..{CLIP_MAX_T} frames")
     _need(B > 0 and patch.shape[1] > 0, "patch must be (B,K) with B, K positive")
-    _need(bool((count > 0).all() and (frame_first >= 0).all()
-               and (frame_first.astype(np.int64) + count[None, :] <= pos.shape[0]).all()),
-          "every frame must be a non-empty slice of pos")
+    _check_frames(frame_first, count, pos.shape[0], "pos")
     _need(bool(((centroid_row >= 0) & (centroid_row < centroids.shape[0])).all()), "centroid_row out of range")
     be = backend_for(pos)
     with torch.no_grad():
@@ -1116,7 +1119,7 @@ def clip_gather_low(high_pos, fps_idx, noise=None, jitter=0.0, vel=None, frame_f
     T, B, K, _ = high_pos.shape
     M = fps_idx.shape[1]
     _need(high_pos.shape[3] == 3 and fps_idx.shape[0] == B and min(T, B, K, M) > 0, "high_pos (T,B,K,3), fps_idx (B,M)")
-    _need(T <= 8, "a clip has 1..8 frames")
+    _need(T <= CLIP_MAX_T, f"a clip has 1..{CLIP_MAX_T} frames")
     if noise is not None:
         _check_float(noise, "noise", 4)
         _same_device(high_pos, noise)
@@ -1128,9 +1131,7 @@ def clip_gather_low(high_pos, fps_idx, noise=None, jitter=0.0, vel=None, frame_f
         _need(frame_first is not None and count is not None, "low-resolution velocities need frame_first and count")
         frame_first = _host_ints(frame_first, "frame_first", (T, B))
         count = _host_ints(count, "count", (B,))
-        _need(bool((count > 0).all() and (frame_first >= 0).all()
-                   and (frame_first.astype(np.int64) + count[None, :] <= vel.shape[0]).all()),
-              "every frame must be a non-empty slice of vel")
+        _check_frames(frame_first, count, vel.shape[0], "vel")
     be = backend_for(high_pos)
     with torch.no_grad():
         if hasattr(be, "clip_gather_low"):
@@ -1198,13 +1199,11 @@ def action_gather(points, frame_first, count, idx, scale=None, mode="train"):
     _need(points.shape[1] == 3, "points must be (P,3)")
     _need(mode in ("train", "test"), 'mode must be "train" or "test"')
     T, B, K = idx.shape
-    _need(1 <= T <= 8, "a clip has 1..8 frames")
+    _need(1 <= T <= CLIP_MAX_T, f"a clip has 1..{CLIP_MAX_T} frames")
     _need(B > 0 and K > 0, "idx must be (T,B,K) with B, K positive")
     frame_first = _host_ints(frame_first, "frame_first", (T, B))
     count = _host_ints(count, "count", (T, B))
-    _need(bool((count > 0).all() and (frame_first >= 0).all()
-               and (frame_first.astype(np.int64) + count <= points.shape[0]).all()),
-          "every frame must be a non-empty slice of points")
+    _check_frames(frame_first, count, points.shape[0], "points")
     if scale is not None:
         _need(mode == "train", "the test split has no scale")
         scale = np.ascontiguousarray(scale.numpy() if isinstance(scale, torch.Tensor) else scale, dtype=np.float64)

@@ -98,8 +98,13 @@ def load_checkpoint(path):
     return torch.load(path, map_location="cpu", weights_only=True)
 
 
-def main(argv=None):
-    opt = parse_args(argv)
+def run(opt, nets_of, sched_of, sampler_of, step):
+    """The training loop both trainers share (--seed, --device, --lr, --amp, --freeze_D, --iters, --resume,
+    --path_to_resume, --log_dir, --log_every and --ckpt_every of `opt`); what differs comes as four callables:
+    nets_of(dev) -> (sr_net, tempo_dis, spatial_dis) on the device; sched_of(optimiser) -> its scheduler;
+    sampler_of(dev, seed) -> the clip sampler, its `generator` seeded with `seed`;
+    step((sr_net, tempo_dis, spatial_dis), (sr_optim, tempo_optim, spatial_optim), batch, n_iter, freeze_D, sync,
+    amp_dtype) -> the losses of one adversarial step; the last three go to the step function under those names."""
     rank, world, local = ddp.init_from_env(backend=os.environ.get("TPGAN_DDP_BACKEND"))
     dev = torch.device(opt.device)
     if dev.type == "cuda":
@@ -110,51 +115,40 @@ def main(argv=None):
     np.random.seed(opt.seed + 1000 * rank)
     torch.manual_seed(opt.seed)                      # same initial weights on every rank; broadcast below anyway
 
-    sr_net = SRNet(opt.in_node_feats, 128).to(dev)
-    tempo_dis = FluidTempoDis(3).to(dev)
-    spatial_dis = FluidSpatialDis().to(dev)
-    sr_optim = torch.optim.Adam(sr_net.parameters(), lr=opt.lr)
-    tempo_optim = torch.optim.Adam(tempo_dis.parameters(), lr=0.33 * opt.lr)
-    spatial_optim = torch.optim.Adam(spatial_dis.parameters(), lr=0.33 * opt.lr)
-    scheds = [torch.optim.lr_scheduler.StepLR(o, 10000, gamma=0.7) for o in (sr_optim, tempo_optim, spatial_optim)]
+    nets = nets_of(dev)
+    optims = tuple(torch.optim.Adam(net.parameters(), lr=lr)
+                   for net, lr in zip(nets, (opt.lr, 0.33 * opt.lr, 0.33 * opt.lr)))
+    scheds = [sched_of(o) for o in optims]
     sync = ddp.GradSync()
-    sync.broadcast_state(sr_net, tempo_dis, spatial_dis)
+    sync.broadcast_state(*nets)
     torch.manual_seed(opt.seed + 1000 * rank)
+    sampler = sampler_of(dev, opt.seed + 1000 * rank)
 
-    sequences = FluidSequences(opt.train_dataset_path, opt.train_sequence_num, opt.sequence_length, device=dev)
-    sample_num = opt.sample_num or (9216 if opt.batch_size <= 4 and not opt.small_batch else 4096)
-    generator = torch.Generator().manual_seed(opt.seed + 1000 * rank)
-    sampler = ClipSampler(sequences, opt.batch_size, sample_num, generator=generator)
+    held = {"sr_net": nets[0], "tempo_dis": nets[1], "spatial_dis": nets[2],
+            "sr_optim": optims[0], "tempo_optim": optims[1], "spatial_optim": optims[2],
+            "sr_sched": scheds[0], "tempo_sched": scheds[1], "spatial_sched": scheds[2]}
 
     n_iter = 0
     if opt.resume:
         ckpt = load_checkpoint(opt.path_to_resume)
-        sr_net.load_state_dict(ckpt["sr_net"])
-        tempo_dis.load_state_dict(ckpt["tempo_dis"])
-        spatial_dis.load_state_dict(ckpt["spatial_dis"])
-        sr_optim.load_state_dict(ckpt["sr_optim"])
-        tempo_optim.load_state_dict(ckpt["tempo_optim"])
-        spatial_optim.load_state_dict(ckpt["spatial_optim"])
-        for s, k in zip(scheds, ("sr_sched", "tempo_sched", "spatial_sched")):
-            s.load_state_dict(ckpt[k])
+        for k, x in held.items():
+            x.load_state_dict(ckpt[k])
         n_iter = int(ckpt["n_iter"])
         if "tpgan_amd" in ckpt and world == 1:       # (the file holds rank 0's streams; other ranks keep their seeds)
-            _set_rng_state(ckpt["tpgan_amd"], dev, generator)
+            _set_rng_state(ckpt["tpgan_amd"], dev, sampler.generator)
 
     ckpt_dir = os.path.join(opt.log_dir, "model_ckpt")
     if rank == 0:
         os.makedirs(ckpt_dir, exist_ok=True)
     amp_dtype = torch.bfloat16 if opt.amp == "bf16" else None
     batches = prefetch(sampler)
-    sr_net.train(), tempo_dis.train(), spatial_dis.train()
+    for net in nets:
+        net.train()
     window_start, window_iters = time.time(), 0
     while n_iter < opt.iters:
         data = next(batches)
-        high_pos, high_vel, low_pos, low_vel = list(data[0:3]), list(data[3:6]), list(data[6:9]), list(data[9:12])
         n_iter += 1
-        losses = tempo_gan_step(sr_net, spatial_dis, tempo_dis, low_pos, low_vel, high_pos, high_vel, 1., opt, n_iter,
-                                sr_optim, tempo_optim, spatial_optim, freeze_D=opt.freeze_D, sync=sync,
-                                amp_dtype=amp_dtype)
+        losses = step(nets, optims, data, n_iter, opt.freeze_D, sync, amp_dtype)
         for s in scheds:
             s.step()
         window_iters += 1
@@ -166,17 +160,31 @@ def main(argv=None):
                               **{k: float(v) for k, v in losses.items()}}), flush=True)
             window_start, window_iters = now, 0
         if rank == 0 and ((n_iter - 1) % opt.ckpt_every == 0 or n_iter >= opt.iters):
-            save_checkpoint({
-                "sr_net": sr_net.state_dict(), "tempo_dis": tempo_dis.state_dict(),
-                "spatial_dis": spatial_dis.state_dict(), "n_iter": n_iter,
-                "sr_optim": sr_optim.state_dict(), "tempo_optim": tempo_optim.state_dict(),
-                "spatial_optim": spatial_optim.state_dict(),
-                "sr_sched": scheds[0].state_dict(), "tempo_sched": scheds[1].state_dict(),
-                "spatial_sched": scheds[2].state_dict(),
-                "tpgan_amd": _rng_state(dev, batches.resume_state),
-            }, os.path.join(ckpt_dir, f"tpugan_checkpoint{n_iter}.ckpt"))
+            state = {k: x.state_dict() for k, x in held.items()}
+            state.update(n_iter=n_iter, tpgan_amd=_rng_state(dev, batches.resume_state))
+            save_checkpoint({k: state[k] for k in CKPT_KEYS}, os.path.join(ckpt_dir, f"tpugan_checkpoint{n_iter}.ckpt"))
     ddp.barrier()
     return 0
+
+
+def main(argv=None):
+    opt = parse_args(argv)
+
+    def nets_of(dev):
+        return SRNet(opt.in_node_feats, 128).to(dev), FluidTempoDis(3).to(dev), FluidSpatialDis().to(dev)
+
+    def sampler_of(dev, seed):
+        sequences = FluidSequences(opt.train_dataset_path, opt.train_sequence_num, opt.sequence_length, device=dev)
+        sample_num = opt.sample_num or (9216 if opt.batch_size <= 4 and not opt.small_batch else 4096)
+        return ClipSampler(sequences, opt.batch_size, sample_num, generator=torch.Generator().manual_seed(seed))
+
+    def step(nets, optims, data, n_iter, freeze_D, sync, amp_dtype):
+        sr_net, tempo_dis, spatial_dis = nets
+        high_pos, high_vel, low_pos, low_vel = list(data[0:3]), list(data[3:6]), list(data[6:9]), list(data[9:12])
+        return tempo_gan_step(sr_net, spatial_dis, tempo_dis, low_pos, low_vel, high_pos, high_vel, 1., opt, n_iter,
+                              *optims, freeze_D=freeze_D, sync=sync, amp_dtype=amp_dtype)
+
+    return run(opt, nets_of, lambda o: torch.optim.lr_scheduler.StepLR(o, 10000, gamma=0.7), sampler_of, step)
 
 
 if __name__ == "__main__":

@@ -11,8 +11,8 @@ import pytest
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-from test_action_data_cpu import (STEP_GOLDEN, _equal, check_golden_items, check_trainer, gather, subset,  # noqa: E402
-                                  within_one_ulp, write_random_dataset)
+from test_action_data_cpu import (STEP_GOLDEN, _equal, check_golden_items, check_trainer, gather, keys,  # noqa: E402
+                                  subset, within_one_ulp, write_random_dataset)
 
 pytestmark = pytest.mark.gpu
 
@@ -40,6 +40,18 @@ def test_frame_subset_equals_the_rule(dev, n, K):
     assert np.array_equal(got[0], subset(n, K, seed))
     if n == K:
         assert np.array_equal(got[0], np.arange(K))
+
+
+def test_frame_subset_of_all_but_one_point(dev):
+    """n = K + 1 (65 and 64): every key but the largest survives, so in each pass the rank asked of the histogram is the
+    last or the last but one of its entries and the bin found is the last or the last but one that is occupied."""
+    import tpgan_amd.ops as ops
+    n, K = 65, 64
+    seeds = seeds_for(5)
+    got = ops.frame_subset([n] * len(seeds), seeds, K, device=dev).cpu().numpy()
+    for f, seed in enumerate(seeds):
+        assert np.array_equal(got[f], subset(n, K, seed)), f
+        assert np.array_equal(np.setdiff1d(np.arange(n), got[f]), [np.argmax(keys(n, seed))]), f
 
 
 def test_frame_subset_ragged_batch_equals_single_calls_and_repeats(dev):

@@ -103,6 +103,25 @@ def test_patch_select_ties_are_decided_by_index(dev):
         assert np.array_equal(select(dev, [pad], [sd], 6000)[0], rule(pad, sd, 6000)), sd
 
 
+def test_patch_select_ties_across_chunks_of_a_three_chunk_scene(dev):
+    """2 * 1024 + 1 points, K = 1025: the whole first chunk of 1024 candidates, then ONE of the middle chunk, and the
+    third chunk's single candidate stays out.  Every point is 0.5 or 2 from the seed along one axis (d2 = 4^-1 or 4^1,
+    exact in fp32), and everything after the first chunk is at the far distance: the K-th distance has ties in all three
+    chunks, of which the first chunk's and the first of the middle chunk's are taken."""
+    rng = np.random.default_rng(2049)
+    N, K = 2 * 1024 + 1, 1025
+    far = np.ones(N, bool)
+    far[1:1024] = rng.uniform(size=1023) < 0.5
+    step = np.zeros((N, 3), np.float32)
+    step[np.arange(N), rng.integers(3, size=N)] = np.where(far, 2.0, 0.5) * rng.choice([-1.0, 1.0], size=N)
+    step[0] = 0.0
+    pts = (np.asarray((1.0, 0.5, 2.0), np.float32) + step).astype(np.float32)
+    got = select(dev, [pts], [0], K)[0]
+    assert np.array_equal(got, rule(pts, 0, K))
+    near = np.flatnonzero(~far)
+    assert got[0] == 0 and np.array_equal(got[1:1 + len(near)], near) and got[-1] == 1024 and 2048 not in got
+
+
 def test_patch_select_non_finite_coordinates(dev):
     """NaN distances rank after every finite one and after +inf, tied among themselves, by index."""
     rng = np.random.default_rng(3)
