@@ -48,24 +48,23 @@ __global__ __launch_bounds__(CI_WAVES * 64) void cubic_interp_kernel(
     const size_t q = (size_t)b * Nq + i;
     const float qx = query[q * 3], qy = query[q * 3 + 1], qz = query[q * 3 + 2];
     const float *cb = pos + (size_t)b * Np * 3;
-    const tpg_u64 INF = ~0ull;
-    tpg_u64 best = INF, thr = INF;
+    tpg_u64 best = TPG_KNN_INF, thr = TPG_KNN_INF;
     for (int base = 0; base < Np; base += 64) {
         const int j = base + lane;
-        tpg_u64 key = INF;
+        tpg_u64 key = TPG_KNN_INF;
         if (j < Np) {
             const float d = tpg_sq3(qx, qy, qz, cb[(size_t)j * 3], cb[(size_t)j * 3 + 1], cb[(size_t)j * 3 + 2]);
-            if (d < r2) key = ((tpg_u64)__float_as_uint(d) << 32) | (unsigned)j;
+            if (d < r2) key = tpg_knn_key(d, j);
         }
         tpg_knn_merge(best, thr, key, CI_K, lane, slot);
     }
-    const bool has = lane < CI_K && best != INF;
+    const bool has = lane < CI_K && best != TPG_KNN_INF;
     const int nh = __popcll(__ballot(has));
     float w = 0.0f;
     int j = 0;
     if (has) {
-        float d2 = __uint_as_float((unsigned)(best >> 32));
-        j = (int)(unsigned)best;
+        float d2 = tpg_knn_key_dist(best);
+        j = (int)tpg_knn_key_idx(best);
         if (d2 < 1e-8f) d2 = 0.0f;                      // l2dist, interpolation.py:13
         w = bicubic_w(sqrtf(d2), cutoff, coeff);
     }

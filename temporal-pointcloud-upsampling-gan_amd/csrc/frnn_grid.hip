@@ -28,10 +28,6 @@
 
 namespace {
 
-__device__ __forceinline__ tpg_u64 fg_pack(float d, int j) {
-    return ((tpg_u64)__float_as_uint(d) << 32) | (unsigned)j;
-}
-
 // one wave per query: the K nearest stored points with d < r2, ascending (dist, idx); -1 / -1 padding
 __global__ __launch_bounds__(FG_WAVES * 64) void fg_query_kernel(
     const float *__restrict__ p1, const int64_t *__restrict__ len1, int P1, int P2,
@@ -49,7 +45,7 @@ __global__ __launch_bounds__(FG_WAVES * 64) void fg_query_kernel(
     int64_t *oi = idx + q * K;
     const int n1 = len1 ? (int)len1[b] : P1;
     if (i >= n1) {
-        for (int k = lane; k < K; k += 64) { od[k] = -1.0f; oi[k] = -1; }
+        tpg_knn_pad_row(od, oi, K, lane, -1.0f, -1);
         return;
     }
     const GridParams g = gp[b];
@@ -73,8 +69,7 @@ __global__ __launch_bounds__(FG_WAVES * 64) void fg_query_kernel(
         re[t] = end;
         total += end - bgn;
     }
-    const tpg_u64 INF = ~0ull;
-    tpg_u64 best = INF, thr = INF;
+    tpg_u64 best = TPG_KNN_INF, thr = TPG_KNN_INF;
     for (int base = 0; base < total; base += 64) {
         // candidate number base + lane of the concatenated runs
         int c = base + lane, pos = -1;
@@ -84,14 +79,11 @@ __global__ __launch_bounds__(FG_WAVES * 64) void fg_query_kernel(
             if (pos < 0 && c < n) pos = rb[t] + c;
             c -= (pos < 0) ? n : 0;
         }
-        tpg_u64 key = INF;
+        tpg_u64 key = TPG_KNN_INF;
         if (pos >= 0 && base + lane < total) {
             const float4 p = pts[pos];
-            const float t0 = qx - p.x, t1 = qy - p.y, t2 = qz - p.z;
-            float d = t0 * t0;
-            d = d + t1 * t1;
-            d = d + t2 * t2;
-            if (d < r2) key = fg_pack(d, __float_as_int(p.w));
+            const float d = tpg_sq3(qx, qy, qz, p.x, p.y, p.z);
+            if (d < r2) key = tpg_knn_key(d, __float_as_int(p.w));
         }
         if (K == 1) best = key < best ? key : best;
         else tpg_knn_merge(best, thr, key, K, lane, slot);
@@ -99,14 +91,14 @@ __global__ __launch_bounds__(FG_WAVES * 64) void fg_query_kernel(
     if (K == 1) {
         best = tpg_wave_min_u64(best);
         if (lane == 0) {
-            if (best == INF) { od[0] = -1.0f; oi[0] = -1; }
-            else { od[0] = __uint_as_float((unsigned)(best >> 32)); oi[0] = (long long)(unsigned)best; }
+            if (best == TPG_KNN_INF) { od[0] = -1.0f; oi[0] = -1; }
+            else { od[0] = tpg_knn_key_dist(best); oi[0] = tpg_knn_key_idx(best); }
         }
         return;
     }
     if (lane < K) {
-        if (best == INF) { od[lane] = -1.0f; oi[lane] = -1; }
-        else { od[lane] = __uint_as_float((unsigned)(best >> 32)); oi[lane] = (long long)(unsigned)best; }
+        if (best == TPG_KNN_INF) { od[lane] = -1.0f; oi[lane] = -1; }
+        else { od[lane] = tpg_knn_key_dist(best); oi[lane] = tpg_knn_key_idx(best); }
     }
 }
 
@@ -132,7 +124,7 @@ __global__ __launch_bounds__(FG_WAVES * 64) void fg_knn_kernel(
     const GridParams g = gp[b];
     const int *st = start + (size_t)b * (cstride + 1);
     if (i >= n1 || st[g.ncell] <= 0) {
-        for (int k = lane; k < K; k += 64) { od[k] = 0.0f; oi[k] = 0; }
+        tpg_knn_pad_row(od, oi, K, lane, 0.0f, 0);
         return;
     }
     const float4 *pts = sorted + (size_t)b * P2;
@@ -141,28 +133,23 @@ __global__ __launch_bounds__(FG_WAVES * 64) void fg_knn_kernel(
     const int cx = min(max(cell_axis(qx, g.lo[0], g.inv_h), 0), g.dim[0] - 1);
     const int cy = min(max(cell_axis(qy, g.lo[1], g.inv_h), 0), g.dim[1] - 1);
     const int cz = min(max(cell_axis(qz, g.lo[2], g.inv_h), 0), g.dim[2] - 1);
-    const tpg_u64 INF = ~0ull;
-    tpg_u64 best = INF;
+    tpg_u64 best = TPG_KNN_INF;
     for (int R = 1;; ++R) {
         const int x0 = max(cx - R, 0), x1 = min(cx + R, g.dim[0] - 1);
         const int y0 = max(cy - R, 0), y1 = min(cy + R, g.dim[1] - 1);
         const int z0 = max(cz - R, 0), z1 = min(cz + R, g.dim[2] - 1);
-        best = INF;
-        tpg_u64 thr = INF;
+        best = TPG_KNN_INF;
+        tpg_u64 thr = TPG_KNN_INF;
         for (int zz = z0; zz <= z1; ++zz)
             for (int yy = y0; yy <= y1; ++yy) {
                 const int row = (zz * g.dim[1] + yy) * g.dim[0];
                 const int bgn = st[row + x0], end = st[row + x1 + 1];
                 for (int base = bgn; base < end; base += 64) {
                     const int pos = base + lane;
-                    tpg_u64 key = INF;
+                    tpg_u64 key = TPG_KNN_INF;
                     if (pos < end) {
                         const float4 p = pts[pos];
-                        const float t0 = qx - p.x, t1 = qy - p.y, t2 = qz - p.z;
-                        float d = t0 * t0;
-                        d = d + t1 * t1;
-                        d = d + t2 * t2;
-                        key = fg_pack(d, __float_as_int(p.w));
+                        key = tpg_knn_key(tpg_sq3(qx, qy, qz, p.x, p.y, p.z), __float_as_int(p.w));
                     }
                     if (K == 1) best = key < best ? key : best;
                     else tpg_knn_merge(best, thr, key, K, lane, slot);
@@ -180,13 +167,36 @@ __global__ __launch_bounds__(FG_WAVES * 64) void fg_knn_kernel(
         if (z0 > 0) bd = fminf(bd, qz - (g.lo[2] + (float)z0 * h));
         if (z1 < g.dim[2] - 1) bd = fminf(bd, (g.lo[2] + (float)(z1 + 1) * h) - qz);
         bd -= 1.0e-4f * h;                               // a point within rounding of a cell face may sit in either cell
-        if (kth != INF && bd > 0.0f && __uint_as_float((unsigned)(kth >> 32)) < bd * bd * 0.999999f) break;
+        if (kth != TPG_KNN_INF && bd > 0.0f && tpg_knn_key_dist(kth) < bd * bd * 0.999999f) break;
     }
     if (lane < K) {
-        const tpg_u64 mine = best;
-        if (mine == INF) { od[lane] = 0.0f; oi[lane] = 0; }
-        else { od[lane] = __uint_as_float((unsigned)(mine >> 32)); oi[lane] = (long long)(unsigned)mine; }
+        if (best == TPG_KNN_INF) { od[lane] = 0.0f; oi[lane] = 0; }
+        else { od[lane] = tpg_knn_key_dist(best); oi[lane] = tpg_knn_key_idx(best); }
     }
+}
+
+// both entries: the radius search (radius: K nearest within r) or the plain kNN (r unused) of p1 among p2
+int fg_search(bool radius, const float *p1, const float *p2, const int64_t *len1, const int64_t *len2, int B, int P1,
+              int P2, int K, float r, float *dist, int64_t *idx, void *ws, hipStream_t st) {
+    if (B < 0 || P1 < 0 || P2 < 0 || K < 1 || K > 64 || (radius && !(r > 0.0f))) return TPG_ERR_ARG;
+    if (B == 0 || P1 == 0) return TPG_OK;
+    if (!p1 || !dist || !idx) return TPG_ERR_ARG;
+    if (P2 == 0) return TPG_ERR_UNSUPPORTED;             // (the exhaustive entry pads an empty search)
+    if (!p2 || !fg_workspace_ok(ws)) return TPG_ERR_ARG;
+    GridParams *gp; int *start; float4 *sorted;
+    const int rc = fg_build(p2, len2, B, P2, radius ? r : 0.0f, radius ? 0 : K, ws, st, &gp, &start, &sorted);
+    if (rc) return rc;
+    const dim3 grid(fg_query_blocks(P1), B), block(FG_WAVES * 64);
+    if (radius) {
+        const float r2 = r * r;     // fp32(r) * fp32(r), the value the exhaustive entry is given
+        hipLaunchKernelGGL(fg_query_kernel, grid, block, 0, st, p1, len1, P1, P2, gp, FG_CELLS, start, sorted, K, r2,
+                           dist, idx);
+    } else {
+        hipLaunchKernelGGL(fg_knn_kernel, grid, block, 0, st, p1, len1, P1, P2, gp, FG_CELLS, start, sorted, K, dist,
+                           idx);
+    }
+    TPG_RETURN_IF_LAUNCH_FAILED();
+    return TPG_OK;
 }
 
 }  // namespace
@@ -195,35 +205,10 @@ extern "C" size_t tpg_frnn_grid_workspace_bytes(int B, int P2) { return fg_works
 
 extern "C" int tpg_frnn_grid_f32(const float *p1, const float *p2, const int64_t *len1, const int64_t *len2, int B,
                                  int P1, int P2, int K, float r, float *dist, int64_t *idx, void *ws, void *stream) {
-    if (B < 0 || P1 < 0 || P2 < 0 || K < 1 || K > 64 || !(r > 0.0f)) return TPG_ERR_ARG;
-    if (B == 0 || P1 == 0) return TPG_OK;
-    if (!p1 || !dist || !idx) return TPG_ERR_ARG;
-    hipStream_t st = tpg_stream(stream);
-    if (P2 == 0) return TPG_ERR_UNSUPPORTED;             // (the exhaustive entry pads an empty search)
-    if (!p2 || !ws || (reinterpret_cast<uintptr_t>(ws) & 255)) return TPG_ERR_ARG;
-    GridParams *gp; int *start; float4 *sorted;
-    const int rc = fg_build(p2, len2, B, P2, r, 0, ws, st, &gp, &start, &sorted);
-    if (rc) return rc;
-    const float r2 = r * r;     // fp32(r) * fp32(r), the value the exhaustive entry is given
-    hipLaunchKernelGGL(fg_query_kernel, dim3((P1 + FG_WAVES - 1) / FG_WAVES, B), dim3(FG_WAVES * 64), 0, st, p1, len1, P1,
-                       P2, gp, FG_CELLS, start, sorted, K, r2, dist, idx);
-    TPG_RETURN_IF_LAUNCH_FAILED();
-    return TPG_OK;
+    return fg_search(true, p1, p2, len1, len2, B, P1, P2, K, r, dist, idx, ws, tpg_stream(stream));
 }
 
 extern "C" int tpg_knn_grid_f32(const float *p1, const float *p2, const int64_t *len1, const int64_t *len2, int B,
                                 int P1, int P2, int K, float *dist, int64_t *idx, void *ws, void *stream) {
-    if (B < 0 || P1 < 0 || P2 < 0 || K < 1 || K > 64) return TPG_ERR_ARG;
-    if (B == 0 || P1 == 0) return TPG_OK;
-    if (!p1 || !dist || !idx) return TPG_ERR_ARG;
-    hipStream_t st = tpg_stream(stream);
-    if (P2 == 0) return TPG_ERR_UNSUPPORTED;             // (the exhaustive entry pads an empty search)
-    if (!p2 || !ws || (reinterpret_cast<uintptr_t>(ws) & 255)) return TPG_ERR_ARG;
-    GridParams *gp; int *start; float4 *sorted;
-    const int rc = fg_build(p2, len2, B, P2, 0.0f, K, ws, st, &gp, &start, &sorted);
-    if (rc) return rc;
-    hipLaunchKernelGGL(fg_knn_kernel, dim3((P1 + FG_WAVES - 1) / FG_WAVES, B), dim3(FG_WAVES * 64), 0, st, p1, len1, P1,
-                       P2, gp, FG_CELLS, start, sorted, K, dist, idx);
-    TPG_RETURN_IF_LAUNCH_FAILED();
-    return TPG_OK;
+    return fg_search(false, p1, p2, len1, len2, B, P1, P2, K, 0.0f, dist, idx, ws, tpg_stream(stream));
 }

@@ -183,7 +183,13 @@ static inline size_t fg_workspace_bytes(int B, int P2) {
            align256(sizeof(float4) * (size_t)B * P2);
 }
 
-// grid build shared by the two entries; r > 0: radius form, knn_k > 0: kNN form
+// what every entry that builds the grid asks of the workspace pointer
+static inline bool fg_workspace_ok(const void *ws) { return ws && !(reinterpret_cast<uintptr_t>(ws) & 255); }
+
+// workgroups along x of a one-wave-per-query launch over P1 queries (FG_WAVES * 64 threads each)
+static inline unsigned fg_query_blocks(int P1) { return (unsigned)((P1 + FG_WAVES - 1) / FG_WAVES); }
+
+// grid build shared by the entries; r > 0: radius form, knn_k > 0: kNN form
 static int fg_build(const float *p2, const int64_t *len2, int B, int P2, float r, int knn_k, void *ws, hipStream_t st,
                     GridParams **gp_o, int **start_o, float4 **sorted_o) {
     unsigned char *w = static_cast<unsigned char *>(ws);

@@ -34,20 +34,13 @@ namespace {
 
 constexpr int KNN_WAVES = 4;  // waves (= queries) per workgroup
 
-__device__ __forceinline__ tpg_u64 knn_pack(float d, int j) {
-    return ((tpg_u64)__float_as_uint(d) << 32) | (unsigned)j;
-}
-
 // distance between the wave's query (LDS, broadcast reads) and this lane's row.
 template <int D_T>
 __device__ __forceinline__ float knn_dist(const float *__restrict__ qs,
                                           const float *__restrict__ c, int D) {
     float acc = 0.0f;
     if constexpr (D_T == 3) {
-        const float t0 = qs[0] - c[0], t1 = qs[1] - c[1], t2 = qs[2] - c[2];
-        acc = t0 * t0;
-        acc = acc + t1 * t1;
-        acc = acc + t2 * t2;
+        acc = tpg_sq3(qs[0], qs[1], qs[2], c[0], c[1], c[2]);
     } else if constexpr (D_T > 0) {
         static_assert(D_T % 4 == 0, "vector path needs D % 4 == 0");
         const float4 *c4 = reinterpret_cast<const float4 *>(c);
@@ -106,47 +99,43 @@ __global__ __launch_bounds__(KNN_WAVES * 64) void knn_kernel(
     float *od = dist + q * K;
     int64_t *oi = idx + q * K;
     if (i >= n1 || n2 <= 0) {
-        for (int k = lane; k < K; k += 64) { od[k] = pad_d; oi[k] = pad_i; }
+        tpg_knn_pad_row(od, oi, K, lane, pad_d, pad_i);
         return;
     }
 
     const float *cbase = p2 + (size_t)b * P2 * D;
-    const tpg_u64 INF = ~0ull;
 
     if (K == 1) {
-        tpg_u64 best = INF;
+        tpg_u64 best = TPG_KNN_INF;
         for (int j = lane; j < n2; j += 64) {
             const float d = knn_dist<D_T>(qs, cbase + (size_t)j * D, D);
             if (!RADIUS || d < r2) {
-                const tpg_u64 key = knn_pack(d, j);
+                const tpg_u64 key = tpg_knn_key(d, j);
                 best = key < best ? key : best;
             }
         }
         best = tpg_wave_min_u64(best);
         if (lane == 0) {
-            if (best == INF) { od[0] = pad_d; oi[0] = pad_i; }
-            else { od[0] = __uint_as_float((unsigned)(best >> 32)); oi[0] = (long long)(unsigned)best; }
+            if (best == TPG_KNN_INF) { od[0] = pad_d; oi[0] = pad_i; }
+            else { od[0] = tpg_knn_key_dist(best); oi[0] = tpg_knn_key_idx(best); }
         }
         return;
     }
 
-    tpg_u64 best = INF;  // lane l: l-th smallest key so far
-    tpg_u64 thr = INF;   // wave-uniform: key of rank K-1
+    tpg_u64 best = TPG_KNN_INF;  // lane l: l-th smallest key so far
+    tpg_u64 thr = TPG_KNN_INF;   // wave-uniform: key of rank K-1
     for (int base = 0; base < n2; base += 64) {
         const int j = base + lane;
-        tpg_u64 key = INF;
+        tpg_u64 key = TPG_KNN_INF;
         if (j < n2) {
             const float d = knn_dist<D_T>(qs, cbase + (size_t)j * D, D);
-            if (!RADIUS || d < r2) key = knn_pack(d, j);
+            if (!RADIUS || d < r2) key = tpg_knn_key(d, j);
         }
         tpg_knn_merge(best, thr, key, K, lane, slot);
     }
     if (lane < K) {
-        if (best == INF) { od[lane] = pad_d; oi[lane] = pad_i; }
-        else {
-            od[lane] = __uint_as_float((unsigned)(best >> 32));
-            oi[lane] = (long long)(unsigned)best;
-        }
+        if (best == TPG_KNN_INF) { od[lane] = pad_d; oi[lane] = pad_i; }
+        else { od[lane] = tpg_knn_key_dist(best); oi[lane] = tpg_knn_key_idx(best); }
     }
 }
 
@@ -181,10 +170,9 @@ __global__ __launch_bounds__(KNN_WAVES * 64) void knn_tile_kernel(
     __syncthreads();
     const int n1 = len1 ? (int)len1[b] : P1;
     const int n2 = len2 ? min((int)len2[b], P2) : P2;
-    const tpg_u64 INF = ~0ull;
     tpg_u64 best[Q], thr[Q];
 #pragma unroll
-    for (int qq = 0; qq < Q; ++qq) { best[qq] = INF; thr[qq] = INF; }
+    for (int qq = 0; qq < Q; ++qq) { best[qq] = TPG_KNN_INF; thr[qq] = TPG_KNN_INF; }
     const float *cbase = p2 + (size_t)b * P2 * D_T;
     for (int base = 0; base < n2; base += 64) {
         const int j = base + lane;
@@ -214,8 +202,8 @@ __global__ __launch_bounds__(KNN_WAVES * 64) void knn_tile_kernel(
                 t = qv.z - row[d].z; acc = acc + t * t;
                 t = qv.w - row[d].w; acc = acc + t * t;
             }
-            tpg_u64 key = INF;
-            if (j < n2 && (!RADIUS || acc < r2)) key = knn_pack(acc, j);
+            tpg_u64 key = TPG_KNN_INF;
+            if (j < n2 && (!RADIUS || acc < r2)) key = tpg_knn_key(acc, j);
             tpg_knn_merge(best[qq], thr[qq], key, K, lane, slot);
         }
     }
@@ -226,8 +214,8 @@ __global__ __launch_bounds__(KNN_WAVES * 64) void knn_tile_kernel(
         const int i = q0 + qq;
         if (i >= P1 || lane >= K) continue;
         const size_t o = ((size_t)b * P1 + i) * K + lane;
-        if (i >= n1 || n2 <= 0 || best[qq] == INF) { dist[o] = pad_d; idx[o] = pad_i; }
-        else { dist[o] = __uint_as_float((unsigned)(best[qq] >> 32)); idx[o] = (long long)(unsigned)best[qq]; }
+        if (i >= n1 || n2 <= 0 || best[qq] == TPG_KNN_INF) { dist[o] = pad_d; idx[o] = pad_i; }
+        else { dist[o] = tpg_knn_key_dist(best[qq]); idx[o] = tpg_knn_key_idx(best[qq]); }
     }
 }
 
@@ -248,7 +236,6 @@ __global__ __launch_bounds__(KNN_WAVES * 64) void knn_redo_kernel(
     const int n1 = len1 ? (int)len1[b] : P1;
     const int n2 = len2 ? min((int)len2[b], P2) : P2;
     const float *cbase = p2 + (size_t)b * P2 * D_T;
-    const tpg_u64 INF = ~0ull;
     for (int u = 0; u < KNN_WAVES; ++u) {
         const int i = blockIdx.x * KNN_WAVES + u;
         if (i >= P1) break;                                            // (uniform over the workgroup)
@@ -257,22 +244,23 @@ __global__ __launch_bounds__(KNN_WAVES * 64) void knn_redo_kernel(
         __syncthreads();                                               // the previous query's LDS is free
         if (threadIdx.x < D_T) qs[threadIdx.x] = p1[q * D_T + threadIdx.x];
         __syncthreads();
-        tpg_u64 best = INF, thr = INF;
+        tpg_u64 best = TPG_KNN_INF, thr = TPG_KNN_INF;
         if (i < n1)
             for (int base = wave * 64; base < n2; base += KNN_WAVES * 64) {
                 const int j = base + lane;
-                const tpg_u64 key = j < n2 ? knn_pack(knn_dist<D_T>(qs, cbase + (size_t)j * D_T, D_T), j) : INF;
+                const tpg_u64 key =
+                    j < n2 ? tpg_knn_key(knn_dist<D_T>(qs, cbase + (size_t)j * D_T, D_T), j) : TPG_KNN_INF;
                 tpg_knn_merge(best, thr, key, K, lane, slots + wave * 64);
             }
-        lists[wave * 64 + lane] = lane < K ? best : INF;
+        lists[wave * 64 + lane] = lane < K ? best : TPG_KNN_INF;
         __syncthreads();
         if (wave == 0) {
-            best = INF;
-            thr = INF;
+            best = TPG_KNN_INF;
+            thr = TPG_KNN_INF;
             for (int w = 0; w < KNN_WAVES; ++w) tpg_knn_merge(best, thr, lists[w * 64 + lane], K, lane, slots);
             if (lane < K) {
-                if (best == INF) { dist[q * K + lane] = 0.0f; idx[q * K + lane] = 0; }
-                else { dist[q * K + lane] = __uint_as_float((unsigned)(best >> 32)); idx[q * K + lane] = (long long)(unsigned)best; }
+                if (best == TPG_KNN_INF) { dist[q * K + lane] = 0.0f; idx[q * K + lane] = 0; }
+                else { dist[q * K + lane] = tpg_knn_key_dist(best); idx[q * K + lane] = tpg_knn_key_idx(best); }
             }
         }
     }

@@ -330,7 +330,7 @@ __global__ __launch_bounds__(KM_WAVES * 64, 8 / KM_WAVES) void knn_mfma_kernel(
     constexpr float C2 = (float)(8 * D_T + 64) * 5.9604644775390625e-8f;          // (8 D + 64) 2^-24
     float *qs = qrow + wave * D_T;
     tpg_u64 *ks_ = keys + wave * 64;
-    const tpg_u64 INF = ~0ull;
+    const tpg_u64 INF = TPG_KNN_INF;
     // a query's candidate rows are a dependent chain (list entry -> row address -> 2 x D bytes from L2): the rows of
     // query qq + 1 are fetched into a second register set before query qq is ranked
     constexpr int V4 = D_T / 4;
@@ -373,7 +373,7 @@ __global__ __launch_bounds__(KM_WAVES * 64, 8 / KM_WAVES) void knn_mfma_kernel(
                 t = qv.z - row[d].z; acc = acc + t * t;
                 t = qv.w - row[d].w; acc = acc + t * t;
             }
-            key = knn_pack(acc, j);
+            key = tpg_knn_key(acc, j);
         }
         ks_[lane] = key;
         int rank = 0;
@@ -383,7 +383,7 @@ __global__ __launch_bounds__(KM_WAVES * 64, 8 / KM_WAVES) void knn_mfma_kernel(
         bool ok = n <= KM_CAP && kth != 0;
         float dk = -1.0f;
         if (ok) {
-            dk = __uint_as_float((unsigned)(tpg_readlane_u64(key, __builtin_amdgcn_readfirstlane(__builtin_ctzll(kth))) >> 32));
+            dk = tpg_knn_key_dist(tpg_readlane_u64(key, __builtin_amdgcn_readfirstlane(__builtin_ctzll(kth))));
             ok = tq - eq > dk;
         }
 #ifdef KM_DEBUG
@@ -391,8 +391,8 @@ __global__ __launch_bounds__(KM_WAVES * 64, 8 / KM_WAVES) void knn_mfma_kernel(
 #endif
         if (ok) {
             if (rank < K && key != INF) {
-                od[(size_t)i * K + rank] = __uint_as_float((unsigned)(key >> 32));
-                oi[(size_t)i * K + rank] = (long long)(unsigned)key;
+                od[(size_t)i * K + rank] = tpg_knn_key_dist(key);
+                oi[(size_t)i * K + rank] = tpg_knn_key_idx(key);
             }
         } else if (lane == 0) {
             oi[(size_t)i * K] = KM_REDO;

@@ -19,9 +19,22 @@
 #pragma once
 #include "tpg_common.hpp"
 
+constexpr tpg_u64 TPG_KNN_INF = ~0ull;  // "no candidate": above every key
+
+__device__ __forceinline__ tpg_u64 tpg_knn_key(float d, int j) {
+    return ((tpg_u64)__float_as_uint(d) << 32) | (unsigned)j;
+}
+__device__ __forceinline__ float tpg_knn_key_dist(tpg_u64 key) { return __uint_as_float((unsigned)(key >> 32)); }
+__device__ __forceinline__ long long tpg_knn_key_idx(tpg_u64 key) { return (long long)(unsigned)key; }
+
+// all K slots of a query past len1 (or with nothing to search), by the whole wave
+__device__ __forceinline__ void tpg_knn_pad_row(float *od, int64_t *oi, int K, int lane, float pad_d, long long pad_i) {
+    for (int k = lane; k < K; k += 64) { od[k] = pad_d; oi[k] = pad_i; }
+}
+
 __device__ __forceinline__ void tpg_knn_merge(tpg_u64 &best, tpg_u64 &thr, tpg_u64 key, int K, int lane,
                                               tpg_u64 *__restrict__ slot /* LDS, 64 entries, this wave's */) {
-    const tpg_u64 INF = ~0ull;
+    const tpg_u64 INF = TPG_KNN_INF;
     tpg_u64 mask = __ballot(key < thr);
     if (mask == 0) return;
     if ((mask & (mask - 1)) == 0) {       // a single winner: plain insertion is cheaper

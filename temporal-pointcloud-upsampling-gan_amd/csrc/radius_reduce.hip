@@ -116,10 +116,7 @@ __global__ __launch_bounds__(FG_WAVES * 64) void rr_kernel(
                 }
                 if (at >= 0 && base + lane < total) {
                     const float4 p = pts[at];
-                    const float t0 = qx - p.x, t1 = qy - p.y, t2 = qz - p.z;
-                    float d = t0 * t0;
-                    d = d + t1 * t1;
-                    d = d + t2 * t2;
+                    const float d = tpg_sq3(qx, qy, qz, p.x, p.y, p.z);
                     if (d <= r2) {
                         ++cnt;
                         if (sum) acc = rr_sat_add(acc, rr_term(d, r, kernel));
@@ -130,10 +127,7 @@ __global__ __launch_bounds__(FG_WAVES * 64) void rr_kernel(
             const int np = lenp ? min(max((int)lenp[b], 0), Np) : Np;
             const float *x = pos + (size_t)b * Np * 3;
             for (int j = lane; j < np; j += 64) {
-                const float t0 = qx - x[(size_t)j * 3], t1 = qy - x[(size_t)j * 3 + 1], t2 = qz - x[(size_t)j * 3 + 2];
-                float d = t0 * t0;
-                d = d + t1 * t1;
-                d = d + t2 * t2;
+                const float d = tpg_sq3(qx, qy, qz, x[(size_t)j * 3], x[(size_t)j * 3 + 1], x[(size_t)j * 3 + 2]);
                 if (d <= r2) {
                     ++cnt;
                     if (sum) acc = rr_sat_add(acc, rr_term(d, r, kernel));
@@ -176,13 +170,13 @@ extern "C" int tpg_radius_reduce_f32(const float *query, const float *pos, const
                                      int B, int Nq, int Np, float r, int kernel, int32_t *count, float *sum, void *ws,
                                      void *stream) {
     hipStream_t st = tpg_stream(stream);
-    if (B > 0 && Nq > 0 && Np > 0 && (!ws || (reinterpret_cast<uintptr_t>(ws) & 255))) return TPG_ERR_ARG;
+    if (B > 0 && Nq > 0 && Np > 0 && !fg_workspace_ok(ws)) return TPG_ERR_ARG;
     const int chk = rr_check(query, pos, B, Nq, Np, r, kernel, count, sum, st);
     if (chk) return chk > 0 ? TPG_OK : chk;
     GridParams *gp; int *start; float4 *sorted;
     const int rc = fg_build(pos, lenp, B, Np, r, 0, ws, st, &gp, &start, &sorted);
     if (rc) return rc;
-    hipLaunchKernelGGL(rr_kernel<true>, dim3((Nq + FG_WAVES - 1) / FG_WAVES, B), dim3(FG_WAVES * 64), 0, st, query, pos,
+    hipLaunchKernelGGL(rr_kernel<true>, dim3(fg_query_blocks(Nq), B), dim3(FG_WAVES * 64), 0, st, query, pos,
                        lenq, lenp, Nq, Np, gp, FG_CELLS, start, sorted, r, r * r, kernel, count, sum);
     TPG_RETURN_IF_LAUNCH_FAILED();
     return TPG_OK;
@@ -194,7 +188,7 @@ extern "C" int tpg_radius_reduce_exhaustive_f32(const float *query, const float 
     hipStream_t st = tpg_stream(stream);
     const int chk = rr_check(query, pos, B, Nq, Np, r, kernel, count, sum, st);
     if (chk) return chk > 0 ? TPG_OK : chk;
-    hipLaunchKernelGGL(rr_kernel<false>, dim3((Nq + FG_WAVES - 1) / FG_WAVES, B), dim3(FG_WAVES * 64), 0, st, query, pos,
+    hipLaunchKernelGGL(rr_kernel<false>, dim3(fg_query_blocks(Nq), B), dim3(FG_WAVES * 64), 0, st, query, pos,
                        lenq, lenp, Nq, Np, (const GridParams *)nullptr, 0, (const int *)nullptr,
                        (const float4 *)nullptr, r, r * r, kernel, count, sum);
     TPG_RETURN_IF_LAUNCH_FAILED();

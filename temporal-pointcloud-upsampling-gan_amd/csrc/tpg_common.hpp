@@ -1,6 +1,8 @@
-// Shared helpers for the gfx950 kernels: launch plumbing, cross-lane moves, wave reductions.  wave = 64 lanes
-// everywhere.  (Row chunks and bf16 conversion: tpg_rows.hpp; the BatchNorm finalize pieces: tpg_bn_finalize.hpp; the
-// samplers' radix select, LDS sort and clip tables: tpg_select.hpp.)
+// Shared helpers for the gfx950 kernels: launch plumbing, the canonical 3-D distance, cross-lane moves, wave
+// reductions.  wave = 64 lanes everywhere.  (Row chunks and bf16 conversion: tpg_rows.hpp; the BatchNorm finalize
+// pieces: tpg_bn_finalize.hpp; the samplers' radix select, LDS sort and clip tables: tpg_select.hpp; the neighbour
+// searches' 64-bit key, padding row and rank merge: knn_select.hpp; the uniform grid's build and workspace rules:
+// frnn_grid_build.hpp.)
 //
 // Every translation unit is compiled with -ffp-contract=off: the canonical
 // distance sum_d (a_d-b_d)^2 must round each mul and add separately so that

@@ -21,6 +21,7 @@ import torch
 
 from test_analysis_cpu import (CUTOFFS, EPS, GOLDEN, RADII, SUM_FACTOR, check_counts_against_golden, check_density,
                                check_surface_against_golden, members, statement, sum_bound)
+from test_ops_gpu import FAR_QUERIES, LATTICE_R, lattice
 
 pytestmark = pytest.mark.gpu
 
@@ -195,6 +196,38 @@ def test_grid_and_exhaustive_paths_agree_bit_for_bit(hip, n, seed, r):
         ce, se = ops.radius_reduce(x, x, r, kernel, _grid=False)
         assert torch.equal(cg, ce), kernel
         assert torch.equal(sg.view(torch.int32), se.view(torch.int32)), kernel
+
+
+def fp32_counts(query, pos, r):
+    """#{j : d2 <= r2} by brute force, with the canonical float32 distance and r2 = fp32(r) * fp32(r)."""
+    t = query[:, None, :] - pos[None, :, :]
+    d2 = t[..., 0] * t[..., 0]
+    d2 = d2 + t[..., 1] * t[..., 1]
+    d2 = d2 + t[..., 2] * t[..., 2]
+    assert d2.dtype == np.float32
+    return (d2 <= np.float32(r) * np.float32(r)).sum(-1)
+
+
+@pytest.mark.parametrize("nz,far", [(6, False), (1, True)])
+def test_the_grid_walk_on_a_lattice(hip, nz, far):
+    """The 27-cell walk alone (as test_ops_gpu.test_frnn_grid_walk_*): a 6 x 6 x nz lattice at spacing 0.05 and
+    r = 2.1 spacings -- the cell edge is r, 3 cells per axis (1 along a collapsed one), an interior query meets the
+    whole cloud over all nine runs, a corner query's runs are clipped, no squared distance lies near r^2 -- and four
+    queries 10 spacings outside the box: a count of 0 and a sum of 0."""
+    import tpgan_amd.ops as ops
+    r = LATTICE_R
+    pos = lattice(6, 6, nz)
+    query = np.concatenate([pos, FAR_QUERIES]) if far else pos
+    want = fp32_counts(query, pos, r)
+    assert want.max() == (33 if nz == 6 else 13) and (not far or np.all(want[-4:] == 0))
+    for kernel in ("cubic", "linear"):
+        cg, sg = ops.radius_reduce(dev(query), dev(pos), r, kernel, _grid=True)
+        ce, se = ops.radius_reduce(dev(query), dev(pos), r, kernel, _grid=False)
+        assert np.array_equal(cg.cpu().numpy(), want), kernel
+        assert torch.equal(cg, ce), kernel
+        assert torch.equal(sg.view(torch.int32), se.view(torch.int32)), kernel
+        if far:
+            assert int(cg[-4:].abs().sum()) == 0 and float(sg[-4:].abs().sum()) == 0.0, kernel
 
 
 # --------------------------------------------------------------------------------------------- 6: determinism

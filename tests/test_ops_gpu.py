@@ -1041,3 +1041,38 @@ def test_frnn_grid_ragged_dummies_and_far_queries(hip):
     dd, ii = ops.neighbour_search(dev(big[:, :4000]), dev(big), 8, r=0.05)
     rd, ri = R.knn(big[:, :4000], big, 8, r=0.05)
     assert np.array_equal(ii.cpu().numpy(), ri) and np.array_equal(dd.cpu().numpy(), rd)
+
+
+def lattice(nx, ny, nz, spacing=0.05):
+    """(nx * ny * nz, 3) float32 lattice points, x fastest."""
+    z, y, x = np.meshgrid(np.arange(nz), np.arange(ny), np.arange(nx), indexing="ij")
+    return (np.stack([x, y, z], -1).reshape(-1, 3) * spacing).astype(np.float32)
+
+
+LATTICE_R = 2.1 * 0.05        # squared distances are integers in units of the spacing squared; r^2 is 4.41 there
+# 10 spacings outside a 6 x 6 x 1 lattice's box, on either side of x, beyond y and below z
+FAR_QUERIES = np.array([[-0.5, 0.1, 0.0], [0.75, 0.1, 0.0], [0.1, 0.75, 0.0], [0.1, 0.1, -0.5]], np.float32)
+
+
+def test_frnn_grid_walk_on_a_lattice(hip):
+    """The 27-cell walk alone.  216 lattice points, cell edge r: 3 cells per axis holding 3, 2 and 1 lattice planes, so
+    an interior query's 27 cells hold the whole cloud -- four 64-candidate steps across all nine run boundaries --
+    and a corner query's runs are clipped.  Every distance is a tie that only the index resolves."""
+    p = lattice(6, 6, 6)[None]
+    d, i = _grid(hip, p, p, 64, LATTICE_R)
+    rd, ri = R.knn(p, p, 64, r=LATTICE_R)
+    assert (ri >= 0).sum(-1).max() == 33 and (ri >= 0).sum(-1).min() == 11     # interior / corner
+    assert np.array_equal(i.cpu().numpy(), ri)
+    assert np.array_equal(d.cpu().numpy(), rd)
+
+
+def test_frnn_grid_walk_on_a_flat_lattice_with_far_queries(hip):
+    """The same with one grid dimension collapsed to a single cell, and four queries 10 spacings outside the box
+    (cells outside the grid on either side of an axis: empty runs, all -1)."""
+    p = lattice(6, 6, 1)[None]
+    q = np.concatenate([p, FAR_QUERIES[None]], 1)
+    d, i = _grid(hip, q, p, 64, LATTICE_R)
+    rd, ri = R.knn(q, p, 64, r=LATTICE_R)
+    assert (ri[0, -4:] == -1).all() and (ri[0, :-4, 0] >= 0).all()
+    assert np.array_equal(i.cpu().numpy(), ri)
+    assert np.array_equal(d.cpu().numpy(), rd)
