@@ -352,6 +352,24 @@ int tpg_mlp_bn_bwd_apply(const void *g, const void *x, const float *ci, const fl
 int tpg_mlp_bn_bwd_apply_rowsum(const void *g, const void *x, const float *ci, const float *c12, long long P, int K,
                                 int C, int nseg, void *dx, float *qneg, void *stream);
 
+/* ---- forward-only shared-MLP tail with eval-mode BatchNorm, one launch (csrc/mlp_infer.hip) ----
+ * Eval-mode BatchNorm is a constant per-channel affine, so the whole tail behind the row gather runs per group:
+ *   out[b,s,:] = max_{j<K} act_L(a_L * (W_L ... act_1(a_1 * (W_1 act_0(U[b,idx[b,s,j],:] - Q[b,s,:])) + c_1) ...) + c_L)
+ *   act_l(z) = max(z, slope_l * z), 0 <= slope_l <= 1;  L = 1 (C2 == 0) or 2 weights.
+ * U (B,N,C0), Q (B,S,C0) of dtype_in (fp32 or bf16) with the input affine already folded in: the difference is taken in
+ * fp32 on their own values, so fp32 tables are not rounded before it; idx (B,S,K) int32 (clamped into [0,N));
+ * a_l, c_l (C_l) f32; out (B,S,C_L) bf16.  bf16 MFMA operands, fp32 accumulation, affine and activation in fp32 on the
+ * accumulators, one rounding where a value becomes the next MFMA operand and one at the store; the max is taken in
+ * registers and by cross-lane moves (no atomics: bitwise reproducible, independent of B and of the grid).
+ * W1p / W2p: the weights (C1,C0) / (C2,C1) as bf16 in B-fragment order, T = Cout/16, KS = Cin/32:
+ *   Wp[((t*KS + s)*64 + lq*16 + li)*8 + e] = W[li*T + t][32*s + 8*lq + e]      t < T, s < KS, li < 16, lq < 4, e < 8
+ * (16-byte aligned).  Chains (C0,C1,C2): (64,128,0) (128,256,0) (64,64,128) (256,128,256) (256,256,256); K a
+ * multiple of 16, <= 256 -- tpg_mlp_infer_supported says 1 for these, tpg_mlp_infer_fwd TPG_ERR_UNSUPPORTED otherwise. */
+int tpg_mlp_infer_supported(int C0, int C1, int C2, int K);
+int tpg_mlp_infer_fwd(const void *U, const void *Q, const int32_t *idx, int dtype_in, int B, int N, int S, int K, int C0,
+                      int C1, int C2, const void *W1p, const void *W2p, const float *a1, const float *c1, const float *a2,
+                      const float *c2, float slope0, float slope1, float slope2, void *out, void *stream);
+
 /* ---- fused spectral normalisation of a (R x Cn) conv / linear weight ------------------------
  * torch.nn.utils.spectral_norm's forward pre-hook (n_power_iterations = 1) on every conv and
  * linear of the discriminators (discriminator.py:66-68,246-247,351-359,...) in ONE launch:

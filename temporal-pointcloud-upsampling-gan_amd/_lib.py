@@ -68,6 +68,7 @@ SIGNATURES = {
     "tpg_rowlinear_dgrad": [_P, _P, _I, _P, _L, _I, _I, _I, _F, _P, _I, _P],
     "tpg_rowlinear_wgrad": [_P, _I, _P, _P, _I, _L, _I, _I, _I, _F, _P, _P, _P, _P],
     "tpg_mlp_fwd": [_P, _L, _I, _I, _I, _P, _I, _F, _P, _I, _P, _F, _F, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P],
+    "tpg_mlp_infer_fwd": [_P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _F, _F, _F, _P, _P],
     "tpg_context_expand_f32": [_P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P],
     "tpg_radius_reduce_f32": [_P, _P, _P, _P, _I, _I, _I, _F, _I, _P, _P, _P, _P],
     "tpg_radius_reduce_exhaustive_f32": [_P, _P, _P, _P, _I, _I, _I, _F, _I, _P, _P, _P],
@@ -82,7 +83,7 @@ OTHER_GETTERS = ("tpg_spectral_norm_multi_stride", "tpg_spectral_norm_multi_bwd_
                  "tpg_mlp_wgrad_workspace_bytes", "tpg_frnn_grid_workspace_bytes", "tpg_small_tail_workspace_bytes",
                  "tpg_chamfer_bwd_workspace_bytes", "tpg_rowlinear_wgrad_workspace_bytes", "tpg_rowlinear_supported",
                  "tpg_spectral_norm_split_rows", "tpg_spectral_norm_split_max_cn", "tpg_spectral_norm_split_max_rows",
-                 "tpg_patch_select_workspace_bytes", "tpg_patch_select_max_k")
+                 "tpg_patch_select_workspace_bytes", "tpg_patch_select_max_k", "tpg_mlp_infer_supported")
 STRING_GETTERS = ("tpg_version", "tpg_target_arch")
 
 STATUS = {0: "TPG_OK", -1: "TPG_ERR_ARG", -2: "TPG_ERR_LAUNCH", -3: "TPG_ERR_UNSUPPORTED"}
@@ -135,6 +136,8 @@ def load():
         getattr(lib, name).restype = C.c_int
     lib.tpg_rowlinear_supported.argtypes = [C.c_int, C.c_int, C.c_int]
     lib.tpg_rowlinear_supported.restype = C.c_int
+    lib.tpg_mlp_infer_supported.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int]
+    lib.tpg_mlp_infer_supported.restype = C.c_int
     _lib = lib
     return lib
 

@@ -245,15 +245,22 @@ class ActionClipSampler:
     by 300, centred on the middle frame's mean (train) or its own (test); every frame gets its own FPS down to K / 16.
     A batch is four launches whatever its size: ops.frame_subset, ops.action_gather, ONE FPS over all T * B clouds,
     ops.clip_gather_low.  All randomness -- clip indices, one 64-bit subset seed per frame, the scales ~ U(0.9, 1.1) in
-    float64 per clip (train only), one FPS start per frame -- comes from ONE host torch.Generator, in that order."""
+    float64 per clip (train only), one FPS start per frame -- comes from ONE host torch.Generator, in that order.
 
-    def __init__(self, sequences, batch_size, num_points=2048, generator=None):
+    return_lowres=False (the reference's flag of that name, msr_dataset.py:92,128): no FPS and no low-resolution gather,
+    and the T low-resolution tensors are left out of the tuple.  The FPS starts are then NOT drawn, as in the reference,
+    whose FPS draws its own start: the draws of a batch are clip indices, subset seeds, scales (train), in that order.
+    The high-resolution tensors of a batch are those of return_lowres=True from the same generator state, bit for bit;
+    the state after the batch differs (one draw less), so later batches do."""
+
+    def __init__(self, sequences, batch_size, num_points=2048, generator=None, return_lowres=True):
         if num_points < 16 or num_points % 16:
             raise ValueError("num_points must be a positive multiple of 16 (the low resolution is num_points / 16)")
         self.seq, self.batch_size, self.num_points = sequences, int(batch_size), int(num_points)
         self.frames = sequences.frames_per_clip
         self.generator = generator if generator is not None else torch.Generator().manual_seed(0)
         self.device = sequences.device
+        self.return_lowres = bool(return_lowres)
 
     def sample(self, indices=None, subset_idx=None, scales=None, initial_idx=None):
         """One batch.  indices: clip indices (default: batch_size draws); scales: (B,3) float64 per clip (train only;
@@ -273,9 +280,12 @@ class ActionClipSampler:
             scales = drawn if scales is None else np.asarray(scales, np.float64).reshape(B, 3)
         elif scales is not None:
             raise ValueError("the test split has no scales")
-        starts = torch.randint(K, (T, B), generator=g)
-        if initial_idx is not None:
-            starts = torch.as_tensor(np.asarray(initial_idx)).reshape(T, B)
+        if initial_idx is not None and not self.return_lowres:
+            raise ValueError("return_lowres=False runs no FPS: there is no first pick to give")
+        if self.return_lowres:
+            starts = torch.randint(K, (T, B), generator=g)
+            if initial_idx is not None:
+                starts = torch.as_tensor(np.asarray(initial_idx)).reshape(T, B)
         if subset_idx is None:
             subset = ops.frame_subset(count.reshape(-1), (halves[:, 1] << np.uint64(32)) | halves[:, 0], K,
                                       device=self.device).view(T, B, K)
@@ -285,15 +295,20 @@ class ActionClipSampler:
             subset = subset_idx
         high, centres = ops.action_gather(seq.points, frame_first, count, subset, scales,
                                           "train" if seq.train else "test")
+        label = torch.tensor([seq.labels[seq.clip(i)[0]] for i in indices], dtype=torch.int64)
+        video = torch.tensor([seq.clip(i)[0] for i in indices], dtype=torch.int64)
+        if not self.return_lowres:
+            self.last = {"subset_idx": subset, "indices": indices, "scales": scales}
+            if seq.train:
+                return (*high.unbind(0), label)
+            return (*high.unbind(0), *centres.unbind(0), label, video)
         start = starts.to(torch.int32).reshape(T * B).to(self.device, non_blocking=True)
         fps_idx = ops.backend_for(high).fps(high.view(T * B, K, 3), K // 16, start, False)
         low, _ = ops.clip_gather_low(high.view(1, T * B, K, 3), fps_idx)
         low = low.view(T, B, K // 16, 3)
         self.last = {"subset_idx": subset, "fps_idx": fps_idx.view(T, B, K // 16), "indices": indices, "scales": scales}
-        label = torch.tensor([seq.labels[seq.clip(i)[0]] for i in indices], dtype=torch.int64)
         if seq.train:
             return (*high.unbind(0), *low.unbind(0), label)
-        video = torch.tensor([seq.clip(i)[0] for i in indices], dtype=torch.int64)
         return (*high.unbind(0), *low.unbind(0), *centres.unbind(0), label, video)
 
     def __iter__(self):

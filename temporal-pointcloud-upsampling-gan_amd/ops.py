@@ -596,6 +596,25 @@ class HipBackend:
             return y, ci_out, mr[0], mr[1]
         return y, ci_out
 
+    def mlp_infer(self, U, Q, idx, packed, scales, shifts, slopes):
+        """One launch of the eval-mode tail (csrc/mlp_infer.hip): U (B,N,C0), Q (B,S,C0) fp32 or bf16, idx (B,S,K) int32,
+        packed: the L bf16 weights in fragment order (`pack_infer_weight`), scales / shifts: L fp32 vectors,
+        slopes: L+1 floats -> (B,S,C_L) bf16."""
+        B, N, C0 = U.shape
+        _, S, K = idx.shape
+        L = len(packed)
+        chans = [C0] + [int(a.numel()) for a in scales]
+        out = torch.empty((B, S, chans[-1]), dtype=torch.bfloat16, device=U.device)
+        nbytes = U.element_size() * B * C0 * (N + S) + 4 * B * S * K + 2 * B * S * chans[-1]
+        flops = 2 * B * S * K * sum(a * b for a, b in zip(chans[:-1], chans[1:]))
+        two = L == 2
+        self._call("tpg_mlp_infer_fwd", "mlp_infer", nbytes, U,
+                   _ptr(U), _ptr(Q), _ptr(idx), _DTYPE_CODE[U.dtype], B, N, S, K, C0, chans[1], chans[2] if two else 0,
+                   _ptr(packed[0]), _ptr(packed[1] if two else None), _ptr(scales[0]), _ptr(shifts[0]),
+                   _ptr(scales[1] if two else None), _ptr(shifts[1] if two else None),
+                   float(slopes[0]), float(slopes[1]), float(slopes[2]) if two else 1.0, _ptr(out), flops=flops)
+        return out
+
     def rowbn_stats(self, x, eps, momentum, running_mean, running_var, num_batches_tracked, nseg, mean_shift,
                     consts=None):
         """Training-mode batch statistics of x (P,C) alone (the reduction half of rowbn_fwd): mean, rstd
@@ -2052,6 +2071,66 @@ def mlp_tail(x0, bns, weights, slopes, K, nseg=1, shifts=None):
     cfg = (int(nseg), int(K), tuple(float(s) for s in slopes), tuple(eps), tuple(moms), tuple(states),
            tuple(None if s is None else s.detach().float().contiguous() for s in shifts))
     return _MlpTail.apply(x0.contiguous(), cfg, *tensors)
+
+
+# ------------------------------------------- eval-mode tail in one launch (csrc/mlp_infer.hip)
+def gather_mlp_max_supported(U, channels, K, rows_dtype=None):
+    """Can `gather_mlp_max` run this tail?  Tables on the GPU, bf16 rows, one of the channel chains (C_0, .., C_L) and a K
+    the library is built for (tpg_mlp_infer_supported: the one list).  rows_dtype: the dtype the per-layer path would
+    store the grouped rows in (default: U's own); fp32 rows stay on that path -- the kernel's operands are bf16.
+    Everything it refuses stays on the per-layer path (row_combine, rows_matmul, row_bn_act)."""
+    if not (torch.is_tensor(U) and U.is_cuda and U.dtype in _DTYPE_CODE and (rows_dtype or U.dtype) == torch.bfloat16):
+        return False
+    chans = [int(c) for c in channels]
+    if len(chans) not in (2, 3):
+        return False
+    return bool(_lib.load().tpg_mlp_infer_supported(chans[0], chans[1], chans[2] if len(chans) == 3 else 0, int(K)))
+
+
+def pack_infer_weight(W):
+    """(Cout,Cin) weight -> bf16 in the MFMA B-fragment order of csrc/mlp_infer.hip (include/tpgan_ops.h):
+    packed[t, s, lq, li, e] = W[li*T + t, 32*s + 8*lq + e], T = Cout/16."""
+    Cout, Cin = W.shape
+    _need(Cout % 16 == 0 and Cin % 32 == 0, "pack_infer_weight: Cout % 16 == 0 and Cin % 32 == 0")
+    w = W.detach().to(torch.bfloat16).view(16, Cout // 16, Cin // 32, 4, 8)          # li, t, s, lq, e
+    return w.permute(1, 2, 3, 0, 4).contiguous()
+
+
+def gather_mlp_max(U, Q, idx, weights, scales, shifts, slopes, out_dtype=torch.bfloat16):
+    """The eval-mode tail behind a row gather, in one forward-only launch:
+
+        out[b,s,:] = max_{j<K} act_L(a_L * (W_L ... act_1(a_1 * (W_1 act_0(U[b,idx[b,s,j],:] - Q[b,s,:])) + c_1) ...) + c_L)
+        act_l(z) = max(z, slope_l * z)
+
+    U (B,N,C_0), Q (B,S,C_0) both fp32 or both bf16 (the difference is taken in fp32 on their own values: fp32 tables
+    are not rounded before it); idx (B,S,K) int32 or a NeighbourList into N rows; weights: L = 1 or 2 tensors
+    (C_l, C_{l-1}) (rounded to bf16); scales / shifts: L per-channel vectors a_l / c_l (fp32); slopes: L+1 floats in
+    [0,1] (slope_0 first) -> (B,S,C_L) bf16.  Not differentiable: raises when grad is enabled and an input requires it."""
+    L = len(weights)
+    _need(L in (1, 2) and len(scales) == L and len(shifts) == L and len(slopes) == L + 1,
+          "gather_mlp_max: 1 or 2 weights, as many scales / shifts, one slope more")
+    _need(out_dtype == torch.bfloat16, "gather_mlp_max writes bf16 rows")
+    _need(all(0.0 <= float(sl) <= 1.0 for sl in slopes), "gather_mlp_max: LeakyReLU slopes in [0, 1]")
+    _need(torch.is_tensor(U) and U.dim() == 3 and torch.is_tensor(Q) and Q.dim() == 3, "U (B,N,C), Q (B,S,C)")
+    idx = neighbour_list(idx, U.shape[1]).idx
+    B, N, C0 = U.shape
+    _need(Q.shape[0] == B and Q.shape[2] == C0 and idx.shape[:2] == Q.shape[:2], "Q must be (B,S,C), idx (B,S,K)")
+    _need(U.dtype in _DTYPE_CODE and Q.dtype == U.dtype, "gather_mlp_max: U and Q are both fp32 or both bf16")
+    chans = [C0]
+    for W, a, c in zip(weights, scales, shifts):
+        _need(W.dim() == 2 and W.shape[1] == chans[-1], f"weight {tuple(W.shape)} does not follow {chans[-1]} channels")
+        _need(a.shape == (W.shape[0],) and c.shape == (W.shape[0],), "one scale and one shift per output channel")
+        chans.append(int(W.shape[0]))
+    _need(gather_mlp_max_supported(U, chans, idx.shape[2], out_dtype),
+          f"gather_mlp_max: chain {tuple(chans)} with K = {idx.shape[2]} is not built (see gather_mlp_max_supported)")
+    tensors = [U, Q, idx] + list(weights) + list(scales) + list(shifts)
+    _same_device(*tensors)
+    _need(not (torch.is_grad_enabled() and any(t.requires_grad for t in tensors)),
+          "gather_mlp_max is forward-only: run it under no_grad or take the per-layer path")
+    packed = [pack_infer_weight(W) for W in weights]
+    return backend_for(U).mlp_infer(U.contiguous(), Q.contiguous(), idx.contiguous(), packed,
+                                    [a.detach().float().contiguous() for a in scales],
+                                    [c.detach().float().contiguous() for c in shifts], [float(sl) for sl in slopes])
 
 
 # ---------------------------------------------------------------------- row-wise linear layers

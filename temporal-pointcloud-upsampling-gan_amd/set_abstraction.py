@@ -4,7 +4,7 @@ Host-side mirror of the reference's `discriminator.py` (knn :13-21, ball_query_w
 :24-40, index_points :43-60, build_shared_mlp :63-78, _PointnetSAModuleBase :83-153,
 MSGSetConv :156-200, SSGSetConv :203-232, FlowEmbedding :235-283, FlowModule :286-322,
 ActionTempoDis :325-402, ActionSpatialDis :405-470, FluidTempoDis :473-559,
-FluidSpatialDis :562-629) with identical parameter / buffer names.  FPS, ball query and the
+FluidSpatialDis :562-629, ActionCls :632-722) with identical parameter / buffer names.  FPS, ball query and the
 neighbour searches run on the HIP kernels.
 
 Inner loop, MI355X-first (same results up to fp32 rounding, pinned by tests/golden):
@@ -266,6 +266,97 @@ def _try_fused_tail(bns, convs, slopes, x, K, nseg):
     return ops.mlp_tail(x, bns, Ws, slopes, K, nseg, shifts=[None] + [c.bias for c in convs])
 
 
+def _parse_eval_tail(layers):
+    """[BN, act, (conv, BN, act)*] -> (BatchNorms, convs, slopes), else None: `_parse_tail` without its training-mode
+    condition (the eval-mode conditions are `_fused_eval_ok`'s)."""
+    bns, convs, slopes = [], [], []
+    i, n = 0, len(layers)
+    while i < n:
+        if i > 0:
+            if not isinstance(layers[i], nn.Conv2d) or layers[i].kernel_size != (1, 1):
+                return None
+            convs.append(layers[i])
+            i += 1
+        if i + 1 >= n or not isinstance(layers[i], (nn.BatchNorm2d, nn.BatchNorm1d)):
+            return None
+        slope = _act_slope(layers[i + 1])
+        if slope is None:
+            return None
+        bns.append(layers[i])
+        slopes.append(slope)
+        i += 2
+    return (bns, convs, slopes) if convs else None
+
+
+def _fused_eval_ok(first_conv, bns, convs, K, inputs):
+    """May this tail go through ops.gather_mlp_max?  Every BatchNorm in eval mode with running statistics, spectral-norm
+    convs in eval mode (one weight for every call), GPU rows under bf16 autocast, a chain and K the kernel is built for,
+    and nothing that wants a gradient.  No side effects: no spectral-norm weight is consumed."""
+    ref = inputs[0]
+    if not (rows_first() and ref.is_cuda and amp_dtype(ref) == torch.bfloat16):
+        return False
+    if any(bn.training or bn.running_mean is None or bn.running_var is None for bn in bns):
+        return False
+    if any(hasattr(c, "weight_orig") and c.training for c in [first_conv] + list(convs)):
+        return False
+    chans = [first_conv.out_channels] + [c.out_channels for c in convs]
+    if any(c.in_channels != a for c, a in zip(convs, chans[:-1])):
+        return False
+    if not ops.gather_mlp_max_supported(ref, chans, K, torch.bfloat16):
+        return False
+    if torch.is_grad_enabled():
+        params = [p for m in [first_conv] + list(convs) + list(bns) for p in m.parameters()]
+        if any(t is not None and t.requires_grad for t in list(inputs) + params):
+            return False
+    return True
+
+
+def _eval_affine(bn):
+    """Eval-mode BatchNorm as a per-channel affine, fp32: scale = weight * rsqrt(running_var + eps),
+    shift = bias - running_mean * scale."""
+    scale = torch.rsqrt(bn.running_var.float() + bn.eps)
+    if bn.weight is not None:
+        scale = bn.weight.detach().float() * scale
+    shift = -bn.running_mean.float() * scale
+    if bn.bias is not None:
+        shift = bn.bias.detach().float() + shift
+    return scale, shift
+
+
+def _fused_eval_tail(bns, convs, slopes, U, Q, idx):
+    """The tail behind the row gather in ONE launch (ops.gather_mlp_max, csrc/mlp_infer.hip): U (B,N,C0), Q (B,S,C0) fp32
+    = the first conv's output on the points / its centre term, idx (B,S,K) -> (B,S,C_L) bf16 rows.  The first
+    BatchNorm's affine is folded into the two tables (N and S rows: cheap), which stay fp32; the biases of the later
+    convs go into the shifts."""
+    with no_autocast(U):
+        a0, c0 = _eval_affine(bns[0])
+        Uf = U.detach().float() * a0                       # fp32 tables: the kernel subtracts before it rounds, as
+        Qf = Q.detach().float() * a0 - c0                  # row_combine does (graph_conv.no_autocast says why)
+        Ws, scales, shifts = [], [], []
+        for conv, bn in zip(convs, bns[1:]):
+            a, c = _eval_affine(bn)
+            if conv.bias is not None:
+                c = c + a * conv.bias.detach().float()
+            Ws.append(conv_weight2d(conv).detach())
+            scales.append(a)
+            shifts.append(c)
+        with torch.no_grad():
+            return ops.gather_mlp_max(Uf, Qf, idx, Ws, scales, shifts, slopes)
+
+
+def _list_k(idx):
+    return (idx.idx if isinstance(idx, ops.NeighbourList) else idx).shape[2]
+
+
+def set_fused_eval(module, flag):
+    """Switch the one-launch eval-mode tails (`fused_eval`) on or off on every set-abstraction level and flow
+    embedding inside `module`.  It only matters where `_fused_eval_ok` holds; everything else is unchanged."""
+    for m in module.modules():
+        if isinstance(m, (_PointnetSAModuleBase, FlowEmbedding)):
+            m.fused_eval = bool(flag)
+    return module
+
+
 def mlp_tail_rows(layers, x, reduce_max=False, nseg=1):
     """Run [conv, (bn), act]* layers (from a given position) on rows x (...,K,C).
 
@@ -379,6 +470,8 @@ class _PointnetSAModuleBase(nn.Module):
         # set False by a caller that KNOWS the cloud carries no 999-dummies (skips one
         # host sync per call without changing any result)
         self.check_dummies = True
+        # eval-mode tails in one launch (ops.gather_mlp_max) where `_fused_eval_ok` holds; see `set_fused_eval`
+        self.fused_eval = False
 
     def sample_centres(self, xyz, prefix=None):
         """FPS centres of this level.  prefix: a one-element list holding the flag tensor of the sampling that produced
@@ -407,8 +500,9 @@ class _PointnetSAModuleBase(nn.Module):
         g = self.groupers[0]
         return centres, new_xyz, ops.NeighbourList(ops.ball_query(g.radius, g.nsample, xyz, new_xyz), xyz.shape[1])
 
-    def _first_layer(self, grouper, mlp, xyz, new_xyz, feat_rows, idx=None):
-        """Rows of the first conv's output for every grouped position: (B,S,ns,C1)."""
+    def _first_layer(self, grouper, mlp, xyz, new_xyz, feat_rows, idx=None, tables=False):
+        """Rows of the first conv's output for every grouped position: (B,S,ns,C1).
+        tables (QueryAndGroup with use_xyz only): the un-gathered (U, Q, idx) instead."""
         conv = mlp[0]
         rows_dtype = amp_dtype(xyz)           # decided OUTSIDE the fp32 island below
         with no_autocast(xyz):
@@ -423,6 +517,8 @@ class _PointnetSAModuleBase(nn.Module):
                 idx = ops.ball_query(grouper.radius, grouper.nsample, xyz, new_xyz)
             if grouper.use_xyz:
                 Q = rows_matmul(new_xyz, W[:, :3])                  # centre term of (xyz_j - c_i)
+                if tables:
+                    return U, Q, idx
                 return ops.row_combine(U, Q, idx, ops.ROW_SUB, out_dtype=rows_dtype)
             return ops.row_combine(U, None, idx, ops.ROW_GATHER, out_dtype=rows_dtype)
 
@@ -442,6 +538,11 @@ class _PointnetSAModuleBase(nn.Module):
         outs = []
         for grouper, mlp in zip(self.groupers, self.mlps):
             if rows_first():
+                tail = self._eval_tail(grouper, mlp, [xyz, feat_rows])
+                if tail is not None:
+                    outs.append(_fused_eval_tail(*tail, *self._first_layer(grouper, mlp, xyz, new_xyz, feat_rows, pidx,
+                                                                           tables=True)))
+                    continue
                 y = self._first_layer(grouper, mlp, xyz, new_xyz, feat_rows, pidx)
                 outs.append(mlp_tail_rows(list(mlp)[1:], y, reduce_max=True))   # (B,S,C')
             else:                                                  # discriminator.py:139-150
@@ -449,6 +550,15 @@ class _PointnetSAModuleBase(nn.Module):
                 g = mlp(grouper(xyz, new_xyz, planes))             # (B,C',S,ns)
                 outs.append(F.max_pool2d(g, kernel_size=[1, g.size(3)]).squeeze(-1).transpose(1, 2))
         return new_xyz, torch.cat(outs, dim=-1)
+
+    def _eval_tail(self, grouper, mlp, inputs):
+        """(BatchNorms, convs, slopes) when this grouper's tail takes the one-launch eval path, else None."""
+        if not (self.fused_eval and self.npoint is not None and isinstance(grouper, QueryAndGroup) and grouper.use_xyz):
+            return None
+        tail = _parse_eval_tail(list(mlp)[1:])
+        if tail is None or not _fused_eval_ok(mlp[0], tail[0], tail[1], grouper.nsample, inputs):
+            return None
+        return tail
 
     def frames_stackable(self):
         single = len(self.groupers) == 1 and isinstance(self.groupers[0], QueryAndGroup)
@@ -497,6 +607,9 @@ class _PointnetSAModuleBase(nn.Module):
             Q = rows_matmul_seg(new_xyz.view(NB * S, 3), W[:, :, :3].contiguous()).view(NB, S, -1)
             if conv.bias is not None:
                 Q = Q - conv.bias.float()
+        tail = self._eval_tail(grouper, mlp, [xyz, feat]) if _list_k(idx) == grouper.nsample else None
+        if tail is not None:                 # eval mode: the nseg calls are one call on the stacked clouds
+            return new_xyz, _fused_eval_tail(*tail, U, Q, idx)
         y = ops.row_combine(U, Q, idx, ops.ROW_SUB, out_dtype=rows_dtype)        # (nseg*B, S, K, C1)
         feats = mlp_tail_rows(list(mlp)[1:], y, reduce_max=True, nseg=nseg)     # (nseg*B, S, C')
         return new_xyz, feats
@@ -559,6 +672,7 @@ class FlowEmbedding(nn.Module):
         if corr_func != "concat":
             raise NotImplementedError("only corr_func='concat' is defined by the reference")
         self.pooling, self.corr_func = pooling, corr_func
+        self.fused_eval = False              # as _PointnetSAModuleBase.fused_eval
         self.mlp_convs = nn.ModuleList()
         self.mlp_bns = nn.ModuleList()
         last = in_channel * 2 + 3
@@ -567,6 +681,10 @@ class FlowEmbedding(nn.Module):
             self.mlp_convs.append(spectral_norm(conv) if sn else conv)
             self.mlp_bns.append(nn.BatchNorm2d(out_channel))
             last = out_channel
+
+    def _eval_tail_ok(self, idx, inputs):
+        return self.fused_eval and _fused_eval_ok(self.mlp_convs[0], list(self.mlp_bns), list(self.mlp_convs)[1:],
+                                                  _list_k(idx), inputs)
 
     def forward_rows(self, p1, p2, f1, f2, radius, idx=None):
         """p (B,N,3), f (B,N,C) rows -> (B,N,mlp[-1]) rows; idx = precomputed neighbour list.
@@ -591,6 +709,8 @@ class FlowEmbedding(nn.Module):
             W = conv_weight2d(self.mlp_convs[0]).float()
             U = rows_matmul(torch.cat([p2.float(), f2.float()], dim=-1), W[:, :3 + C])
             Q = rows_matmul(p1.float(), W[:, :3]) - rows_matmul(f1.float(), W[:, 3 + C:])
+        if self._eval_tail_ok(idx, [p1, p2, f1, f2]):
+            return _fused_eval_tail(list(self.mlp_bns), list(self.mlp_convs)[1:], [0.01] * len(self.mlp_convs), U, Q, idx)
         x = ops.row_combine(U, Q, idx, ops.ROW_SUB, out_dtype=amp_dtype(p1))     # (B,N,32,C1)
         B, N, K, _ = x.shape
         x = x.view(B * N * K, -1)
@@ -622,6 +742,8 @@ class FlowEmbedding(nn.Module):
                                 W[:, :, :3 + C].contiguous()).view(NB, N, -1)
             Q = (rows_matmul_seg(p1.float().reshape(NB * N, 3), W[:, :, :3].contiguous())
                  - rows_matmul_seg(f1.float().reshape(NB * N, C), W[:, :, 3 + C:].contiguous())).view(NB, N, -1)
+        if self._eval_tail_ok(idx, [p1, p2, f1, f2]):
+            return _fused_eval_tail(list(self.mlp_bns), list(self.mlp_convs)[1:], [0.01] * len(self.mlp_convs), U, Q, idx)
         x = ops.row_combine(U, Q, idx, ops.ROW_SUB, out_dtype=amp_dtype(p1))     # (nseg*B,N,32,C1)
         K = x.shape[2]
         x = x.view(NB * N * K, -1)
@@ -931,6 +1053,46 @@ class ActionTempoDis(_TempoDis):
         self.flow_module = FlowModule(256, 256, 256, sequence_length, sn=sn)
         self.SA_pooling = SSGSetConv(mlp=[256, 256, 512], use_xyz=True, sn=sn)
         self.fc_layers = _head([512, 256, 64, 1], [0.3, 0.1])
+
+    def forward(self, pos_lst, cutoff, plan=None):
+        return self._forward(pos_lst, cutoff, None, 512, plan)
+
+
+class ActionCls(_TempoDis):
+    """20-way action recognition on the feature extractor of a trained ActionTempoDis (discriminator.py:632-722): the
+    same two levels and flow module without spectral norm, a wider pooling level and a plain-Linear head; parameter and
+    buffer names as the reference's.  `init_feature_extractor` copies and freezes the extractor.  The eval-mode
+    forward takes the one-launch tails (`fused_eval` is on).  npoints: centres per level (tests shrink them)."""
+
+    def __init__(self, sequence_length, npoints=(512, 256)):
+        super().__init__()
+        self.coarse_graining_module = nn.ModuleList([
+            SSGSetConv(npoint=npoints[0], radius=0.8, nsample=64, mlp=[3, 64, 64, 128], use_xyz=True, sn=False),
+            SSGSetConv(npoint=npoints[1], radius=1.2, nsample=32, mlp=[128, 128, 256], use_xyz=True, sn=False)])
+        self.flow_module = FlowModule(256, 256, 256, sequence_length, sn=False)
+        self.SA_pooling = SSGSetConv(mlp=[256, 512, 512], use_xyz=True, sn=False)
+        self.fc_layers = nn.Sequential(nn.Linear(512, 256), nn.BatchNorm1d(256), nn.LeakyReLU(), nn.Dropout(0.3),
+                                       nn.Linear(256, 64), nn.BatchNorm1d(64), nn.LeakyReLU(), nn.Dropout(0.1),
+                                       nn.Linear(64, 20))
+        set_fused_eval(self, True)
+
+    def copy_params(self, module1, module2, trainable=False):
+        """Parameters of module2 into the same-named parameters of module1.  Quirks kept from the reference: a
+        spectral-norm `..._orig` name loses its last five characters, so the UN-normalised weight_orig lands in
+        `weight`; buffers (BatchNorm running statistics, u / v) are not copied; every parameter that was copied
+        gets requires_grad = trainable."""
+        mine = dict(module1.named_parameters())
+        for name, src in module2.named_parameters():
+            key = name[:-5] if "orig" in name else name
+            dst = mine.get(key)
+            if dst is not None:
+                dst.data.copy_(src.data)
+                dst.requires_grad = trainable
+
+    def init_feature_extractor(self, trained_model):
+        """Both levels and the flow module from a trained ActionTempoDis, frozen; pooling level and head untouched."""
+        self.copy_params(self.coarse_graining_module, trained_model.coarse_graining_module, False)
+        self.copy_params(self.flow_module, trained_model.flow_module, False)
 
     def forward(self, pos_lst, cutoff, plan=None):
         return self._forward(pos_lst, cutoff, None, 512, plan)
