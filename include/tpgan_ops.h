@@ -514,6 +514,53 @@ int tpg_radius_reduce_exhaustive_f32(const float *query, const float *pos, const
                                      int B, int Nq, int Np, float r, int kernel, int32_t *count, float *sum,
                                      void *stream);
 
+/* ---- earth mover's distance: auction matching of equal-size clouds (csrc/emd.hip) ------------------------------
+ * Replaces the `emd` auction extension behind emdModule -- train_fluid/analysis_helper.py:14-64,224,255;
+ * train_action/analysis_helper.py:11-49,67; loss.py:311.  xyz1 (B,n,3) are the persons, xyz2 (B,n,3) the objects;
+ * every person gets one object and every object one person.  The rule, which the kernels follow bit for bit:
+ *   cost    c_ij = the canonical fp32 squared distance;  value v_ij = (-c_ij) - p_j in fp32;  prices p start at 0
+ *   phases  k = phases, phases-1, .., 0 with eps_k = eps * scaling^k, rounded to fp32 at each multiplication; a phase
+ *           starts with every person unassigned and every owner cleared, keeps the prices, and ends when no person
+ *           is unassigned
+ *   round   every unassigned person i finds the best value v1 at j1 (ties: lowest j) and the best value v2 over
+ *           j != j1, and bids p' = p_j1 + ((v1 - v2) + eps_k) in fp32, or nextafter(p_j1, +inf) where p' <= p_j1;
+ *           every object with bids takes the highest p' (ties: lowest i): its previous owner becomes unassigned and
+ *           its price p'.  All bids of a round see the prices of the round's start.
+ *   rounds  counted per cloud over all phases; a cloud with persons unassigned when the count reaches `iters` is
+ *           CAPPED and takes no further rounds.  n = 1 is assigned directly, in 0 rounds.
+ * A cloud's results depend on that cloud alone: not on the batch, not on wide_rounds / narrow_rounds / narrow_at.
+ * The caller drives three steps over one workspace of tpg_emd_workspace_bytes(B, n) bytes, 256-byte aligned:
+ *   tpg_emd_init_f32    objects and prices into the workspace, assignment = -1 (m must equal n: TPG_ERR_ARG)
+ *   tpg_emd_rounds_f32  `wide_rounds` rounds of two launches each (a wave per unassigned person bids; a workgroup
+ *                       per cloud assigns) for clouds with more than `narrow_at` persons unassigned, then ONE launch
+ *                       that runs up to `narrow_rounds` rounds, a workgroup per cloud between workgroup barriers,
+ *                       for clouds with at most `narrow_at`.  Launches for a cloud that is done, capped or on the
+ *                       other path do nothing.  The call must be able to advance every cloud: narrow_rounds >= 1
+ *                       when narrow_at > 0, wide_rounds >= 1 (and <= 4096) when narrow_at < n.  eps > 0,
+ *                       scaling >= 1, 0 <= phases <= 64, iters >= 1.
+ *                       Afterwards the workspace starts with B records of 8 int32:
+ *                       {phase, rounds, unassigned persons, status (0 active, 1 done, 2 capped), 4 unused};
+ *                       the caller reads them and calls again while a cloud is active.
+ *   tpg_emd_finish_f32  dist (B,n) = c of every person to its object, price (B,n), rounds (B).
+ * TPG_ERR_UNSUPPORTED for B > 65535. */
+size_t tpg_emd_workspace_bytes(int B, int n);
+int tpg_emd_init_f32(const float *xyz2, int B, int n, int m, int phases, int32_t *assignment, void *ws, void *stream);
+int tpg_emd_rounds_f32(const float *xyz1, int B, int n, float eps, float scaling, int phases, int iters,
+                       int wide_rounds, int narrow_rounds, int narrow_at, int32_t *assignment, void *ws,
+                       void *stream);
+int tpg_emd_finish_f32(const float *xyz1, int B, int n, const int32_t *assignment, void *ws, float *dist, float *price,
+                       int32_t *rounds, void *stream);
+
+/* ---- Gaussian row sums, the building block of the Gaussian MMD (csrc/gauss_sum.hip) -----------------------------
+ * geomloss.SamplesLoss('gaussian', blur) of train_fluid/analysis_helper.py:226-227,256-260.  a (B,N,3), b (B,M,3);
+ * lena / lenb (B) int64 or NULL (= full).  out (B,N) FLOAT64: out[i] = sum over the points j of b of
+ * expf(-(c_ij * s)), c the canonical fp32 squared distance, s = fp32(1 / (2 sigma^2)) with the division in double.
+ * Rows at or beyond lena[b] get 0.  Every term is truncated to a multiple of 2^-32 and the terms are added as 64-bit
+ * integers: the same bits whatever the order, the batch and the run, and an exact float64.  sigma <= 0: TPG_ERR_ARG;
+ * M >= 2^17 or B > 65535: TPG_ERR_UNSUPPORTED. */
+int tpg_gaussian_row_sums_f32(const float *a, const float *b, const int64_t *lena, const int64_t *lenb, int B, int N,
+                              int M, float sigma, double *out, void *stream);
+
 /* ---- training clips from device-resident sequences (csrc/clip_sample.hip) -------------------------------------
  * train_fluid/tempo_dataset.py:58-105 (SiamData.__getitem__) with train_utils.py:98-139 (sample_patch_with_fps) and
  * :214-221 (normalize_point_cloud), which the reference runs per clip on host workers (np.load, a scipy KD-tree, a

@@ -77,8 +77,13 @@ SIGNATURES = {
     "tpg_clip_gather_low_f32": [_P, _P, _P, _F, _P, _L, _P, _P, _I, _I, _I, _I, _P, _P, _P],
     "tpg_frame_subset": [_P, _P, _I, _I, _P, _P],
     "tpg_action_gather_f32": [_P, _L, _P, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P],
+    "tpg_emd_init_f32": [_P, _I, _I, _I, _I, _P, _P, _P],
+    "tpg_emd_rounds_f32": [_P, _I, _I, _F, _F, _I, _I, _I, _I, _I, _P, _P, _P],
+    "tpg_emd_finish_f32": [_P, _I, _I, _P, _P, _P, _P, _P, _P],
+    "tpg_gaussian_row_sums_f32": [_P, _P, _P, _P, _I, _I, _I, _F, _P, _P],
 }
-SIZE_GETTERS = ("tpg_rowbn_workspace_bytes", "tpg_mlp_workspace_bytes", "tpg_context_expand_workspace_bytes")
+SIZE_GETTERS = ("tpg_rowbn_workspace_bytes", "tpg_mlp_workspace_bytes", "tpg_context_expand_workspace_bytes",
+                "tpg_emd_workspace_bytes")
 OTHER_GETTERS = ("tpg_spectral_norm_multi_stride", "tpg_spectral_norm_multi_bwd_scratch",
                  "tpg_mlp_wgrad_workspace_bytes", "tpg_frnn_grid_workspace_bytes", "tpg_small_tail_workspace_bytes",
                  "tpg_chamfer_bwd_workspace_bytes", "tpg_rowlinear_wgrad_workspace_bytes", "tpg_rowlinear_supported",

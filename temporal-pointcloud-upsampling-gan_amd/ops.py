@@ -243,6 +243,82 @@ class HipBackend:
             self._call("tpg_radius_reduce_exhaustive_f32", "radius_reduce", nbytes, query, *args)
         return count, total
 
+    # Auction matching (csrc/emd.hip).  A cloud takes wide rounds (two launches each) while more than `narrow_at` of its
+    # persons are unassigned and the narrow path (EMD_NARROW_ROUNDS rounds per launch, one workgroup per cloud) below;
+    # the host reads the per-cloud records once per batch of EMD_CHECK_EVERY wide rounds + one narrow launch.  On the
+    # narrow path the workgroup's 16 waves scan the n objects once per bidder, so its cost per round grows as
+    # bidders x n while a wide round spreads the bidders over the chip: the threshold is a bound on that WORK,
+    # narrow_at = EMD_NARROW_WORK / n, but never below one bidder per wave.  The values are tuning only -- the results
+    # do not depend on them -- and come from the sweep in profiles/metrics.txt (tools/metrics_time.py).
+    EMD_NARROW_WORK = 256 * 1024
+    EMD_NARROW_MIN = 16
+    EMD_CHECK_EVERY = 8
+    EMD_NARROW_ROUNDS = 256
+
+    def emd_narrow_at(self, n):
+        return max(0, min(n, max(self.EMD_NARROW_MIN, self.EMD_NARROW_WORK // max(n, 1))))
+
+    def emd_begin(self, xyz1, xyz2, phases):
+        """tpg_emd_init_f32 -> the handle the next two steps take (outputs and workspace of one matching)."""
+        B, n, _ = xyz1.shape
+        dev = xyz1.device
+        st = {"xyz1": xyz1, "B": B, "n": n, "phases": int(phases),
+              "dist": torch.empty((B, n), dtype=torch.float32, device=dev),
+              "assignment": torch.empty((B, n), dtype=torch.int32, device=dev),
+              "price": torch.empty((B, n), dtype=torch.float32, device=dev),
+              "rounds": torch.zeros((B,), dtype=torch.int32, device=dev)}
+        st["ws"] = self._workspace("emd", xyz1, self.lib.tpg_emd_workspace_bytes(B, n), dtype=torch.uint8)
+        self._call("tpg_emd_init_f32", "emd_init", 16 * B * n, xyz1, _ptr(xyz2), B, n, xyz2.shape[1], int(phases),
+                   _ptr(st["assignment"]), _ptr(st["ws"]))
+        return st
+
+    def emd_batch(self, st, eps, iters, scaling, narrow_at, wide):
+        """tpg_emd_rounds_f32 once, then the per-cloud records on the host (the one synchronisation per batch):
+        -> (B,8) int32 {phase, rounds, unassigned, status, ..}, the number of kernel launches issued."""
+        B, n = st["B"], st["n"]
+        self._call("tpg_emd_rounds_f32", "emd_rounds", 16 * B * n, st["xyz1"], _ptr(st["xyz1"]), B, n, float(eps),
+                   float(scaling), st["phases"], int(iters), int(wide), self.EMD_NARROW_ROUNDS, int(narrow_at),
+                   _ptr(st["assignment"]), _ptr(st["ws"]))
+        launches = (2 * int(wide) if narrow_at < n else 0) + (1 if narrow_at > 0 else 0)
+        return st["ws"][:32 * B].view(torch.int32).view(B, 8).cpu(), launches
+
+    def emd_end(self, st):
+        B, n = st["B"], st["n"]
+        self._call("tpg_emd_finish_f32", "emd_finish", 16 * B * n, st["xyz1"], _ptr(st["xyz1"]), B, n,
+                   _ptr(st["assignment"]), _ptr(st["ws"]), _ptr(st["dist"]), _ptr(st["price"]), _ptr(st["rounds"]))
+        return st["dist"], st["assignment"], st["price"], st["rounds"]
+
+    def emd_match(self, xyz1, xyz2, eps, iters, phases, scaling, narrow_at=None, check_every=None):
+        """-> dist (B,n) f32, assignment (B,n) i32, price (B,n) f32, rounds (B,) i32; RuntimeError at the round cap."""
+        B, n, _ = xyz1.shape
+        if B == 0 or n == 0:
+            dev = xyz1.device
+            return (torch.empty((B, n), dtype=torch.float32, device=dev),
+                    torch.empty((B, n), dtype=torch.int32, device=dev),
+                    torch.empty((B, n), dtype=torch.float32, device=dev),
+                    torch.zeros((B,), dtype=torch.int32, device=dev))
+        narrow_at = self.emd_narrow_at(n) if narrow_at is None else max(0, min(int(narrow_at), n))
+        wide = self.EMD_CHECK_EVERY if check_every is None else int(check_every)
+        st = self.emd_begin(xyz1, xyz2, phases)
+        while True:
+            rec, _ = self.emd_batch(st, eps, iters, scaling, narrow_at, wide)
+            status = rec[:, 3]
+            if bool((status == 2).any()):
+                b = int(torch.nonzero(status == 2)[0])
+                raise RuntimeError(f"emd_match: cloud {b} still has {int(rec[b, 2])} unassigned persons after "
+                                   f"{int(rec[b, 1])} rounds (iters = {int(iters)})")
+            if bool((status == 1).all()):
+                return self.emd_end(st)
+
+    def gaussian_row_sums(self, a, b, lena, lenb, sigma):
+        """csrc/gauss_sum.hip: (B,N) float64 sums of exp(-c / (2 sigma^2)) over the points of b."""
+        B, N, _ = a.shape
+        M = b.shape[1]
+        out = torch.empty((B, N), dtype=torch.float64, device=a.device)
+        self._call("tpg_gaussian_row_sums_f32", "gaussian_row_sums", 12 * B * (N + M) + 8 * B * N, a, _ptr(a), _ptr(b),
+                   _ptr(lena), _ptr(lenb), B, N, M, float(np.float32(sigma)), _ptr(out))
+        return out
+
     def chamfer_fwd(self, src, tgt):
         B, N, _ = src.shape
         M = tgt.shape[1]
@@ -1449,6 +1525,80 @@ def radius_reduce(query, pos, r, kernel="cubic", lengths_q=None, lengths_p=None,
     if squeeze:
         return count[0], None if total is None else total[0]
     return count, total
+
+
+# ------------------------------------------------- earth mover's distance, Gaussian sums
+EMD_DEFAULTS = dict(eps=1e-4, iters=1_000_000, phases=3, scaling=4.0)
+
+
+class _Emd(torch.autograd.Function):
+    """dist of the auction's assignment with the gradient of |x1 - x2[a]|^2 attached; the assignment is a constant."""
+
+    @staticmethod
+    def forward(ctx, xyz1, xyz2, eps, iters, phases, scaling, narrow_at, check_every):
+        dist, assignment, price, rounds = backend_for(xyz1).emd_match(xyz1, xyz2, eps, iters, phases, scaling,
+                                                                      narrow_at, check_every)
+        ctx.save_for_backward(xyz1, xyz2, assignment)
+        ctx.mark_non_differentiable(assignment, price, rounds)
+        return dist, assignment, price, rounds
+
+    @staticmethod
+    def backward(ctx, g, _ga, _gp, _gr):
+        xyz1, xyz2, assignment = ctx.saved_tensors
+        a = assignment.long().unsqueeze(-1).expand(-1, -1, 3)
+        g1 = 2.0 * g.unsqueeze(-1) * (xyz1 - torch.gather(xyz2, 1, a))
+        g2 = torch.empty_like(g1).scatter_(1, a, -g1)          # a is a permutation: the gather by its inverse
+        return g1, g2, None, None, None, None, None, None
+
+
+def emd_match(xyz1, xyz2, eps=EMD_DEFAULTS["eps"], iters=EMD_DEFAULTS["iters"], phases=EMD_DEFAULTS["phases"],
+              scaling=EMD_DEFAULTS["scaling"], _narrow_at=None, _check_every=None):
+    """One-to-one assignment of the points of xyz1 to the points of xyz2 (both (B,n,3)) that approximately minimises
+    the sum of squared distances: a forward auction with Jacobi rounds and epsilon scaling (csrc/emd.hip;
+    include/tpgan_ops.h states the rule, which is reproduced bit for bit).  `eps` is the final epsilon -- the sum of
+    costs ends within n * eps of the optimum -- the phases run at eps * scaling^k, k = phases .. 0; `iters` caps the
+    rounds per cloud (RuntimeError beyond it).
+
+    -> dist (B,n) f32 squared distance of every point of xyz1 to its partner, differentiable wrt both clouds with the
+    assignment held fixed; assignment (B,n) int32; price (B,n) f32; rounds (B,) int32.  A cloud's results do not
+    depend on the rest of the batch.  `_narrow_at` / `_check_every` force the launch arrangement (tests, tuning)."""
+    _need(isinstance(xyz1, torch.Tensor) and isinstance(xyz2, torch.Tensor), "xyz1 and xyz2 must be tensors")
+    _need(xyz1.dim() == 3 and xyz2.dim() == 3 and xyz1.shape[2] == 3 and xyz2.shape[2] == 3, "clouds must be (B,n,3)")
+    _need(xyz1.shape[0] == xyz2.shape[0], "batch mismatch")
+    _need(xyz1.shape[1] == xyz2.shape[1], f"emd_match needs equal-size clouds, got {xyz1.shape[1]} and {xyz2.shape[1]}")
+    _need(xyz1.is_floating_point() and xyz2.is_floating_point(), "xyz1 and xyz2 must be float tensors")
+    _need(float(eps) > 0.0, "eps must be positive")
+    _need(int(iters) >= 1, "iters must be >= 1")
+    _need(0 <= int(phases) <= 64, "phases must be in [0, 64]")
+    _need(float(scaling) >= 1.0, "scaling must be >= 1")
+    _need(_narrow_at is None or int(_narrow_at) >= 0, "_narrow_at must be >= 0")
+    _need(_check_every is None or 1 <= int(_check_every) <= 4096, "_check_every must be in [1, 4096]")
+    _same_device(xyz1, xyz2)
+    be = backend_for(xyz1)
+    _need(hasattr(be, "emd_match"), "this backend has no emd_match")
+    return _Emd.apply(xyz1.float().contiguous(), xyz2.float().contiguous(), float(eps), int(iters), int(phases),
+                      float(scaling), _narrow_at, _check_every)
+
+
+def gaussian_row_sums(a, b, sigma, lengths_a=None, lengths_b=None):
+    """(B,N,3), (B,M,3) -> (B,N) float64: entry i is sum_j exp(-|a_i - b_j|^2 / (2 sigma^2)) over the points of b
+    (csrc/gauss_sum.hip; lengths (B,) or None as in `neighbour_search`, rows beyond lengths_a get 0).  Summed in
+    fixed point: the same bits on every run and at every batch position.  No gradient."""
+    _need(isinstance(a, torch.Tensor) and isinstance(b, torch.Tensor), "a and b must be tensors")
+    _need(a.dim() == 3 and b.dim() == 3 and a.shape[2] == 3 and b.shape[2] == 3 and a.shape[0] == b.shape[0],
+          "a (B,N,3), b (B,M,3)")
+    _need(a.is_floating_point() and b.is_floating_point(), "a and b must be float tensors")
+    _need(float(sigma) > 0.0, "sigma must be positive")
+    _need(b.shape[1] < (1 << 17), "gaussian_row_sums: at most 2^17 - 1 points per cloud")
+    _same_device(a, b)
+    x = a.detach().float().contiguous()
+    y = x if b is a else b.detach().float().contiguous()
+    be = backend_for(x)
+    _need(hasattr(be, "gaussian_row_sums"), "this backend has no gaussian_row_sums")
+    B = x.shape[0]
+    with torch.no_grad():
+        return be.gaussian_row_sums(x, y, _lengths(lengths_a, B, x.shape[1], x.device),
+                                    _lengths(lengths_b, B, y.shape[1], x.device), float(sigma))
 
 
 def cubic_interpolation(query_pos, field, pos, cutoff):
