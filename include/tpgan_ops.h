@@ -651,6 +651,42 @@ int tpg_action_gather_f32(const float *points, long long P, const int32_t *frame
                           const int32_t *idx, const double *scale, int mode, int T, int B, int K, float *high,
                           float *centre, void *stream);
 
+/* ---- point-cloud pictures (csrc/render.hip) --------------------------------------------------------------------
+ * A z-buffered square splat of F clouds, one picture each (the reference looks at its results through an Open3D
+ * window, train_utils.py:224-238; the look here is this project's own).  points (F,N,3) f32; lengths (F) int64 or
+ * NULL: rows at or beyond lengths[f] are never read; scalar (F,N) f32 or NULL: the value a point is coloured by
+ * (NULL: its depth t).  cams: a HOST table (the exception stated for the clip sampler above) of ncam = 1 (shared by
+ * all frames) or ncam = F cameras of TPG_RENDER_CAM_FLOATS floats each:
+ *     [0..2] eye   [3..5] r   [6..8] d   [9..11] f   (orthonormal rows: image-right, image-DOWN, forward)
+ *     [12] scale   [13] cx   [14] cy   [15] near   [16] far   [17] mode (0 = ortho, 1 = pinhole)
+ * Everything is fp32, each operation rounded on its own (no FMA), dot products as (a.x*b.x + a.y*b.y) + a.z*b.z:
+ *     q = p - eye;  xv = q.r;  yv = q.d;  zv = q.f
+ *     ortho:    u = xv*scale + cx;         v = yv*scale + cy
+ *     pinhole:  u = (xv/zv)*scale + cx;    v = (yv/zv)*scale + cy
+ *     t = zv - near;  the point is dropped unless
+ *         t >= 0 && zv <= far && u >= -S && u < W+S && v >= -S && v < H+S           (S = size)
+ *     which a NaN or an infinity anywhere fails; the test comes BEFORE any conversion to an integer.
+ * With px = (int)floorf(u), py = (int)floorf(v) the point covers columns px - S/2 .. px - S/2 + S - 1 (integer
+ * division) and rows likewise, clipped to the image.  Per covered pixel the smallest 64-bit key
+ * (bits(t) << 32) | index wins (a non-negative fp32 orders like its bit pattern; equal depths: the lower index; t = -0.0,
+ * which only zv = -0.0 with near = 0 gives, ranks by its pattern, behind every other depth): a 64-bit atomic min on
+ * `keys`, (F,H,W) uint64, 8-byte aligned, set to all ones by the call itself.  The result does not depend on the order
+ * of execution: bit-identical from run to run and at every batch position.
+ * winner (F,H,W) int32: the visible point's index, -1 for background.  image (F,H,W,3) uint8: background (3) uint8
+ * where winner is -1, else lut[level] (lut (256,3) uint8) with s = scalar[f][winner] (or t), inv = 255/(hi - lo)
+ * rounded to fp32 once, c = (s - lo)*inv and level = 0 unless c > 0 (so NaN gives 0), 255 if c >= 255, else
+ * (int)(c + 0.5f).
+ * NULL image / winner, size outside 1..TPG_RENDER_MAX_SIZE, W or H < 1, hi <= lo: TPG_ERR_ARG.  F == 0 or N == 0:
+ * TPG_OK, nothing written.  Then: another NULL pointer, ncam not 1 or F, a non-finite camera entry, lo or inv, a mode
+ * other than 0 / 1, a pinhole camera with near <= 0: TPG_ERR_ARG; W or H > TPG_RENDER_MAX_EXTENT, F > 65535 or more than
+ * 2^31 pixels in all: TPG_ERR_UNSUPPORTED.  All of it is decided before anything is launched. */
+#define TPG_RENDER_CAM_FLOATS 18
+#define TPG_RENDER_MAX_SIZE 16
+#define TPG_RENDER_MAX_EXTENT 16384
+int tpg_render_points_f32(const float *points, const int64_t *lengths, const float *scalar, int F, int N,
+                          const float *cams, int ncam, int W, int H, int size, float lo, float hi, const uint8_t *lut,
+                          const uint8_t *background, void *keys, uint8_t *image, int32_t *winner, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -81,6 +81,7 @@ SIGNATURES = {
     "tpg_emd_rounds_f32": [_P, _I, _I, _F, _F, _I, _I, _I, _I, _I, _P, _P, _P],
     "tpg_emd_finish_f32": [_P, _I, _I, _P, _P, _P, _P, _P, _P],
     "tpg_gaussian_row_sums_f32": [_P, _P, _P, _P, _I, _I, _I, _F, _P, _P],
+    "tpg_render_points_f32": [_P, _P, _P, _I, _I, _P, _I, _I, _I, _I, _F, _F, _P, _P, _P, _P, _P, _P],
 }
 SIZE_GETTERS = ("tpg_rowbn_workspace_bytes", "tpg_mlp_workspace_bytes", "tpg_context_expand_workspace_bytes",
                 "tpg_emd_workspace_bytes")

@@ -316,6 +316,73 @@ class ActionClipSampler:
             yield self.sample()
 
 
+# ---------------------------------------------------------------------------------------------------------------------
+# Held-out clips for the trainers' test pass (train.run): drawn ONCE from a generator of their own, only the chosen
+# frames go to the device, and nothing of numpy's, torch's or the device's global RNG is touched.
+TEST_PATCH_MAX = 9216          # train_utils.py:106-111, the rule of sample_num=None: the test data loader's
+TEST_PATCH_SCENE = 10000
+
+
+def held_out_fluid_clips(root, case_num, case_steps, n, generator, device, use_vel=False, jitter=0.003, case_prefix="data",
+                         case_to_start=1):
+    """`n` test clips as the reference's test loader makes them (tempo_dataset.py:118, SiamData with sample_num=None),
+    centre frame only -- the test pass reads nothing else: a list of dicts with `gt` (K,3), `input` (K/8,3) and
+    `feature` (1,K/8,3), or (1,K/8,6) = position and 0.025 x velocity under `use_vel`.  K = 9216 if the scene has more
+    than 10000 particles, else (count // 1024) * 1024; the low resolution is the dataset-side FPS plus `jitter` x noise
+    from a device generator of this function's own.  Clip indices, seed particles, FPS starts and noise seeds come from
+    `generator`, clip by clip in that order."""
+    device = torch.device(device)
+    if case_num < 1 or case_steps < 3:
+        raise ValueError("need at least one case of at least 3 steps")
+    noise_gen = torch.Generator(device=device)
+    clips = []
+    for idx in torch.randint(case_num * (case_steps - 2), (int(n),), generator=generator).tolist():
+        case, step = idx // case_steps, idx % (case_steps - 2)                 # SiamData's rule, quirk included
+        path = os.path.join(root, f"case{case + case_to_start}/{case_prefix}_{step + 1}.npz")
+        with np.load(path) as f:
+            p, v = f["pos"].astype(np.float32), f["vel"].astype(np.float32)
+        if p.ndim != 2 or p.shape[1] != 3 or v.shape != p.shape:
+            raise ValueError(f"{path}: pos and vel must be (N,3) arrays of one shape, got {p.shape} / {v.shape}")
+        count = p.shape[0]
+        K = TEST_PATCH_MAX if count > TEST_PATCH_SCENE else count // 1024 * 1024
+        if K == 0:
+            raise ValueError(f"{path}: a test scene needs at least 1024 particles, got {count}")
+        seed, start, noise_seed = (int(torch.randint(int(high), (1,), generator=generator)) for high in (count, K, 2 ** 62))
+        pos, vel = torch.from_numpy(p).to(device), torch.from_numpy(v).to(device)
+        centroid = torch.from_numpy(p.astype(np.float64).mean(0).astype(np.float32)).view(1, 3).to(device)
+        zero = np.zeros((1, 1), np.int64)
+        patch = ops.patch_select(pos, [0], [count], [seed], K)
+        high, _ = ops.clip_gather_high(pos, None, zero, [count], centroid, [0], patch)               # (1,1,K,3)
+        fps_idx = ops.backend_for(high).fps(high[0], K // 8, torch.tensor([start], dtype=torch.int32).to(device), False)
+        noise_gen.manual_seed(noise_seed)
+        noise = torch.randn((1, 1, K // 8, 3), dtype=torch.float32, device=device, generator=noise_gen)
+        low, low_vel = ops.clip_gather_low(high, fps_idx, noise, jitter, vel, zero, [count])
+        feature = torch.cat([low[0], low_vel[0] * 0.025], dim=2) if use_vel else low[0]
+        clips.append({"gt": high[0, 0], "input": low[0, 0], "feature": feature.contiguous()})
+    return clips
+
+
+def held_out_action_clips(root, n, generator, device, num_points=2048):
+    """`n` clips of the test subjects under `root`, first frame only (train_msr.py:249-254): a list of dicts with `gt`
+    (num_points,3) and `input` = `feature` (num_points/16,3), prepared as `ActionClipSampler` prepares the test split.
+    The videos are read into HOST memory; only the chosen frames go to the device.  Clip indices, subset seeds and FPS
+    starts come from `generator`, in that order."""
+    device, n, K = torch.device(device), int(n), int(num_points)
+    seq = ActionSequences(root, train=False, frames_per_clip=3, device="cpu")
+    indices = torch.randint(len(seq), (n,), generator=generator).tolist()
+    halves = torch.randint(2 ** 32, (n, 2), generator=generator).numpy().astype(np.uint64)
+    starts = torch.randint(K, (n,), generator=generator)
+    rows = np.array([int(seq.frame_rows(i)[0]) for i in indices])
+    count = seq.count[rows]
+    points = torch.cat([seq.points[f:f + c] for f, c in zip(seq.first[rows].tolist(), count.tolist())]).to(device)
+    first = np.concatenate([[0], np.cumsum(count)[:-1]]).astype(np.int64)
+    subset = ops.frame_subset(count, (halves[:, 1] << np.uint64(32)) | halves[:, 0], K, device=device).view(1, n, K)
+    high, _ = ops.action_gather(points, first.reshape(1, n), count.reshape(1, n), subset, None, "test")
+    fps_idx = ops.backend_for(high).fps(high.view(n, K, 3), K // 16, starts.to(torch.int32).to(device), False)
+    low, _ = ops.clip_gather_low(high.view(1, n, K, 3), fps_idx)
+    return [{"gt": high[0, j], "input": low[0, j], "feature": low[0, j:j + 1].contiguous()} for j in range(n)]
+
+
 class prefetch:
     """Iterator over `sampler`'s batches that prepares batch n+1 on `stream` while batch n is consumed (two batches in
     flight).  The hand-off is per batch: an event recorded on the side stream after the batch's last launch, waited for

@@ -319,6 +319,25 @@ class HipBackend:
                    _ptr(lena), _ptr(lenb), B, N, M, float(np.float32(sigma)), _ptr(out))
         return out
 
+    def render_points(self, points, lengths, scalar, cams, W, H, size, lo, hi, lut, background, max_key_bytes):
+        """csrc/render.hip: cams (1 or F, 18) is a host fp32 array (numpy); -> (image (F,H,W,3) uint8, winner (F,H,W)
+        int32).  The 64-bit key buffer is a per-stream workspace of at most `max_key_bytes` (one frame's at least): F is
+        rendered in chunks of that many frames, each chunk one call."""
+        F, N, _ = points.shape
+        image = torch.empty((F, H, W, 3), dtype=torch.uint8, device=points.device)
+        winner = torch.empty((F, H, W), dtype=torch.int32, device=points.device)
+        chunk = max(1, min(65535, int(max_key_bytes) // (8 * H * W)))
+        keys = self._workspace("render_keys", points, min(chunk, max(F, 1)) * H * W, dtype=torch.int64)
+        for f0 in range(0, F, chunk):
+            f1 = min(F, f0 + chunk)
+            c = cams if cams.shape[0] == 1 else np.ascontiguousarray(cams[f0:f1])
+            self._call("tpg_render_points_f32", "render_points",
+                       (f1 - f0) * (12 * N + (4 * N if scalar is not None else 0) + 23 * H * W), points,
+                       _ptr(points[f0:f1]), _ptr(None if lengths is None else lengths[f0:f1]),
+                       _ptr(None if scalar is None else scalar[f0:f1]), f1 - f0, N, c.ctypes.data, c.shape[0], W, H, size,
+                       lo, hi, _ptr(lut), _ptr(background), _ptr(keys), _ptr(image[f0:f1]), _ptr(winner[f0:f1]))
+        return image, winner
+
     def chamfer_fwd(self, src, tgt):
         B, N, _ = src.shape
         M = tgt.shape[1]
@@ -1599,6 +1618,125 @@ def gaussian_row_sums(a, b, sigma, lengths_a=None, lengths_b=None):
     with torch.no_grad():
         return be.gaussian_row_sums(x, y, _lengths(lengths_a, B, x.shape[1], x.device),
                                     _lengths(lengths_b, B, y.shape[1], x.device), float(sigma))
+
+
+# ------------------------------------------------------------------------ point-cloud pictures (csrc/render.hip)
+RENDER_CAM_FLOATS = 18                 # eye, r, d, f, scale, cx, cy, near, far, mode: include/tpgan_ops.h
+RENDER_ORTHO, RENDER_PINHOLE = 0, 1
+RENDER_MAX_SIZE = 16
+RENDER_MAX_EXTENT = 16384
+RENDER_KEY_BYTES = 256 << 20           # cap of the 64-bit key buffer; more frames than fit are rendered in chunks
+_KEY_FLIP = -2 ** 63                   # unsigned 64-bit order on int64: flip the top bit
+
+
+def _render_points_torch(points, lengths, scalar, cams, W, H, size, lo, hi, lut, background):
+    """`render_points` composed of torch ops (backends without the kernel): the rule of include/tpgan_ops.h frame by
+    frame -- fp32 operations in the stated order, the cull before any conversion to an integer, one `amin` scatter of
+    the 64-bit keys per splat offset (kept as int64 with the top bit flipped, which orders them as unsigned)."""
+    F, N, _ = points.shape
+    dev = points.device
+    image = torch.empty((F, H, W, 3), dtype=torch.uint8, device=dev)
+    winner = torch.empty((F, H, W), dtype=torch.int32, device=dev)
+    lo_t = torch.tensor(np.float32(lo), device=dev)
+    inv = torch.tensor(np.float32(255.0) / (np.float32(hi) - np.float32(lo)), device=dev)
+    lens = [N] * F if lengths is None else [min(max(int(v), 0), N) for v in lengths.tolist()]
+    for f in range(F):
+        cam = torch.from_numpy(cams[f if cams.shape[0] > 1 else 0]).to(dev)
+        p = points[f, :lens[f]]
+        q = p - cam[0:3]
+
+        def dot(b):
+            return (q[:, 0] * b[0] + q[:, 1] * b[1]) + q[:, 2] * b[2]
+        xv, yv, zv = dot(cam[3:6]), dot(cam[6:9]), dot(cam[9:12])
+        if float(cam[17]) != 0.0:
+            u, v = (xv / zv) * cam[12] + cam[13], (yv / zv) * cam[12] + cam[14]
+        else:
+            u, v = xv * cam[12] + cam[13], yv * cam[12] + cam[14]
+        t = zv - cam[15]
+        keep = (t >= 0) & (zv <= cam[16]) & (u >= -size) & (u < W + size) & (v >= -size) & (v < H + size)
+        index = torch.nonzero(keep).view(-1)
+        px, py = torch.floor(u[index]).long(), torch.floor(v[index]).long()
+        key = (((t[index].view(torch.int32).long() & 0xFFFFFFFF) << 32) | index) ^ _KEY_FLIP
+        keys = torch.full((H * W,), 2 ** 63 - 1, dtype=torch.int64, device=dev)
+        for dy in range(size):
+            for dx in range(size):
+                x, y = px - size // 2 + dx, py - size // 2 + dy
+                ok = (x >= 0) & (x < W) & (y >= 0) & (y < H)
+                keys.scatter_reduce_(0, (y * W + x)[ok], key[ok], "amin")
+        hit = keys != 2 ** 63 - 1
+        ukey = keys ^ _KEY_FLIP
+        win = torch.where(hit, ukey & 0xFFFFFFFF, torch.full_like(keys, -1))
+        if scalar is None:
+            s = ((ukey >> 32) & 0xFFFFFFFF).to(torch.int32).view(torch.float32)
+        else:
+            s = scalar[f][win.clamp(min=0)] if N > 0 else torch.zeros_like(keys, dtype=torch.float32)
+        c = (s - lo_t) * inv
+        c = torch.where(c > 0, c, torch.zeros_like(c)).clamp(max=255.0)         # NaN: c > 0 is false, level 0
+        level = torch.where(c >= 255.0, torch.full_like(keys, 255), (c + 0.5).long())
+        image[f] = torch.where(hit.view(-1, 1), lut[level], background.view(1, 3)).view(H, W, 3)
+        winner[f] = win.to(torch.int32).view(H, W)
+    return image, winner
+
+
+def render_points(points, cams, width, height, lut, size=1, lengths=None, scalar=None, lo=None, hi=None,
+                  background=(255, 255, 255), max_key_bytes=RENDER_KEY_BYTES):
+    """One picture per cloud of a ragged batch: a z-buffered square splat (csrc/render.hip; the rule in full:
+    include/tpgan_ops.h).
+
+    points (F,N,3) fp32; lengths (F,) or None: rows at or beyond lengths[f] are never read; scalar (F,N) fp32 or None:
+    what a point is coloured by (None: its depth t = zv - near).  cams: HOST fp32, (18,) / (1,18) shared by all frames
+    or (F,18) one per frame: eye, the rows r / d / f (image-right, image-DOWN, forward), scale, cx, cy, near, far, mode
+    (`render.Camera.row()` builds one).  lut (256,3) uint8 and background (3 values 0..255); the colour is lut[level]
+    with c = (s - lo) * (255 / (hi - lo)), level = 0 unless c > 0, 255 from c >= 255, else int(c + 0.5); lo / hi
+    default to 0 and far - near of the first camera when the colour is the depth, and must be given with `scalar`.
+    size: the splat's edge in pixels, 1..16.  max_key_bytes: cap of the kernel's 64-bit key buffer; F is rendered in
+    chunks that stay under it (the pictures do not depend on it).
+    -> (image (F,height,width,3) uint8, winner (F,height,width) int32: the visible point's index, -1 = background).
+    Bit-identical from run to run and at every batch position; no gradient."""
+    _check_float(points, "points", 3)
+    _need(points.shape[2] == 3, "points must be (F,N,3)")
+    F, N, _ = points.shape
+    W, H, size = int(width), int(height), int(size)
+    _need(1 <= W <= RENDER_MAX_EXTENT and 1 <= H <= RENDER_MAX_EXTENT, f"width and height must be 1..{RENDER_MAX_EXTENT}")
+    _need(1 <= size <= RENDER_MAX_SIZE, f"size must be 1..{RENDER_MAX_SIZE}")
+    _need(int(max_key_bytes) > 0, "max_key_bytes must be positive")
+    if isinstance(cams, torch.Tensor):
+        _need(not cams.is_cuda, "cams is a host table: pass a CPU tensor or a numpy array")
+        cams = cams.numpy()
+    cams = np.ascontiguousarray(np.asarray(cams, dtype=np.float32).reshape(-1, RENDER_CAM_FLOATS))
+    _need(cams.shape[0] in (1, F) or F == 0, f"cams must hold 1 or {F} cameras, got {cams.shape[0]}")
+    _need(bool(np.isfinite(cams).all()), "cams must be finite")
+    _need(bool(np.isin(cams[:, 17], (RENDER_ORTHO, RENDER_PINHOLE)).all()), "camera mode must be 0 (ortho) or 1 (pinhole)")
+    _need(bool((cams[cams[:, 17] == RENDER_PINHOLE, 15] > 0).all()), "a pinhole camera needs near > 0")
+    if scalar is not None:
+        _check_float(scalar, "scalar", 2)
+        _same_device(points, scalar)
+        _need(tuple(scalar.shape) == (F, N), f"scalar must be ({F}, {N})")
+        _need(lo is not None and hi is not None, "a scalar colour needs its range lo / hi")
+    if lo is None:
+        lo = 0.0
+    if hi is None:
+        hi = float(np.float32(cams[0, 16]) - np.float32(cams[0, 15]))
+    lo, hi = float(np.float32(lo)), float(np.float32(hi))
+    _need(hi > lo and np.isfinite(np.float32(255.0) / (np.float32(hi) - np.float32(lo))) and np.isfinite(lo),
+          f"the colour range needs finite lo < hi, got {lo} .. {hi}")
+    lut = torch.as_tensor(lut)
+    _need(lut.dtype == torch.uint8 and tuple(lut.shape) == (256, 3), "lut must be (256,3) uint8")
+    lut = lut.to(points.device).contiguous()
+    bg = np.asarray(background)
+    _need(bg.shape == (3,) and bg.dtype.kind in "iu" and 0 <= bg.min() and bg.max() <= 255, "background must be 3 values 0..255")
+    background = torch.tensor(bg.tolist(), dtype=torch.uint8).to(points.device)
+    lengths = _lengths(lengths, F, N, points.device)
+    if F == 0 or N == 0:
+        return (background.view(1, 1, 1, 3).expand(F, H, W, 3).contiguous(),
+                torch.full((F, H, W), -1, dtype=torch.int32, device=points.device))
+    be = backend_for(points)
+    with torch.no_grad():
+        args = (points.detach(), lengths, None if scalar is None else scalar.detach(), cams, W, H, size, lo, hi, lut,
+                background)
+        if hasattr(be, "render_points"):
+            return be.render_points(*args, int(max_key_bytes))
+        return _render_points_torch(*args)
 
 
 def cubic_interpolation(query_pos, field, pos, cutoff):

@@ -1,0 +1,324 @@
+"""Pictures of point clouds on the GPU: cameras, colours, PNG files.
+
+    python -m tpgan_amd.render --frames 'bunny_demo/pcd_{i}.npy' --count 800 --out PNGDIR
+        [--size 3 --width 768 --height 768 --mode pinhole --color depth|density|free_surface
+         --cutoff 0.0775 --direction x y z --frames_per_call T]
+
+The reference looks at its results through an Open3D window (train_utils.py:224-238) and hands its demo frames to an
+external renderer; neither works on a display-less GPU node.  Here a picture is one op, `ops.render_points`
+(csrc/render.hip): a z-buffered square splat, many frames per call, the same bits on every run.  This file is the thin
+layer above it: `Camera` (host maths in float64, rounded to fp32 once), the colour of a point (its depth, or the
+density / free surface / speed the project already computes on the device), a closed-form colour ramp and a PNG writer
+on the standard library.  The look is this project's own: no parity with Open3D's picture is claimed.
+"""
+import argparse
+import os
+import struct
+import zlib
+
+import numpy as np
+import torch
+
+from . import analysis, ops
+
+PADDING = 900.0                # rows with any |coordinate| >= this are the 999 padding of hard masking, not points
+FRAMES_PER_CALL = 16
+MODES = {"ortho": ops.RENDER_ORTHO, "pinhole": ops.RENDER_PINHOLE}
+
+
+def _unit(v, what):
+    v = np.asarray(v, dtype=np.float64).reshape(3)
+    n = np.linalg.norm(v)
+    if not np.isfinite(n) or n == 0.0:
+        raise ValueError(f"{what} must be a finite non-zero vector")
+    return v / n
+
+
+def _frame(direction, up):
+    """-> rows r, d, f (image-right, image-DOWN, forward), orthonormal, float64."""
+    f = _unit(direction, "direction")
+    r = np.cross(f, np.asarray(up, dtype=np.float64).reshape(3))
+    if np.linalg.norm(r) < 1e-9:
+        raise ValueError("up must not be parallel to the viewing direction")
+    r = _unit(r, "up")
+    return r, np.cross(f, r), f
+
+
+class Camera:
+    """eye, the rows r / d / f, mode, scale, cx, cy, near, far (the 18 floats of include/tpgan_ops.h) and the picture's
+    width and height.  Everything is kept in float64; `row()` rounds to fp32 once."""
+
+    def __init__(self, eye, r, d, f, mode, scale, cx, cy, near, far, width, height):
+        if mode not in MODES:
+            raise ValueError(f"mode must be one of {sorted(MODES)}")
+        self.eye, self.r, self.d, self.f = (np.asarray(a, dtype=np.float64).reshape(3) for a in (eye, r, d, f))
+        self.mode, self.scale, self.cx, self.cy = mode, float(scale), float(cx), float(cy)
+        self.near, self.far, self.width, self.height = float(near), float(far), int(width), int(height)
+        if mode == "pinhole" and not self.near > 0:
+            raise ValueError("a pinhole camera needs near > 0")
+        if not self.far > self.near:
+            raise ValueError("far must exceed near")
+
+    def row(self):
+        return np.concatenate([self.eye, self.r, self.d, self.f,
+                               [self.scale, self.cx, self.cy, self.near, self.far, MODES[self.mode]]]).astype(np.float32)
+
+    def project(self, points):
+        """(N,3) -> (u, v, t) float64 with the fp32-rounded camera: where the kernel puts the points, up to its rounding."""
+        c = self.row().astype(np.float64)
+        q = np.asarray(points, dtype=np.float64).reshape(-1, 3) - c[0:3]
+        xv, yv, zv = q @ c[3:6], q @ c[6:9], q @ c[9:12]
+        if self.mode == "pinhole":
+            xv, yv = xv / zv, yv / zv
+        return xv * c[12] + c[13], yv * c[12] + c[14], zv - c[15]
+
+    @classmethod
+    def look_at(cls, eye, target, up=(0.0, 1.0, 0.0), mode="pinhole", width=768, height=768, scale=None, near=None,
+                far=None):
+        """A camera at `eye` looking at `target`, which lands on the picture's centre.  scale: pixels per unit length in
+        the plane through the target, the same in both modes (default: that plane's unit square fills the smaller
+        picture edge); near / far default to 0.01 x / 2 x the distance to the target."""
+        eye, target = np.asarray(eye, dtype=np.float64).reshape(3), np.asarray(target, dtype=np.float64).reshape(3)
+        dist = float(np.linalg.norm(target - eye))
+        r, d, f = _frame(target - eye, up)
+        scale = float(min(width, height)) if scale is None else float(scale)
+        return cls(eye, r, d, f, mode, scale * dist if mode == "pinhole" else scale, width / 2.0, height / 2.0,
+                   0.01 * dist if near is None else near, 2.0 * dist if far is None else far, width, height)
+
+    @classmethod
+    def fit(cls, points, lengths=None, direction=(0.0, 0.0, -1.0), up=(0.0, 1.0, 0.0), mode="pinhole", width=768,
+            height=768, margin=0.05):
+        """A camera that looks along `direction` and holds the bounding box of the valid rows of one cloud (N,3), a batch
+        (F,N,3) with optional lengths (F,), or a list of clouds: every valid point lands at least margin x the half
+        extent away from the picture's edges, and near .. far is the box's depth range.  Rows that are not finite, or
+        have any |coordinate| >= 900 (the 999 padding of hard masking), are ignored."""
+        if not 0.0 <= margin < 1.0:
+            raise ValueError("margin must be in [0, 1)")
+        lo, hi = bounding_box(points, lengths)
+        centre, radius = (lo + hi) / 2.0, float(np.linalg.norm(hi - lo)) / 2.0
+        radius = radius if radius > 0 else 1.0
+        r, d, f = _frame(direction, up)
+        dist = 3.0 * radius
+        eye = centre - dist * f
+        corners = np.array([[x, y, z] for x in (lo[0], hi[0]) for y in (lo[1], hi[1]) for z in (lo[2], hi[2])]) - eye
+        xv, yv, zv = corners @ r, corners @ d, corners @ f
+        near, far = float(zv.min()) - 0.01 * radius, float(zv.max()) + 0.01 * radius
+        if mode == "pinhole":
+            xv, yv = xv / zv, yv / zv                       # zv >= dist - radius > 0
+        ext_x, ext_y = max(float(np.abs(xv).max()), 1e-12), max(float(np.abs(yv).max()), 1e-12)
+        scale = (1.0 - margin) * min(width / 2.0 / ext_x, height / 2.0 / ext_y)
+        return cls(eye, r, d, f, mode, scale, width / 2.0, height / 2.0, near, far, width, height)
+
+
+def bounding_box(points, lengths=None):
+    """(lo (3,), hi (3,)) float64 of the valid rows (finite, every |coordinate| < 900, below the frame's length) of a
+    cloud, a batch or a list of clouds; the reduction runs where the points live."""
+    if isinstance(points, (list, tuple)):
+        if lengths is not None:
+            raise ValueError("lengths go with one (F,N,3) batch, not with a list of clouds")
+        boxes = [bounding_box(p) for p in points]
+        return np.min([b[0] for b in boxes], axis=0), np.max([b[1] for b in boxes], axis=0)
+    p = torch.as_tensor(points).detach().float()
+    p = p.reshape(1, -1, 3) if p.dim() == 2 else p
+    if p.dim() != 3 or p.shape[2] != 3:
+        raise ValueError("points must be (N,3) or (F,N,3)")
+    valid = torch.isfinite(p).all(-1) & (p.abs() < PADDING).all(-1)
+    if lengths is not None:
+        n = torch.as_tensor(lengths, device=p.device).view(-1, 1)
+        valid &= torch.arange(p.shape[1], device=p.device).view(1, -1) < n
+    if not bool(valid.any()):
+        raise ValueError("no valid point to fit a camera to")
+    v = valid.unsqueeze(-1)
+    lo = torch.where(v, p, torch.full_like(p, float("inf"))).amin((0, 1))
+    hi = torch.where(v, p, torch.full_like(p, float("-inf"))).amax((0, 1))
+    return lo.double().cpu().numpy(), hi.double().cpu().numpy()
+
+
+def default_lut():
+    """(256,3) uint8: blue - cyan - green - yellow - red, each channel the closed form clamp(1.5 - |4x - k|, 0, 1) with
+    k = 3, 2, 1 for red, green, blue and x = level / 255."""
+    x = np.arange(256, dtype=np.float64) / 255.0
+    rgb = np.stack([np.clip(1.5 - np.abs(4.0 * x - k), 0.0, 1.0) for k in (3.0, 2.0, 1.0)], axis=1)
+    return np.floor(rgb * 255.0 + 0.5).astype(np.uint8)
+
+
+def _finite_range(s, lengths):
+    """(min, max) of the finite values of the valid rows of s (F,N); (0, 1) if there is none."""
+    ok = torch.isfinite(s)
+    if lengths is not None:
+        ok &= torch.arange(s.shape[1], device=s.device).view(1, -1) < torch.as_tensor(lengths, device=s.device).view(-1, 1)
+    if not bool(ok.any()):
+        return 0.0, 1.0
+    return float(s[ok].min()), float(s[ok].max())
+
+
+def point_scalar(points, color, lengths=None, cutoff=None, radius=analysis.BASE_RADIUS, velocity=None):
+    """The per-point value (F,N) fp32 behind a named colour: "density" (`analysis.particle_density_batch` within
+    `cutoff`), "free_surface" (1 on the free surface of `analysis.free_surface_mask` at `radius`, else 0) or "speed"
+    (|velocity|, velocity (F,N,3))."""
+    F, N, _ = points.shape
+    if color == "density":
+        if cutoff is None:
+            raise ValueError('color="density" needs a cutoff')
+        return analysis.particle_density_batch(points, cutoff, lengths)
+    if color == "free_surface":
+        num = analysis.neighbor_num_batch(points, radius, lengths)
+        lens = [N] * F if lengths is None else [int(v) for v in torch.as_tensor(lengths).tolist()]
+        out = torch.zeros((F, N), dtype=torch.float32, device=points.device)
+        for t in range(F):
+            out[t, :lens[t]] = analysis.free_surface_mask(num[t, :lens[t]]).float()
+        return out
+    if color == "speed":
+        if velocity is None or tuple(velocity.shape) != (F, N, 3):
+            raise ValueError(f'color="speed" needs velocity of shape {(F, N, 3)}')
+        v = velocity.to(points.device).float()
+        return torch.sqrt((v[..., 0] * v[..., 0] + v[..., 1] * v[..., 1]) + v[..., 2] * v[..., 2]).contiguous()
+    raise ValueError(f"unknown color {color!r}")
+
+
+def render(points, camera, color=None, size=3, lengths=None, lo=None, hi=None, cutoff=None, radius=analysis.BASE_RADIUS,
+           velocity=None, lut=None, background=(255, 255, 255), return_winner=False,
+           max_key_bytes=ops.RENDER_KEY_BYTES):
+    """Pictures of a cloud (N,3) -> (H,W,3) uint8, or of a batch (F,N,3) with optional lengths (F,) -> (F,H,W,3), on the
+    points' device.  camera: one `Camera` for all frames or a list of F.  color: None / "depth" (the distance from the
+    near plane, range 0 .. far - near), "density", "free_surface", "speed" (`point_scalar`), or a tensor (F,N) / (N,)
+    of values per point.  lo / hi: the values that map to the ramp's ends; taken from the finite values when not
+    given.  return_winner: also the (F,H,W) int32 map of the visible point per pixel (-1: background)."""
+    single = points.dim() == 2
+    pts = points.detach().float().contiguous()
+    pts = pts.unsqueeze(0) if single else pts
+    cams = [camera] if isinstance(camera, Camera) else list(camera)
+    if any((c.width, c.height) != (cams[0].width, cams[0].height) for c in cams):
+        raise ValueError("the cameras of one call share the picture's size")
+    scalar = None
+    if color is not None and not (isinstance(color, str) and color == "depth"):
+        if isinstance(color, str):
+            scalar = point_scalar(pts, color, lengths, cutoff, radius,
+                                  None if velocity is None else velocity.reshape(pts.shape))
+            if color == "free_surface":
+                lo, hi = 0.0 if lo is None else lo, 1.0 if hi is None else hi
+        else:
+            scalar = color.detach().to(pts.device).float().reshape(pts.shape[:2])
+        scalar = scalar.contiguous()
+        if lo is None or hi is None:
+            a, b = _finite_range(scalar, lengths)
+            lo, hi = a if lo is None else lo, b if hi is None else hi
+        if not hi > lo:
+            hi = lo + 1.0
+    image, winner = ops.render_points(pts, np.stack([c.row() for c in cams]), cams[0].width, cams[0].height,
+                                      default_lut() if lut is None else lut, size, lengths, scalar, lo, hi, background,
+                                      max_key_bytes)
+    if single:
+        image, winner = image[0], winner[0]
+    return (image, winner) if return_winner else image
+
+
+def write_png(path, image):
+    """(H,W,3) uint8 (tensor or array) -> an 8-bit RGB PNG, every scanline with filter type 0; standard library only.
+    Deflate level 1: the encoding is most of what a picture costs, and level 6 takes about three times as
+    long for files a third smaller."""
+    a = image.detach().cpu().numpy() if isinstance(image, torch.Tensor) else np.asarray(image)
+    if a.ndim != 3 or a.shape[2] != 3 or a.dtype != np.uint8 or a.shape[0] < 1 or a.shape[1] < 1:
+        raise ValueError("image must be (H,W,3) uint8")
+    h, w = a.shape[:2]
+    rows = np.concatenate([np.zeros((h, 1), np.uint8), np.ascontiguousarray(a).reshape(h, w * 3)], axis=1)
+
+    def chunk(kind, data):
+        return struct.pack(">I", len(data)) + kind + data + struct.pack(">I", zlib.crc32(kind + data) & 0xFFFFFFFF)
+    with open(path, "wb") as f:
+        f.write(b"\x89PNG\r\n\x1a\n" + chunk(b"IHDR", struct.pack(">IIBBBBB", w, h, 8, 2, 0, 0, 0))
+                + chunk(b"IDAT", zlib.compress(rows.tobytes(), 1)) + chunk(b"IEND", b""))
+
+
+def pad_frames(frames, device):
+    """list of (n_t,3) arrays / tensors -> ((T,max n,3) fp32 on `device`, zero rows beyond a frame's own, lengths (T,))."""
+    frames = [torch.as_tensor(f).detach().float().reshape(-1, 3) for f in frames]
+    lens = [f.shape[0] for f in frames]
+    batch = torch.zeros((len(frames), max(max(lens), 1), 3), dtype=torch.float32, device=device)
+    for t, f in enumerate(frames):
+        batch[t, :lens[t]] = f.to(device)
+    return batch, torch.tensor(lens, dtype=torch.int64, device=device)
+
+
+class SequenceRenderer:
+    """Pictures of a sequence, `pcd_{i:04d}.png` in `out_dir`, under ONE camera: fitted to the frames of the first
+    `push` unless `camera` is given.  The range of a "density" colour is that of the first `push` as well, so the
+    pictures of a sequence are comparable.  `push(frames, first)`: frames = list of (n_t,3) clouds, first = index of
+    the first one; they are rendered in one call."""
+
+    def __init__(self, out_dir, size=3, width=768, height=768, mode="pinhole", color="depth", cutoff=None,
+                 direction=(0.0, 0.0, -1.0), camera=None, device="cuda"):
+        if color not in ("depth", "density", "free_surface"):
+            raise ValueError("color must be depth, density or free_surface")
+        self.out_dir, self.size, self.width, self.height, self.mode = out_dir, int(size), int(width), int(height), mode
+        self.color, self.cutoff, self.direction, self.camera = color, cutoff, tuple(direction), camera
+        self.device, self.range = torch.device(device), (None, None)
+        os.makedirs(out_dir, exist_ok=True)
+
+    def fit(self, frames):
+        self.camera = Camera.fit(list(frames), direction=self.direction, mode=self.mode, width=self.width,
+                                 height=self.height)
+        return self.camera
+
+    def push(self, frames, first):
+        if self.camera is None:
+            self.fit(frames)
+        batch, lengths = pad_frames(frames, self.device)
+        lo, hi = self.range
+        if self.color == "density" and lo is None:
+            s = point_scalar(batch, "density", lengths, self.cutoff)
+            self.range = lo, hi = 0.0, max(_finite_range(s, lengths)[1], 1e-12)
+        images = render(batch, self.camera, self.color, self.size, lengths, lo, hi, self.cutoff).cpu().numpy()
+        for t, image in enumerate(images):
+            write_png(os.path.join(self.out_dir, f"pcd_{first + t:04d}.png"), image)
+
+
+def add_render_options(ap):
+    ap.add_argument("--size", type=int, default=3, help="edge of a point's square in pixels, 1..16")
+    ap.add_argument("--width", type=int, default=768)
+    ap.add_argument("--height", type=int, default=768)
+    ap.add_argument("--mode", choices=sorted(MODES), default="pinhole")
+    ap.add_argument("--color", choices=("depth", "density", "free_surface"), default="depth")
+    ap.add_argument("--cutoff", type=float, default=0.0775, help="density cutoff of --color density")
+    ap.add_argument("--direction", type=float, nargs=3, default=(0.0, 0.0, -1.0), metavar=("X", "Y", "Z"),
+                    help="viewing direction (y is up)")
+
+
+def renderer_from(a, out_dir, device):
+    return SequenceRenderer(out_dir, a.size, a.width, a.height, a.mode, a.color, a.cutoff, a.direction, device=device)
+
+
+def load_frame(path):
+    """`evaluate.load_frame` (.npy, or .npz with `pos`), and the action demo's .npz files, whose entry is `pred`."""
+    from .evaluate import load_frame as load
+    if path.endswith(".npz"):
+        with np.load(path) as data:
+            if "pos" not in data.files and "pred" in data.files:
+                return np.ascontiguousarray(data["pred"], dtype=np.float32).reshape(-1, 3)
+    return load(path)
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser(prog="python -m tpgan_amd.render", description="Render a sequence of frames to PNG files.")
+    ap.add_argument("--frames", required=True, help="frame files, '{i}' = frame index, e.g. 'out/pcd_{i}.npy'")
+    ap.add_argument("--count", type=int, required=True, help="frames 0 .. count-1")
+    ap.add_argument("--out", required=True, help="output directory for pcd_{i:04d}.png")
+    add_render_options(ap)
+    ap.add_argument("--frames_per_call", type=int, default=FRAMES_PER_CALL, help="frames rendered per call")
+    ap.add_argument("--device", default="cuda")
+    a = ap.parse_args(argv)
+    if "{i}" not in a.frames:
+        ap.error("--frames must contain '{i}'")
+    if a.count < 1 or a.frames_per_call < 1:
+        ap.error("--count and --frames_per_call must be at least 1")
+    seq = renderer_from(a, a.out, torch.device(a.device))
+    # one camera for the whole sequence: the union box of the first, the middle and the last frame
+    seq.fit([load_frame(a.frames.format(i=i)) for i in sorted({0, a.count // 2, a.count - 1})])
+    for i in range(0, a.count, a.frames_per_call):
+        idx = range(i, min(i + a.frames_per_call, a.count))
+        seq.push([load_frame(a.frames.format(i=j)) for j in idx], i)
+    print(f"wrote {a.count} pictures to {a.out}")
+
+
+if __name__ == "__main__":
+    main()

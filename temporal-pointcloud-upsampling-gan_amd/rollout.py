@@ -11,6 +11,10 @@ Reference semantics, kept on purpose: the body is called as `net.body(feature, N
 neighbours in the 6-D feature space (this project's `SRNet.forward_with_context` differs there: INTEGRATION.md).
 
     python -m tpgan_amd.rollout --checkpoint X.ckpt --frames 'dir/data_{i}.npz' --count 800 [--in-feats 6] --out DIR
+        [--render PNGDIR --size 3 --width 768 --height 768 --mode pinhole --color depth --direction 0 0 -1]
+
+--render writes one picture per frame (render.SequenceRenderer) from each chunk's outputs while they are still on the
+device; the camera is fitted to the first chunk.
 """
 import argparse
 import os
@@ -18,7 +22,7 @@ import os
 import numpy as np
 import torch
 
-from . import ops
+from . import ops, render
 
 # Default chunk: this many low-resolution points per chunk (T = CHUNK_POINTS // N frames, 1 <= T <= MAX_CHUNK), from
 # tools/rollout_chunks.py on MI355X (profiles/rollout_chunks.txt, DESIGN.md "Sequence upsampling").
@@ -132,12 +136,15 @@ def main(argv=None):
     ap.add_argument("--chunk", type=int, default=None, help="frames per network call (default: by point count)")
     ap.add_argument("--out", required=True, help="output directory for pcd_{i}.npy")
     ap.add_argument("--device", default="cuda")
+    ap.add_argument("--render", default=None, metavar="PNGDIR", help="also write pcd_{i:04d}.png pictures there")
+    render.add_render_options(ap)
     a = ap.parse_args(argv)
     if "{i}" not in a.frames:
         ap.error("--frames must contain '{i}'")
     dev = torch.device(a.device)
     net = load_generator(a.checkpoint, a.in_feats, dev)
     os.makedirs(a.out, exist_ok=True)
+    pictures = render.renderer_from(a, a.render, dev) if a.render else None
     up = SequenceUpsampler(net, a.chunk)
     step = a.chunk
     i = 0
@@ -147,6 +154,9 @@ def main(argv=None):
         idx = range(i, min(i + step, a.count))
         feats, poss, cents, hs = load_frames(a.frames, idx, a.in_feats)
         outs = up.push(feats.to(dev), poss.to(dev))
+        if pictures is not None:    # the frames' own coordinates, as the .npy files below hold them
+            pictures.push([out[0] * float(hs[j - i]) + torch.from_numpy(cents[j - i]).to(dev)
+                           for j, out in zip(idx, outs)], i)
         for j, out in zip(idx, outs):
             pcd = out[0].cpu().numpy()
             pcd *= hs[j - i]

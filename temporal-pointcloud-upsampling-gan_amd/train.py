@@ -13,6 +13,12 @@ per --log_every iterations goes to stdout.  Checkpoints hold the reference's ten
 generator state and the numpy / torch RNG states, which make a resumed run repeat the uninterrupted one bit for bit.
 Under torch.distributed.run every rank samples its own clips (seed + 1000 * rank), gradients are averaged by
 ddp.GradSync and rank 0 writes the checkpoints.
+
+The test pass (train_tempo.py:259-297): under --samples N (or --dump_visualization = --samples 4) N clips of
+--test_dataset_path / --test_sequence_num are drawn once at start-up from a generator of their own, and whenever a
+checkpoint is written rank 0 upsamples them in eval mode, writes LOG/samples/{gt,input,pred}_iter:{n_iter}_{j}.png
+(render.py instead of the reference's Open3D window) and prints one JSON line with `test_cd` and `test_points`.  The
+pass touches no random stream of the training: a run with and a run without it write the same checkpoints, bit for bit.
 """
 import argparse
 import json
@@ -24,7 +30,7 @@ import numpy as np
 import torch
 
 from . import ddp
-from .data import ClipSampler, FluidSequences, prefetch
+from .data import ClipSampler, FluidSequences, held_out_fluid_clips, prefetch
 from .gan_step import tempo_gan_step
 from .set_abstraction import FluidSpatialDis, FluidTempoDis
 from .srnet import SRNet
@@ -59,7 +65,23 @@ def parse_args(argv=None):
     ap.add_argument("--log_every", type=int, default=100)
     ap.add_argument("--sample_num", type=int, default=None,
                     help="patch size (default, as the reference: 9216 if batch_size <= 4 and not --small_batch, else 4096)")
-    return ap.parse_args(argv)
+    # the test pass: held-out clips upsampled and rendered at every checkpoint (the reference's --dump_visualization)
+    ap.add_argument("--test_dataset_path", type=str, default="../../data/test_data_0.025_fine")
+    ap.add_argument("--test_sequence_num", type=int, default=4)
+    ap.add_argument("--dump_visualization", action="store_true", help="--samples 4, unless --samples is given")
+    add_sample_options(ap, default=None)
+    opt = ap.parse_args(argv)
+    if opt.samples is None:
+        opt.samples = 4 if opt.dump_visualization else 0
+    return opt
+
+
+def add_sample_options(ap, default=0):
+    ap.add_argument("--samples", type=int, default=default,
+                    help="held-out clips upsampled at every checkpoint: LOG/samples/{gt,input,pred}_iter:{n}_{j}.png and "
+                         "one JSON line with their Chamfer distances (0: off)")
+    ap.add_argument("--samples_width", type=int, default=512, help="width of the sample pictures")
+    ap.add_argument("--samples_height", type=int, default=512, help="height of the sample pictures")
 
 
 def _rng_state(device, sampler_state):
@@ -98,13 +120,58 @@ def load_checkpoint(path):
     return torch.load(path, map_location="cpu", weights_only=True)
 
 
-def run(opt, nets_of, sched_of, sampler_of, step):
+class HeldOutPass:
+    """The reference's test pass (train_tempo.py:259-297, train_msr.py:230-262) without a window: at every checkpoint
+    the SAME held-out clips -- `clips`, a list of dicts with `gt` (K,3), `input` (M,3) and `feature`, drawn once at
+    start-up -- are upsampled by `predict(sr_net, clip) -> (P,3)` in eval mode and written as
+    `{gt,input,pred}_iter:{n_iter}_{j}.png` into `sample_dir` (the reference's names): coloured by depth, one camera per
+    clip fitted to its ground truth, so that the three pictures of a clip and those of successive checkpoints compare;
+    splats of 3 pixels, 5 for the sparse input.  -> {"n_iter", "test_cd": Chamfer distance of prediction against ground
+    truth per clip (losses.chamfer_distance), "test_points": predicted points per clip}.
+
+    The pass draws no random number, runs on the current stream like the step (the prefetcher's hand-off is untouched)
+    and puts the generator back into the mode it found it in."""
+
+    def __init__(self, clips, predict, sample_dir, width, height, amp_dtype=None):
+        from . import render
+        self.clips, self.predict, self.sample_dir, self.amp_dtype = clips, predict, sample_dir, amp_dtype
+        self.cameras = [render.Camera.fit(c["gt"], width=width, height=height) for c in clips]
+        os.makedirs(sample_dir, exist_ok=True)
+        for j, (clip, cam) in enumerate(zip(clips, self.cameras)):           # what does not change is rendered once
+            clip["pictures"] = {"gt": render.render(clip["gt"], cam, size=3).cpu(),
+                                "input": render.render(clip["input"], cam, size=5).cpu()}
+
+    def __call__(self, sr_net, n_iter):
+        from . import render
+        from .gan_step import _autocast
+        from .losses import chamfer_distance
+        was_training = sr_net.training
+        sr_net.eval()
+        cds, counts = [], []
+        try:
+            with torch.no_grad():
+                for j, (clip, cam) in enumerate(zip(self.clips, self.cameras)):
+                    with _autocast(self.amp_dtype, clip["gt"].device):
+                        pred = self.predict(sr_net, clip).float().reshape(-1, 3).contiguous()
+                    cds.append(float(chamfer_distance(pred[None], clip["gt"][None])))
+                    counts.append(int(pred.shape[0]))
+                    pictures = dict(clip["pictures"], pred=render.render(pred, cam, size=3).cpu())
+                    for name, image in pictures.items():
+                        render.write_png(os.path.join(self.sample_dir, f"{name}_iter:{n_iter}_{j}.png"), image)
+        finally:
+            sr_net.train(was_training)
+        return {"n_iter": n_iter, "test_cd": cds, "test_points": counts}
+
+
+def run(opt, nets_of, sched_of, sampler_of, step, samples_of=None):
     """The training loop both trainers share (--seed, --device, --lr, --amp, --freeze_D, --iters, --resume,
-    --path_to_resume, --log_dir, --log_every and --ckpt_every of `opt`); what differs comes as four callables:
+    --path_to_resume, --log_dir, --log_every, --ckpt_every and --samples of `opt`); what differs comes as callables:
     nets_of(dev) -> (sr_net, tempo_dis, spatial_dis) on the device; sched_of(optimiser) -> its scheduler;
     sampler_of(dev, seed) -> the clip sampler, its `generator` seeded with `seed`;
     step((sr_net, tempo_dis, spatial_dis), (sr_optim, tempo_optim, spatial_optim), batch, n_iter, freeze_D, sync,
-    amp_dtype) -> the losses of one adversarial step; the last three go to the step function under those names."""
+    amp_dtype) -> the losses of one adversarial step; the last three go to the step function under those names;
+    samples_of(dev, generator, n) -> (the n held-out clips of `HeldOutPass`, drawn from `generator`, and its `predict`):
+    called once, on rank 0, and only under --samples n > 0; the pass then runs whenever a checkpoint is written."""
     rank, world, local = ddp.init_from_env(backend=os.environ.get("TPGAN_DDP_BACKEND"))
     dev = torch.device(opt.device)
     if dev.type == "cuda":
@@ -141,6 +208,14 @@ def run(opt, nets_of, sched_of, sampler_of, step):
     if rank == 0:
         os.makedirs(ckpt_dir, exist_ok=True)
     amp_dtype = torch.bfloat16 if opt.amp == "bf16" else None
+    held_out = None
+    if rank == 0 and getattr(opt, "samples", 0) > 0:
+        if samples_of is None:
+            raise ValueError("--samples needs the trainer's samples_of")
+        # before the prefetcher starts: its side stream waits for what the current stream has been given so far
+        clips, predict = samples_of(dev, torch.Generator().manual_seed(opt.seed), opt.samples)
+        held_out = HeldOutPass(clips, predict, os.path.join(opt.log_dir, "samples"), opt.samples_width,
+                               opt.samples_height, amp_dtype)
     batches = prefetch(sampler)
     for net in nets:
         net.train()
@@ -160,6 +235,8 @@ def run(opt, nets_of, sched_of, sampler_of, step):
                               **{k: float(v) for k, v in losses.items()}}), flush=True)
             window_start, window_iters = now, 0
         if rank == 0 and ((n_iter - 1) % opt.ckpt_every == 0 or n_iter >= opt.iters):
+            if held_out is not None:
+                print(json.dumps(held_out(nets[0], n_iter)), flush=True)
             state = {k: x.state_dict() for k, x in held.items()}
             state.update(n_iter=n_iter, tpgan_amd=_rng_state(dev, batches.resume_state))
             save_checkpoint({k: state[k] for k in CKPT_KEYS}, os.path.join(ckpt_dir, f"tpugan_checkpoint{n_iter}.ckpt"))
@@ -184,7 +261,12 @@ def main(argv=None):
         return tempo_gan_step(sr_net, spatial_dis, tempo_dis, low_pos, low_vel, high_pos, high_vel, 1., opt, n_iter,
                               *optims, freeze_D=freeze_D, sync=sync, amp_dtype=amp_dtype)
 
-    return run(opt, nets_of, lambda o: torch.optim.lr_scheduler.StepLR(o, 10000, gamma=0.7), sampler_of, step)
+    def samples_of(dev, generator, n):
+        clips = held_out_fluid_clips(opt.test_dataset_path, opt.test_sequence_num, opt.sequence_length, n, generator, dev,
+                                     use_vel=opt.use_vel and opt.in_node_feats == 6)
+        return clips, lambda sr_net, clip: sr_net(clip["feature"], clip["input"][None], hard_masking=True)[2]
+
+    return run(opt, nets_of, lambda o: torch.optim.lr_scheduler.StepLR(o, 10000, gamma=0.7), sampler_of, step, samples_of)
 
 
 if __name__ == "__main__":

@@ -10,19 +10,20 @@ The loop is the reference's: NoMaskSRNet(in, emb, upsample_ratio=16) + ActionTem
 2 x Adam(0.33 lr), StepLR(iters // 10, 0.72) x 3, the eager step gan_step.tempo_gan_step_no_mask, a checkpoint when
 (n_iter - 1) % ckpt_every == 0 or at the end.  The loop itself is train.run: optimisers, logging, the checkpoint's keys
 (the reference's ten plus `tpgan_amd`), the bit-exact --resume and the multi-process rules are written there once; this
-file says only what the action trainer's flags, networks, scheduler, sampler and step are.  --dump_visualization is
-accepted and ignored.
+file says only what the action trainer's flags, networks, scheduler, sampler, step and held-out clips are.
+--dump_visualization is accepted and ignored; the test pass it stood for (train_msr.py:230-262) is --samples N: the first
+frames of N clips of the test subjects under --data_dir, upsampled and rendered whenever a checkpoint is written.
 """
 import argparse
 import sys
 
 import torch
 
-from .data import ActionClipSampler, ActionSequences
+from .data import ActionClipSampler, ActionSequences, held_out_action_clips
 from .gan_step import tempo_gan_step_no_mask
 from .set_abstraction import ActionSpatialDis, ActionTempoDis
 from .srnet import NoMaskSRNet
-from .train import run
+from .train import add_sample_options, run
 
 
 def parse_args(argv=None):
@@ -40,13 +41,15 @@ def parse_args(argv=None):
     ap.add_argument("--R", type=float, default=2.0, help="radius of the temporal discriminator's flow embedding")
     ap.add_argument("--w", type=float, default=2.0, help="weight of the temporal loss")
     ap.add_argument("--freeze_D", action="store_true")
-    ap.add_argument("--dump_visualization", action="store_true", help="accepted for the reference's command lines; ignored")
+    ap.add_argument("--dump_visualization", action="store_true",
+                    help="accepted for the reference's command lines; ignored (the test pass is --samples N)")
     # not in the reference
     ap.add_argument("--seed", type=int, default=1)
     ap.add_argument("--amp", choices=("bf16", "none"), default="bf16")
     ap.add_argument("--device", type=str, default="cuda")
     ap.add_argument("--log_every", type=int, default=100)
     ap.add_argument("--num_points", type=int, default=2048, help="points per high-resolution frame (low: 1/16 of it)")
+    add_sample_options(ap)
     return ap.parse_args(argv)
 
 
@@ -67,8 +70,12 @@ def main(argv=None):
         return tempo_gan_step_no_mask(sr_net, spatial_dis, tempo_dis, low_pos, high_pos, opt, n_iter, *optims,
                                       freeze_D=freeze_D, sync=sync, amp_dtype=amp_dtype)
 
+    def samples_of(dev, generator, n):
+        clips = held_out_action_clips(opt.data_dir, n, generator, dev, opt.num_points)
+        return clips, lambda sr_net, clip: sr_net(clip["feature"], clip["feature"])[0]
+
     return run(opt, nets_of, lambda o: torch.optim.lr_scheduler.StepLR(o, max(opt.iters // 10, 1), gamma=0.72), sampler_of,
-               step)
+               step, samples_of)
 
 
 if __name__ == "__main__":
