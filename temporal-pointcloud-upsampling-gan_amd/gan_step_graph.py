@@ -42,7 +42,7 @@ import os
 import numpy as np
 import torch
 
-from .graph_conv import shadows, wgrad_side_stream
+from .graph_conv import shadows
 from .gan_step import _frozen, _autocast, _set_dummy_check, _NoSync, tempo_gan_step
 from .losses import tpugan_sr_loss
 from .set_abstraction import _plan_tensors, attach_plan_inverses, run_index_plan, sn_discard_prepared
@@ -124,7 +124,7 @@ def _rotation_matrix_np():
 
 class GraphedFluidStep:
     def __init__(self, sr_net, spatial_dis, tempo_dis, optims, opt, lowres_pos_lst, highres_pos_lst,
-                 furthest_distance=1.0, amp_dtype=None, sync=None, warmup=2, segmented=None):
+                 furthest_distance=1.0, amp_dtype=None, sync=None, warmup=2, segmented=None, defer_inverses=True):
         self.G, self.Ds, self.Dt = sr_net, spatial_dis, tempo_dis
         self.og, self.ot, self.os = optims
         for o in optims:
@@ -150,22 +150,11 @@ class GraphedFluidStep:
         # index-plan streams: [0] the temporal discriminator's clouds, [1] the spatial one's (real
         # clouds at the start of the step, fake ones as soon as the generator's forward is done)
         self.sides = [torch.cuda.Stream(dev) for _ in range(2)]
-        self.branch = torch.cuda.Stream(dev)       # the discriminators' updates
-        # the temporal update is the branch that finishes last (tools/ab_env.py TPGAN_WHATIF_SKIP=t: 12.9 -> 10.0 ms
-        # without it, 11.4 without the spatial one): TPGAN_BRANCH2_PRIO=-1 gives its stream the higher priority (A/B)
-        self.branch2 = torch.cuda.Stream(dev, priority=int(os.environ.get("TPGAN_BRANCH2_PRIO", "0")))
-        # round 3: two more parallel branches INSIDE the generator step -- the generator's mask head beside its
-        # upsampling head (srnet.SRNet.body), and the spatial discriminator's forward (hence backward) of the generator
-        # step beside the temporal one's.  TPGAN_GSTEP_BRANCHES=0: the serial form (A/B timing).
-        mode = os.environ.get("TPGAN_GSTEP_BRANCHES", "0")         # "heads", "dis", "1" = both, "0" = none
-        self.gstep_branches = mode in ("1", "dis")
-        self.aux = torch.cuda.Stream(dev)
-        self.aux2 = torch.cuda.Stream(dev)
-        if mode in ("1", "heads") and hasattr(sr_net, "filter_block"):
-            from .srnet import set_aux_stream
-            set_aux_stream(sr_net, self.aux)
-        self.defer_inverses = os.environ.get("TPGAN_DEFER_INVERSES", "1") != "0"
-        self.wgrad_side = os.environ.get("TPGAN_WGRAD_SIDE", "0") != "0"    # measured: 13.1 -> 14.5 ms with it (a cross-stream edge per weight costs ~40 us): off
+        self.branch = torch.cuda.Stream(dev)       # the spatial discriminator's update
+        # the temporal update is the branch that finishes last (tools/what_if.py skip_t: 12.9 -> 10.0 ms without it,
+        # 11.4 without the spatial one)
+        self.branch2 = torch.cuda.Stream(dev)
+        self.defer_inverses = defer_inverses       # False: inverted indices inside the update plans (`_update_plan`)
         self._keep = {}
         self._graphs = None
         self._capture(lowres_pos_lst, highres_pos_lst, warmup)
@@ -227,7 +216,7 @@ class GraphedFluidStep:
         # fake and real batch run as segments of ONE discriminator pass: one plan for both, put
         # together after the generator step's plan is out (same stream as the real batch's plan)
         # (their inverted indices -- read by the backward only -- are built BEHIND the event the update's forward waits
-        # for: `_update_plan`; TPGAN_DEFER_INVERSES=0 for the A/B: 12.52 -> 12.32 ms at cfg2.  The same for the generator
+        # for: `_update_plan`; `defer_inverses=False` for the A/B: 12.52 -> 12.32 ms at cfg2.  The same for the generator
         # step's own plans measured SLOWER, 12.62 -> 12.84: its backward then waits for the side streams once more)
         k["plan_s"], k["join_plan_s"] = self._update_plan(lambda: Ds.merge_plans([upd_s, k["plan_true_s"]]), self.sides[1])
         k["plan_t"], k["join_plan_t"] = self._update_plan(lambda: Dt.merge_plans([upd_t, k["plan_true_t"]]), self.sides[0])
@@ -262,30 +251,9 @@ class GraphedFluidStep:
         self.Ds.prepare_sn(1)
         self.Dt.prepare_sn(self.T, 1)
 
-    def _spatial_term(self, forward, join_plan, inputs, lab):
-        """The generator step's spatial-discriminator term (train_step_final.py:120-122), issued FIRST (the heads'
-        dropout draws keep the eager step's order) on its own stream when `gstep_branches`: it then runs -- forward
-        and backward -- beside the temporal discriminator's.  -> the loss tensor (`_join_spatial_term` before use)."""
-        if not self.gstep_branches:
-            join_plan()
-            return (0.5 * (forward().float() - lab[2]) ** 2).mean()
-        main = torch.cuda.current_stream(self.dev)
-        self.aux2.wait_stream(main)
-        with torch.cuda.stream(self.aux2):
-            join_plan()
-            for t in inputs:
-                t.record_stream(self.aux2)
-            loss = (0.5 * (forward().float() - lab[2]) ** 2).mean()
-        return loss
-
-    def _join_spatial_term(self, loss):
-        if self.gstep_branches:
-            torch.cuda.current_stream(self.dev).wait_stream(self.aux2)
-            loss.record_stream(torch.cuda.current_stream(self.dev))
-
     def _join_sides(self, stream=None):
         stream = stream or torch.cuda.current_stream(self.dev)
-        for sd in self.sides + [self.aux, self.aux2]:
+        for sd in self.sides:
             stream.wait_stream(sd)
 
     def _seg_generator(self, update_D):
@@ -339,11 +307,12 @@ class GraphedFluidStep:
             # this stream is about to wait ~0.5 ms for the index plans: the power iterations of the
             # two forwards below (they depend on the weights alone) fill the gap
             self._prepare_sn_in_gap()
-            spatial_loss = self._spatial_term(lambda: Ds(fake_s_in, plan=plan_fs), join_fs, [fake_s_in] + _plan_tensors(plan_fs), lab)
+            # the spatial term (train_step_final.py:120-122) first: the heads' dropout draws keep the eager step's order
+            join_fs()
+            spatial_loss = (0.5 * (Ds(fake_s_in, plan=plan_fs).float() - lab[2]) ** 2).mean()
             join_ft()
             fake = Dt.forward_passes([fake_t_in], opt.R, plan=plan_ft)[0]
             tempo_loss = (0.5 * (fake.float() - lab[3]) ** 2).mean()
-            self._join_spatial_term(spatial_loss)
         sr_loss = tempo_loss + spatial_loss + opt.w * position_loss
         k.update(tempo_loss=tempo_loss.detach(), spatial_loss=spatial_loss.detach(), cd=cd.detach(), ml=ml.detach())
         self.viol.copy_(viol.float().reshape(1))
@@ -381,7 +350,7 @@ class GraphedFluidStep:
 
     def _grads_body(self, update_D):
         sr_loss = self._seg_generator(update_D)
-        k, lab = self._keep, self.lab
+        k = self._keep
         main = torch.cuda.current_stream(self.dev)
         if update_D:
             self.branch.wait_stream(main)
@@ -393,38 +362,37 @@ class GraphedFluidStep:
             # issue order = the eager step's (and the reference's, train_step_final.py:171-214): the
             # temporal update first.  The streams decide what runs where; the ISSUE order decides
             # which Philox offsets the heads' dropout draws get inside a captured graph.
-            def update(dis, optim, branch, passes, plan, key, **kw):
-                with torch.cuda.stream(branch):
-                    for t in [x for p in passes for x in (p if isinstance(p, list) else [p])] + [lab] + _plan_tensors(plan):
-                        t.record_stream(branch)
-                    with _autocast(self.amp, self.dev):
-                        fake, true = dis.forward_passes(passes, *kw.get("args", ()), plan=plan)
-                    loss = (0.5 * ((true.float() - lab[0]) ** 2 + (fake.float() - lab[1]) ** 2)).mean()
-                    optim.zero_grad(set_to_none=True)
-                    branch.wait_stream(kw["side"])          # the plan's inverted indices (built behind its lists)
-                    loss.backward()
-                    k[key] = loss.detach()
-                    k[key].record_stream(main)
-            skip = os.environ.get("TPGAN_WHATIF_SKIP", "")        # timing aid (tools/ab_env.py): leave an update out
-            if skip:
-                k["tempo_dis_loss"] = k["spatial_dis_loss"] = torch.zeros((), device=self.dev)
-            if "t" not in skip:
-                update(self.Dt, self.ot, self.branch2, [k["fakes"], k["trues"]], k["plan_t"], "tempo_dis_loss", args=(self.opt.R,),
-                       side=self.sides[0])
-            if "s" not in skip:
-                update(self.Ds, self.os, self.branch, [k["fake_s"], k["true_s"]], k["plan_s"], "spatial_dis_loss", side=self.sides[1])
+            self._update(self.Dt, self.ot, self.branch2, [k["fakes"], k["trues"]], k["plan_t"], "tempo_dis_loss",
+                         side=self.sides[0], args=(self.opt.R,))
+            self._update(self.Ds, self.os, self.branch, [k["fake_s"], k["true_s"]], k["plan_s"], "spatial_dis_loss",
+                         side=self.sides[1])
         else:
             k["tempo_dis_loss"] = torch.zeros((), device=self.dev)
             k["spatial_dis_loss"] = torch.zeros((), device=self.dev)
         self.og.zero_grad(set_to_none=True)
-        # the generator's weight gradients leave its backward chain: computed on an index-plan stream (idle by now) as
-        # parallel leaves of the graph (graph_conv.wgrad_side_stream); the join below orders them before the optimizers
-        with wgrad_side_stream(main, self.sides[0] if self.wgrad_side else None):
-            sr_loss.backward()
+        sr_loss.backward()
         self._join_sides(main)                     # every branch rejoins (required inside a capture)
         if update_D:
             main.wait_stream(self.branch)
             main.wait_stream(self.branch2)
+
+    def _update(self, dis, optim, branch, passes, plan, key, side, args=()):
+        """Forward and backward of one discriminator update on `branch` (fake and real batch as segments of one pass
+        under `plan`, whose inverted indices `side` builds); the loss goes to self._keep[key].  The optimizer step
+        comes in `_phase_apply`."""
+        k, lab = self._keep, self.lab
+        main = torch.cuda.current_stream(self.dev)
+        with torch.cuda.stream(branch):
+            for t in [x for p in passes for x in (p if isinstance(p, list) else [p])] + [lab] + _plan_tensors(plan):
+                t.record_stream(branch)
+            with _autocast(self.amp, self.dev):
+                fake, true = dis.forward_passes(passes, *args, plan=plan)
+            loss = (0.5 * ((true.float() - lab[0]) ** 2 + (fake.float() - lab[1]) ** 2)).mean()
+            optim.zero_grad(set_to_none=True)
+            branch.wait_stream(side)                # the plan's inverted indices (built behind its lists)
+            loss.backward()
+            k[key] = loss.detach()
+            k[key].record_stream(main)
 
     def _phase_apply(self, update_D):
         """The three optimizer steps and the loss report."""
@@ -531,7 +499,7 @@ class GraphedFluidStep:
                     except BaseException:
                         # leave the capture joinable: an unjoined side stream turns the original
                         # error into "capturing stream has unjoined work" and poisons the stream
-                        self._join_sides()                   # (index-plan streams and the generator step's branches)
+                        self._join_sides()                   # (the index-plan streams)
                         torch.cuda.current_stream(self.dev).wait_stream(self.branch)
                         torch.cuda.current_stream(self.dev).wait_stream(self.branch2)
                         raise
@@ -698,11 +666,11 @@ class GraphedActionStep(GraphedFluidStep):
                 lambda: [p.detach() for p in pred_lst])
             position_loss, cd, _ = tpugan_sr_loss(0, high[1], pred_c, 0., 0., 0., 0)
             self._prepare_sn_in_gap()
-            spatial_loss = self._spatial_term(lambda: Ds(fake_s_in, plan=plan_fs), join_fs, [fake_s_in] + _plan_tensors(plan_fs), lab)
+            join_fs()                          # (the spatial term first: the eager step's order of dropout draws)
+            spatial_loss = (0.5 * (Ds(fake_s_in, plan=plan_fs).float() - lab[2]) ** 2).mean()
             join_ft()
             fake = Dt.forward_passes([pred_lst], opt.R, plan=plan_ft)[0]
             tempo_loss = (0.5 * (fake.float() - lab[3]) ** 2).mean()
-            self._join_spatial_term(spatial_loss)
         sr_loss = tempo_loss + spatial_loss + opt.w * position_loss
         k.update(tempo_loss=tempo_loss.detach(), spatial_loss=spatial_loss.detach(), cd=cd.detach(),
                  ml=torch.zeros((), device=self.dev))

@@ -20,7 +20,6 @@ Layers with batch/instance norm or spectral norm keep the reference order
 (`_forward_planes`); the generator never builds those.
 """
 import contextlib
-import os
 from typing import List
 
 import torch
@@ -160,43 +159,6 @@ class shadows:
         return False
 
 
-# Weight gradients beside the chain.  Nothing downstream of a backward pass waits for dW before the optimizer,
-# but on ONE stream its launches (split-K product + sum of the partials, bias sum) sit between two data-gradient
-# launches of a latency-bound chain.  A step that owns a spare stream registers it here for the stream its
-# backward runs on (gan_step_graph: an index-plan stream, idle by then); the weight-gradient launches go there --
-# parallel leaves of the captured graph -- and the step joins that stream before its optimizers run.
-_WGRAD_SIDE = {}
-
-
-@contextlib.contextmanager
-def wgrad_side_stream(main, side):
-    """Inside: `_TallLinear*` backward passes running on stream `main` compute dW / db on `side`.  The caller makes
-    `main` (or whatever reads the gradients) wait for `side` afterwards."""
-    if side is None:
-        yield
-        return
-    _WGRAD_SIDE[main.cuda_stream] = side
-    try:
-        yield
-    finally:
-        _WGRAD_SIDE.pop(main.cuda_stream, None)
-
-
-def _wgrad_ctx(*reads):
-    """Context for the weight-gradient launches of a backward pass: the registered side stream (ordered behind
-    everything the current stream has issued, `reads` kept alive for it) or nothing."""
-    if not _WGRAD_SIDE or not reads[0].is_cuda:
-        return contextlib.nullcontext()
-    cur = torch.cuda.current_stream(reads[0].device)
-    side = _WGRAD_SIDE.get(cur.cuda_stream)
-    if side is None:
-        return contextlib.nullcontext()
-    side.wait_stream(cur)
-    for t in reads:
-        t.record_stream(side)
-    return torch.cuda.stream(side)
-
-
 class _TallLinear(torch.autograd.Function):
     """y = x @ W^T for TALL x (P rows >> C): same forward GEMM as F.linear, but the weight
     gradient dW = gy^T x -- a (Cout x Cin) output with K = P up to 2.6e5 -- is computed as a
@@ -225,11 +187,10 @@ class _TallLinear(torch.autograd.Function):
         P, cin, cout, e = xd.shape[0], xd.shape[1], wd.shape[0], xd.element_size()
         if ctx.needs_input_grad[0]:
             dx = ops.timed("gemm_dgrad", e * P * (cin + cout), 2 * P * cin * cout, gy, lambda: gy @ wd).to(ctx.x_dtype)
-        with _wgrad_ctx(gy, xd):
-            if ctx.needs_input_grad[1]:
-                dw = _tall_wgrad(gy, xd).to(ctx.w_dtype)
-            if ctx.b_dtype is not None and ctx.needs_input_grad[2]:
-                db = gy.sum(0, dtype=torch.float32).to(ctx.b_dtype)
+        if ctx.needs_input_grad[1]:
+            dw = _tall_wgrad(gy, xd).to(ctx.w_dtype)
+        if ctx.b_dtype is not None and ctx.needs_input_grad[2]:
+            db = gy.sum(0, dtype=torch.float32).to(ctx.b_dtype)
         return dx, dw, db, None
 
 
@@ -296,17 +257,16 @@ class _TallLinearSeg(torch.autograd.Function):
             dx = ops.timed("gemm_dgrad", e * nseg * P * (cin + cout), 2 * nseg * P * cin * cout, gy,
                            lambda: torch.bmm(gy, wd)).view(nseg * P, cin).to(ctx.x_dtype)
         if ctx.needs_input_grad[1]:
-            with _wgrad_ctx(gy, xd):
-                S = _split_k(P, cout, cin)
-                rows = P // S
-                head = S * rows
-                part = ops.timed("gemm_wgrad", e * nseg * P * (cin + cout), 2 * nseg * P * cin * cout, gy,
-                                 lambda: _mm_f32(torch.bmm, gy[:, :head].reshape(nseg * S, rows, cout).transpose(1, 2),
-                                                 xd[:, :head].reshape(nseg * S, rows, cin)))
-                dw = part.view(nseg, S, cout, cin).sum(1) if S > 1 else part.view(nseg, cout, cin)
-                if head < P:
-                    dw = dw + _mm_f32(torch.bmm, gy[:, head:].transpose(1, 2), xd[:, head:])
-                dw = dw.to(ctx.w_dtype)
+            S = _split_k(P, cout, cin)
+            rows = P // S
+            head = S * rows
+            part = ops.timed("gemm_wgrad", e * nseg * P * (cin + cout), 2 * nseg * P * cin * cout, gy,
+                             lambda: _mm_f32(torch.bmm, gy[:, :head].reshape(nseg * S, rows, cout).transpose(1, 2),
+                                             xd[:, :head].reshape(nseg * S, rows, cin)))
+            dw = part.view(nseg, S, cout, cin).sum(1) if S > 1 else part.view(nseg, cout, cin)
+            if head < P:
+                dw = dw + _mm_f32(torch.bmm, gy[:, head:].transpose(1, 2), xd[:, head:])
+            dw = dw.to(ctx.w_dtype)
         return dx, dw, None
 
 
@@ -319,9 +279,6 @@ def _stacked_weight(we, wn):
             and we.untyped_storage().data_ptr() == wn.untyped_storage().data_ptr()):
         return we.as_strided((2 * we.shape[0], we.shape[1]), (we.shape[1], 1), we.storage_offset())
     return torch.cat([we, wn], 0)
-
-
-EDGE_FRONT = [os.environ.get("TPGAN_EDGE_FRONT", "1") != "0"]     # EdgeConv front end on one product (off: two GEMMs + LeakyReLU + ops.row_combine, for A/B runs)
 
 
 class _EdgeFront(torch.autograd.Function):
@@ -356,8 +313,7 @@ class _EdgeFront(torch.autograd.Function):
         if ctx.needs_input_grad[0]:
             dx = ops.timed("gemm_dgrad", 4 * P * (cin + 2 * H), 4 * P * cin * H, gY, lambda: gY @ wc).view(B, N, cin)
         if ctx.needs_input_grad[1] or ctx.needs_input_grad[2]:
-            with _wgrad_ctx(gY, xr):
-                dw = _tall_wgrad(gY, xr)
+            dw = _tall_wgrad(gY, xr)
             dwe, dwn = dw[:H], dw[H:]
         return dx, dwe, dwn, None, None, None, None
 
@@ -547,7 +503,7 @@ class EdgeConv(nn.Module):
             idx = self.dilated_knn_graph(pos if pos is not None else x).to(torch.int32).contiguous()
         na, ea = self.node_affine[0], self.edge_affine[0]
         H = na.out_channels
-        if (EDGE_FRONT[0] and na.bias is None and ea.bias is None and H == ea.out_channels
+        if (na.bias is None and ea.bias is None and H == ea.out_channels
                 and H % (4 if amp_dtype(x) == torch.float32 else 8) == 0):
             with no_autocast(x):                                         # one product for both terms (_EdgeFront)
                 h = edge_front(x.float(), ea.weight.view(H, -1), na.weight.view(H, -1), idx, 0.2, 0.2, amp_dtype(x))

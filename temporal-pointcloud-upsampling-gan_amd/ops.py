@@ -981,9 +981,9 @@ class HipBackend:
         return dw
 
 
-# spectral norm of a forward's weights with every weight's rows split over several workgroups (TPGAN_SN_SPLIT=0: the
-# one-workgroup-per-weight kernel, for A/B runs)
-SN_SPLIT = [os.environ.get("TPGAN_SN_SPLIT", "1") != "0"]
+# spectral norm of a forward's weights with every weight's rows split over several workgroups (False: the
+# one-workgroup-per-weight kernel; set by tests and tools/tune_sn.py)
+SN_SPLIT = [True]
 
 
 def sn_multi_stride(R, Cn):
@@ -1856,7 +1856,7 @@ class _RowsumSlots(dict):
 
 
 _ROWSUM_SLOT = _RowsumSlots()
-_ROWSUM_HANDOFF = [os.environ.get("TPG_ROWSUM_HANDOFF", "1") != "0"]
+_ROWSUM_HANDOFF = [True]
 
 
 def set_rowsum_handoff(flag):

@@ -20,7 +20,6 @@ weight, same single power iteration per call) is applied to the N un-grouped row
 BatchNorm over the (B*S*ns) row axis -- the same statistics as BatchNorm2d over (B,S,ns).
 """
 import contextlib
-import os
 from typing import List
 
 import numpy as np
@@ -847,7 +846,6 @@ def _head(dims, drops):
     return nn.Sequential(*layers)
 
 
-FUSED_HEAD = [os.environ.get("TPGAN_FUSED_HEAD", "1") != "0"]     # off: PyTorch's BatchNorm1d / LeakyReLU / Dropout (A/B runs)
 _ONES = {}
 
 
@@ -872,7 +870,7 @@ def _head_fp32(fc_layers, x):
             m = mods[i]
             if isinstance(m, nn.Linear):
                 x = rows_matmul(x, sn_weight(m), m.bias)
-            elif (FUSED_HEAD[0] and isinstance(m, nn.BatchNorm1d) and m.training and m.momentum is not None
+            elif (isinstance(m, nn.BatchNorm1d) and m.training and m.momentum is not None
                   and m.track_running_stats and x.dim() == 2 and x.shape[0] > 1 and i + 1 < len(mods)
                   and isinstance(mods[i + 1], nn.LeakyReLU)):
                 # BatchNorm1d -> LeakyReLU [-> Dropout] in ONE launch each way (ops.head_bn_act, csrc/head.hip); the

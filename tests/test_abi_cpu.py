@@ -65,6 +65,17 @@ def test_product_package_never_imports_the_oracle():
         assert not re.search(r"^\s*(from|import)\s+oracle\b", src, flags=re.M), path
 
 
+def test_module_switches_do_not_start_from_the_environment():
+    """The programmatic switches start at their shipped values whatever the shell holds: variables that once chose their
+    initial value (or a module flag that is gone) change nothing in a fresh interpreter."""
+    code = ("import sys; sys.path.insert(0, %r); import tpgan_amd, tpgan_amd.ops as ops; "
+            "from tpgan_amd import graph_conv, set_abstraction; "
+            "assert ops.SN_SPLIT == [True], ops.SN_SPLIT; "
+            "assert ops._ROWSUM_HANDOFF == [True], ops._ROWSUM_HANDOFF") % ROOT
+    env = dict(os.environ, TPGAN_SN_SPLIT="0", TPG_ROWSUM_HANDOFF="0", TPGAN_FUSED_HEAD="0", TPGAN_EDGE_FRONT="0")
+    subprocess.check_call([sys.executable, "-c", code], env=env)
+
+
 def test_validation_errors_match_upstream_style(oracle_cpu):
     import tpgan_amd.ops as ops
     f = torch.zeros(1, 2, 8)

@@ -227,7 +227,8 @@ def test_inverted_indices_behind_their_lists_change_nothing(monkeypatch):
     ops.deferred_inverses): the same index, read by the backward only, so a replayed step with the deferral equals the
     step without it bit for bit in the discriminators (losses, parameters, BatchNorm / spectral-norm state); a missing
     wait in front of the backward would show as stale or garbage gradients.  The generator is held to 1e-6 like in
-    test_replay_is_bitwise_its_own_body_launched_eagerly (library GEMM split-K)."""
+    test_replay_is_bitwise_its_own_body_launched_eagerly (library GEMM split-K).  The choice is the constructor's
+    `defer_inverses`; the environment selects nothing in a stepper."""
     from tpgan_amd.gan_step_graph import GraphedFluidStep
     from tpgan_amd.synthetic import fluid_clip
     dev = torch.device("cuda", 0)
@@ -235,10 +236,15 @@ def test_inverted_indices_behind_their_lists_change_nothing(monkeypatch):
     Bm = copy.deepcopy(A)
     oa, ob = _optims(*A), _optims(*Bm)
     clips = [fluid_clip(4, 1024, 8, 3, seed=s, device=dev) for s in (1, 2)]
-    monkeypatch.setenv("TPGAN_DEFER_INVERSES", "1")
-    sa = GraphedFluidStep(A[0], A[1], A[2], oa, OPT, clips[0][0], clips[0][1], 1.0, None, None)
-    monkeypatch.setenv("TPGAN_DEFER_INVERSES", "0")
-    sb = GraphedFluidStep(Bm[0], Bm[1], Bm[2], ob, OPT, clips[0][0], clips[0][1], 1.0, None, None)
+    # a stepper reads none of the environment switches the step once had: `sa` is captured with all of them set
+    removed = {"TPGAN_WHATIF_SKIP": "ts", "TPGAN_WGRAD_SIDE": "1", "TPGAN_GSTEP_BRANCHES": "1", "TPGAN_BRANCH2_PRIO": "-1",
+               "TPGAN_DEFER_INVERSES": "0"}
+    for name, value in removed.items():
+        monkeypatch.setenv(name, value)
+    sa = GraphedFluidStep(A[0], A[1], A[2], oa, OPT, clips[0][0], clips[0][1], 1.0, None, None, defer_inverses=True)
+    for name in removed:
+        monkeypatch.delenv(name)
+    sb = GraphedFluidStep(Bm[0], Bm[1], Bm[2], ob, OPT, clips[0][0], clips[0][1], 1.0, None, None, defer_inverses=False)
     assert sa.defer_inverses and not sb.defer_inverses
     init_g = [p.detach().clone() for p in A[0].parameters()]
     np.random.seed(7); torch.manual_seed(7)
