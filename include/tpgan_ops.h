@@ -131,7 +131,9 @@ int tpg_gather_bwd_f32(const float *gout, const int32_t *idx, int B, int C, int 
 
 /* gather_operation on channels-last rows (the layout this build keeps clouds in): out[b,s,:] = rows[b,idx[b,s],:];
  * rows (B,N,C), idx (B,S) int32, out (B,S,C).  Same semantics as tpg_gather_fwd_f32 / _bwd_f32 on the transposed
- * tensors (discriminator.py:131-137), without the two transpose copies around it. */
+ * tensors (discriminator.py:131-137), without the two transpose copies around it.  The backward overwrites grows
+ * (B,N,C): a row named by several slots (FPS repeats a pick once a cloud runs out of candidates) gets 0.0f plus their
+ * gradients in ascending slot order, each addition rounded -- no float atomics, the same bits from run to run. */
 int tpg_gather_rows_fwd_f32(const float *rows, const int32_t *idx, int B, int N, int S, int C, float *out, void *stream);
 int tpg_gather_rows_bwd_f32(const float *gout, const int32_t *idx, int B, int N, int S, int C, float *grows,
                             void *stream);
@@ -650,6 +652,33 @@ int tpg_frame_subset(const int32_t *count, const uint64_t *seed, int F, int K, i
 int tpg_action_gather_f32(const float *points, long long P, const int32_t *frame_first, const int32_t *count,
                           const int32_t *idx, const double *scale, int mode, int T, int B, int K, float *high,
                           float *centre, void *stream);
+
+/* ---- dummy-centre replacement on the device (csrc/dummy_centres.hip) --------------------------------------------
+ * discriminator.py:115-130: FPS picks that landed on a 999-padded point are swapped for other points of the cloud.  The
+ * reference finds them on the host and draws with np.random.choice; this entry does the same job with no host
+ * involvement, so a captured step can replay it.  xyz (B,N,3) f32; centres (B,S) int32 (entries are clamped into the
+ * cloud; S > N is what FPS gives for a cloud smaller than npoint, with repeated picks); draw_key: 2 int64 words ON THE DEVICE, [seed, n_iter], read by the kernel; site >= 0: the ordinal of the
+ * call within a step, a launch argument.  out (B,S) int32, not centres itself.  For cloud b, all integer:
+ *     hit[s] = fabsf(xyz[b, centres[b,s], 0] - 999.0f) < 1e-4f;  k = the number of hits
+ *     k == 0:     out[b] = centres[b]; prefix_flag[b] is left alone
+ *     pool      = every j in [0,N) that is not a hit SLOT POSITION (j < S && hit[j]) -- the reference's quirk: slot
+ *                 positions are excluded, not point ids, so a pick may itself be a dummy; N - k members while S <= N
+ *     pool < k:   (the reference's choice() raises; N - k < k while S <= N) out[b] = centres[b], *short_flag = 1
+ *     otherwise:  out[b] = the surviving centres in slot order, then the k pool members smallest in (key(j), j),
+ *                 ascending; prefix_flag[b] = 0 (the centres are no longer in pick order: the level after must not take
+ *                 tpg_fps_prefix_f32's shortcut)
+ * key(j) is tpg_frame_subset's, with mix as stated there and a seed per cloud, uint32 arithmetic, wrapping:
+ *     seed_lo = mix( lo32(seed) ^ mix(lo32(n_iter) * 0x9E3779B1 + site) )
+ *     seed_hi = mix( hi32(seed) ^ mix(b * 0x85EBCA6B + site) )                  (b: the cloud's index within the call)
+ *     key(j)  = mix( mix(j * 0x9E3779B1 + seed_lo) ^ seed_hi )
+ * short_flag (1) int32 is zeroed by the call and set if any cloud was short; prefix_flag (B) int32 or NULL.
+ * A pure function of its inputs: bit-identical from run to run (integer LDS atomics and a sort of unique keys only).
+ * One workgroup per cloud; a cloud without a hit costs one gather of S rows.  No workspace.
+ * Negative B, N, S or site: TPG_ERR_ARG.  B == 0 or S == 0: TPG_OK, nothing written.  Then N == 0, a NULL xyz, centres,
+ * draw_key, out or short_flag, out == centres: TPG_ERR_ARG; S > tpg_patch_select_max_k(): TPG_ERR_UNSUPPORTED.  All of
+ * it is decided before anything is launched. */
+int tpg_replace_dummy_centres(const float *xyz, const int32_t *centres, const int64_t *draw_key, int site, int B, int N,
+                              int S, int32_t *out, int32_t *prefix_flag, int32_t *short_flag, void *stream);
 
 /* ---- point-cloud pictures (csrc/render.hip) --------------------------------------------------------------------
  * A z-buffered square splat of F clouds, one picture each (the reference looks at its results through an Open3D

@@ -77,6 +77,7 @@ SIGNATURES = {
     "tpg_clip_gather_low_f32": [_P, _P, _P, _F, _P, _L, _P, _P, _I, _I, _I, _I, _P, _P, _P],
     "tpg_frame_subset": [_P, _P, _I, _I, _P, _P],
     "tpg_action_gather_f32": [_P, _L, _P, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P],
+    "tpg_replace_dummy_centres": [_P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P],
     "tpg_emd_init_f32": [_P, _I, _I, _I, _I, _P, _P, _P],
     "tpg_emd_rounds_f32": [_P, _I, _I, _F, _F, _I, _I, _I, _I, _I, _P, _P, _P],
     "tpg_emd_finish_f32": [_P, _I, _I, _P, _P, _P, _P, _P, _P],

@@ -13,10 +13,10 @@
 // ONE workgroup per frame does the whole selection: a depth frame has 10^3..10^5 points and a key costs a dozen integer
 // instructions, so the frame's keys are simply recomputed in each of the four passes (three 11 + 11 + 10-bit histogram
 // passes of a radix select in LDS for the ksel-th smallest key, one pass that collects the keys up to it) and the
-// survivors are ordered by a bitonic sort in LDS, as sel_sort_kernel orders a patch (digits, block scan and sort are
-// tpg_select.hpp's, shared with clip_sample.hip; the two-bin resolve is written out here).  LDS atomics on integers
-// and a sort of unique keys only: the result is a pure function of (count, seed, K), and nothing but idx is written to
-// memory.
+// survivors are ordered by a bitonic sort in LDS, as sel_sort_kernel orders a patch (key, digits, block scan and sort
+// are tpg_select.hpp's, shared with clip_sample.hip and dummy_centres.hip; the two-bin resolve is written out here).
+// LDS atomics on integers and a sort of unique keys only: the result is a pure function of (count, seed, K), and nothing
+// but idx is written to memory.
 //
 // tpg_action_gather_f32: all high-resolution clouds of the batch and their centroid in one launch, one workgroup per
 // frame.  The centroid is an fp64 sum in a FIXED order (thread t adds rows t, t + 256, ... in that order; the 256
@@ -36,18 +36,6 @@ struct FsFrames {                                        // host arrays of one g
     unsigned seed_lo[FS_GROUP], seed_hi[FS_GROUP];
 };
 
-__host__ __device__ inline unsigned fs_mix(unsigned h) {
-    h ^= h >> 16;
-    h *= 0x7FEB352Du;
-    h ^= h >> 15;
-    h *= 0x846CA68Bu;
-    h ^= h >> 16;
-    return h;
-}
-__host__ __device__ inline unsigned fs_key(unsigned j, unsigned seed_lo, unsigned seed_hi) {
-    return fs_mix(fs_mix(j * 0x9E3779B1u + seed_lo) ^ seed_hi);
-}
-
 // Points of the frame selected by the K % n (n <= K) or K (n > K) smallest keys.
 __host__ __device__ inline int fs_selected(int n, int K) { return n > K ? K : K % n; }
 
@@ -59,7 +47,7 @@ __device__ __forceinline__ void fs_digit(int n, unsigned lo, unsigned hi, unsign
     for (int i = t; i < TPG_SEL_BINS; i += FS_THREADS) h[i] = 0;
     __syncthreads();
     for (int j = t; j < n; j += FS_THREADS) {
-        const unsigned key = fs_key((unsigned)j, lo, hi);
+        const unsigned key = tpg_subset_key((unsigned)j, lo, hi);
         if (tpg_sel_matches<PASS>(key, *prefix)) atomicAdd(&h[tpg_sel_digit<PASS>(key)], 1u);
     }
     __syncthreads();
@@ -104,7 +92,7 @@ __global__ __launch_bounds__(FS_THREADS) void frame_subset_kernel(FsFrames fr, i
     for (int i = t; i < n2; i += FS_THREADS) fs_keys[i] = ~0ull;
     __syncthreads();
     for (int j = t; j < n; j += FS_THREADS) {
-        const unsigned key = fs_key((unsigned)j, lo, hi);
+        const unsigned key = tpg_subset_key((unsigned)j, lo, hi);
         if (key <= kth) {
             const unsigned slot = atomicAdd(&s_out[2], 1u);              // any slot: the sort below fixes the order
             if (slot < (unsigned)n2) fs_keys[slot] = ((tpg_u64)key << 32) | (unsigned)j;

@@ -198,16 +198,34 @@ __global__ __launch_bounds__(256) void gather_rows_fwd_kernel(const float *__res
     out[t] = rows[((size_t)b * N + n) * C + c];
 }
 
+// Backward of the rows gather without float atomics: FPS repeats a pick once a cloud runs out of candidates (a cloud of
+// npoint points of which the sampler skips some, |x|^2 <= 1e-3), so a row can be named by several slots, and
+// three or more addends landing in an order that changes from run to run change the sum's last bits.  One thread per
+// slot: the FIRST slot that names a row adds, in slot order, every slot that names it; rows no slot names keep the zero of
+// the memset in front.  0.0f + x first, as the sum into a zeroed row always began.
 __global__ __launch_bounds__(256) void gather_rows_bwd_kernel(const float *__restrict__ gout,
                                                               const int32_t *__restrict__ idx, int N, int S, int C,
-                                                              float *__restrict__ grows, long long total) {
+                                                              float *__restrict__ grows, long long slots) {
     const long long t = (long long)blockIdx.x * 256 + threadIdx.x;
-    if (t >= total) return;
-    const long long bs = t / C;
-    const int c = (int)(t - bs * C);
-    const long long b = bs / S;
-    const int n = tpg_clamp_idx(idx[bs], N);
-    atomicAdd(grows + ((size_t)b * N + n) * C + c, gout[t]);
+    if (t >= slots) return;
+    const long long b = t / S;
+    const int s = (int)(t - b * S);
+    const int32_t *row = idx + b * S;
+    const int n = tpg_clamp_idx(row[s], N);
+    // (both scans without a branch on the loaded index: the loads of a row then overlap instead of waiting one by one)
+    int earlier = 0, later = 0;
+    for (int e = 0; e < s; ++e) earlier |= tpg_clamp_idx(row[e], N) == n ? 1 : 0;
+    if (earlier) return;                                               // an earlier slot owns this row
+    float *dst = grows + ((size_t)b * N + n) * C;
+    const float *src = gout + (size_t)t * C;
+    for (int c = 0; c < C; ++c) dst[c] = 0.0f + src[c];
+    for (int e = s + 1; e < S; ++e) later |= tpg_clamp_idx(row[e], N) == n ? 1 : 0;
+    if (!later) return;
+    for (int e = s + 1; e < S; ++e) {
+        if (tpg_clamp_idx(row[e], N) != n) continue;
+        const float *more = gout + ((size_t)b * S + e) * C;
+        for (int c = 0; c < C; ++c) dst[c] += more[c];
+    }
 }
 
 bool grid_ok(long long x, long long y, long long z) {
@@ -339,9 +357,9 @@ extern "C" int tpg_gather_rows_bwd_f32(const float *gout, const int32_t *idx, in
     const long long total = (long long)B * S * C;
     if (total == 0) return TPG_OK;
     if (!gout || !idx) return TPG_ERR_ARG;
-    const long long gx = (total + 255) / 256;
+    const long long slots = (long long)B * S, gx = (slots + 255) / 256;
     if (!grid_ok(gx, 1, 1)) return TPG_ERR_ARG;
-    hipLaunchKernelGGL(gather_rows_bwd_kernel, dim3((unsigned)gx), dim3(256), 0, st, gout, idx, N, S, C, grows, total);
+    hipLaunchKernelGGL(gather_rows_bwd_kernel, dim3((unsigned)gx), dim3(256), 0, st, gout, idx, N, S, C, grows, slots);
     TPG_RETURN_IF_LAUNCH_FAILED();
     return TPG_OK;
 }

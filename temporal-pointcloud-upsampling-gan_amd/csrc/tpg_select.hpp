@@ -1,5 +1,6 @@
-// What the two clip samplers (clip_sample.hip, action_sample.hip) share: the radix select of the k-th smallest 32-bit
-// key, the LDS sort of the survivors, and the per-launch tables of a group of clips.
+// What the two clip samplers (clip_sample.hip, action_sample.hip) and dummy_centres.hip share: the subset key, the
+// radix select of the k-th smallest 32-bit key, the LDS sort of the survivors, and the per-launch tables of a group of
+// clips.
 //
 // ONE definition of "the k-th smallest key is found digit by digit (bits 31..21, 20..10, 9..0) from a 2048-bin histogram
 // of the keys that match the digits found so far; the survivors are ordered as (key << 32) | index": patch select walks
@@ -7,6 +8,20 @@
 // threads of a 1-D workgroup.
 #pragma once
 #include "tpg_common.hpp"
+
+// ---- the keyed order of tpg_frame_subset and tpg_replace_dummy_centres (include/tpgan_ops.h) ---------------------------
+// Every step is a bijection of uint32 (an odd multiplier, an add, xor-shifts, xors): the keys of one seed are distinct.
+__host__ __device__ inline unsigned tpg_mix32(unsigned h) {
+    h ^= h >> 16;
+    h *= 0x7FEB352Du;
+    h ^= h >> 15;
+    h *= 0x846CA68Bu;
+    h ^= h >> 16;
+    return h;
+}
+__host__ __device__ inline unsigned tpg_subset_key(unsigned j, unsigned seed_lo, unsigned seed_hi) {
+    return tpg_mix32(tpg_mix32(j * 0x9E3779B1u + seed_lo) ^ seed_hi);
+}
 
 // ---- digits ---------------------------------------------------------------------------------------------------------
 constexpr int TPG_SEL_BINS = 2048;

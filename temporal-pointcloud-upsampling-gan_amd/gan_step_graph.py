@@ -8,7 +8,10 @@ both discriminator updates, forward, backward and Adam -- into HIP graphs once a
 Valid only in the STATIC regime of the step, which is checked on the device every replay:
   * `n_iter > 10` (mask loss active), gate open (`masking_loss < 0.1`),
   * the generator keeps every slot (no 999 padding => no host-side dummy replacement,
-    discriminator.py:115-130, and shapes are fixed).
+    discriminator.py:115-130, and shapes are fixed),
+  * or, with `padded=True`, every frame keeps every slot or PADS (its samples keep different numbers of slots, so hard
+    masking fills with 999 and the shape stays): the dummy centres are then replaced on the device
+    (`set_abstraction.device_dummy_draws`).  Equal counts with drops (the compress case) stays a violation.
 If a replay finds the regime violated, all state (parameters, buffers, optimizer state, RNG) is
 restored from the pre-step snapshot and the step is re-run eagerly with the same random draws,
 so results never depend on which path ran.  `tempo_gan_step_no_mask` has no gate and no mask
@@ -45,7 +48,8 @@ import torch
 from .graph_conv import shadows
 from .gan_step import _frozen, _autocast, _set_dummy_check, _NoSync, tempo_gan_step
 from .losses import tpugan_sr_loss
-from .set_abstraction import _plan_tensors, attach_plan_inverses, run_index_plan, sn_discard_prepared
+from .set_abstraction import (_plan_tensors, attach_plan_inverses, device_dummy_draws, run_index_plan,
+                              sn_discard_prepared)
 
 
 def _state_tensors(modules, optims):
@@ -123,9 +127,20 @@ def _rotation_matrix_np():
 
 
 class GraphedFluidStep:
+    """padded=True: a step whose frames pad (see the module docstring) replays too.  The discriminators' index plans
+    then run with their dummy checks on under `device_dummy_draws`, keyed by [draw_seed, n_iter] (two int64 words
+    behind the permutations in the staging buffer, rewritten before each replay); no new host draw is made, so an
+    all-keep step gives the same bits as under padded=False.  DEVIATION from the reference: a padded step that replays
+    draws its replacement centres from the keyed rule of include/tpgan_ops.h, not from numpy's stream, so it is not
+    comparable number for number with the eager step.  Which path a step takes is still a function of state and batch
+    alone, and every fallback (a violation, n_iter <= 10, other shapes) is the reference-order eager step with host
+    draws."""
+
     def __init__(self, sr_net, spatial_dis, tempo_dis, optims, opt, lowres_pos_lst, highres_pos_lst,
-                 furthest_distance=1.0, amp_dtype=None, sync=None, warmup=2, segmented=None, defer_inverses=True):
+                 furthest_distance=1.0, amp_dtype=None, sync=None, warmup=2, segmented=None, defer_inverses=True,
+                 padded=False, draw_seed=0):
         self.G, self.Ds, self.Dt = sr_net, spatial_dis, tempo_dis
+        self.padded, self.draw_seed, self._draws = bool(padded), int(draw_seed), None
         self.og, self.ot, self.os = optims
         for o in optims:
             if not all(g.get("capturable", True) for g in o.param_groups):   # Adam & co. expose the flag
@@ -157,6 +172,7 @@ class GraphedFluidStep:
         self.defer_inverses = defer_inverses       # False: inverted indices inside the update plans (`_update_plan`)
         self._keep = {}
         self._graphs = None
+        self.replays = 0                           # steps answered by a replay (not by the eager step) so far
         self._capture(lowres_pos_lst, highres_pos_lst, warmup)
 
     KEYS = ["tempo_G_loss", "tempo_D_loss", "Chamfer_distance_no_norm", "masking_loss", "spatial_G_loss",
@@ -170,9 +186,13 @@ class GraphedFluidStep:
         # (an async copy from a temporary pageable tensor may read freed memory on HIP)
         nf = 4 + 9 * (2 * T + 2 * B)
         self._host_f = torch.zeros(nf, dtype=torch.float32).pin_memory()
-        self._host_i = torch.zeros(T * n_pred, dtype=torch.int64).pin_memory()
+        extra = 2 if self.padded else 0           # [draw_seed, n_iter] behind the permutations
+        self._host_i = torch.zeros(T * n_pred + extra, dtype=torch.int64).pin_memory()
         self._dev_f = torch.zeros(nf, dtype=torch.float32, device=dev)
-        self._dev_i = torch.arange(n_pred, device=dev).repeat(T).contiguous()
+        self._dev_i = torch.cat([torch.arange(n_pred, device=dev).repeat(T),
+                                 torch.zeros(extra, dtype=torch.int64, device=dev)])
+        if self.padded:
+            self._draws = device_dummy_draws(self._dev_i[T * n_pred:])
         f = self._dev_f
         self.lab = f[:4]
         o = 4
@@ -260,8 +280,8 @@ class GraphedFluidStep:
         G, Ds, Dt, opt, k = self.G, self.Ds, self.Dt, self.opt, self._keep
         low, high, lab = self.low, self.high, self.lab
         others = [0] + list(range(2, self.T))
-        _set_dummy_check(Ds, False)
-        _set_dummy_check(Dt, False)
+        _set_dummy_check(Ds, self.padded)      # (padded: checked and replaced on the device, `_phase_grads`)
+        _set_dummy_check(Dt, self.padded)
         if update_D:
             # the real clouds exist already: their (rotated) copies and index plans start now
             def real_t():
@@ -283,7 +303,11 @@ class GraphedFluidStep:
         mask = mask_all[:self.B]              # (the centre frame's: the only one a loss reads)
         # the position expansion of all T frames in one call on the stacked clouds (elementwise: the same values as T calls,
         # a third of the launches in front of the fork of the fake clouds' index plans); `keep_all` = every frame kept all
-        pred_all, padded_all, keep_all = G.expand_pos_static(stacked, edge_all, mask_all)       # (12.20 -> 12.08 ms, same-box A/B)
+        if self.padded:                       # every frame keeps all or pads; a frame that compresses is a violation
+            pred_all, padded_all, _, static_ok = G.expand_pos_static(stacked, edge_all, mask_all, frames=nT)
+            keep_all = static_ok.all()
+        else:
+            pred_all, padded_all, keep_all = G.expand_pos_static(stacked, edge_all, mask_all)   # (12.20 -> 12.08 ms, same-box A/B)
         preds = pred_all.reshape(nT, self.B, *pred_all.shape[1:]).unbind(0)
         paddeds = padded_all.reshape(nT, self.B, *padded_all.shape[1:]).unbind(0)
         pred_c, padded_c = preds[0], paddeds[0]
@@ -315,6 +339,13 @@ class GraphedFluidStep:
             tempo_loss = (0.5 * (fake.float() - lab[3]) ** 2).mean()
         sr_loss = tempo_loss + spatial_loss + opt.w * position_loss
         k.update(tempo_loss=tempo_loss.detach(), spatial_loss=spatial_loss.detach(), cd=cd.detach(), ml=ml.detach())
+        if self.padded:
+            # a cloud with fewer candidates than dummies (the reference's choice() raises there): the eager step decides.
+            # Every replacement ran on a side stream in front of the plans joined above.
+            k["shorts"] = list(self._draws.shorts)
+            for t in k["shorts"]:
+                t.record_stream(torch.cuda.current_stream(self.dev))
+            viol = viol | (torch.cat(k["shorts"]).sum() != 0)
         self.viol.copy_(viol.float().reshape(1))
         return sr_loss
 
@@ -331,7 +362,7 @@ class GraphedFluidStep:
         norm iterations, BatchNorm running statistics), and every optimizer step comes in
         `_phase_apply`, after the generator's backward -- which still reads the discriminators'
         parameters -- has finished."""
-        with self._shadows():
+        with self._shadows(), (self._draws or contextlib.nullcontext()):
             try:
                 self._grads_body(update_D)
             finally:
@@ -533,7 +564,7 @@ class GraphedFluidStep:
         host_f = self._host_f.numpy()                  # the pinned buffer itself
         host_f[:4] = (valid, invalid, lab_s, lab_t)
         host_f[4:] = np.stack(rft + rtt + rfs + rts).reshape(-1)
-        torch.cat(perms, out=self._host_i)
+        torch.cat(perms, out=self._host_i[:self.T * n_pred])
 
     def __call__(self, lowres_pos_lst, highres_pos_lst, n_iter, freeze_D=False, launch_eagerly=False):
         """Same contract as the eager step function (without velocities); returns its loss dict.
@@ -549,6 +580,8 @@ class GraphedFluidStep:
         np_state, cpu_rng = np.random.get_state(), torch.get_rng_state()
         cuda_rng = torch.cuda.get_rng_state(self.dev)
         self._stage_host_draws(update_D)
+        if self.padded:
+            self._host_i[-2], self._host_i[-1] = self.draw_seed, int(n_iter)
         self._load(lowres_pos_lst, highres_pos_lst)
         self._dev_f.copy_(self._host_f, non_blocking=True)
         self._dev_i.copy_(self._host_i, non_blocking=True)
@@ -589,6 +622,7 @@ class GraphedFluidStep:
             torch.set_rng_state(cpu_rng)
             torch.cuda.set_rng_state(cuda_rng, self.dev)
             return self._eager(lowres_pos_lst, highres_pos_lst, n_iter, freeze_D)
+        self.replays += 0 if launch_eagerly else 1
         return {k: v for k, v in zip(self.KEYS, out[:6]) if k is not None}
 
     def run_body_eagerly(self, lowres_pos_lst, highres_pos_lst, update_D=True):

@@ -377,6 +377,17 @@ class HipBackend:
                    _ptr(xyz), B, N, m, _ptr(temp), _ptr(idx), _ptr(prefix_in), _ptr(flag))
         return idx, flag
 
+    def replace_dummy_centres(self, xyz, centres, draw_key, site, prefix_flag=None):
+        """tpg_replace_dummy_centres: -> (out (B,S) int32, short (1,) int32); prefix_flag (B,) int32 is cleared in place
+        where a cloud's centres were replaced."""
+        B, N, _ = xyz.shape
+        S = centres.shape[1]
+        out = torch.empty_like(centres)
+        short = torch.empty((1,), dtype=torch.int32, device=xyz.device)
+        self._call("tpg_replace_dummy_centres", "replace_dummy_centres", 8 * B * S, xyz, _ptr(xyz), _ptr(centres),
+                   _ptr(draw_key), int(site), B, N, S, _ptr(out), _ptr(prefix_flag), _ptr(short))
+        return out, short
+
     def context_expand(self, pos, edge, mask, state, t0):
         """Hard-masked expansion of T rollout frames with the running mask average (tpg_context_expand_f32):
         -> (points (T*N*r, 3): frame t is rows offsets[t]..offsets[t+1], offsets (T+1,) int64); `state` is updated."""
@@ -1056,6 +1067,82 @@ def furthest_point_sample_prefix(xyz, npoint, prefix_flag=None):
         if hasattr(be, "fps_prefix"):
             return be.fps_prefix(xyz.detach(), int(npoint), prefix_flag)
         return be.fps(xyz.detach(), int(npoint)), None
+
+
+# ------------------------------------ dummy-centre replacement on the device (csrc/dummy_centres.hip)
+_U32 = 0xFFFFFFFF
+
+
+def _mix32(h):
+    """include/tpgan_ops.h's mix on int64 tensors that hold uint32 values (int64 products wrap; the low words are right)."""
+    h = h ^ (h >> 16)
+    h = (h * 0x7FEB352D) & _U32
+    h = h ^ (h >> 15)
+    h = (h * 0x846CA68B) & _U32
+    return h ^ (h >> 16)
+
+
+def _replace_dummy_centres_torch(xyz, centres, draw_key, site, prefix_flag=None):
+    """`replace_dummy_centres` composed of torch ops (backends without the kernel): the rule of include/tpgan_ops.h,
+    cloud by cloud (it reads the hit counts on the host, which the kernel never does)."""
+    B, N, _ = xyz.shape
+    S = centres.shape[1]
+    dev = xyz.device
+    hit = torch.abs(torch.gather(xyz[:, :, 0], 1, centres.long()) - 999) < 1e-4
+    out = centres.clone()
+    short = torch.zeros((1,), dtype=torch.int32, device=dev)
+    seed, n_iter = draw_key[0], draw_key[1]
+    j = torch.arange(N, dtype=torch.int64, device=dev)
+    lo = _mix32((seed & _U32) ^ _mix32((((n_iter & _U32) * 0x9E3779B1) + site) & _U32))
+    for b, k in enumerate(hit.sum(1).tolist()):
+        if k == 0:
+            continue
+        pool = torch.ones(N, dtype=torch.bool, device=dev)
+        pool[:S] = ~hit[b, :N]
+        if int(pool.sum()) < k:
+            short[0] = 1
+            continue
+        hi = _mix32(((seed >> 32) & _U32) ^ _mix32((b * 0x85EBCA6B + site) & _U32))
+        key = _mix32(_mix32((j * 0x9E3779B1 + lo) & _U32) ^ hi)
+        picks = j[pool][torch.argsort(key[pool])[:k]]      # key() is a bijection: distinct keys, j never decides
+        out[b] = torch.cat((centres[b][~hit[b]], picks.to(centres.dtype)))
+        if prefix_flag is not None:
+            prefix_flag[b] = 0
+    return out, short
+
+
+def replace_dummy_centres(xyz, centres, draw_key, site, prefix_flag=None):
+    """The discriminators' dummy-centre replacement (discriminator.py:115-130) with no host involvement: centres that
+    point at a 999-padded row of their cloud are dropped, the survivors keep their order and as many other points,
+    drawn by tpg_frame_subset's keyed order, follow them (the rule: include/tpgan_ops.h).
+
+    xyz (B,N,3) fp32, centres (B,S) int32; draw_key: a DEVICE int64 tensor (2,) holding [seed, n_iter], read
+    by the kernel (a captured step rewrites it before each replay); site: a host int >= 0, the ordinal of the call within
+    the step.  prefix_flag: the (B,) int32 flags of `furthest_point_sample_prefix` or None; cleared IN PLACE for every
+    cloud whose centres were replaced.  -> (centres_out (B,S) int32, short (1,) int32: set if a cloud had fewer
+    candidates than dummies -- where the reference's choice() raises -- and kept its row)."""
+    _check_float(xyz, "xyz", 3)
+    _check_int(centres, "centres", 2)
+    _need(xyz.shape[2] == 3 and centres.shape[0] == xyz.shape[0], "xyz must be (B,N,3) and centres (B,S)")
+    _need(xyz.shape[1] > 0 or centres.shape[1] == 0, "an empty cloud has no centres")
+    _need(isinstance(draw_key, torch.Tensor) and draw_key.dtype == torch.int64 and tuple(draw_key.shape) == (2,)
+          and draw_key.is_contiguous(), "draw_key must be an int64 tensor [seed, n_iter]")
+    _need(int(site) >= 0, "site must be >= 0")
+    _same_device(xyz, centres, draw_key)
+    if prefix_flag is not None:
+        _check_int(prefix_flag, "prefix_flag", 1)
+        _need(prefix_flag.shape[0] == xyz.shape[0], "prefix_flag must hold one flag per cloud")
+        _same_device(xyz, prefix_flag)
+    if centres.numel() == 0:
+        return centres.clone(), torch.zeros((1,), dtype=torch.int32, device=xyz.device)
+    be = backend_for(xyz)
+    with torch.no_grad():
+        if hasattr(be, "replace_dummy_centres"):
+            if xyz.is_cuda:
+                _need(centres.shape[1] <= frame_subset_max_k(),
+                      f"S = {centres.shape[1]} exceeds the selection's capacity ({frame_subset_max_k()})")
+            return be.replace_dummy_centres(xyz.detach(), centres, draw_key, int(site), prefix_flag)
+        return _replace_dummy_centres_torch(xyz.detach(), centres, draw_key, int(site), prefix_flag)
 
 
 # --------------------------------------------------- rollout: running mask average (upsampling_network.py:159-174)

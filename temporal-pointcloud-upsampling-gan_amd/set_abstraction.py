@@ -459,6 +459,35 @@ def replace_dummy_centres(xyz, centres, rng=np.random):
     return centres
 
 
+_DEVICE_DRAWS = [None]      # the active `device_dummy_draws` context
+
+
+class device_dummy_draws:
+    """While active, a level with `mask_dummy and check_dummies` replaces its dummy centres ON THE DEVICE
+    (ops.replace_dummy_centres: the keyed draw of include/tpgan_ops.h) instead of `replace_dummy_centres`' host rule:
+    no host sync and no np.random, so the level can be captured into a graph and replayed.  draw_key: the device int64
+    tensor [seed, n_iter] the kernel reads.  Every such call gets the next `site` ordinal, counted from 0 and reset
+    when the context is entered, so capture, warm-up, replay and an eager launch of the same body see the same
+    ordinals.  `shorts` collects the calls' (1,) int32 flags (a cloud had fewer candidates than dummies and kept its
+    row) for the owner to act on.  Outside the context nothing changes."""
+
+    def __init__(self, draw_key):
+        self.draw_key, self.shorts, self._site, self._outer = draw_key, [], 0, None
+
+    def next_site(self):
+        self._site += 1
+        return self._site - 1
+
+    def __enter__(self):
+        self.shorts, self._site = [], 0
+        self._outer, _DEVICE_DRAWS[0] = _DEVICE_DRAWS[0], self
+        return self
+
+    def __exit__(self, *exc):
+        _DEVICE_DRAWS[0] = self._outer
+        return False
+
+
 class _PointnetSAModuleBase(nn.Module):
     def __init__(self):
         super().__init__()
@@ -478,6 +507,14 @@ class _PointnetSAModuleBase(nn.Module):
         for the level after (ops.furthest_point_sample_prefix: the sampling of an FPS prefix is 0..m-1, exactly)."""
         if prefix is not None and xyz.is_cuda and not (self.mask_dummy and self.check_dummies):
             centres, prefix[0] = ops.furthest_point_sample_prefix(xyz, self.npoint, prefix[0])
+            return centres
+        ctx = _DEVICE_DRAWS[0]
+        if ctx is not None and self.mask_dummy and self.check_dummies:
+            centres, flag = ops.furthest_point_sample_prefix(xyz, self.npoint, None if prefix is None else prefix[0])
+            centres, short = ops.replace_dummy_centres(xyz, centres, ctx.draw_key, ctx.next_site(), flag)
+            ctx.shorts.append(short)
+            if prefix is not None:
+                prefix[0] = flag                 # (cleared where centres were replaced: no shortcut for those clouds)
             return centres
         if prefix is not None:
             prefix[0] = None                     # (dummy replacement re-orders the centres: no shortcut downstream)

@@ -165,11 +165,15 @@ class SRNet(nn.Module):
             return expanded, padded
         return expanded, expanded[hard].view(B, -1, 3)
 
-    def expand_pos_static(self, pos, upsample_edge, binary_mask):
+    def expand_pos_static(self, pos, upsample_edge, binary_mask, frames=None):
         """Hard masking without a host decision (for hipGraph capture): always the padded form
         `where(hard, expanded, 999)`, plus a device flag `all_keep`.  When every slot survives
         (`all_keep`), this IS what `expand_pos_with_masking(hard_masking=True)` returns; otherwise
-        the caller must not use the static path (dummy handling needs the host)."""
+        the caller must not use the static path (dummy handling needs the host) -- unless it handles the dummies on
+        the device: frames = F (pos holds F frames of B / F clouds each, frame-major) adds a fourth result, the (F,) bool
+        flags `static_ok`: the padded form is what `expand_pos_with_masking` returns for the frame, because it keeps
+        every slot or its clouds keep DIFFERENT numbers of slots (the pad case; equal counts with drops is the
+        compress case, whose shape changes)."""
         B = pos.shape[0]
         r = self.upsample_ratio
         keep = binary_mask.detach().view(B, -1, 1) > self.epsilon
@@ -179,7 +183,12 @@ class SRNet(nn.Module):
         hard[:, :, 0] = True
         hard = hard.view(B, -1, 1)
         padded = torch.where(hard, expanded, torch.full_like(expanded, 999.0))
-        return expanded, padded, hard.all()
+        if frames is None:
+            return expanded, padded, hard.all()
+        counts = hard.view(frames, B // frames, -1).sum(2)
+        full = counts == hard.shape[1]
+        differ = (counts != counts.max(1, keepdim=True).values).any(1)        # (never with one cloud per frame)
+        return expanded, padded, full.all(), full.all(1) | differ
 
     def forward(self, feature, pos, hard_masking=False):
         edge, mask = self.body(feature, pos)

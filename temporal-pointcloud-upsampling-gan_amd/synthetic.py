@@ -66,3 +66,19 @@ def force_all_keep(sr_net):
         last.weight.zero_()
         last.bias.fill_(1.0)
     return sr_net
+
+
+def force_drop_by_x(sr_net, thr):
+    """Padded regime for measurements: `force_all_keep`, then the mask is 0 for the low-resolution points whose x is at or
+    below `thr` -- a function of each cloud alone, so eager and captured calls agree.  With unequal counts per sample hard
+    masking pads with 999 and the discriminators' first levels meet dummy centres (the SRNet's class is swapped for a
+    subclass, which copy.deepcopy keeps)."""
+    from .srnet import SRNet
+
+    class DropByX(SRNet):
+        def body(self, feature, pos):
+            edge, mask = super().body(feature, pos)
+            return edge, mask * (pos[:, :, :1] > self.drop_thr).to(mask.dtype).reshape(mask.shape)
+    force_all_keep(sr_net)
+    sr_net.__class__, sr_net.drop_thr = DropByX, float(thr)
+    return sr_net

@@ -8,9 +8,14 @@ Data layout: DATA/case{c}/data_{s}.npz for c = 1 .. train_sequence_num, s = 0 ..
 
 The loop is the reference's: SRNet + FluidTempoDis(3) + FluidSpatialDis, Adam(lr) and 2 x Adam(0.33 lr), StepLR(10000,
 0.7) x 3, the EAGER step gan_step.tempo_gan_step (the one with the reference's regimes: n_iter <= 10, closed gate,
-999-padding), a checkpoint when (n_iter - 1) % ckpt_every == 0 or at the end.  Instead of tensorboardX one JSON line
-per --log_every iterations goes to stdout.  Checkpoints hold the reference's ten keys plus `tpgan_amd`: the sampler's
-generator state and the numpy / torch RNG states, which make a resumed run repeat the uninterrupted one bit for bit.
+999-padding), a checkpoint when (n_iter - 1) % ckpt_every == 0 or at the end.  Under --graph the step is
+gan_step_graph.GraphedFluidStep(padded=True), captured from the first batch: steps whose frames keep every slot or pad
+replay from hipGraphs, every other step (n_iter <= 10, a closed gate, a frame that compresses, a ragged batch) falls back
+to that eager step with the same draws; a padded step that replays draws its replacement centres from the keyed device
+rule instead of numpy's stream.  Instead of tensorboardX one JSON line per --log_every iterations
+goes to stdout (under --graph with `replayed`, the replays in the window).  Checkpoints hold the reference's ten keys
+plus `tpgan_amd`: the sampler's generator state and the numpy / torch RNG states, which make a resumed run repeat the
+uninterrupted one bit for bit.
 Under torch.distributed.run every rank samples its own clips (seed + 1000 * rank), gradients are averaged by
 ddp.GradSync and rank 0 writes the checkpoints.
 
@@ -70,7 +75,9 @@ def parse_args(argv=None):
     ap.add_argument("--test_sequence_num", type=int, default=4)
     ap.add_argument("--dump_visualization", action="store_true", help="--samples 4, unless --samples is given")
     add_sample_options(ap, default=None)
+    add_graph_option(ap)
     opt = ap.parse_args(argv)
+    check_graph_option(ap, opt)
     if opt.samples is None:
         opt.samples = 4 if opt.dump_visualization else 0
     return opt
@@ -82,6 +89,22 @@ def add_sample_options(ap, default=0):
                          "one JSON line with their Chamfer distances (0: off)")
     ap.add_argument("--samples_width", type=int, default=512, help="width of the sample pictures")
     ap.add_argument("--samples_height", type=int, default=512, help="height of the sample pictures")
+
+
+def add_graph_option(ap):
+    ap.add_argument("--graph", action="store_true",
+                    help="replay the step from hipGraphs captured on the first batch (gan_step_graph); steps outside the "
+                         "captured regime fall back to the eager step")
+
+
+def check_graph_option(ap, opt):
+    """--graph's argument errors, raised at parse time."""
+    if not opt.graph:
+        return
+    if getattr(opt, "use_vel", False) or opt.in_node_feats == 6:
+        ap.error("--graph cannot be combined with --use_vel or --in_node_feats 6: the captured step has no velocities")
+    if torch.device(opt.device).type != "cuda":
+        ap.error("--graph needs a cuda --device")
 
 
 def _rng_state(device, sampler_state):
@@ -163,7 +186,7 @@ class HeldOutPass:
         return {"n_iter": n_iter, "test_cd": cds, "test_points": counts}
 
 
-def run(opt, nets_of, sched_of, sampler_of, step, samples_of=None):
+def run(opt, nets_of, sched_of, sampler_of, step, samples_of=None, graph_step_of=None):
     """The training loop both trainers share (--seed, --device, --lr, --amp, --freeze_D, --iters, --resume,
     --path_to_resume, --log_dir, --log_every, --ckpt_every and --samples of `opt`); what differs comes as callables:
     nets_of(dev) -> (sr_net, tempo_dis, spatial_dis) on the device; sched_of(optimiser) -> its scheduler;
@@ -171,7 +194,11 @@ def run(opt, nets_of, sched_of, sampler_of, step, samples_of=None):
     step((sr_net, tempo_dis, spatial_dis), (sr_optim, tempo_optim, spatial_optim), batch, n_iter, freeze_D, sync,
     amp_dtype) -> the losses of one adversarial step; the last three go to the step function under those names;
     samples_of(dev, generator, n) -> (the n held-out clips of `HeldOutPass`, drawn from `generator`, and its `predict`):
-    called once, on rank 0, and only under --samples n > 0; the pass then runs whenever a checkpoint is written."""
+    called once, on rank 0, and only under --samples n > 0; the pass then runs whenever a checkpoint is written.
+    Under --graph, graph_step_of((nets), (optims), batch, sync, amp_dtype, draw_seed) -> (a gan_step_graph stepper
+    captured from that batch, clouds_of(batch) -> its (low, high) lists) replaces `step`: it is called once, on the first
+    batch and after any --resume load.  The optimisers are then capturable and their learning rate is a device tensor,
+    which the schedulers fill in place: the captured Adam follows the schedule."""
     rank, world, local = ddp.init_from_env(backend=os.environ.get("TPGAN_DDP_BACKEND"))
     dev = torch.device(opt.device)
     if dev.type == "cuda":
@@ -183,8 +210,12 @@ def run(opt, nets_of, sched_of, sampler_of, step, samples_of=None):
     torch.manual_seed(opt.seed)                      # same initial weights on every rank; broadcast below anyway
 
     nets = nets_of(dev)
-    optims = tuple(torch.optim.Adam(net.parameters(), lr=lr)
-                   for net, lr in zip(nets, (opt.lr, 0.33 * opt.lr, 0.33 * opt.lr)))
+    graph = bool(getattr(opt, "graph", False))
+    if graph and graph_step_of is None:
+        raise ValueError("--graph needs the trainer's graph_step_of")
+    adam = (lambda p, lr: torch.optim.Adam(p, lr=torch.tensor(lr, device=dev), capturable=True)) if graph else \
+        (lambda p, lr: torch.optim.Adam(p, lr=lr))
+    optims = tuple(adam(net.parameters(), lr) for net, lr in zip(nets, (opt.lr, 0.33 * opt.lr, 0.33 * opt.lr)))
     scheds = [sched_of(o) for o in optims]
     sync = ddp.GradSync()
     sync.broadcast_state(*nets)
@@ -203,6 +234,10 @@ def run(opt, nets_of, sched_of, sampler_of, step, samples_of=None):
         n_iter = int(ckpt["n_iter"])
         if "tpgan_amd" in ckpt and world == 1:       # (the file holds rank 0's streams; other ranks keep their seeds)
             _set_rng_state(ckpt["tpgan_amd"], dev, sampler.generator)
+        if graph:                                    # (the file's learning rates were mapped to the host)
+            for o in optims:
+                for g in o.param_groups:
+                    g["lr"] = torch.as_tensor(g["lr"], dtype=torch.float32).to(dev)
 
     ckpt_dir = os.path.join(opt.log_dir, "model_ckpt")
     if rank == 0:
@@ -219,11 +254,17 @@ def run(opt, nets_of, sched_of, sampler_of, step, samples_of=None):
     batches = prefetch(sampler)
     for net in nets:
         net.train()
-    window_start, window_iters = time.time(), 0
+    window_start, window_iters, window_replays = time.time(), 0, 0
+    stepper = None
     while n_iter < opt.iters:
         data = next(batches)
         n_iter += 1
-        losses = step(nets, optims, data, n_iter, opt.freeze_D, sync, amp_dtype)
+        if graph:
+            if stepper is None:
+                stepper, clouds_of = graph_step_of(nets, optims, data, sync, amp_dtype, opt.seed + 1000 * rank)
+            losses = stepper(*clouds_of(data), n_iter, freeze_D=opt.freeze_D)
+        else:
+            losses = step(nets, optims, data, n_iter, opt.freeze_D, sync, amp_dtype)
         for s in scheds:
             s.step()
         window_iters += 1
@@ -231,9 +272,10 @@ def run(opt, nets_of, sched_of, sampler_of, step, samples_of=None):
             if dev.type == "cuda":
                 torch.cuda.synchronize(dev)
             now = time.time()
-            print(json.dumps({"n_iter": n_iter, "steps_per_s": window_iters / max(now - window_start, 1e-9),
+            replayed = {"replayed": stepper.replays - window_replays} if graph else {}
+            print(json.dumps({"n_iter": n_iter, "steps_per_s": window_iters / max(now - window_start, 1e-9), **replayed,
                               **{k: float(v) for k, v in losses.items()}}), flush=True)
-            window_start, window_iters = now, 0
+            window_start, window_iters, window_replays = now, 0, stepper.replays if graph else 0
         if rank == 0 and ((n_iter - 1) % opt.ckpt_every == 0 or n_iter >= opt.iters):
             if held_out is not None:
                 print(json.dumps(held_out(nets[0], n_iter)), flush=True)
@@ -261,12 +303,23 @@ def main(argv=None):
         return tempo_gan_step(sr_net, spatial_dis, tempo_dis, low_pos, low_vel, high_pos, high_vel, 1., opt, n_iter,
                               *optims, freeze_D=freeze_D, sync=sync, amp_dtype=amp_dtype)
 
+    def graph_step_of(nets, optims, data, sync, amp_dtype, draw_seed):
+        from .gan_step_graph import GraphedFluidStep
+        sr_net, tempo_dis, spatial_dis = nets
+
+        def clouds_of(data):
+            return list(data[6:9]), list(data[0:3])
+        low, high = clouds_of(data)
+        return GraphedFluidStep(sr_net, spatial_dis, tempo_dis, optims, opt, low, high, 1., amp_dtype, sync, padded=True,
+                                draw_seed=draw_seed), clouds_of
+
     def samples_of(dev, generator, n):
         clips = held_out_fluid_clips(opt.test_dataset_path, opt.test_sequence_num, opt.sequence_length, n, generator, dev,
                                      use_vel=opt.use_vel and opt.in_node_feats == 6)
         return clips, lambda sr_net, clip: sr_net(clip["feature"], clip["input"][None], hard_masking=True)[2]
 
-    return run(opt, nets_of, lambda o: torch.optim.lr_scheduler.StepLR(o, 10000, gamma=0.7), sampler_of, step, samples_of)
+    return run(opt, nets_of, lambda o: torch.optim.lr_scheduler.StepLR(o, 10000, gamma=0.7), sampler_of, step, samples_of,
+               graph_step_of)
 
 
 if __name__ == "__main__":

@@ -7,7 +7,8 @@ Data layout: DATA/MSR-Action3D/a{label}_s{subject}_e{..}_sdepth.npz, each holdin
 come from data.ActionClipSampler through data.prefetch on a side stream.
 
 The loop is the reference's: NoMaskSRNet(in, emb, upsample_ratio=16) + ActionTempoDis(3) + ActionSpatialDis, Adam(lr) and
-2 x Adam(0.33 lr), StepLR(iters // 10, 0.72) x 3, the eager step gan_step.tempo_gan_step_no_mask, a checkpoint when
+2 x Adam(0.33 lr), StepLR(iters // 10, 0.72) x 3, the eager step gan_step.tempo_gan_step_no_mask (under --graph its
+replay from hipGraphs, gan_step_graph.GraphedActionStep, captured from the first batch), a checkpoint when
 (n_iter - 1) % ckpt_every == 0 or at the end.  The loop itself is train.run: optimisers, logging, the checkpoint's keys
 (the reference's ten plus `tpgan_amd`), the bit-exact --resume and the multi-process rules are written there once; this
 file says only what the action trainer's flags, networks, scheduler, sampler, step and held-out clips are.
@@ -23,7 +24,7 @@ from .data import ActionClipSampler, ActionSequences, held_out_action_clips
 from .gan_step import tempo_gan_step_no_mask
 from .set_abstraction import ActionSpatialDis, ActionTempoDis
 from .srnet import NoMaskSRNet
-from .train import add_sample_options, run
+from .train import add_graph_option, add_sample_options, check_graph_option, run
 
 
 def parse_args(argv=None):
@@ -50,7 +51,10 @@ def parse_args(argv=None):
     ap.add_argument("--log_every", type=int, default=100)
     ap.add_argument("--num_points", type=int, default=2048, help="points per high-resolution frame (low: 1/16 of it)")
     add_sample_options(ap)
-    return ap.parse_args(argv)
+    add_graph_option(ap)
+    opt = ap.parse_args(argv)
+    check_graph_option(ap, opt)
+    return opt
 
 
 def main(argv=None):
@@ -70,12 +74,21 @@ def main(argv=None):
         return tempo_gan_step_no_mask(sr_net, spatial_dis, tempo_dis, low_pos, high_pos, opt, n_iter, *optims,
                                       freeze_D=freeze_D, sync=sync, amp_dtype=amp_dtype)
 
+    def graph_step_of(nets, optims, data, sync, amp_dtype, draw_seed):
+        from .gan_step_graph import GraphedActionStep
+        sr_net, tempo_dis, spatial_dis = nets
+
+        def clouds_of(data):
+            return list(data[3:6]), list(data[0:3])
+        low, high = clouds_of(data)
+        return GraphedActionStep(sr_net, spatial_dis, tempo_dis, optims, opt, low, high, 1., amp_dtype, sync), clouds_of
+
     def samples_of(dev, generator, n):
         clips = held_out_action_clips(opt.data_dir, n, generator, dev, opt.num_points)
         return clips, lambda sr_net, clip: sr_net(clip["feature"], clip["feature"])[0]
 
     return run(opt, nets_of, lambda o: torch.optim.lr_scheduler.StepLR(o, max(opt.iters // 10, 1), gamma=0.72), sampler_of,
-               step, samples_of)
+               step, samples_of, graph_step_of)
 
 
 if __name__ == "__main__":
