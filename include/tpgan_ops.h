@@ -716,6 +716,72 @@ int tpg_render_points_f32(const float *points, const int64_t *lengths, const flo
                           const float *cams, int ncam, int W, int H, int size, float lo, float hi, const uint8_t *lut,
                           const uint8_t *background, void *keys, uint8_t *image, int32_t *winner, void *stream);
 
+/* ---- fluid surface pictures (csrc/surface.hip) ------------------------------------------------------------------
+ * Screen-space fluid rendering in three entries: every particle is a sphere of radius rad (world units), the nearest
+ * sphere front per pixel is kept (a), that depth image is smoothed without crossing silhouettes (b, called as often as
+ * wanted), normals are taken from it and it is shaded (c).  (The reference's demo notebooks write .bgeo files for an
+ * external tool to do this; the look here is this project's own.)  points, lengths, cams, ncam, keys and the projection
+ * of a point to u, v, zv, t = zv - near are tpg_render_points_f32's, word for word; everything is fp32, each operation
+ * rounded on its own, dot products as (a.x*b.x + a.y*b.y) + a.z*b.z.
+ *
+ * (a) tpg_render_spheres_f32 -> depth (F,H,W) f32, winner (F,H,W) int32.  Per point:
+ *     rp = rad*scale (ortho) or (rad/zv)*scale (pinhole), then rp = fminf(rp, (float)TPG_SURFACE_MAX_RADIUS): a nearer
+ *     or larger sphere is drawn as a disc of 64 pixels radius with its true bulge (stated, not an error).
+ *     The point is dropped unless
+ *         t >= 0 && zv <= far && rp > 0 && u >= -rp && u < W+rp && v >= -rp && v < H+rp
+ *     which a NaN or an infinity anywhere fails; the test comes BEFORE any conversion to an integer.
+ *     Candidate pixels: columns (int)floorf(u - rp) .. (int)floorf(u + rp), rows likewise with v, clipped to the image.
+ *     For a candidate (x, y): dx = (((float)x + 0.5f) - u) / rp, dy = (((float)y + 0.5f) - v) / rp, s = dx*dx + dy*dy;
+ *     it is covered iff s < 1.0f.  Then h = sqrtf(1.0f - s), tp = t - rad*h, and tp is replaced by 0.0f unless tp > 0
+ *     (the front is clamped at the near plane).  Key (bits(tp) << 32) | index, 64-bit atomic min on `keys`, (F,H,W)
+ *     uint64, 8-byte aligned, set to all ones by the call itself.
+ *   winner: the key's low word, -1 where the key is still all ones; depth: the float whose bits are the key's high
+ *   word, +inf for background.  Equal fronts show the lower index; the result does not depend on the order of execution
+ *   nor on how the discs are spread over the lanes: bit-identical from run to run and at every batch position.
+ *
+ * (b) tpg_surface_smooth_f32: in (F,H,W) -> out (F,H,W), out != in; half-width k = 1..TPG_SURFACE_MAX_HALF, delta > 0.
+ *   bw is the binomial row of order 2k in integers (1 2 1; 1 4 6 4 1; ...; every product <= 70*70, exact in fp32).
+ *   A pixel whose `in` zi is not finite is copied unchanged.  Otherwise acc = 0, ws = 0, and for oy = -k..k (outer),
+ *   ox = -k..k (inner): the neighbour (x+ox, y+oy) contributes if it is inside the image, its depth zj is finite and
+ *   fabsf(zj - zi) <= delta, with w = (float)(bw[oy+k]*bw[ox+k]), acc = acc + w*zj, ws = ws + w; out = acc / ws.  The
+ *   summation order is part of the rule.  The centre always contributes: background never becomes surface, surface
+ *   never background, and a step larger than delta is not smeared.
+ *
+ * (c) tpg_surface_shade_f32: depth (F,H,W) (smoothed), winner (F,H,W), scalar (F,N) or NULL, lo, hi, lut, background
+ *   as for tpg_render_points_f32 -> image (F,H,W,3) uint8.  shade: a HOST table of TPG_SURFACE_SHADE_FLOATS floats:
+ *     [0..2] L (unit, towards the light)   [3..5] Hh (unit half vector of L and V = (0,0,-1), computed by the host)
+ *     [6] ka   [7] kd   [8] ks   [9] kf   [10] p (an integer 0..8 stored as a float)
+ *   in view coordinates: x right, y down, z forward.  A pixel is surface iff its depth z is finite; every other pixel
+ *   gets `background`.  The view-space point of a surface pixel (x, y):
+ *     Zv = z + near;  a = (((float)x + 0.5f) - cx) / scale;  b = (((float)y + 0.5f) - cy) / scale
+ *     ortho: P = (a, b, Zv);   pinhole: P = (a*Zv, b*Zv, Zv)
+ *   ddx: the forward candidate P(x+1,y) - P(x,y) if that pixel exists and is surface, the backward candidate
+ *   P(x,y) - P(x-1,y) likewise; the one with the smaller fabsf of its z component, forward on equality or if it is the
+ *   only one; if neither exists (1/scale, 0, 0) for ortho, (Zv/scale, 0, 0) for pinhole.  ddy: the same with rows, down
+ *   being forward, and (0, 1/scale, 0) / (0, Zv/scale, 0).  n = cross(ddy, ddx), each component a*b - c*d:
+ *     nx = ddy.y*ddx.z - ddy.z*ddx.y;  ny = ddy.z*ddx.x - ddy.x*ddx.z;  nz = ddy.x*ddx.y - ddy.y*ddx.x
+ *   (a plane facing the camera gives (0,0,-1)); len = sqrtf((nx*nx + ny*ny) + nz*nz); n = n / len componentwise if
+ *   len > 0, else (0,0,-1).  dif = fmaxf(n.L, 0); sp = fmaxf(n.Hh, 0), then sp = sp*sp p times; c = fmaxf(-nz, 0),
+ *   m = 1 - c, m2 = m*m, fr = (m2*m2)*m.  Base colour: lut[level] by tpg_render_points_f32's level rule with
+ *   s = scalar[f][winner] (winner is read at surface pixels only and only with a scalar, taken into 0..N-1), or s = z
+ *   when scalar is NULL.  Per channel val = (float)base*(ka + kd*dif) + 255.0f*(ks*sp + kf*fr), stored as 0 unless
+ *   val > 0, 255 if val >= 255, else (int)(val + 0.5f).
+ *
+ * Checks, all before anything is launched.  TPG_ERR_ARG: negative F or N, a NULL output, W or H < 1, rad or delta not
+ * positive and finite, k outside 1..TPG_SURFACE_MAX_HALF, out == in, hi <= lo, a NULL or non-finite shade table, p not
+ * an integer 0..8.  Then F == 0 (and for (a), (c): N == 0): TPG_OK, nothing written.  Then another NULL pointer, keys
+ * not 8-byte aligned, and the camera and lo / inv conditions of tpg_render_points_f32: TPG_ERR_ARG; its limits on W, H,
+ * F and the pixels in all: TPG_ERR_UNSUPPORTED. */
+#define TPG_SURFACE_MAX_RADIUS 64
+#define TPG_SURFACE_MAX_HALF 4
+#define TPG_SURFACE_SHADE_FLOATS 11
+int tpg_render_spheres_f32(const float *points, const int64_t *lengths, int F, int N, const float *cams, int ncam, int W,
+                           int H, float rad, void *keys, float *depth, int32_t *winner, void *stream);
+int tpg_surface_smooth_f32(const float *in, int F, int W, int H, int k, float delta, float *out, void *stream);
+int tpg_surface_shade_f32(const float *depth, const int32_t *winner, const float *scalar, int F, int N, const float *cams,
+                          int ncam, int W, int H, float lo, float hi, const uint8_t *lut, const uint8_t *background,
+                          const float *shade, uint8_t *image, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -83,6 +83,9 @@ SIGNATURES = {
     "tpg_emd_finish_f32": [_P, _I, _I, _P, _P, _P, _P, _P, _P],
     "tpg_gaussian_row_sums_f32": [_P, _P, _P, _P, _I, _I, _I, _F, _P, _P],
     "tpg_render_points_f32": [_P, _P, _P, _I, _I, _P, _I, _I, _I, _I, _F, _F, _P, _P, _P, _P, _P, _P],
+    "tpg_render_spheres_f32": [_P, _P, _I, _I, _P, _I, _I, _I, _F, _P, _P, _P, _P],
+    "tpg_surface_smooth_f32": [_P, _I, _I, _I, _I, _F, _P, _P],
+    "tpg_surface_shade_f32": [_P, _P, _P, _I, _I, _P, _I, _I, _I, _F, _F, _P, _P, _P, _P, _P],
 }
 SIZE_GETTERS = ("tpg_rowbn_workspace_bytes", "tpg_mlp_workspace_bytes", "tpg_context_expand_workspace_bytes",
                 "tpg_emd_workspace_bytes")

@@ -22,22 +22,9 @@
 //            already smaller: keys only ever decrease, so a value read early can only be larger than the final one
 //            and the skip never changes the result; on dense clouds most of the S*S atomics of a hidden point go.
 //   resolve  one lane per pixel: key -> winner index (or -1) and the colour from the look-up table
-#include "tpg_common.hpp"
+#include "render_common.hpp"
 
 namespace {
-
-constexpr int RD_THREADS = 256;
-constexpr int RD_GROUP = 16;          // per-frame cameras travel as kernel arguments, this many frames per launch
-constexpr int RD_CAM = TPG_RENDER_CAM_FLOATS;
-constexpr tpg_u64 RD_EMPTY = ~0ull;
-
-struct RenderCams {
-    float c[RD_GROUP][RD_CAM];
-};
-
-__device__ __forceinline__ float rd_dot(float ax, float ay, float az, float bx, float by, float bz) {
-    return (ax * bx + ay * by) + az * bz;
-}
 
 // frames f0 .. f0 + gridDim.y - 1; per_frame == 0: every frame uses camera 0 of `cams`
 __global__ __launch_bounds__(RD_THREADS) void render_splat_kernel(
@@ -53,21 +40,9 @@ __global__ __launch_bounds__(RD_THREADS) void render_splat_kernel(
     if (i >= n) return;
     const float *cam = cams.c[per_frame ? blockIdx.y : 0];
     const float *p = points + ((size_t)f * N + i) * 3;
-    const float qx = p[0] - cam[0], qy = p[1] - cam[1], qz = p[2] - cam[2];
-    const float xv = rd_dot(qx, qy, qz, cam[3], cam[4], cam[5]);
-    const float yv = rd_dot(qx, qy, qz, cam[6], cam[7], cam[8]);
-    const float zv = rd_dot(qx, qy, qz, cam[9], cam[10], cam[11]);
-    const float scale = cam[12], cx = cam[13], cy = cam[14], near = cam[15], far = cam[16];
-    float u, v;
-    if (cam[17] != 0.0f) {
-        u = (xv / zv) * scale + cx;
-        v = (yv / zv) * scale + cy;
-    } else {
-        u = xv * scale + cx;
-        v = yv * scale + cy;
-    }
-    const float t = zv - near;
-    const float fs = (float)S;
+    float u, v, zv, t;
+    rd_project(p, cam, u, v, zv, t);
+    const float fs = (float)S, far = cam[16];
     // every comparison is false for a NaN operand: only a point for which ALL hold goes on
     if (!(t >= 0.0f && zv <= far && u >= -fs && u < (float)W + fs && v >= -fs && v < (float)H + fs)) return;
     const int px = (int)floorf(u), py = (int)floorf(v);        // in [-S, W+S) x [-S, H+S): the conversion is safe
@@ -94,9 +69,7 @@ __global__ __launch_bounds__(RD_THREADS) void render_resolve_kernel(
     if (key != RD_EMPTY) {
         win = (int)(unsigned)key;
         const float s = scalar ? scalar[(at / HW) * N + win] : __uint_as_float((unsigned)(key >> 32));
-        const float c = (s - lo) * inv;
-        int level = 0;
-        if (c > 0.0f) level = c >= 255.0f ? 255 : (int)(c + 0.5f);      // NaN: no comparison holds, level 0
+        const int level = rd_level(s, lo, inv);
         r = lut[level * 3];
         g = lut[level * 3 + 1];
         b = lut[level * 3 + 2];
@@ -106,8 +79,6 @@ __global__ __launch_bounds__(RD_THREADS) void render_resolve_kernel(
     image[at * 3 + 2] = b;
     winner[at] = win;
 }
-
-inline bool rd_finite(float x) { return x - x == 0.0f; }
 
 }  // namespace
 
@@ -120,13 +91,7 @@ extern "C" int tpg_render_points_f32(const float *points, const int64_t *lengths
     if (F == 0 || N == 0) return TPG_OK;
     if (!points || !cams || !lut || !background || !keys || ((uintptr_t)keys & 7) != 0) return TPG_ERR_ARG;
     if (ncam != 1 && ncam != F) return TPG_ERR_ARG;
-    for (int c = 0; c < ncam; ++c) {                      // HOST table: every camera is checked before anything is launched
-        const float *cam = cams + (size_t)c * RD_CAM;
-        for (int j = 0; j < RD_CAM; ++j)
-            if (!rd_finite(cam[j])) return TPG_ERR_ARG;
-        if (cam[17] != 0.0f && cam[17] != 1.0f) return TPG_ERR_ARG;
-        if (cam[17] == 1.0f && !(cam[15] > 0.0f)) return TPG_ERR_ARG;       // pinhole divides by zv >= near
-    }
+    if (!rd_cams_ok(cams, ncam)) return TPG_ERR_ARG;
     if (W > TPG_RENDER_MAX_EXTENT || H > TPG_RENDER_MAX_EXTENT || F > 65535) return TPG_ERR_UNSUPPORTED;
     const long long pixels = (long long)F * H * W;
     if (pixels > (1ll << 31)) return TPG_ERR_UNSUPPORTED;       // 16 GiB of keys: the caller renders F in chunks
@@ -137,16 +102,14 @@ extern "C" int tpg_render_points_f32(const float *points, const int64_t *lengths
     const int blocks = (N + RD_THREADS - 1) / RD_THREADS;
     RenderCams rc;
     if (ncam == 1) {
-        for (int g = 0; g < RD_GROUP; ++g)
-            for (int j = 0; j < RD_CAM; ++j) rc.c[g][j] = cams[j];
+        rd_fill_cams(rc, cams, 1, 0, F);
         hipLaunchKernelGGL(render_splat_kernel, dim3(blocks, F), dim3(RD_THREADS), 0, st, points, lengths, rc, 0, 0, N, W,
                            H, size, (tpg_u64 *)keys);
         TPG_RETURN_IF_LAUNCH_FAILED();
     } else {
         for (int f0 = 0; f0 < F; f0 += RD_GROUP) {
             const int nf = F - f0 < RD_GROUP ? F - f0 : RD_GROUP;
-            for (int g = 0; g < RD_GROUP; ++g)
-                for (int j = 0; j < RD_CAM; ++j) rc.c[g][j] = cams[(size_t)(f0 + (g < nf ? g : 0)) * RD_CAM + j];
+            rd_fill_cams(rc, cams, ncam, f0, nf);
             hipLaunchKernelGGL(render_splat_kernel, dim3(blocks, nf), dim3(RD_THREADS), 0, st, points, lengths, rc, 1, f0,
                                N, W, H, size, (tpg_u64 *)keys);
             TPG_RETURN_IF_LAUNCH_FAILED();

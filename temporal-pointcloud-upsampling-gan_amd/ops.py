@@ -338,6 +338,40 @@ class HipBackend:
                        lo, hi, _ptr(lut), _ptr(background), _ptr(keys), _ptr(image[f0:f1]), _ptr(winner[f0:f1]))
         return image, winner
 
+    def render_surface(self, points, lengths, scalar, cams, W, H, radius, lo, hi, lut, background, half_width, iters,
+                       delta, shade, max_key_bytes):
+        """csrc/surface.hip: sphere fronts, `iters` smoothing passes, shading; cams and shade are host fp32 arrays.
+        -> (image (F,H,W,3) uint8, depth (F,H,W) fp32, winner (F,H,W) int32).  Frames go in chunks as in
+        `render_points`; the keys and the two depth buffers the passes alternate between are per-stream workspaces, and
+        the last pass of a chunk writes into the returned depth."""
+        F, N, _ = points.shape
+        dev = points.device
+        image = torch.empty((F, H, W, 3), dtype=torch.uint8, device=dev)
+        depth = torch.empty((F, H, W), dtype=torch.float32, device=dev)
+        winner = torch.empty((F, H, W), dtype=torch.int32, device=dev)
+        chunk = max(1, min(65535, int(max_key_bytes) // (8 * H * W)))
+        held = min(chunk, F) * H * W
+        keys = self._workspace("render_keys", points, held, dtype=torch.int64)
+        ping = [self._workspace(f"surface_depth{j}", points, held) for j in range(2)] if iters > 0 else []
+        for f0 in range(0, F, chunk):
+            f1 = min(F, f0 + chunk)
+            n, pix = f1 - f0, (f1 - f0) * H * W
+            c = cams if cams.shape[0] == 1 else np.ascontiguousarray(cams[f0:f1])
+            src = ping[0] if iters > 0 else depth[f0:f1]
+            self._call("tpg_render_spheres_f32", "render_spheres", 12 * n * N + 24 * pix, points, _ptr(points[f0:f1]),
+                       _ptr(None if lengths is None else lengths[f0:f1]), n, N, c.ctypes.data, c.shape[0], W, H, radius,
+                       _ptr(keys), _ptr(src), _ptr(winner[f0:f1]))
+            for it in range(iters):
+                dst = depth[f0:f1] if it == iters - 1 else ping[(it + 1) % 2]
+                self._call("tpg_surface_smooth_f32", "surface_smooth", 8 * pix, points, _ptr(src), n, W, H, half_width,
+                           delta, _ptr(dst))
+                src = dst
+            self._call("tpg_surface_shade_f32", "surface_shade", 11 * pix + (4 * pix if scalar is not None else 0), points,
+                       _ptr(depth[f0:f1]), _ptr(winner[f0:f1]), _ptr(None if scalar is None else scalar[f0:f1]), n, N,
+                       c.ctypes.data, c.shape[0], W, H, lo, hi, _ptr(lut), _ptr(background), shade.ctypes.data,
+                       _ptr(image[f0:f1]))
+        return image, depth, winner
+
     def chamfer_fwd(self, src, tgt):
         B, N, _ = src.shape
         M = tgt.shape[1]
@@ -1765,27 +1799,14 @@ def _render_points_torch(points, lengths, scalar, cams, W, H, size, lo, hi, lut,
     return image, winner
 
 
-def render_points(points, cams, width, height, lut, size=1, lengths=None, scalar=None, lo=None, hi=None,
-                  background=(255, 255, 255), max_key_bytes=RENDER_KEY_BYTES):
-    """One picture per cloud of a ragged batch: a z-buffered square splat (csrc/render.hip; the rule in full:
-    include/tpgan_ops.h).
-
-    points (F,N,3) fp32; lengths (F,) or None: rows at or beyond lengths[f] are never read; scalar (F,N) fp32 or None:
-    what a point is coloured by (None: its depth t = zv - near).  cams: HOST fp32, (18,) / (1,18) shared by all frames
-    or (F,18) one per frame: eye, the rows r / d / f (image-right, image-DOWN, forward), scale, cx, cy, near, far, mode
-    (`render.Camera.row()` builds one).  lut (256,3) uint8 and background (3 values 0..255); the colour is lut[level]
-    with c = (s - lo) * (255 / (hi - lo)), level = 0 unless c > 0, 255 from c >= 255, else int(c + 0.5); lo / hi
-    default to 0 and far - near of the first camera when the colour is the depth, and must be given with `scalar`.
-    size: the splat's edge in pixels, 1..16.  max_key_bytes: cap of the kernel's 64-bit key buffer; F is rendered in
-    chunks that stay under it (the pictures do not depend on it).
-    -> (image (F,height,width,3) uint8, winner (F,height,width) int32: the visible point's index, -1 = background).
-    Bit-identical from run to run and at every batch position; no gradient."""
+def _picture_args(points, cams, width, height, lut, lengths, scalar, lo, hi, background, max_key_bytes):
+    """What `render_points` and `render_surface` ask of their common arguments; -> F, N, W, H, cams (host fp32 (1 or
+    F, 18)), scalar, lo, hi (rounded to fp32), lut and background (uint8 on the points' device), lengths."""
     _check_float(points, "points", 3)
     _need(points.shape[2] == 3, "points must be (F,N,3)")
     F, N, _ = points.shape
-    W, H, size = int(width), int(height), int(size)
+    W, H = int(width), int(height)
     _need(1 <= W <= RENDER_MAX_EXTENT and 1 <= H <= RENDER_MAX_EXTENT, f"width and height must be 1..{RENDER_MAX_EXTENT}")
-    _need(1 <= size <= RENDER_MAX_SIZE, f"size must be 1..{RENDER_MAX_SIZE}")
     _need(int(max_key_bytes) > 0, "max_key_bytes must be positive")
     if isinstance(cams, torch.Tensor):
         _need(not cams.is_cuda, "cams is a host table: pass a CPU tensor or a numpy array")
@@ -1814,6 +1835,28 @@ def render_points(points, cams, width, height, lut, size=1, lengths=None, scalar
     _need(bg.shape == (3,) and bg.dtype.kind in "iu" and 0 <= bg.min() and bg.max() <= 255, "background must be 3 values 0..255")
     background = torch.tensor(bg.tolist(), dtype=torch.uint8).to(points.device)
     lengths = _lengths(lengths, F, N, points.device)
+    return F, N, W, H, cams, scalar, lo, hi, lut, background, lengths
+
+
+def render_points(points, cams, width, height, lut, size=1, lengths=None, scalar=None, lo=None, hi=None,
+                  background=(255, 255, 255), max_key_bytes=RENDER_KEY_BYTES):
+    """One picture per cloud of a ragged batch: a z-buffered square splat (csrc/render.hip; the rule in full:
+    include/tpgan_ops.h).
+
+    points (F,N,3) fp32; lengths (F,) or None: rows at or beyond lengths[f] are never read; scalar (F,N) fp32 or None:
+    what a point is coloured by (None: its depth t = zv - near).  cams: HOST fp32, (18,) / (1,18) shared by all frames
+    or (F,18) one per frame: eye, the rows r / d / f (image-right, image-DOWN, forward), scale, cx, cy, near, far, mode
+    (`render.Camera.row()` builds one).  lut (256,3) uint8 and background (3 values 0..255); the colour is lut[level]
+    with c = (s - lo) * (255 / (hi - lo)), level = 0 unless c > 0, 255 from c >= 255, else int(c + 0.5); lo / hi
+    default to 0 and far - near of the first camera when the colour is the depth, and must be given with `scalar`.
+    size: the splat's edge in pixels, 1..16.  max_key_bytes: cap of the kernel's 64-bit key buffer; F is rendered in
+    chunks that stay under it (the pictures do not depend on it).
+    -> (image (F,height,width,3) uint8, winner (F,height,width) int32: the visible point's index, -1 = background).
+    Bit-identical from run to run and at every batch position; no gradient."""
+    size = int(size)
+    _need(1 <= size <= RENDER_MAX_SIZE, f"size must be 1..{RENDER_MAX_SIZE}")
+    F, N, W, H, cams, scalar, lo, hi, lut, background, lengths = _picture_args(
+        points, cams, width, height, lut, lengths, scalar, lo, hi, background, max_key_bytes)
     if F == 0 or N == 0:
         return (background.view(1, 1, 1, 3).expand(F, H, W, 3).contiguous(),
                 torch.full((F, H, W), -1, dtype=torch.int32, device=points.device))
@@ -1824,6 +1867,68 @@ def render_points(points, cams, width, height, lut, size=1, lengths=None, scalar
         if hasattr(be, "render_points"):
             return be.render_points(*args, int(max_key_bytes))
         return _render_points_torch(*args)
+
+
+# ---------------------------------------------------------------------- fluid surface pictures (csrc/surface.hip)
+SURFACE_MAX_RADIUS = 64                # pixels: a nearer or larger sphere is drawn as a disc of this radius
+SURFACE_MAX_HALF = 4                   # the smoothing window's half-width, 1..4
+SURFACE_SHADE_FLOATS = 11              # L, Hh, ka, kd, ks, kf, p: include/tpgan_ops.h
+
+
+def surface_shade(light=(-0.4, -0.6, -0.7), ka=0.25, kd=0.65, ks=0.35, kf=0.25, p=5):
+    """The 11 floats `render_surface` shades with: `light` is the direction TOWARDS the light in view coordinates (x
+    right, y down, z forward; the default comes from up, left and in front of the surface) and is normalised here, Hh
+    is the unit half vector of it and the direction to the viewer (0,0,-1); ambient ka, diffuse kd, specular ks with
+    the exponent 2^p (p an integer 0..8), kf the weight of the Fresnel rim (1 - max(-nz, 0))^5.  Host maths in
+    float64, rounded to fp32 once."""
+    L = np.asarray(light, dtype=np.float64).reshape(3)
+    n = float(np.linalg.norm(L))
+    _need(np.isfinite(n) and n > 0.0, "light must be a finite non-zero vector")
+    L = L / n
+    half = L + np.array([0.0, 0.0, -1.0])
+    h = float(np.linalg.norm(half))
+    _need(h > 1e-9, "the light must not shine from straight behind the surface")
+    _need(int(p) == p and 0 <= int(p) <= 8, "p must be an integer 0..8")
+    table = np.concatenate([L, half / h, [ka, kd, ks, kf, float(int(p))]]).astype(np.float32)
+    _need(bool(np.isfinite(table).all()), "the shading table must be finite")
+    return table
+
+
+def render_surface(points, cams, width, height, lut, radius, lengths=None, scalar=None, lo=None, hi=None, half_width=2,
+                   iters=3, delta=None, shade=None, background=(255, 255, 255), max_key_bytes=RENDER_KEY_BYTES):
+    """One picture of the fluid's SURFACE per cloud of a ragged batch: screen-space fluid rendering (csrc/surface.hip;
+    the rule in full: include/tpgan_ops.h).  Every point is a sphere of `radius` world units; the nearest sphere front
+    per pixel is kept, that depth image is smoothed `iters` times (a binomial window of half-width `half_width` = 1..4
+    that leaves out neighbours further than `delta` in depth, default 2 x radius, so silhouettes stay sharp and the
+    background stays background; iters = 0 shades the raw sphere fronts), normals are taken from the smoothed depth and
+    it is shaded with `shade` (`surface_shade()`: 11 host floats) over the colour lut[level] of `scalar` (None: of the
+    depth).  points, cams, width, height, lut, lengths, scalar, lo, hi, background and max_key_bytes are
+    `render_points`'s.  Needs the HIP backend: there is no composition of torch ops for it.
+    -> (image (F,height,width,3) uint8, depth (F,height,width) fp32: the smoothed front's distance from the near plane,
+    +inf = background, winner (F,height,width) int32: the point whose sphere is in front, -1 = background).
+    Bit-identical from run to run, at every batch position and under every chunking; no gradient."""
+    F, N, W, H, cams, scalar, lo, hi, lut, background, lengths = _picture_args(
+        points, cams, width, height, lut, lengths, scalar, lo, hi, background, max_key_bytes)
+    radius = float(np.float32(radius))
+    _need(np.isfinite(radius) and radius > 0.0, "radius must be positive and finite")
+    half_width, iters = int(half_width), int(iters)
+    _need(1 <= half_width <= SURFACE_MAX_HALF, f"half_width must be 1..{SURFACE_MAX_HALF}")
+    _need(iters >= 0, "iters must not be negative")
+    delta = float(np.float32(2.0 * radius if delta is None else delta))
+    _need(np.isfinite(delta) and delta > 0.0, "delta must be positive and finite")
+    shade = surface_shade() if shade is None else np.ascontiguousarray(np.asarray(shade, dtype=np.float32).reshape(-1))
+    _need(shade.shape == (SURFACE_SHADE_FLOATS,) and bool(np.isfinite(shade).all()),
+          f"shade must be {SURFACE_SHADE_FLOATS} finite floats (surface_shade() builds them)")
+    _need(shade[10] == int(shade[10]) and 0 <= shade[10] <= 8, "p must be an integer 0..8")
+    if F == 0 or N == 0:
+        return (background.view(1, 1, 1, 3).expand(F, H, W, 3).contiguous(),
+                torch.full((F, H, W), float("inf"), dtype=torch.float32, device=points.device),
+                torch.full((F, H, W), -1, dtype=torch.int32, device=points.device))
+    be = backend_for(points)
+    _need(hasattr(be, "render_surface"), "this backend has no render_surface")
+    with torch.no_grad():
+        return be.render_surface(points.detach(), lengths, None if scalar is None else scalar.detach(), cams, W, H,
+                                 radius, lo, hi, lut, background, half_width, iters, delta, shade, int(max_key_bytes))
 
 
 def cubic_interpolation(query_pos, field, pos, cutoff):

@@ -2,14 +2,17 @@
 
     python -m tpgan_amd.render --frames 'bunny_demo/pcd_{i}.npy' --count 800 --out PNGDIR
         [--size 3 --width 768 --height 768 --mode pinhole --color depth|density|free_surface
-         --cutoff 0.0775 --direction x y z --frames_per_call T]
+         --cutoff 0.0775 --direction x y z --frames_per_call T
+         --style points|surface --particle_radius 0.025 --smooth_iters 3 --smooth_half_width 2]
 
 The reference looks at its results through an Open3D window (train_utils.py:224-238) and hands its demo frames to an
 external renderer; neither works on a display-less GPU node.  Here a picture is one op, `ops.render_points`
 (csrc/render.hip): a z-buffered square splat, many frames per call, the same bits on every run.  This file is the thin
 layer above it: `Camera` (host maths in float64, rounded to fp32 once), the colour of a point (its depth, or the
 density / free surface / speed the project already computes on the device), a closed-form colour ramp and a PNG writer
-on the standard library.  The look is this project's own: no parity with Open3D's picture is claimed.
+on the standard library.  `--style surface` draws the fluid's surface instead of its particles, `ops.render_surface`
+(csrc/surface.hip): spheres, a depth image smoothed within silhouettes, normals, shading -- what the reference leaves to
+an external renderer.  The look is this project's own: no parity with Open3D's or any renderer's picture is claimed.
 """
 import argparse
 import os
@@ -24,6 +27,7 @@ from . import analysis, ops
 PADDING = 900.0                # rows with any |coordinate| >= this are the 999 padding of hard masking, not points
 FRAMES_PER_CALL = 16
 MODES = {"ortho": ops.RENDER_ORTHO, "pinhole": ops.RENDER_PINHOLE}
+STYLES = ("points", "surface")
 
 
 def _unit(v, what):
@@ -176,14 +180,9 @@ def point_scalar(points, color, lengths=None, cutoff=None, radius=analysis.BASE_
     raise ValueError(f"unknown color {color!r}")
 
 
-def render(points, camera, color=None, size=3, lengths=None, lo=None, hi=None, cutoff=None, radius=analysis.BASE_RADIUS,
-           velocity=None, lut=None, background=(255, 255, 255), return_winner=False,
-           max_key_bytes=ops.RENDER_KEY_BYTES):
-    """Pictures of a cloud (N,3) -> (H,W,3) uint8, or of a batch (F,N,3) with optional lengths (F,) -> (F,H,W,3), on the
-    points' device.  camera: one `Camera` for all frames or a list of F.  color: None / "depth" (the distance from the
-    near plane, range 0 .. far - near), "density", "free_surface", "speed" (`point_scalar`), or a tensor (F,N) / (N,)
-    of values per point.  lo / hi: the values that map to the ramp's ends; taken from the finite values when not
-    given.  return_winner: also the (F,H,W) int32 map of the visible point per pixel (-1: background)."""
+def _prepare(points, camera, color, lengths, lo, hi, cutoff, radius, velocity):
+    """What `render` and `render_surface` do with their common arguments -> (single, points (F,N,3) fp32, cameras,
+    scalar (F,N) or None, lo, hi)."""
     single = points.dim() == 2
     pts = points.detach().float().contiguous()
     pts = pts.unsqueeze(0) if single else pts
@@ -205,12 +204,43 @@ def render(points, camera, color=None, size=3, lengths=None, lo=None, hi=None, c
             lo, hi = a if lo is None else lo, b if hi is None else hi
         if not hi > lo:
             hi = lo + 1.0
+    return single, pts, cams, scalar, lo, hi
+
+
+def render(points, camera, color=None, size=3, lengths=None, lo=None, hi=None, cutoff=None, radius=analysis.BASE_RADIUS,
+           velocity=None, lut=None, background=(255, 255, 255), return_winner=False,
+           max_key_bytes=ops.RENDER_KEY_BYTES):
+    """Pictures of a cloud (N,3) -> (H,W,3) uint8, or of a batch (F,N,3) with optional lengths (F,) -> (F,H,W,3), on the
+    points' device.  camera: one `Camera` for all frames or a list of F.  color: None / "depth" (the distance from the
+    near plane, range 0 .. far - near), "density", "free_surface", "speed" (`point_scalar`), or a tensor (F,N) / (N,)
+    of values per point.  lo / hi: the values that map to the ramp's ends; taken from the finite values when not
+    given.  return_winner: also the (F,H,W) int32 map of the visible point per pixel (-1: background)."""
+    single, pts, cams, scalar, lo, hi = _prepare(points, camera, color, lengths, lo, hi, cutoff, radius, velocity)
     image, winner = ops.render_points(pts, np.stack([c.row() for c in cams]), cams[0].width, cams[0].height,
                                       default_lut() if lut is None else lut, size, lengths, scalar, lo, hi, background,
                                       max_key_bytes)
     if single:
         image, winner = image[0], winner[0]
     return (image, winner) if return_winner else image
+
+
+def render_surface(points, camera, particle_radius=analysis.BASE_RADIUS, color=None, lengths=None, lo=None, hi=None,
+                   cutoff=None, radius=analysis.BASE_RADIUS, velocity=None, lut=None, background=(255, 255, 255),
+                   half_width=2, iters=3, delta=None, light=None, return_depth=False, return_winner=False,
+                   max_key_bytes=ops.RENDER_KEY_BYTES):
+    """Pictures of the fluid's SURFACE (`ops.render_surface`: every point a sphere of `particle_radius`, the nearest
+    fronts smoothed `iters` times over a window of half-width `half_width` without crossing depth steps above `delta`,
+    default 2 x particle_radius, then shaded).  points, camera, color, lengths, lo, hi, cutoff, radius, velocity, lut
+    and background are `render`'s and give the surface's base colour.  light: the direction towards the light in view
+    coordinates (x right, y down, z forward; None: `ops.surface_shade()`'s).  return_depth / return_winner: also the
+    smoothed depth (F,H,W) fp32 (+inf: background) / the (F,H,W) int32 map of the point in front."""
+    single, pts, cams, scalar, lo, hi = _prepare(points, camera, color, lengths, lo, hi, cutoff, radius, velocity)
+    out = ops.render_surface(pts, np.stack([c.row() for c in cams]), cams[0].width, cams[0].height,
+                             default_lut() if lut is None else lut, particle_radius, lengths, scalar, lo, hi, half_width,
+                             iters, delta, None if light is None else ops.surface_shade(light), background, max_key_bytes)
+    image, depth, winner = (o[0] for o in out) if single else out
+    extra = ((depth,) if return_depth else ()) + ((winner,) if return_winner else ())
+    return (image,) + extra if extra else image
 
 
 def write_png(path, image):
@@ -244,12 +274,18 @@ class SequenceRenderer:
     """Pictures of a sequence, `pcd_{i:04d}.png` in `out_dir`, under ONE camera: fitted to the frames of the first
     `push` unless `camera` is given.  The range of a "density" colour is that of the first `push` as well, so the
     pictures of a sequence are comparable.  `push(frames, first)`: frames = list of (n_t,3) clouds, first = index of
-    the first one; they are rendered in one call."""
+    the first one; they are rendered in one call.  style: "points" (`render`, squares of `size` pixels) or "surface"
+    (`render_surface`: spheres of `particle_radius`, `smooth_iters` passes of half-width `half_width`)."""
 
     def __init__(self, out_dir, size=3, width=768, height=768, mode="pinhole", color="depth", cutoff=None,
-                 direction=(0.0, 0.0, -1.0), camera=None, device="cuda"):
+                 direction=(0.0, 0.0, -1.0), camera=None, device="cuda", style="points",
+                 particle_radius=analysis.BASE_RADIUS, smooth_iters=3, half_width=2):
         if color not in ("depth", "density", "free_surface"):
             raise ValueError("color must be depth, density or free_surface")
+        if style not in STYLES:
+            raise ValueError(f"style must be one of {STYLES}")
+        self.style, self.particle_radius = style, float(particle_radius)
+        self.smooth_iters, self.half_width = int(smooth_iters), int(half_width)
         self.out_dir, self.size, self.width, self.height, self.mode = out_dir, int(size), int(width), int(height), mode
         self.color, self.cutoff, self.direction, self.camera = color, cutoff, tuple(direction), camera
         self.device, self.range = torch.device(device), (None, None)
@@ -268,7 +304,12 @@ class SequenceRenderer:
         if self.color == "density" and lo is None:
             s = point_scalar(batch, "density", lengths, self.cutoff)
             self.range = lo, hi = 0.0, max(_finite_range(s, lengths)[1], 1e-12)
-        images = render(batch, self.camera, self.color, self.size, lengths, lo, hi, self.cutoff).cpu().numpy()
+        if self.style == "surface":
+            images = render_surface(batch, self.camera, self.particle_radius, self.color, lengths, lo, hi, self.cutoff,
+                                    half_width=self.half_width, iters=self.smooth_iters)
+        else:
+            images = render(batch, self.camera, self.color, self.size, lengths, lo, hi, self.cutoff)
+        images = images.cpu().numpy()
         for t, image in enumerate(images):
             write_png(os.path.join(self.out_dir, f"pcd_{first + t:04d}.png"), image)
 
@@ -282,10 +323,19 @@ def add_render_options(ap):
     ap.add_argument("--cutoff", type=float, default=0.0775, help="density cutoff of --color density")
     ap.add_argument("--direction", type=float, nargs=3, default=(0.0, 0.0, -1.0), metavar=("X", "Y", "Z"),
                     help="viewing direction (y is up)")
+    ap.add_argument("--style", choices=STYLES, default="points",
+                    help="points: a square per point; surface: the shaded fluid surface")
+    ap.add_argument("--particle_radius", type=float, default=analysis.BASE_RADIUS,
+                    help="--style surface: a point's sphere radius in world units")
+    ap.add_argument("--smooth_iters", type=int, default=3, help="--style surface: smoothing passes over the depth")
+    ap.add_argument("--smooth_half_width", type=int, default=2,
+                    help="--style surface: half-width of the smoothing window, 1..4")
 
 
 def renderer_from(a, out_dir, device):
-    return SequenceRenderer(out_dir, a.size, a.width, a.height, a.mode, a.color, a.cutoff, a.direction, device=device)
+    return SequenceRenderer(out_dir, a.size, a.width, a.height, a.mode, a.color, a.cutoff, a.direction, device=device,
+                            style=a.style, particle_radius=a.particle_radius, smooth_iters=a.smooth_iters,
+                            half_width=a.smooth_half_width)
 
 
 def load_frame(path):

@@ -11,7 +11,8 @@ Reference semantics, kept on purpose: the body is called as `net.body(feature, N
 neighbours in the 6-D feature space (this project's `SRNet.forward_with_context` differs there: INTEGRATION.md).
 
     python -m tpgan_amd.rollout --checkpoint X.ckpt --frames 'dir/data_{i}.npz' --count 800 [--in-feats 6] --out DIR
-        [--render PNGDIR --size 3 --width 768 --height 768 --mode pinhole --color depth --direction 0 0 -1]
+        [--render PNGDIR --size 3 --width 768 --height 768 --mode pinhole --color depth --direction 0 0 -1
+         --style points|surface --particle_radius 0.025 --smooth_iters 3 --smooth_half_width 2]
 
 --render writes one picture per frame (render.SequenceRenderer) from each chunk's outputs while they are still on the
 device; the camera is fitted to the first chunk.
