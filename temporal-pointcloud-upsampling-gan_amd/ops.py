@@ -892,7 +892,7 @@ class HipBackend:
 
     def mlp_bn_bwd_apply(self, g, x, ci, c12, nseg, K=0):
         """dx of the tail's first BatchNorm; K > 0: also qneg (P/K, C) f32 = -sum over each group of K rows of dx
-        (the ROW_SUB gather's gradient of Q, see _RowCombine.backward) -> (dx, qneg)."""
+        (the ROW_SUB gather's gradient of Q, see _GatherMlpTail.backward) -> (dx, qneg)."""
         P, Cc = x.shape
         dx = torch.empty_like(x)
         if K:
@@ -2029,51 +2029,6 @@ def chamfer_nn(src, tgt):
 ROW_GATHER, ROW_SUB, ROW_EDGE = 0, 1, 2
 
 
-# Hand-off between two autograd nodes: a fused tail's backward (_MlpTail) writes its input gradient dx0 group by group
-# and has each group's row sum in registers; when dx0 then arrives at the ROW_SUB gather that made the tail's input,
-# that node needs exactly those sums (gQ[s] = -sum_k dx0[s,k]) and would read all of dx0 again for them.  The slot
-# holds (dx0, qneg, K) of the LAST tail backward -- a strong reference, so dx0's memory cannot have been handed to
-# another tensor while the slot is full, and "same pointer, size and type" means "these very rows".  A gradient that
-# was accumulated with another (a new tensor) or anything else simply does not match and takes the ordinary path.
-# One slot PER DEVICE (autograd runs one backward thread per device, two devices must not race on a shared
-# slot), and an offer REPLACES whatever an earlier tail left behind (a tail whose input did not come from a ROW_SUB
-# gather never has its offer taken: the next tail's offer, or the next gather's look, drops it).
-class _RowsumSlots(dict):
-    """device index -> (dx0, qneg, K); `slots[0]` reads / clears EVERY device's slot (tests, the A/B switch)."""
-
-    def __getitem__(self, key):
-        if key == 0 and 0 not in self:
-            return next((v for v in self.values() if v is not None), None)
-        return dict.get(self, key)
-
-
-_ROWSUM_SLOT = _RowsumSlots()
-_ROWSUM_HANDOFF = [True]
-
-
-def set_rowsum_handoff(flag):
-    """A/B and test switch for the hand-off above; returns the previous setting."""
-    prev, _ROWSUM_HANDOFF[0] = _ROWSUM_HANDOFF[0], bool(flag)
-    _ROWSUM_SLOT.clear()
-    return prev
-
-
-def _offer_rowsum(dx0, qneg, K):
-    _ROWSUM_SLOT[("dev", dx0.device.index)] = (dx0, qneg, K)
-
-
-def _take_rowsum(gout):
-    """qneg if gout (B,S,K,C) is the dx0 of its device's slot, else None; empties that slot either way."""
-    slot = _ROWSUM_SLOT.pop(("dev", gout.device.index), None)
-    if slot is None:
-        return None
-    dx0, qneg, K = slot
-    if (gout.data_ptr() == dx0.data_ptr() and gout.numel() == dx0.numel() and gout.dtype == dx0.dtype
-            and gout.dim() == 4 and gout.shape[2] == K and gout.shape[3] == dx0.shape[1]):
-        return qneg
-    return None
-
-
 class _RowCombine(torch.autograd.Function):
     @staticmethod
     def forward(ctx, U, QE, idx, mode, slope, out_dtype, inverse):
@@ -2092,12 +2047,6 @@ class _RowCombine(torch.autograd.Function):
         if gout.dtype not in _DTYPE_CODE:
             gout = gout.float()
         kw = {} if ctx.inverse is None else {"inverse": ctx.inverse}
-        ready = _take_rowsum(gout) if (ctx.mode == ROW_SUB and ctx.in_dtype == torch.float32) else None
-        if ready is not None:
-            # the producer of gout (a fused tail's backward) has summed its rows over k already: what is left of the
-            # SUB backward is the plain gather's scatter
-            gU, _ = backend_for(gout).rowcombine_bwd(gout, idx, None, ROW_GATHER, ctx.N, ctx.slope, ctx.in_dtype, **kw)
-            return gU, (ready.view(gout.shape[0], gout.shape[1], gout.shape[3]) if ctx.has_q else None), None, None, None, None, None
         gU, gQE = backend_for(gout).rowcombine_bwd(gout, idx, E, ctx.mode, ctx.N, ctx.slope, ctx.in_dtype, **kw)
         return gU, (gQE if ctx.has_q else None), None, None, None, None, None
 
@@ -2322,6 +2271,78 @@ def row_act_max(x, slope, K, out_dtype=None):
 MLP_CHANNELS = ((64, 64), (64, 128), (128, 64), (128, 128), (128, 256), (256, 128), (256, 256))
 
 
+def _mlp_tail_fwd(x0, cfg, tensors):
+    """Forward body of the fused tail (`_MlpTail`): -> (out, the tensors its backward body reads)."""
+    nseg, K, slopes, eps, moms, states, shifts = cfg
+    be = backend_for(x0)
+    L = (len(tensors) - 2) // 3
+    gam = [tensors[0]] + [tensors[3 * l + 3] for l in range(L)]
+    bet = [tensors[1]] + [tensors[3 * l + 4] for l in range(L)]
+    Ws = [tensors[3 * l + 2] for l in range(L)]
+    xs, cis = [x0], []
+    rm, rv, nbt = states[0]
+    cis.append(be.rowbn_stats(x0, eps[0], moms[0], rm, rv, nbt, nseg, shifts[0], consts=(gam[0], bet[0]))[2])  # sc | sh | mu | rs
+    for l in range(L):
+        rm, rv, nbt = states[l + 1]
+        y, ci, *mr = be.mlp_fwd(xs[-1], cis[-1], slopes[l], Ws[l], nseg, eps[l + 1], moms[l + 1], rm, rv, nbt,
+                                shifts[l + 1], gam[l + 1], bet[l + 1], mean_rstd=(l == L - 1))
+        xs.append(y)
+        cis.append(ci)
+    mean_L, rstd_L = mr                          # of the last BatchNorm, written by the same finalize launch
+    out, arg = be.rowbn_apply_max(xs[-1], K, mean_L, rstd_L, gam[-1], bet[-1], slopes[L], torch.bfloat16, nseg)
+    return out, (*xs, *cis, *gam, *bet, *Ws, mean_L, rstd_L, out, *([arg] if arg is not None else []))
+
+
+def _mlp_tail_bwd(saved, cfg, gout, need, want_dx, want_sums=False):
+    """Backward body of the fused tail on what `_mlp_tail_fwd` saved; cfg = (nseg, K, slopes); need: which of gamma_0,
+    beta_0, [W_l, gamma_l, beta_l]*L want a gradient; want_dx: so does x_0; want_sums: the launch that writes dx0 also
+    writes qneg (P/K, C_0) f32 = -(its sum over each group of K rows) -> (dx0, qneg, the gradients in `need`'s order)."""
+    (nseg, K, slopes), t = cfg, list(saved)
+    n = len(slopes)
+    L = n - 1
+    xs, cis, gam, bet = t[:n], t[n:2 * n], t[2 * n:3 * n], t[3 * n:4 * n]
+    Ws = t[4 * n:4 * n + L]
+    mean_L, rstd_L, out = t[4 * n + L:4 * n + L + 3]
+    arg = t[4 * n + L + 3] if K else None
+    be = backend_for(xs[0])
+    gout = gout.contiguous()
+    if gout.dtype != torch.bfloat16:
+        gout = gout.to(torch.bfloat16)
+    need_aff = [need[0] or need[1]] + [need[3 * l + 3] or need[3 * l + 4] for l in range(L)]
+    need_w = [need[3 * l + 2] for l in range(L)]
+    grads_aff = [None] * n
+    grads_w = [None] * L
+    # the last BatchNorm (+ act, + max): its sums come from (gout, out) alone
+    c12, dg, db, cb, ag = be.rowbn_bwd_sums(gout, xs[L], arg, out if K else None, K, mean_L, rstd_L, gam[L], bet[L],
+                                            slopes[L], need_aff[L], nseg, want_cb=True)
+    grads_aff[L] = (dg, db)
+    # the arriving gradient lives on each group's arg-max row: a * lrelu'(y) * gout per (group, channel)
+    # (normally a by-product of the reduction above)
+    g_next, arg_next, K_next = (ag if ag is not None else be.mlp_max_prep(gout, out, cb, slopes[L], nseg)), arg, K
+    for l in range(L, 0, -1):                    # layer l: x_{l-1} -> x_l
+        if need_w[l - 1]:
+            grads_w[l - 1] = be.mlp_wgrad(xs[l], g_next, arg_next, K_next, cb, xs[l - 1], cis[l - 1], slopes[l - 1],
+                                          nseg)
+        g_in, c12, cb, dg, db = be.mlp_dgrad(xs[l], g_next, arg_next, K_next, cb, xs[l - 1], cis[l - 1],
+                                             slopes[l - 1], Ws[l - 1], nseg, need_aff[l - 1])
+        grads_aff[l - 1] = (dg, db)
+        g_next, arg_next, K_next = g_in, None, 0
+    dx0 = qneg = None
+    if want_dx and want_sums:
+        dx0, qneg = be.mlp_bn_bwd_apply(g_next, xs[0], cis[0], c12, nseg, K)
+    elif want_dx:
+        dx0 = be.mlp_bn_bwd_apply(g_next, xs[0], cis[0], c12, nseg)
+    grads = [grads_aff[0][0], grads_aff[0][1]]
+    for l in range(L):
+        gw = grads_w[l]
+        if gw is not None and Ws[l].dim() == 2:
+            gw = gw.sum(0) if gw.shape[0] > 1 else gw[0]
+        elif gw is not None and Ws[l].shape[0] != gw.shape[0]:
+            gw = gw.sum(0, keepdim=True)
+        grads += [gw, grads_aff[l + 1][0], grads_aff[l + 1][1]]
+    return dx0, qneg, grads
+
+
 class _MlpTail(torch.autograd.Function):
     """[BN_0 + act] -> W_1 -> [BN_1 + act] -> ... -> W_L -> [BN_L + act (+ max over K)] on bf16 rows, every
     BatchNorm in training mode, `nseg` calls of the tail in one pass (csrc/mlp_fused.hip).
@@ -2335,76 +2356,47 @@ class _MlpTail(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x0, cfg, *tensors):
-        nseg, K, slopes, eps, moms, states, shifts = cfg
-        be = backend_for(x0)
-        L = (len(tensors) - 2) // 3
-        gam = [tensors[0]] + [tensors[3 * l + 3] for l in range(L)]
-        bet = [tensors[1]] + [tensors[3 * l + 4] for l in range(L)]
-        Ws = [tensors[3 * l + 2] for l in range(L)]
-        xs, cis = [x0], []
-        rm, rv, nbt = states[0]
-        cis.append(be.rowbn_stats(x0, eps[0], moms[0], rm, rv, nbt, nseg, shifts[0], consts=(gam[0], bet[0]))[2])  # sc | sh | mu | rs
-        for l in range(L):
-            rm, rv, nbt = states[l + 1]
-            y, ci, *mr = be.mlp_fwd(xs[-1], cis[-1], slopes[l], Ws[l], nseg, eps[l + 1], moms[l + 1], rm, rv, nbt,
-                                    shifts[l + 1], gam[l + 1], bet[l + 1], mean_rstd=(l == L - 1))
-            xs.append(y)
-            cis.append(ci)
-        mean_L, rstd_L = mr                          # of the last BatchNorm, written by the same finalize launch
-        out, arg = be.rowbn_apply_max(xs[-1], K, mean_L, rstd_L, gam[-1], bet[-1], slopes[L], torch.bfloat16, nseg)
-        ctx.save_for_backward(*xs, *cis, *gam, *bet, *Ws, mean_L, rstd_L, out, *([arg] if arg is not None else []))
-        ctx.cfg = (nseg, K, slopes, L)
+        out, saved = _mlp_tail_fwd(x0, cfg, tensors)
+        ctx.save_for_backward(*saved)
+        ctx.cfg = cfg[:3]
         return out
 
     @staticmethod
     def backward(ctx, gout):
-        nseg, K, slopes, L = ctx.cfg
-        t = list(ctx.saved_tensors)
-        n = L + 1
-        xs, cis, gam, bet = t[:n], t[n:2 * n], t[2 * n:3 * n], t[3 * n:4 * n]
-        Ws = t[4 * n:4 * n + L]
-        mean_L, rstd_L, out = t[4 * n + L:4 * n + L + 3]
-        arg = t[4 * n + L + 3] if K else None
-        be = backend_for(xs[0])
-        gout = gout.contiguous()
-        if gout.dtype != torch.bfloat16:
-            gout = gout.to(torch.bfloat16)
-        # which gradients are wanted: (x0, cfg, gamma_0, beta_0, [W, gamma, beta]*L)
-        need = ctx.needs_input_grad
-        need_aff = [need[2] or need[3]] + [need[3 * l + 5] or need[3 * l + 6] for l in range(L)]
-        need_w = [need[3 * l + 4] for l in range(L)]
-        grads_aff = [None] * n
-        grads_w = [None] * L
-        # the last BatchNorm (+ act, + max): its sums come from (gout, out) alone
-        c12, dg, db, cb, ag = be.rowbn_bwd_sums(gout, xs[L], arg, out if K else None, K, mean_L, rstd_L, gam[L], bet[L],
-                                                slopes[L], need_aff[L], nseg, want_cb=True)
-        grads_aff[L] = (dg, db)
-        # the arriving gradient lives on each group's arg-max row: a * lrelu'(y) * gout per (group, channel)
-        # (normally a by-product of the reduction above)
-        g_next, arg_next, K_next = (ag if ag is not None else be.mlp_max_prep(gout, out, cb, slopes[L], nseg)), arg, K
-        for l in range(L, 0, -1):                    # layer l: x_{l-1} -> x_l
-            if need_w[l - 1]:
-                grads_w[l - 1] = be.mlp_wgrad(xs[l], g_next, arg_next, K_next, cb, xs[l - 1], cis[l - 1], slopes[l - 1],
-                                              nseg)
-            g_in, c12, cb, dg, db = be.mlp_dgrad(xs[l], g_next, arg_next, K_next, cb, xs[l - 1], cis[l - 1],
-                                                 slopes[l - 1], Ws[l - 1], nseg, need_aff[l - 1])
-            grads_aff[l - 1] = (dg, db)
-            g_next, arg_next, K_next = g_in, None, 0
-        dx0 = None
-        if need[0] and K and _ROWSUM_HANDOFF[0]:
-            dx0, qneg = be.mlp_bn_bwd_apply(g_next, xs[0], cis[0], c12, nseg, K)
-            _offer_rowsum(dx0, qneg, K)              # for the ROW_SUB gather this tail's input came from, if any
-        elif need[0]:
-            dx0 = be.mlp_bn_bwd_apply(g_next, xs[0], cis[0], c12, nseg)
-        res = [dx0, None, grads_aff[0][0], grads_aff[0][1]]
-        for l in range(L):
-            gw = grads_w[l]
-            if gw is not None and Ws[l].dim() == 2:
-                gw = gw.sum(0) if gw.shape[0] > 1 else gw[0]
-            elif gw is not None and Ws[l].shape[0] != gw.shape[0]:
-                gw = gw.sum(0, keepdim=True)
-            res += [gw, grads_aff[l + 1][0], grads_aff[l + 1][1]]
-        return tuple(res)
+        need = ctx.needs_input_grad                  # (x0, cfg, gamma_0, beta_0, [W, gamma, beta]*L)
+        dx0, _, grads = _mlp_tail_bwd(ctx.saved_tensors, ctx.cfg, gout, need[2:], need[0])
+        return (dx0, None, *grads)
+
+
+class _GatherMlpTail(torch.autograd.Function):
+    """The ROW_SUB gather of (U, Q, idx) into bf16 rows and the fused tail (`_MlpTail`) on them as ONE node: the tail's
+    last backward launch writes the rows' gradient dx0 group by group with each group's sum in registers, and those sums
+    are the gather's gradient of Q (gQ[s] = -sum_k dx0[s,k]): dx0 is read once, by the plain gather's scatter."""
+
+    @staticmethod
+    def forward(ctx, U, Q, idx, inverse, cfg, *tensors):
+        rows = backend_for(U).rowcombine_fwd(U, Q, idx, ROW_SUB, 0.0, torch.bfloat16)
+        out, saved = _mlp_tail_fwd(rows.view(-1, rows.shape[3]), cfg, tensors)
+        ctx.save_for_backward(idx, *saved)
+        ctx.inverse = inverse          # (offs, lst) int32 tensors prepared ahead of time, or None
+        ctx.cfg, ctx.N, ctx.in_dtype = cfg[:3], U.shape[1], U.dtype
+        return out.view(idx.shape[0], idx.shape[1], -1)
+
+    @staticmethod
+    def backward(ctx, gout):
+        idx, *saved = ctx.saved_tensors
+        need = ctx.needs_input_grad                  # (U, Q, idx, inverse, cfg, gamma_0, beta_0, [W, gamma, beta]*L)
+        want_dx = need[0] or need[1]
+        sums = ctx.in_dtype == torch.float32         # (fp32 tables: the sums are gQ as they are; bf16: the SUB backward)
+        dx0, qneg, grads = _mlp_tail_bwd(saved, ctx.cfg, gout.reshape(-1, gout.shape[-1]), need[5:], want_dx, sums)
+        gU = gQ = None
+        if want_dx:
+            kw = {} if ctx.inverse is None else {"inverse": ctx.inverse}
+            gU, gQ = backend_for(dx0).rowcombine_bwd(dx0.view(*idx.shape, -1), idx, None, ROW_GATHER if sums else ROW_SUB,
+                                                     ctx.N, 0.0, ctx.in_dtype, **kw)
+            if sums:
+                gQ = qneg.view(idx.shape[0], idx.shape[1], -1)
+        return (gU, gQ, None, None, None, *grads)
 
 
 _IDENT = {}
@@ -2515,22 +2507,16 @@ def small_tail(h, W1, W2, slope1, slope2, K):
     return _SmallTail.apply(h.contiguous(), W1, W2, float(slope1), float(slope2), int(K))
 
 
-def mlp_tail_supported(x, channels, K):
-    """Can `mlp_tail` run this tail?  bf16 rows on the GPU, supported channel pairs, a max over K."""
-    if not (x.is_cuda and x.dtype == torch.bfloat16 and 0 < K <= 255 and len(channels) >= 2):
+def mlp_tail_supported(x, channels, K, rows_dtype=None):
+    """Can `mlp_tail` run this tail on the rows x (`gather_mlp_tail`: on rows of `rows_dtype` gathered from the table
+    x)?  bf16 rows on the GPU, supported channel pairs, a max over K."""
+    if not (x.is_cuda and (rows_dtype or x.dtype) == torch.bfloat16 and 0 < K <= 255 and len(channels) >= 2):
         return False
     return all((a, b) in MLP_CHANNELS for a, b in zip(channels[:-1], channels[1:]))
 
 
-def mlp_tail(x0, bns, weights, slopes, K, nseg=1, shifts=None):
-    """The tail of a shared MLP on bf16 rows x0 (P, C_0), fused on MFMA tiles (csrc/mlp_fused.hip):
-
-        out = max_K lrelu(BN_L(W_L ... lrelu(BN_1(W_1 lrelu(BN_0(x0))))))          (P/K, C_L) bf16
-
-    bns: the L+1 BatchNorm modules (training mode, fixed momentum; state updated like their own forward),
-    weights: L tensors (C_l, C_{l-1}) or (nseg, C_l, C_{l-1}) fp32 (e.g. successive spectral-norm iterates),
-    slopes: L+1 LeakyReLU slopes, nseg: calls of the tail on equal consecutive row blocks,
-    shifts: per BatchNorm an optional bias of the preceding conv that was left out of its input."""
+def _mlp_tail_args(bns, weights, slopes, K, nseg, shifts):
+    """The validated (cfg, tensors) of `_mlp_tail_fwd` from what `mlp_tail` is given."""
     L = len(weights)
     _need(len(bns) == L + 1 and len(slopes) == L + 1 and L >= 1, "mlp_tail: L weights, L+1 BatchNorms / slopes")
     _need(all(0.0 <= float(sl) <= 1.0 for sl in slopes), "mlp_tail: LeakyReLU slopes in [0, 1] (lrelu = max(z, slope*z))")
@@ -2550,7 +2536,36 @@ def mlp_tail(x0, bns, weights, slopes, K, nseg=1, shifts=None):
         tensors += [w.contiguous(), bns[l + 1].weight.float(), bns[l + 1].bias.float()]
     cfg = (int(nseg), int(K), tuple(float(s) for s in slopes), tuple(eps), tuple(moms), tuple(states),
            tuple(None if s is None else s.detach().float().contiguous() for s in shifts))
+    return cfg, tensors
+
+
+def mlp_tail(x0, bns, weights, slopes, K, nseg=1, shifts=None):
+    """The tail of a shared MLP on bf16 rows x0 (P, C_0), fused on MFMA tiles (csrc/mlp_fused.hip):
+
+        out = max_K lrelu(BN_L(W_L ... lrelu(BN_1(W_1 lrelu(BN_0(x0))))))          (P/K, C_L) bf16
+
+    bns: the L+1 BatchNorm modules (training mode, fixed momentum; state updated like their own forward),
+    weights: L tensors (C_l, C_{l-1}) or (nseg, C_l, C_{l-1}) fp32 (e.g. successive spectral-norm iterates),
+    slopes: L+1 LeakyReLU slopes, nseg: calls of the tail on equal consecutive row blocks,
+    shifts: per BatchNorm an optional bias of the preceding conv that was left out of its input."""
+    cfg, tensors = _mlp_tail_args(bns, weights, slopes, K, nseg, shifts)
     return _MlpTail.apply(x0.contiguous(), cfg, *tensors)
+
+
+def gather_mlp_tail(U, Q, idx, bns, weights, slopes, nseg=1, shifts=None):
+    """The training-mode counterpart of `gather_mlp_max`: `mlp_tail` (K = idx's last axis) on the bf16 rows
+    U[b,idx[b,s,j],:] - Q[b,s,:] of `row_combine` (ROW_SUB) as ONE autograd node -> (B,S,C_L) bf16.
+    U (B,N,C_0) fp32 or bf16, Q (B,S,C_0), idx (B,S,K) int32 or a NeighbourList into N rows (its prepared inverse goes
+    to the backward); the rest as `mlp_tail` takes it.  The launches and bits of the two ops one after the other, except
+    that with fp32 tables the backward's last tail launch is tpg_mlp_bn_bwd_apply_rowsum (see _GatherMlpTail)."""
+    _need(U.dim() == 3 and U.dtype in _DTYPE_CODE, "U (B,N,C) fp32/bf16, idx (B,S,K) int32")
+    nl = neighbour_list(idx, U.shape[1])
+    idx = nl.idx
+    _need(U.shape[0] == idx.shape[0], "batch mismatch")
+    _need(Q is not None and Q.shape == (U.shape[0], idx.shape[1], U.shape[2]), "Q must be (B,S,C)")
+    _need(U.shape[2] % 8 == 0, f"channel count {U.shape[2]} must be a multiple of 8")
+    cfg, tensors = _mlp_tail_args(bns, weights, slopes, idx.shape[2], nseg, shifts)
+    return _GatherMlpTail.apply(U.contiguous(), Q.to(U.dtype).contiguous(), idx, nl.inverse, cfg, *tensors)
 
 
 # ------------------------------------------- eval-mode tail in one launch (csrc/mlp_infer.hip)

@@ -20,6 +20,7 @@ weight, same single power iteration per call) is applied to the N un-grouped row
 BatchNorm over the (B*S*ns) row axis -- the same statistics as BatchNorm2d over (B,S,ns).
 """
 import contextlib
+import functools
 from typing import List
 
 import numpy as np
@@ -208,6 +209,11 @@ def conv_weights_seg(conv, nseg):
     return torch.stack([conv_weight2d(conv) for _ in range(nseg)])
 
 
+def _rows_matmul_seg(x, w):
+    """`rows_matmul_seg` on rows with leading axes, as `rows_matmul` takes them: x (..., Cin), w (nseg, Cout, Cin)."""
+    return rows_matmul_seg(x.reshape(-1, x.shape[-1]), w).view(*x.shape[:-1], -1)
+
+
 def _segmentable(layers, x, K):
     """Can `nseg` calls of this tail run as ONE segmented pass?  Every conv must be followed by a
     BatchNorm + (Leaky)ReLU pair the fused kernel takes (training-mode statistics, fixed
@@ -229,9 +235,10 @@ def _segmentable(layers, x, K):
     return K <= 256 and x.shape[-1] % 8 == 0 and x.shape[-1] <= 1024
 
 
-def _parse_tail(layers):
-    """[BN, act, (conv, BN, act)*] -> (BatchNorms, convs, slopes), else None: the shape of tail the
-    fused MFMA kernels take (ops.mlp_tail)."""
+def _parse_tail(layers, training=True):
+    """[BN, act, (conv, BN, act)*] -> (BatchNorms, convs, slopes), else None: the shape of tail the fused kernels
+    take.  training: every BatchNorm must also be what ops.mlp_tail takes (training mode, fixed momentum, affine);
+    the eval-mode conditions of ops.gather_mlp_max are `_fused_eval_ok`'s."""
     bns, convs, slopes = [], [], []
     i, n = 0, len(layers)
     while i < n:
@@ -243,7 +250,7 @@ def _parse_tail(layers):
         if i + 1 >= n or not isinstance(layers[i], (nn.BatchNorm2d, nn.BatchNorm1d)):
             return None
         bn, slope = layers[i], _act_slope(layers[i + 1])
-        if slope is None or not (bn.training and bn.momentum is not None and bn.affine):
+        if slope is None or (training and not (bn.training and bn.momentum is not None and bn.affine)):
             return None
         bns.append(bn)
         slopes.append(slope)
@@ -254,37 +261,28 @@ def _parse_tail(layers):
 FUSED_TAILS = [True]      # ops.mlp_tail for bf16 tails (off: the separate BN / GEMM launches, for A/B runs)
 
 
-def _try_fused_tail(bns, convs, slopes, x, K, nseg):
-    """x (P,C0) rows -> (P/K, C_L) through ops.mlp_tail, or None when the tail is not one it takes."""
-    if not (FUSED_TAILS[0] and x.is_cuda and x.dtype == torch.bfloat16 and rows_first()):
+def _fused_tail_weights(convs, x, K, nseg, rows_dtype=None):
+    """The weights of a tail on the rows x (or on `rows_dtype` rows gathered from the table x) when the fused training
+    kernels take it, else None (and no spectral-norm weight is consumed)."""
+    if not (FUSED_TAILS[0] and x.is_cuda and rows_first()):
         return None
     chans = [x.shape[-1]] + [c.out_channels for c in convs]
-    if not ops.mlp_tail_supported(x, chans, K) or any(c.in_channels != a for c, a in zip(convs, chans[:-1])):
+    if not ops.mlp_tail_supported(x, chans, K, rows_dtype) or any(c.in_channels != a for c, a in zip(convs, chans[:-1])):
         return None
-    Ws = [(conv_weights_seg(c, nseg) if nseg > 1 else conv_weight2d(c)).float() for c in convs]
-    return ops.mlp_tail(x, bns, Ws, slopes, K, nseg, shifts=[None] + [c.bias for c in convs])
+    return [(conv_weights_seg(c, nseg) if nseg > 1 else conv_weight2d(c)).float() for c in convs]
 
 
-def _parse_eval_tail(layers):
-    """[BN, act, (conv, BN, act)*] -> (BatchNorms, convs, slopes), else None: `_parse_tail` without its training-mode
-    condition (the eval-mode conditions are `_fused_eval_ok`'s)."""
-    bns, convs, slopes = [], [], []
-    i, n = 0, len(layers)
-    while i < n:
-        if i > 0:
-            if not isinstance(layers[i], nn.Conv2d) or layers[i].kernel_size != (1, 1):
-                return None
-            convs.append(layers[i])
-            i += 1
-        if i + 1 >= n or not isinstance(layers[i], (nn.BatchNorm2d, nn.BatchNorm1d)):
-            return None
-        slope = _act_slope(layers[i + 1])
-        if slope is None:
-            return None
-        bns.append(layers[i])
-        slopes.append(slope)
-        i += 2
-    return (bns, convs, slopes) if convs else None
+def _try_fused_tail(bns, convs, slopes, x, K, nseg):
+    """x (P,C0) rows -> (P/K, C_L) through ops.mlp_tail, or None when the tail is not one it takes."""
+    Ws = _fused_tail_weights(convs, x, K, nseg)
+    return None if Ws is None else ops.mlp_tail(x, bns, Ws, slopes, K, nseg, shifts=[None] + [c.bias for c in convs])
+
+
+def _try_gather_tail(bns, convs, slopes, U, Q, idx, nseg, rows_dtype):
+    """Tables U (B,N,C0), Q (B,S,C0), idx (B,S,K) -> (B,S,C_L) through ops.gather_mlp_tail (the gather into `rows_dtype`
+    rows included), or None where `_try_fused_tail` would not take those rows: gather them and go layer by layer."""
+    Ws = _fused_tail_weights(convs, U, _list_k(idx), nseg, rows_dtype)
+    return None if Ws is None else ops.gather_mlp_tail(U, Q, idx, bns, Ws, slopes, nseg, [None] + [c.bias for c in convs])
 
 
 def _fused_eval_ok(first_conv, bns, convs, K, inputs):
@@ -536,9 +534,9 @@ class _PointnetSAModuleBase(nn.Module):
         g = self.groupers[0]
         return centres, new_xyz, ops.NeighbourList(ops.ball_query(g.radius, g.nsample, xyz, new_xyz), xyz.shape[1])
 
-    def _first_layer(self, grouper, mlp, xyz, new_xyz, feat_rows, idx=None, tables=False):
+    def _first_layer(self, grouper, mlp, xyz, new_xyz, feat_rows, idx=None):
         """Rows of the first conv's output for every grouped position: (B,S,ns,C1).
-        tables (QueryAndGroup with use_xyz only): the un-gathered (U, Q, idx) instead."""
+        QueryAndGroup with use_xyz: the un-gathered (U, Q, idx) instead, for `_sub_tail`."""
         conv = mlp[0]
         rows_dtype = amp_dtype(xyz)           # decided OUTSIDE the fp32 island below
         with no_autocast(xyz):
@@ -552,10 +550,7 @@ class _PointnetSAModuleBase(nn.Module):
             if idx is None:
                 idx = ops.ball_query(grouper.radius, grouper.nsample, xyz, new_xyz)
             if grouper.use_xyz:
-                Q = rows_matmul(new_xyz, W[:, :3])                  # centre term of (xyz_j - c_i)
-                if tables:
-                    return U, Q, idx
-                return ops.row_combine(U, Q, idx, ops.ROW_SUB, out_dtype=rows_dtype)
+                return U, rows_matmul(new_xyz, W[:, :3]), idx       # Q: centre term of (xyz_j - c_i)
             return ops.row_combine(U, None, idx, ops.ROW_GATHER, out_dtype=rows_dtype)
 
     def forward_rows(self, xyz, feat_rows, plan=None):
@@ -573,14 +568,12 @@ class _PointnetSAModuleBase(nn.Module):
             new_xyz = None
         outs = []
         for grouper, mlp in zip(self.groupers, self.mlps):
-            if rows_first():
-                tail = self._eval_tail(grouper, mlp, [xyz, feat_rows])
-                if tail is not None:
-                    outs.append(_fused_eval_tail(*tail, *self._first_layer(grouper, mlp, xyz, new_xyz, feat_rows, pidx,
-                                                                           tables=True)))
-                    continue
+            if rows_first() and isinstance(grouper, QueryAndGroup) and grouper.use_xyz:
+                tables = self._first_layer(grouper, mlp, xyz, new_xyz, feat_rows, pidx)
+                outs.append(self._sub_tail(grouper, mlp, *tables, [xyz, feat_rows], amp_dtype(xyz)))   # (B,S,C')
+            elif rows_first():
                 y = self._first_layer(grouper, mlp, xyz, new_xyz, feat_rows, pidx)
-                outs.append(mlp_tail_rows(list(mlp)[1:], y, reduce_max=True))   # (B,S,C')
+                outs.append(mlp_tail_rows(list(mlp)[1:], y, reduce_max=True))
             else:                                                  # discriminator.py:139-150
                 planes = None if feat_rows is None else feat_rows.float().transpose(1, 2).contiguous()
                 g = mlp(grouper(xyz, new_xyz, planes))             # (B,C',S,ns)
@@ -591,10 +584,26 @@ class _PointnetSAModuleBase(nn.Module):
         """(BatchNorms, convs, slopes) when this grouper's tail takes the one-launch eval path, else None."""
         if not (self.fused_eval and self.npoint is not None and isinstance(grouper, QueryAndGroup) and grouper.use_xyz):
             return None
-        tail = _parse_eval_tail(list(mlp)[1:])
+        tail = _parse_tail(list(mlp)[1:], training=False)
         if tail is None or not _fused_eval_ok(mlp[0], tail[0], tail[1], grouper.nsample, inputs):
             return None
         return tail
+
+    def _sub_tail(self, grouper, mlp, U, Q, idx, inputs, rows_dtype, nseg=1):
+        """The layers of `mlp` behind its first conv on the rows U[idx] - Q (tables of `_first_layer`), `nseg` calls in
+        one pass -> (B,S,C') rows: the one-launch eval tail, the fused training tail (ops.gather_mlp_tail, gather
+        included), or the gathered rows layer by layer."""
+        layers, K = list(mlp)[1:], _list_k(idx)
+        tail = self._eval_tail(grouper, mlp, inputs) if K == grouper.nsample else None
+        if tail is not None:                 # eval mode: the nseg calls are one call on the stacked clouds
+            return _fused_eval_tail(*tail, U, Q, idx)
+        tail = _parse_tail(layers)
+        if tail is not None and (nseg == 1 or _segmentable(layers, U, K)):
+            out = _try_gather_tail(*tail, U, Q, idx, nseg, rows_dtype)
+            if out is not None:
+                return out
+        y = ops.row_combine(U, Q, idx, ops.ROW_SUB, out_dtype=rows_dtype)        # (B, S, K, C1)
+        return mlp_tail_rows(layers, y, reduce_max=True, nseg=nseg)
 
     def frames_stackable(self):
         single = len(self.groupers) == 1 and isinstance(self.groupers[0], QueryAndGroup)
@@ -627,28 +636,19 @@ class _PointnetSAModuleBase(nn.Module):
         assert self.frames_stackable()
         grouper, mlp = self.groupers[0], self.mlps[0]
         xyz = xyz.float().contiguous()
-        NB, N, _ = xyz.shape
         centres = plan[0] if plan is not None else self.sample_centres(xyz)
         new_xyz = _gather_centres(xyz, centres)
         idx = plan[1] if plan is not None else ops.ball_query(grouper.radius, grouper.nsample, xyz, new_xyz)
-        S = new_xyz.shape[1]
         conv = mlp[0]
-        rows_dtype = amp_dtype(xyz)
         with no_autocast(xyz):
             # first conv BEFORE the gather, per call with that call's weight: y = U[idx] - Q,
             # U = W_s [xyz|feat] (all points), Q = W_s[:, :3] centre - bias (bias folded into Q)
             W = conv_weights_seg(conv, nseg).float()                           # (nseg, C1, Cin)
-            src = xyz if feat is None else torch.cat([xyz, feat.float()], dim=-1)
-            U = rows_matmul_seg(src.view(NB * N, -1), W).view(NB, N, -1)
-            Q = rows_matmul_seg(new_xyz.view(NB * S, 3), W[:, :, :3].contiguous()).view(NB, S, -1)
+            U = _rows_matmul_seg(xyz if feat is None else torch.cat([xyz, feat.float()], dim=-1), W)
+            Q = _rows_matmul_seg(new_xyz, W[:, :, :3].contiguous())
             if conv.bias is not None:
                 Q = Q - conv.bias.float()
-        tail = self._eval_tail(grouper, mlp, [xyz, feat]) if _list_k(idx) == grouper.nsample else None
-        if tail is not None:                 # eval mode: the nseg calls are one call on the stacked clouds
-            return new_xyz, _fused_eval_tail(*tail, U, Q, idx)
-        y = ops.row_combine(U, Q, idx, ops.ROW_SUB, out_dtype=rows_dtype)        # (nseg*B, S, K, C1)
-        feats = mlp_tail_rows(list(mlp)[1:], y, reduce_max=True, nseg=nseg)     # (nseg*B, S, C')
-        return new_xyz, feats
+        return new_xyz, self._sub_tail(grouper, mlp, U, Q, idx, [xyz, feat], amp_dtype(xyz), nseg)   # (nseg*B, S, C')
 
     def forward_rows_pool_stacked(self, xyz, feat, nseg):
         """`nseg` calls of a GroupAll level (npoint None: one group holding all N points) in one
@@ -722,17 +722,20 @@ class FlowEmbedding(nn.Module):
         return self.fused_eval and _fused_eval_ok(self.mlp_convs[0], list(self.mlp_bns), list(self.mlp_convs)[1:],
                                                   _list_k(idx), inputs)
 
-    def forward_rows(self, p1, p2, f1, f2, radius, idx=None):
+    def forward_rows(self, p1, p2, f1, f2, radius, idx=None, nseg=1):
         """p (B,N,3), f (B,N,C) rows -> (B,N,mlp[-1]) rows; idx = precomputed neighbour list.
+        nseg > 1: `nseg` calls of this layer in one pass, stacked along the cloud axis in call order (B = nseg * the
+        batch of a call): batched GEMMs with the calls' successive weights, segmented BatchNorm passes.  One stacked
+        segment is the single call (2-D weights), whichever entry it came through.
 
         First conv on cat([pos2_j - pos1_i, feat2_j, feat1_i]) (discriminator.py:270-280) split
         by input columns: U = W[:, :3+C] [pos2|feat2] is gathered, Q = W[:, :3] pos1 - W[:, 3+C:] feat1
         is the per-centre term."""
         C = f1.shape[-1]
+        B, N, _ = p1.shape
         if idx is None:
             idx = ball_query_wrapper(radius, self.NSAMPLE, p1, p2).to(torch.int32).contiguous()
-        if not rows_first():                         # discriminator.py:270-283
-            B, N, _ = p1.shape
+        if nseg == 1 and not rows_first():           # discriminator.py:270-283
             pos1, pos2 = p1.transpose(1, 2).contiguous(), p2.transpose(1, 2).contiguous()
             pos_diff = ops.grouping_operation(pos2.float(), idx) - pos1.view(B, -1, N, 1)
             feat2 = ops.grouping_operation(f2.float().transpose(1, 2).contiguous(), idx)
@@ -741,58 +744,39 @@ class FlowEmbedding(nn.Module):
             for conv, bn in zip(self.mlp_convs, self.mlp_bns):
                 x = F.leaky_relu(bn(conv(x)))
             return torch.max(x, -1)[0].transpose(1, 2)
+        weight, matmul = conv_weight2d, rows_matmul
+        if nseg > 1:                                 # weights (nseg, Cout, Cin), one per call
+            weight, matmul = functools.partial(conv_weights_seg, nseg=nseg), _rows_matmul_seg
         with no_autocast(p1):
-            W = conv_weight2d(self.mlp_convs[0]).float()
-            U = rows_matmul(torch.cat([p2.float(), f2.float()], dim=-1), W[:, :3 + C])
-            Q = rows_matmul(p1.float(), W[:, :3]) - rows_matmul(f1.float(), W[:, 3 + C:])
+            W = weight(self.mlp_convs[0]).float()                                  # ([nseg,] C1, 3+2C)
+            Wu, Wp, Wf = (w.contiguous() if nseg > 1 else w for w in (W[..., :3 + C], W[..., :3], W[..., 3 + C:]))
+            U = matmul(torch.cat([p2.float(), f2.float()], dim=-1), Wu)
+            Q = matmul(p1.float(), Wp) - matmul(f1.float(), Wf)
+        bns, convs, K = list(self.mlp_bns), list(self.mlp_convs)[1:], _list_k(idx)
+        slopes = [0.01] * len(bns)                                 # F.leaky_relu default slope 0.01
         if self._eval_tail_ok(idx, [p1, p2, f1, f2]):
-            return _fused_eval_tail(list(self.mlp_bns), list(self.mlp_convs)[1:], [0.01] * len(self.mlp_convs), U, Q, idx)
-        x = ops.row_combine(U, Q, idx, ops.ROW_SUB, out_dtype=amp_dtype(p1))     # (B,N,32,C1)
-        B, N, K, _ = x.shape
-        x = x.view(B * N * K, -1)
-        nl = len(self.mlp_convs)
-        if all(bn.training and bn.momentum is not None for bn in self.mlp_bns):
-            out = _try_fused_tail(list(self.mlp_bns), list(self.mlp_convs)[1:], [0.01] * nl, x, K, 1)
+            return _fused_eval_tail(bns, convs, slopes, U, Q, idx)
+        if all(bn.training and bn.momentum is not None for bn in bns):
+            out = _try_gather_tail(bns, convs, slopes, U, Q, idx, nseg, amp_dtype(p1))
             if out is not None:
-                return out.view(B, N, -1)
-        for l in range(nl):                                        # F.leaky_relu default slope 0.01
+                return out
+        x = ops.row_combine(U, Q, idx, ops.ROW_SUB, out_dtype=amp_dtype(p1))     # (B,N,32,C1)
+        x = x.view(B * N * K, -1)
+        for l, bn in enumerate(bns):
             if l:
-                x = rows_matmul(x, conv_weight2d(self.mlp_convs[l]))
-            last = l == nl - 1
-            if _fusable(x, K if last else 0):
-                x = bn_act_rows(self.mlp_bns[l], x, 0.01, K if last else 0)
+                x = matmul(x, weight(convs[l - 1]))
+            last = l == len(bns) - 1
+            if nseg > 1 or _fusable(x, K if last else 0):
+                x = bn_act_rows(bn, x, slopes[l], K if last else 0, nseg=nseg)
             else:
-                x = F.leaky_relu(bn_rows(self.mlp_bns[l], x))
+                x = F.leaky_relu(bn_rows(bn, x))
                 if last:
                     x = x.view(B * N, K, -1).max(dim=1)[0]
         return x.view(B, N, -1)
 
     def forward_rows_stacked(self, p1, p2, f1, f2, idx, nseg):
-        """`nseg` calls of this layer in one pass (calls stacked along the cloud axis, in call
-        order): p (nseg*B,N,3), f (nseg*B,N,C), idx (nseg*B,N,32) -> (nseg*B,N,mlp[-1])."""
-        C = f1.shape[-1]
-        NB, N, _ = p1.shape
-        with no_autocast(p1):
-            W = conv_weights_seg(self.mlp_convs[0], nseg).float()              # (nseg, C1, 3+2C)
-            U = rows_matmul_seg(torch.cat([p2.float(), f2.float()], dim=-1).view(NB * N, -1),
-                                W[:, :, :3 + C].contiguous()).view(NB, N, -1)
-            Q = (rows_matmul_seg(p1.float().reshape(NB * N, 3), W[:, :, :3].contiguous())
-                 - rows_matmul_seg(f1.float().reshape(NB * N, C), W[:, :, 3 + C:].contiguous())).view(NB, N, -1)
-        if self._eval_tail_ok(idx, [p1, p2, f1, f2]):
-            return _fused_eval_tail(list(self.mlp_bns), list(self.mlp_convs)[1:], [0.01] * len(self.mlp_convs), U, Q, idx)
-        x = ops.row_combine(U, Q, idx, ops.ROW_SUB, out_dtype=amp_dtype(p1))     # (nseg*B,N,32,C1)
-        K = x.shape[2]
-        x = x.view(NB * N * K, -1)
-        nl = len(self.mlp_convs)
-        if all(bn.training and bn.momentum is not None for bn in self.mlp_bns):
-            out = _try_fused_tail(list(self.mlp_bns), list(self.mlp_convs)[1:], [0.01] * nl, x, K, nseg)
-            if out is not None:
-                return out.view(NB, N, -1)
-        for l in range(nl):                                        # F.leaky_relu default slope 0.01
-            if l:
-                x = rows_matmul_seg(x, conv_weights_seg(self.mlp_convs[l], nseg))
-            x = bn_act_rows(self.mlp_bns[l], x, 0.01, K if l == nl - 1 else 0, nseg=nseg)
-        return x.view(NB, N, -1)
+        """`forward_rows` on `nseg` stacked calls: p (nseg*B,N,3), f (nseg*B,N,C), idx (nseg*B,N,32)."""
+        return self.forward_rows(p1, p2, f1, f2, None, idx, nseg)
 
     def forward(self, pos1, pos2, feature1, feature2, radius):
         """Reference signature: pos (B,3,N), feature (B,C,N) -> pos1, (B,mlp[-1],N)."""

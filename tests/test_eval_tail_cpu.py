@@ -55,5 +55,5 @@ def test_cpu_rows_and_other_shapes_stay_on_the_per_layer_path(oracle_cpu):
     assert level._eval_tail(level.groupers[0], level.mlps[0], [xyz, xyz]) is None      # CPU tensors: today's path
     with torch.no_grad():
         assert level.forward_rows(xyz, xyz)[1].shape == (2, 4, 128)
-    tail = SA._parse_eval_tail(list(level.mlps[0])[1:])
+    tail = SA._parse_tail(list(level.mlps[0])[1:], training=False)
     assert tail is not None and [c.out_channels for c in tail[1]] == [128] and tail[2] == [0.0, 0.0]

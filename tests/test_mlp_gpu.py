@@ -220,39 +220,61 @@ def test_mlp_tail_is_bitwise_reproducible():
         assert torch.equal(a, b)
 
 
-@pytest.mark.parametrize("C,K,S,nseg", [(64, 32, 256, 1), (64, 12, 300, 2), (128, 7, 96, 3)])
-def test_tail_hands_its_row_sums_to_the_gather_that_fed_it(C, K, S, nseg):
-    """A set-abstraction level is row_combine(ROW_SUB) -> fused tail.  The tail's backward sums its input gradient
-    over each group of K rows while writing it (tpg_mlp_bn_bwd_apply_rowsum) and the gather's backward takes those
-    sums as the gradient of Q instead of reading the rows again: same bits as the two-pass route, and a gradient
-    that is NOT the tail's own tensor (here: accumulated with a second consumer's) must not pick the sums up."""
+def _gather_tail_case(C, K, S, nseg, fused, table_dtype=torch.float32, inverse=False, need_u=True, need_q=True,
+                      second=False):
+    """row_combine(ROW_SUB) -> mlp_tail on fixed inputs, as the two ops (`fused` False) or as ops.gather_mlp_tail:
+    -> [out, the gradients of whichever of U, Q is wanted, of W and of every BatchNorm affine, the running statistics]."""
     import tpgan_amd.ops as ops
     torch.manual_seed(C + K)
     B, N = 2 * nseg, 500
-    U0 = torch.randn(B, N, C, device="cuda")
-    Q0 = torch.randn(B, S, C, device="cuda")
+    U = torch.randn(B, N, C, device="cuda").to(table_dtype).requires_grad_(need_u)
+    Q = torch.randn(B, S, C, device="cuda").to(table_dtype).requires_grad_(need_q)
     idx = torch.randint(0, N, (B, S, K), device="cuda", dtype=torch.int32)
     W = (torch.randn(128, C) / C ** 0.5).cuda().requires_grad_(True)
-    res = {}          # (the inverted index keeps entry order: the scatter sums are reproducible, bits can be compared)
-    for tag, handoff, second in (("two-pass", False, False), ("handed", True, False), ("shared", True, True)):
-        prev = ops.set_rowsum_handoff(handoff)
-        try:
-            bns = [torch.nn.BatchNorm1d(c).cuda().train() for c in (C, 128)]
-            U, Q = U0.clone().requires_grad_(True), Q0.clone().requires_grad_(True)
-            y = ops.row_combine(U, Q, idx, ops.ROW_SUB, out_dtype=torch.bfloat16)
-            out = ops.mlp_tail(y.view(-1, C), bns, [W], [0.01, 0.01], K, nseg)
-            loss = (out.float() * torch.linspace(-1, 1, out.numel(), device="cuda").view_as(out)).sum()
-            if second:
-                loss = loss + y.float().square().sum() * 1e-3
-            res[tag] = torch.autograd.grad(loss, [U, Q])
-            assert ops._ROWSUM_SLOT[0] is None or second        # taken (and emptied) by the gather's backward
-        finally:
-            ops.set_rowsum_handoff(prev)
-    for a, b in zip(res["two-pass"], res["handed"]):
-        assert torch.equal(a, b)
-    # the shared case went the ordinary way: finite, and different from the tail-only gradient
-    assert all(torch.isfinite(t).all() for t in res["shared"])
-    assert not torch.equal(res["shared"][1], res["handed"][1])
+    bns = [torch.nn.BatchNorm1d(c).cuda().train() for c in (C, 128)]
+    lst = ops.attach_inverse(idx, N) if inverse else idx
+    if fused:
+        out = ops.gather_mlp_tail(U, Q, lst, bns, [W], [0.01, 0.01], nseg).view(-1, 128)
+    else:
+        y = ops.row_combine(U, Q, lst, ops.ROW_SUB, out_dtype=torch.bfloat16)
+        out = ops.mlp_tail(y.view(-1, C), bns, [W], [0.01, 0.01], K, nseg)
+    loss = (out.float() * torch.linspace(-1, 1, out.numel(), device="cuda").view_as(out)).sum()
+    if second:
+        loss = loss + y.float().square().sum() * 1e-3
+    wrt = [t for t in (U, Q) if t.requires_grad] + [W] + [p for bn in bns for p in (bn.weight, bn.bias)]
+    stats = [t.clone() for bn in bns for t in (bn.running_mean, bn.running_var, bn.num_batches_tracked)]
+    return [out.detach()] + list(torch.autograd.grad(loss, wrt)) + stats
+
+
+@pytest.mark.parametrize("C,K,S,nseg", [(64, 32, 256, 1), (64, 12, 300, 2), (128, 7, 96, 3)])
+def test_tail_hands_its_row_sums_to_the_gather_that_fed_it(C, K, S, nseg):
+    """A set-abstraction level is row_combine(ROW_SUB) -> fused tail.  As ONE node (ops.gather_mlp_tail) the tail's
+    backward sums its input gradient over each group of K rows while writing it (tpg_mlp_bn_bwd_apply_rowsum) and the
+    gather's backward takes those sums as the gradient of Q instead of reading the rows again: same bits as the two
+    separate ops (the two-pass route) in the output, every gradient and the BatchNorms' running statistics.  On the
+    separate ops a second consumer of the gathered rows adds its gradient to the tail's, as ever."""
+    # (the inverted index keeps entry order: the scatter sums are reproducible, bits can be compared)
+    two_pass = _gather_tail_case(C, K, S, nseg, fused=False)
+    for a, b in zip(two_pass, _gather_tail_case(C, K, S, nseg, fused=True)):
+        assert a.shape == b.shape and torch.equal(a, b)
+    shared = _gather_tail_case(C, K, S, nseg, fused=False, second=True)
+    assert all(torch.isfinite(t).all() for t in shared)
+    assert not torch.equal(shared[2], two_pass[2])                       # Q's gradient
+    if nseg > 1:
+        return
+    # the node's other routes, at the first shape: a NeighbourList with a prepared inverse (also against the bare
+    # tensor), bf16 tables (plain last tail launch + the ROW_SUB backward), and fewer wanted gradients (with neither
+    # table wanting one no input gradient is computed at all)
+    for kw in (dict(inverse=True), dict(table_dtype=torch.bfloat16), dict(need_q=False), dict(need_u=False),
+               dict(need_u=False, need_q=False)):
+        want = _gather_tail_case(C, K, S, nseg, fused=False, **kw)
+        got = _gather_tail_case(C, K, S, nseg, fused=True, **kw)
+        assert len(got) == len(want) == 1 + kw.get("need_u", True) + kw.get("need_q", True) + 5 + 6, kw
+        for a, b in zip(want, got):
+            assert a.shape == b.shape and a.dtype == b.dtype and torch.equal(a, b), kw
+        if kw.get("inverse"):
+            for a, b in zip(got, _gather_tail_case(C, K, S, nseg, fused=True)):
+                assert torch.equal(a, b)
 
 
 # ------------------------------------------------------------------ EdgeConv MLP: the tail without BatchNorm
