@@ -782,6 +782,70 @@ int tpg_surface_shade_f32(const float *depth, const int32_t *winner, const float
                           int ncam, int W, int H, float lo, float hi, const uint8_t *lut, const uint8_t *background,
                           const float *shade, uint8_t *image, void *stream);
 
+/* ---- particle fluid simulator (csrc/pbf.hip) ---------------------------------------------------------------------
+ * Position Based Fluids (Macklin and Mueller 2013) with Jacobi iterations in gather form: the simulator that writes the
+ * training sequences (the reference drives an external DFSPH solver, fluid_data_generation/; look and statistics here
+ * are this project's own).  A batch holds B scenes of up to N particles: x, v, p (B,N,3) f32, lengths (B) int64 or NULL
+ * (rows at or beyond lengths[b] are never read and never written), box a HOST table (B,6) f32 (the exception stated
+ * for the clip sampler above): lo xyz, hi xyz of the scene's axis-aligned box; gravity: 3 HOST floats.
+ *
+ * Constants, computed by the host in fp64 and rounded to fp32 once: particle radius a, support h (= 4a), h2 = h*h in
+ * fp32, and with the lattice sum S0 = sum over z in Z^3, |z| < 2, of (1 - |z|^2/4)^3 (a cubic lattice of spacing
+ * s = h/2, self included; 5.15625):  wq = (1 - 0.2^2)^3 (the weight at d = 0.2 h),  dp_scale = -7 h S0 / 64,
+ * cs = c / S0.  Everything below is fp32, each operation rounded on its own (no FMA), only + - * / and sqrtf;
+ * comparisons and selections are exact.  clamp(p, l, u) per axis: p = p < l ? l : p; p = p > u ? u : p, with
+ * l = lo + a, u = hi - a.
+ *
+ * Weights of a pair at the canonical distance d2 = ((dx*dx) + dy*dy) + dz*dz, dx = p_i.x - p_j.x ...; a pair counts iff
+ * d2 < h2, STRICT (both weights vanish at the rim, so membership there cannot matter):
+ *     u = (h2 - d2) / h2;  W = (u*u)*u                       (the density weight (h^2 - d^2)^3 over h^6: <= 1, and far
+ *                                                            from the denormals the unscaled h^6 ~ 1e-8 form would meet)
+ *     d = sqrtf(d2);  t = (h - d) / h;  t2 = t*t             (the gradient weight (h - d)^2 over h^2)
+ *     G = (t2*(dx/d), t2*(dy/d), t2*(dz/d))                  (none for d2 == 0: duplicates and the particle itself add
+ *                                                            to n and have no gradient)
+ * The gradient of C_i = n_i/S0 - 1 with the spiky gradient, in these units, is g_ij = G_ij / dp_scale (poly6 over spiky
+ * normalisation: 64 / (7 h S0), pointing from i to j); the rule carries the factor outside the sums:
+ *     lambda_i (in units of dp_scale^2) = -C_i / (sum |G|^2 + |sum G|^2 + eps)
+ *     dp_i = dp_scale * sum_j (lambda_i + lambda_j + s_ij) G_ij
+ *
+ * One substep of dt = 1 / (40 * substeps), as entries:
+ *   tpg_pbf_predict_f32   v' = v + dt*gravity;  p = clamp(x + dt*v')                          -> p_out, v_out
+ *   then `iters` times, each on a grid built from the current p so that every neighbour set is exact:
+ *   tpg_pbf_grid_f32      the uniform grid of the grid searches with cell edge >= h * 1.0001, into ws
+ *   tpg_pbf_lambda_f32    n = sum W (self included);  C = n / S0 - 1;  C = C > 0 ? C : 0;
+ *                         lambda = -(C / ((sum |G|^2 + ((Sx*Sx + Sy*Sy) + Sz*Sz)) + eps)),  S = sum G,
+ *                         |G|^2 = (Gx*Gx + Gy*Gy) + Gz*Gz per pair                            -> lam, C_out (or NULL)
+ *   tpg_pbf_dp_f32        per pair r = W / wq;  r2 = r*r;  co = (lambda_i + lambda_j) + -(k*(r2*r2));  term = co * G;
+ *                         dp = dp_scale * sum term;  p_out = clamp(p + dp)  (p_out may be p; dp_out or NULL).  Reads the
+ *                         lambda of the launch before: Jacobi.
+ *   and once more tpg_pbf_grid_f32 on the final p, then
+ *   tpg_pbf_finish_f32    v_i = (p_i - x_i) / dt per axis;  per pair (self included, its term is 0)
+ *                         term = (v_j - v_i) * W;  v_out = v_i + cs * sum term;  x_out = p    (x_out != x)
+ *
+ * Sums.  The grid's order inside a cell is not fixed from run to run, so every sum is taken in 64-bit fixed point: each
+ * term converted on its own by truncation, integers added, one conversion back (round to nearest) and one multiply:
+ *     n, sum |G|^2     (uint64)(term * 2^32),  result (float)acc * 2^-32
+ *     sum G            (int64)(term * 2^32) per axis, result (float)acc * 2^-32
+ *     dp, XSPH         term clamped into [-1024, 1024] first, (int64)(term * 2^30), result (float)acc * 2^-30
+ * Terms of the first two lie within 1 + 2^-20, N <= 2^22 is checked, so no sum can wrap (csrc/pbf.hip has the
+ * arithmetic).  The results do not depend on the order of execution, the batch position or the rest of the batch.
+ *
+ * Checks, all before anything is launched.  TPG_ERR_ARG: negative B or N, h, dt, a, S0 or wq not positive and finite,
+ * eps, k or cs negative or not finite, a NULL output, x_out == x, a workspace that is NULL or not 256-byte aligned
+ * (when B, N > 0).  Then B == 0 or N == 0: TPG_OK, nothing written.  Then B > 65535 or N > 2^22: TPG_ERR_UNSUPPORTED;
+ * another NULL pointer, a box that is not finite or has lo >= hi on an axis: TPG_ERR_ARG.  ws: tpg_pbf_workspace_bytes(B,
+ * N) bytes; lambda, dp and finish read the grid the last tpg_pbf_grid_f32 with the same B, N left there. */
+size_t tpg_pbf_workspace_bytes(int B, int N);
+int tpg_pbf_predict_f32(const float *x, const float *v, const int64_t *lengths, const float *box, int B, int N, float dt,
+                        float a, const float *gravity, float *p_out, float *v_out, void *stream);
+int tpg_pbf_grid_f32(const float *p, const int64_t *lengths, int B, int N, float h, void *ws, void *stream);
+int tpg_pbf_lambda_f32(const float *p, const int64_t *lengths, int B, int N, float h, float S0, float eps, const void *ws,
+                       float *lam, float *C_out, void *stream);
+int tpg_pbf_dp_f32(const float *p, const float *lam, const int64_t *lengths, const float *box, int B, int N, float h,
+                   float a, float wq, float k, float dp_scale, const void *ws, float *p_out, float *dp_out, void *stream);
+int tpg_pbf_finish_f32(const float *p, const float *x, const int64_t *lengths, int B, int N, float h, float dt, float cs,
+                       const void *ws, float *x_out, float *v_out, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -86,9 +86,14 @@ SIGNATURES = {
     "tpg_render_spheres_f32": [_P, _P, _I, _I, _P, _I, _I, _I, _F, _P, _P, _P, _P],
     "tpg_surface_smooth_f32": [_P, _I, _I, _I, _I, _F, _P, _P],
     "tpg_surface_shade_f32": [_P, _P, _P, _I, _I, _P, _I, _I, _I, _F, _F, _P, _P, _P, _P, _P],
+    "tpg_pbf_predict_f32": [_P, _P, _P, _P, _I, _I, _F, _F, _P, _P, _P, _P],
+    "tpg_pbf_grid_f32": [_P, _P, _I, _I, _F, _P, _P],
+    "tpg_pbf_lambda_f32": [_P, _P, _I, _I, _F, _F, _F, _P, _P, _P, _P],
+    "tpg_pbf_dp_f32": [_P, _P, _P, _P, _I, _I, _F, _F, _F, _F, _F, _P, _P, _P, _P],
+    "tpg_pbf_finish_f32": [_P, _P, _P, _I, _I, _F, _F, _F, _P, _P, _P, _P],
 }
 SIZE_GETTERS = ("tpg_rowbn_workspace_bytes", "tpg_mlp_workspace_bytes", "tpg_context_expand_workspace_bytes",
-                "tpg_emd_workspace_bytes")
+                "tpg_emd_workspace_bytes", "tpg_pbf_workspace_bytes")
 OTHER_GETTERS = ("tpg_spectral_norm_multi_stride", "tpg_spectral_norm_multi_bwd_scratch",
                  "tpg_mlp_wgrad_workspace_bytes", "tpg_frnn_grid_workspace_bytes", "tpg_small_tail_workspace_bytes",
                  "tpg_chamfer_bwd_workspace_bytes", "tpg_rowlinear_wgrad_workspace_bytes", "tpg_rowlinear_supported",

@@ -189,19 +189,26 @@ static inline bool fg_workspace_ok(const void *ws) { return ws && !(reinterpret_
 // workgroups along x of a one-wave-per-query launch over P1 queries (FG_WAVES * 64 threads each)
 static inline unsigned fg_query_blocks(int P1) { return (unsigned)((P1 + FG_WAVES - 1) / FG_WAVES); }
 
+// where fg_build keeps its results in the workspace: whoever queries a grid that an earlier call built asks here
+static inline void fg_carve(void *ws, int B, int P2, GridParams **gp_o, int **counts_o, int **start_o, int **cellid_o,
+                            float4 **sorted_o) {
+    unsigned char *w = static_cast<unsigned char *>(ws);
+    *gp_o = reinterpret_cast<GridParams *>(w);
+    w += align256(sizeof(GridParams) * (size_t)B);
+    *counts_o = reinterpret_cast<int *>(w);
+    w += align256(sizeof(int) * (size_t)B * FG_CELLS);
+    *start_o = reinterpret_cast<int *>(w);
+    w += align256(sizeof(int) * (size_t)B * (FG_CELLS + 1));
+    *cellid_o = reinterpret_cast<int *>(w);
+    w += align256(sizeof(int) * (size_t)B * P2);
+    *sorted_o = reinterpret_cast<float4 *>(w);
+}
+
 // grid build shared by the entries; r > 0: radius form, knn_k > 0: kNN form
 static int fg_build(const float *p2, const int64_t *len2, int B, int P2, float r, int knn_k, void *ws, hipStream_t st,
                     GridParams **gp_o, int **start_o, float4 **sorted_o) {
-    unsigned char *w = static_cast<unsigned char *>(ws);
-    GridParams *gp = reinterpret_cast<GridParams *>(w);
-    w += align256(sizeof(GridParams) * (size_t)B);
-    int *counts = reinterpret_cast<int *>(w);
-    w += align256(sizeof(int) * (size_t)B * FG_CELLS);
-    int *start = reinterpret_cast<int *>(w);
-    w += align256(sizeof(int) * (size_t)B * (FG_CELLS + 1));
-    int *cellid = reinterpret_cast<int *>(w);
-    w += align256(sizeof(int) * (size_t)B * P2);
-    float4 *sorted = reinterpret_cast<float4 *>(w);
+    GridParams *gp; int *counts, *start, *cellid; float4 *sorted;
+    fg_carve(ws, B, P2, &gp, &counts, &start, &cellid, &sorted);
     if (hipMemsetAsync(counts, 0, sizeof(int) * (size_t)B * FG_CELLS, st) != hipSuccess) return TPG_ERR_LAUNCH;
     const dim3 pg((P2 + 255) / 256, B);
     hipLaunchKernelGGL(fg_bbox_kernel, dim3(B), dim3(1024), 0, st, p2, len2, P2, r, knn_k, gp);

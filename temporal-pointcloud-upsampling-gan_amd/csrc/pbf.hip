@@ -1,0 +1,348 @@
+// Position Based Fluids, Jacobi iterations in gather form (the rule in full: include/tpgan_ops.h, "particle fluid
+// simulator"; the numpy statement: tests/pbf_rule.py).  One substep of every scene of a batch is
+//     predict | iters x ( grid | lambda | dp ) | grid | finish
+// with the scenes on gridDim.y and ragged lengths, as in the grid searches.
+//
+// Launch shapes.  predict is one thread per particle (streaming, 24 bytes in, 24 out).  lambda, dp and finish are
+// rr_kernel's shape (csrc/radius_reduce.hip): one wave per particle, the 27 cells around it as 9 runs of 3 x-adjacent
+// cells of the cell-sorted array, 64 candidates of the concatenated runs per trip, an xor butterfly of integer additions
+// at the end, no LDS.  A neighbour's position comes from the grid's cell-sorted COPY (x, y, z, index), its lambda or
+// previous position through the index; a wave writes its own particle only, and only into arrays no wave of the launch
+// reads a neighbour from, so the Jacobi passes have no races by construction.
+//
+// Summation order.  The order inside a cell follows an atomic cursor (frnn_grid_build.hpp), so every neighbourhood sum
+// is taken in 64-bit FIXED POINT, term by term a function of the pair alone, integer additions, one conversion back:
+//   n, sum |g|^2   terms in [0, 1 + 2^-20]; unit 2^-32, unsigned.  Fewer than 2^22 terms (N is checked) of less than 2^33
+//                  units stay below 2^55.
+//   sum g          components in [-(1 + 2^-20), 1 + 2^-20]; unit 2^-32, signed: |sum| < 2^55.
+//   dp, XSPH       a term is clamped into [-1024, 1024] (far outside anything a fluid at this scale produces: 1024
+//                  supports per pair, 1024 m/s), unit 2^-30, signed: |term| <= 2^40 units, |sum| < 2^62.
+// None can wrap, so no saturation is needed.  Truncation towards zero loses < 2^-30 per term against terms whose own
+// fp32 rounding is 2^-24 relative.
+//
+// fp32 operations are + - * / and sqrtf only, each rounded on its own (-ffp-contract=off, no fast-math); comparisons
+// and selections are exact.  Finite inputs are the caller's business: a NaN coordinate contributes unspecified
+// (but in-bounds, fault-free) values to its neighbours' sums.
+#include "frnn_grid_build.hpp"
+#include "tpg_common.hpp"
+
+namespace {
+
+constexpr int PBF_MAX_N = 1 << 22;          // terms per sum: the overflow argument above
+constexpr int PBF_BOX_CHUNK = 64;           // scenes per launch of the kernels that clamp (boxes ride in the arguments)
+constexpr float PBF_U32 = 4294967296.0f, PBF_INV_U32 = 2.3283064365386963e-10f;      // 2^32, 2^-32
+constexpr float PBF_U30 = 1073741824.0f, PBF_INV_U30 = 9.313225746154785e-10f;       // 2^30, 2^-30
+constexpr float PBF_TERM_MAX = 1024.0f;
+
+struct PbfBoxes { float c[PBF_BOX_CHUNK][6]; };      // lo xyz, hi xyz per scene of the chunk
+
+__device__ __forceinline__ int pbf_len(const int64_t *lengths, int b, int N) {
+    return lengths ? (int)min(max(lengths[b], (int64_t)0), (int64_t)N) : N;
+}
+
+__device__ __forceinline__ float pbf_clamp(float p, float lo, float hi) {
+    p = p < lo ? lo : p;
+    return p > hi ? hi : p;
+}
+
+__device__ __forceinline__ long long pbf_fix30(float t) {
+    t = t < -PBF_TERM_MAX ? -PBF_TERM_MAX : t;
+    t = t > PBF_TERM_MAX ? PBF_TERM_MAX : t;
+    return (long long)(t * PBF_U30);
+}
+
+// W = ((h2 - d2) / h2)^3, the density weight over h^6
+__device__ __forceinline__ float pbf_w(float d2, float h2) {
+    const float u = (h2 - d2) / h2;
+    return (u * u) * u;
+}
+
+// every candidate of the 27 cells around (px, py, pz), 64 per trip: f(candidate) on the lane that holds it
+template <class F>
+__device__ __forceinline__ void pbf_walk(const GridParams &g, const int *__restrict__ st, const float4 *__restrict__ pts,
+                                         float px, float py, float pz, int lane, F &&f) {
+    int cx = cell_axis(px, g.lo[0], g.inv_h), cy = cell_axis(py, g.lo[1], g.inv_h), cz = cell_axis(pz, g.lo[2], g.inv_h);
+    cx = min(max(cx, 0), g.dim[0] - 1);
+    cy = min(max(cy, 0), g.dim[1] - 1);
+    cz = min(max(cz, 0), g.dim[2] - 1);
+    const int x0 = max(cx - 1, 0), x1 = min(cx + 1, g.dim[0] - 1);
+    int rb[9], re[9], total = 0;
+#pragma unroll
+    for (int t = 0; t < 9; ++t) {
+        const int zz = cz + t / 3 - 1, yy = cy + t % 3 - 1;
+        int bgn = 0, end = 0;
+        if (zz >= 0 && zz < g.dim[2] && yy >= 0 && yy < g.dim[1]) {
+            const int row = (zz * g.dim[1] + yy) * g.dim[0];
+            bgn = st[row + x0];
+            end = st[row + x1 + 1];
+        }
+        rb[t] = bgn;
+        re[t] = end;
+        total += end - bgn;
+    }
+    for (int base = 0; base < total; base += 64) {
+        int c = base + lane, at = -1;
+#pragma unroll
+        for (int t = 0; t < 9; ++t) {
+            const int n = re[t] - rb[t];
+            if (at < 0 && c < n) at = rb[t] + c;
+            c -= (at < 0) ? n : 0;
+        }
+        if (at >= 0 && base + lane < total) f(pts[at]);
+    }
+}
+
+__device__ __forceinline__ tpg_u64 pbf_wave_add(tpg_u64 v) {
+#pragma unroll
+    for (int s = 32; s > 0; s >>= 1) v += __shfl_xor(v, s);
+    return v;
+}
+__device__ __forceinline__ long long pbf_wave_add(long long v) { return (long long)pbf_wave_add((tpg_u64)v); }
+
+// step 1: v += dt g; p = clamp(x + dt v)                 grid (ceil(N/256), chunk of scenes)
+__global__ __launch_bounds__(256) void pbf_predict_kernel(const float *__restrict__ x, const float *__restrict__ v,
+                                                          const int64_t *__restrict__ lengths, PbfBoxes box, int b0, int N,
+                                                          float dt, float a, float gx, float gy, float gz,
+                                                          float *__restrict__ p_out, float *__restrict__ v_out) {
+    const int b = b0 + blockIdx.y, i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= pbf_len(lengths, b, N)) return;
+    const size_t q = ((size_t)b * N + i) * 3;
+    const float g[3] = {gx, gy, gz};
+#pragma unroll
+    for (int d = 0; d < 3; ++d) {
+        const float vv = v[q + d] + dt * g[d];
+        v_out[q + d] = vv;
+        p_out[q + d] = pbf_clamp(x[q + d] + dt * vv, box.c[blockIdx.y][d] + a, box.c[blockIdx.y][3 + d] - a);
+    }
+}
+
+// lambda pass: n, C, lambda of every particle               grid (ceil(N/FG_WAVES), B)
+__global__ __launch_bounds__(FG_WAVES * 64) void pbf_lambda_kernel(
+    const float *__restrict__ p, const int64_t *__restrict__ lengths, int N, const GridParams *__restrict__ gp,
+    const int *__restrict__ start, const float4 *__restrict__ sorted, float h, float h2, float S0, float eps,
+    float *__restrict__ lam, float *__restrict__ C_out) {
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int b = blockIdx.y, i = blockIdx.x * FG_WAVES + wave;
+    if (i >= pbf_len(lengths, b, N)) return;
+    const size_t q = (size_t)b * N + i;
+    const float px = p[q * 3], py = p[q * 3 + 1], pz = p[q * 3 + 2];
+    tpg_u64 an = 0, ag2 = 0;
+    long long ax = 0, ay = 0, az = 0;
+    pbf_walk(gp[b], start + (size_t)b * (FG_CELLS + 1), sorted + (size_t)b * N, px, py, pz, lane, [&](const float4 c) {
+        const float d2 = tpg_sq3(px, py, pz, c.x, c.y, c.z);
+        if (!(d2 < h2)) return;
+        an += (tpg_u64)(pbf_w(d2, h2) * PBF_U32);
+        if (d2 == 0.0f) return;
+        const float d = sqrtf(d2), t = (h - d) / h, t2 = t * t;
+        const float gx = t2 * ((px - c.x) / d), gy = t2 * ((py - c.y) / d), gz = t2 * ((pz - c.z) / d);
+        ag2 += (tpg_u64)(((gx * gx + gy * gy) + gz * gz) * PBF_U32);
+        ax += (long long)(gx * PBF_U32);
+        ay += (long long)(gy * PBF_U32);
+        az += (long long)(gz * PBF_U32);
+    });
+    an = pbf_wave_add(an);
+    ag2 = pbf_wave_add(ag2);
+    ax = pbf_wave_add(ax);
+    ay = pbf_wave_add(ay);
+    az = pbf_wave_add(az);
+    if (lane == 0) {
+        const float n = (float)an * PBF_INV_U32, sg2 = (float)ag2 * PBF_INV_U32;
+        const float sx = (float)ax * PBF_INV_U32, sy = (float)ay * PBF_INV_U32, sz = (float)az * PBF_INV_U32;
+        float C = n / S0 - 1.0f;
+        C = C > 0.0f ? C : 0.0f;
+        lam[q] = -(C / ((sg2 + ((sx * sx + sy * sy) + sz * sz)) + eps));
+        if (C_out) C_out[q] = C;
+    }
+}
+
+// dp pass: p_out = clamp(p + dp); p_out may be p itself (a wave reads only its own row of p, the neighbours' positions
+// come from the grid's copy), hence no __restrict__ on the two        grid (ceil(N/FG_WAVES), chunk of scenes)
+__global__ __launch_bounds__(FG_WAVES * 64) void pbf_dp_kernel(
+    const float *p, const float *__restrict__ lam, const int64_t *__restrict__ lengths, PbfBoxes box, int b0,
+    int N, const GridParams *__restrict__ gp, const int *__restrict__ start, const float4 *__restrict__ sorted, float h,
+    float h2, float a, float wq, float k, float dp_scale, float *p_out, float *__restrict__ dp_out) {
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int b = b0 + blockIdx.y, i = blockIdx.x * FG_WAVES + wave;
+    const int n = pbf_len(lengths, b, N);
+    if (i >= n) return;
+    const size_t q = (size_t)b * N + i;
+    const float px = p[q * 3], py = p[q * 3 + 1], pz = p[q * 3 + 2];
+    const float li = lam[q];
+    const float *lb = lam + (size_t)b * N;
+    long long ax = 0, ay = 0, az = 0;
+    pbf_walk(gp[b], start + (size_t)b * (FG_CELLS + 1), sorted + (size_t)b * N, px, py, pz, lane, [&](const float4 c) {
+        const float d2 = tpg_sq3(px, py, pz, c.x, c.y, c.z);
+        if (!(d2 < h2) || d2 == 0.0f) return;
+        const float r = pbf_w(d2, h2) / wq, r2 = r * r;
+        const float co = (li + lb[tpg_clamp_idx(__float_as_int(c.w), n)]) + -(k * (r2 * r2));
+        const float d = sqrtf(d2), t = (h - d) / h, t2 = t * t;
+        ax += pbf_fix30(co * (t2 * ((px - c.x) / d)));
+        ay += pbf_fix30(co * (t2 * ((py - c.y) / d)));
+        az += pbf_fix30(co * (t2 * ((pz - c.z) / d)));
+    });
+    ax = pbf_wave_add(ax);
+    ay = pbf_wave_add(ay);
+    az = pbf_wave_add(az);
+    if (lane == 0) {
+        const float dp[3] = {dp_scale * ((float)ax * PBF_INV_U30), dp_scale * ((float)ay * PBF_INV_U30),
+                             dp_scale * ((float)az * PBF_INV_U30)};
+        const float pi[3] = {px, py, pz};
+#pragma unroll
+        for (int d = 0; d < 3; ++d) {
+            p_out[q * 3 + d] = pbf_clamp(pi[d] + dp[d], box.c[blockIdx.y][d] + a, box.c[blockIdx.y][3 + d] - a);
+            if (dp_out) dp_out[q * 3 + d] = dp[d];
+        }
+    }
+}
+
+// step 3: v = (p - x) / dt, XSPH, x = p                     grid (ceil(N/FG_WAVES), B)
+__global__ __launch_bounds__(FG_WAVES * 64) void pbf_finish_kernel(
+    const float *__restrict__ p, const float *__restrict__ x, const int64_t *__restrict__ lengths, int N,
+    const GridParams *__restrict__ gp, const int *__restrict__ start, const float4 *__restrict__ sorted, float h2, float dt,
+    float cs, float *__restrict__ x_out, float *__restrict__ v_out) {
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int b = blockIdx.y, i = blockIdx.x * FG_WAVES + wave;
+    const int n = pbf_len(lengths, b, N);
+    if (i >= n) return;
+    const size_t q = (size_t)b * N + i;
+    const float px = p[q * 3], py = p[q * 3 + 1], pz = p[q * 3 + 2];
+    const float vx = (px - x[q * 3]) / dt, vy = (py - x[q * 3 + 1]) / dt, vz = (pz - x[q * 3 + 2]) / dt;
+    const float *xb = x + (size_t)b * N * 3;
+    long long ax = 0, ay = 0, az = 0;
+    pbf_walk(gp[b], start + (size_t)b * (FG_CELLS + 1), sorted + (size_t)b * N, px, py, pz, lane, [&](const float4 c) {
+        const float d2 = tpg_sq3(px, py, pz, c.x, c.y, c.z);
+        if (!(d2 < h2)) return;
+        const float w = pbf_w(d2, h2);
+        const float *xj = xb + (size_t)tpg_clamp_idx(__float_as_int(c.w), n) * 3;
+        ax += pbf_fix30(((c.x - xj[0]) / dt - vx) * w);
+        ay += pbf_fix30(((c.y - xj[1]) / dt - vy) * w);
+        az += pbf_fix30(((c.z - xj[2]) / dt - vz) * w);
+    });
+    ax = pbf_wave_add(ax);
+    ay = pbf_wave_add(ay);
+    az = pbf_wave_add(az);
+    if (lane == 0) {
+        v_out[q * 3] = vx + cs * ((float)ax * PBF_INV_U30);
+        v_out[q * 3 + 1] = vy + cs * ((float)ay * PBF_INV_U30);
+        v_out[q * 3 + 2] = vz + cs * ((float)az * PBF_INV_U30);
+        x_out[q * 3] = px;
+        x_out[q * 3 + 1] = py;
+        x_out[q * 3 + 2] = pz;
+    }
+}
+
+// the shape checks every entry shares; > 0: nothing to do (TPG_OK), < 0: the status to return
+int pbf_shape(int B, int N) {
+    if (B < 0 || N < 0) return TPG_ERR_ARG;
+    if (B == 0 || N == 0) return 1;
+    if (B > 65535 || N > PBF_MAX_N) return TPG_ERR_UNSUPPORTED;       // scenes ride on gridDim.y; the sums' headroom
+    return 0;
+}
+
+bool pbf_pos(float v) { return v > 0.0f && v <= 3.0e38f; }            // positive and finite
+
+// box (B,6) host floats: finite, lo < hi on every axis
+bool pbf_box_ok(const float *box, int B) {
+    for (int b = 0; b < B; ++b)
+        for (int d = 0; d < 3; ++d) {
+            const float lo = box[b * 6 + d], hi = box[b * 6 + 3 + d];
+            if (!(lo < hi) || !(lo >= -3.0e38f) || !(hi <= 3.0e38f)) return false;
+        }
+    return true;
+}
+
+void pbf_fill_boxes(PbfBoxes &out, const float *box, int b0, int nb) {
+    for (int j = 0; j < PBF_BOX_CHUNK; ++j)
+        for (int d = 0; d < 6; ++d) out.c[j][d] = j < nb ? box[(size_t)(b0 + j) * 6 + d] : 0.0f;
+}
+
+}  // namespace
+
+extern "C" size_t tpg_pbf_workspace_bytes(int B, int N) { return fg_workspace_bytes(B, N); }
+
+extern "C" int tpg_pbf_predict_f32(const float *x, const float *v, const int64_t *lengths, const float *box, int B, int N,
+                                   float dt, float a, const float *gravity, float *p_out, float *v_out, void *stream) {
+    if (!pbf_pos(dt) || !pbf_pos(a) || !p_out || !v_out) return TPG_ERR_ARG;
+    const int chk = pbf_shape(B, N);
+    if (chk) return chk > 0 ? TPG_OK : chk;
+    if (!x || !v || !box || !gravity || !pbf_box_ok(box, B)) return TPG_ERR_ARG;
+    hipStream_t st = tpg_stream(stream);
+    for (int b0 = 0; b0 < B; b0 += PBF_BOX_CHUNK) {
+        const int nb = min(PBF_BOX_CHUNK, B - b0);
+        PbfBoxes bx;
+        pbf_fill_boxes(bx, box, b0, nb);
+        hipLaunchKernelGGL(pbf_predict_kernel, dim3((N + 255) / 256, nb), dim3(256), 0, st, x, v, lengths, bx, b0, N, dt,
+                           a, gravity[0], gravity[1], gravity[2], p_out, v_out);
+    }
+    TPG_RETURN_IF_LAUNCH_FAILED();
+    return TPG_OK;
+}
+
+extern "C" int tpg_pbf_grid_f32(const float *p, const int64_t *lengths, int B, int N, float h, void *ws, void *stream) {
+    if (!pbf_pos(h)) return TPG_ERR_ARG;
+    if (B > 0 && N > 0 && !fg_workspace_ok(ws)) return TPG_ERR_ARG;
+    const int chk = pbf_shape(B, N);
+    if (chk) return chk > 0 ? TPG_OK : chk;
+    if (!p) return TPG_ERR_ARG;
+    GridParams *gp; int *start; float4 *sorted;
+    const int rc = fg_build(p, lengths, B, N, h, 0, ws, tpg_stream(stream), &gp, &start, &sorted);
+    if (rc) return rc;
+    TPG_RETURN_IF_LAUNCH_FAILED();
+    return TPG_OK;
+}
+
+extern "C" int tpg_pbf_lambda_f32(const float *p, const int64_t *lengths, int B, int N, float h, float S0, float eps,
+                                  const void *ws, float *lam, float *C_out, void *stream) {
+    if (!pbf_pos(h) || !pbf_pos(S0) || !(eps >= 0.0f) || !(eps <= 3.0e38f) || !lam) return TPG_ERR_ARG;
+    if (B > 0 && N > 0 && !fg_workspace_ok(ws)) return TPG_ERR_ARG;
+    const int chk = pbf_shape(B, N);
+    if (chk) return chk > 0 ? TPG_OK : chk;
+    if (!p) return TPG_ERR_ARG;
+    GridParams *gp; int *counts, *start, *cellid; float4 *sorted;
+    fg_carve(const_cast<void *>(ws), B, N, &gp, &counts, &start, &cellid, &sorted);
+    hipLaunchKernelGGL(pbf_lambda_kernel, dim3(fg_query_blocks(N), B), dim3(FG_WAVES * 64), 0, tpg_stream(stream), p,
+                       lengths, N, gp, start, sorted, h, h * h, S0, eps, lam, C_out);
+    TPG_RETURN_IF_LAUNCH_FAILED();
+    return TPG_OK;
+}
+
+extern "C" int tpg_pbf_dp_f32(const float *p, const float *lam, const int64_t *lengths, const float *box, int B, int N,
+                              float h, float a, float wq, float k, float dp_scale, const void *ws, float *p_out,
+                              float *dp_out, void *stream) {
+    if (!pbf_pos(h) || !pbf_pos(a) || !pbf_pos(wq) || !(k >= 0.0f) || !(k <= 3.0e38f) || !(dp_scale >= -3.0e38f) ||
+        !(dp_scale <= 3.0e38f) || !p_out)
+        return TPG_ERR_ARG;
+    if (B > 0 && N > 0 && !fg_workspace_ok(ws)) return TPG_ERR_ARG;
+    const int chk = pbf_shape(B, N);
+    if (chk) return chk > 0 ? TPG_OK : chk;
+    if (!p || !lam || !box || !pbf_box_ok(box, B)) return TPG_ERR_ARG;
+    GridParams *gp; int *counts, *start, *cellid; float4 *sorted;
+    fg_carve(const_cast<void *>(ws), B, N, &gp, &counts, &start, &cellid, &sorted);
+    for (int b0 = 0; b0 < B; b0 += PBF_BOX_CHUNK) {
+        const int nb = min(PBF_BOX_CHUNK, B - b0);
+        PbfBoxes bx;
+        pbf_fill_boxes(bx, box, b0, nb);
+        hipLaunchKernelGGL(pbf_dp_kernel, dim3(fg_query_blocks(N), nb), dim3(FG_WAVES * 64), 0, tpg_stream(stream), p, lam,
+                           lengths, bx, b0, N, gp, start, sorted, h, h * h, a, wq, k, dp_scale, p_out, dp_out);
+    }
+    TPG_RETURN_IF_LAUNCH_FAILED();
+    return TPG_OK;
+}
+
+extern "C" int tpg_pbf_finish_f32(const float *p, const float *x, const int64_t *lengths, int B, int N, float h, float dt,
+                                  float cs, const void *ws, float *x_out, float *v_out, void *stream) {
+    if (!pbf_pos(h) || !pbf_pos(dt) || !(cs >= 0.0f) || !(cs <= 3.0e38f) || !x_out || !v_out || x_out == x) return TPG_ERR_ARG;
+    if (B > 0 && N > 0 && !fg_workspace_ok(ws)) return TPG_ERR_ARG;
+    const int chk = pbf_shape(B, N);
+    if (chk) return chk > 0 ? TPG_OK : chk;
+    if (!p || !x) return TPG_ERR_ARG;
+    GridParams *gp; int *counts, *start, *cellid; float4 *sorted;
+    fg_carve(const_cast<void *>(ws), B, N, &gp, &counts, &start, &cellid, &sorted);
+    hipLaunchKernelGGL(pbf_finish_kernel, dim3(fg_query_blocks(N), B), dim3(FG_WAVES * 64), 0, tpg_stream(stream), p, x,
+                       lengths, N, gp, start, sorted, h * h, dt, cs, x_out, v_out);
+    TPG_RETURN_IF_LAUNCH_FAILED();
+    return TPG_OK;
+}

@@ -372,6 +372,51 @@ class HipBackend:
                        _ptr(image[f0:f1]))
         return image, depth, winner
 
+    # ---- the fluid simulator's launch kinds (csrc/pbf.hip); box (B,6) and gravity (3) are host fp32 arrays ----------
+    def pbf_ws(self, ref, B, N):
+        return self._workspace("pbf", ref, max(int(self.lib.tpg_pbf_workspace_bytes(B, N)), 1), dtype=torch.uint8)
+
+    def pbf_predict(self, x, v, lengths, box, dt, prm, p_out, v_out):
+        B, N, _ = x.shape
+        g = np.asarray(prm.gravity, dtype=np.float32)
+        self._call("tpg_pbf_predict_f32", "pbf_predict", 48 * B * N, x, _ptr(x), _ptr(v), _ptr(lengths), box.ctypes.data,
+                   B, N, dt, prm.radius, g.ctypes.data, _ptr(p_out), _ptr(v_out))
+
+    def pbf_grid(self, p, lengths, prm, ws):
+        B, N, _ = p.shape
+        self._call("tpg_pbf_grid_f32", "pbf_grid", 36 * B * N, p, _ptr(p), _ptr(lengths), B, N, prm.h, _ptr(ws))
+
+    def pbf_lambda(self, p, lengths, prm, ws, lam, C_out=None):
+        B, N, _ = p.shape
+        self._call("tpg_pbf_lambda_f32", "pbf_lambda", 16 * B * N, p, _ptr(p), _ptr(lengths), B, N, prm.h, prm.S0, prm.eps,
+                   _ptr(ws), _ptr(lam), _ptr(C_out))
+
+    def pbf_dp(self, p, lam, lengths, box, prm, ws, p_out, dp_out=None):
+        B, N, _ = p.shape
+        self._call("tpg_pbf_dp_f32", "pbf_dp", 28 * B * N, p, _ptr(p), _ptr(lam), _ptr(lengths), box.ctypes.data, B, N,
+                   prm.h, prm.radius, prm.wq, prm.k, prm.dp_scale, _ptr(ws), _ptr(p_out), _ptr(dp_out))
+
+    def pbf_finish(self, p, x, lengths, dt, prm, ws, x_out, v_out):
+        B, N, _ = p.shape
+        self._call("tpg_pbf_finish_f32", "pbf_finish", 48 * B * N, p, _ptr(p), _ptr(x), _ptr(lengths), B, N, prm.h, dt,
+                   prm.cs, _ptr(ws), _ptr(x_out), _ptr(v_out))
+
+    def pbf_substep(self, x, v, lengths, box, dt, prm, x_out, v_out):
+        """One substep of every scene: predict | iters x (grid | lambda | dp) | grid | finish.  x_out / v_out receive the
+        rows below lengths; p and lambda are per-stream workspaces, the dp pass updates p in place."""
+        B, N, _ = x.shape
+        ws = self.pbf_ws(x, B, N)
+        p = self._workspace("pbf_p", x, B * N * 3)[:B * N * 3].view(B, N, 3)
+        lam = self._workspace("pbf_lam", x, B * N)
+        self.pbf_predict(x, v, lengths, box, dt, prm, p, v_out)
+        for _ in range(prm.iters):
+            self.pbf_grid(p, lengths, prm, ws)
+            self.pbf_lambda(p, lengths, prm, ws, lam)
+            self.pbf_dp(p, lam, lengths, box, prm, ws, p)
+        self.pbf_grid(p, lengths, prm, ws)
+        self.pbf_finish(p, x, lengths, dt, prm, ws, x_out, v_out)
+        return x_out, v_out
+
     def chamfer_fwd(self, src, tgt):
         B, N, _ = src.shape
         M = tgt.shape[1]
@@ -1929,6 +1974,209 @@ def render_surface(points, cams, width, height, lut, radius, lengths=None, scala
     with torch.no_grad():
         return be.render_surface(points.detach(), lengths, None if scalar is None else scalar.detach(), cams, W, H,
                                  radius, lo, hi, lut, background, half_width, iters, delta, shade, int(max_key_bytes))
+
+
+# ------------------------------------------------------------------- particle fluid simulator (csrc/pbf.hip)
+PBF_RADIUS = 0.0125                    # the reference's particle radius a; spacing s = 2a, support h = 4a
+PBF_GRAVITY = (0.0, -9.81, 0.0)
+PBF_ITERS = 4                          # Jacobi iterations per substep
+# Tuned on the host statement (tests/test_simulate_cpu.py holds the properties they were tuned to):
+PBF_EPS = 0.25                         # relaxation, in units of sum |G|^2 (0.47 in a lattice): half a Jacobi step, no overshoot
+PBF_K = 0.2                            # tensile term: at 0.1 and below a splash still drives pairs into one box corner, where
+#                                        the clamp merges them for good (d2 == 0 has no gradient); 0.2 keeps the nearest pair
+#                                        above 0.4 s while a pool at rest stays within 2 % of the lattice density
+PBF_XSPH = 0.05                        # XSPH c: a pool's rms speed falls below 0.02 m/s within 2 s, splashes are not damped
+PBF_MAX_N = 1 << 22                    # particles per scene: the fixed-point sums' headroom (csrc/pbf.hip)
+_F32 = np.float32
+
+
+def pbf_lattice_sum():
+    """S0: the sum of W = (1 - |z|^2 / 4)^3 over the points z of Z^3 with |z| < 2 -- an infinite cubic lattice of
+    spacing s = h / 2 seen from one of its points, self included -- in float64."""
+    r = np.arange(-2, 3, dtype=np.float64)
+    z2 = (r[:, None, None] ** 2 + r[None, :, None] ** 2) + r[None, None, :] ** 2
+    return float((np.clip(1.0 - z2 / 4.0, 0.0, None) ** 3).sum())
+
+
+class PbfParams:
+    """The constants of one simulation, each rounded to fp32 once (include/tpgan_ops.h): radius a, h = 4a, S0, wq,
+    dp_scale = -7 h S0 / 64, cs = c / S0, eps, k, gravity, and the iteration count."""
+
+    def __init__(self, radius=PBF_RADIUS, iters=PBF_ITERS, eps=PBF_EPS, k=PBF_K, c=PBF_XSPH, gravity=PBF_GRAVITY):
+        S0 = pbf_lattice_sum()
+        self.radius = float(_F32(radius))
+        self.h = float(_F32(4.0 * float(radius)))
+        self.S0 = float(_F32(S0))
+        self.wq = float(_F32((1.0 - 0.2 ** 2) ** 3))
+        self.dp_scale = float(_F32(-7.0 * 4.0 * float(radius) * S0 / 64.0))
+        self.c = float(c)
+        self.cs = float(_F32(float(c) / S0))
+        self.eps, self.k = float(_F32(eps)), float(_F32(k))
+        self.gravity = tuple(float(_F32(g)) for g in gravity)
+        self.iters = int(iters)
+        _need(np.isfinite(self.radius) and self.radius > 0.0, "radius must be positive and finite")
+        _need(self.iters >= 0 and self.eps >= 0.0 and self.k >= 0.0 and self.cs >= 0.0 and len(self.gravity) == 3,
+              "iters, eps, k and c must not be negative; gravity has 3 components")
+        _need(all(np.isfinite(v) for v in (self.eps, self.k, self.cs) + self.gravity), "parameters must be finite")
+
+    def as_dict(self):
+        return dict(radius=self.radius, iters=self.iters, eps=self.eps, k=self.k, c=self.c, gravity=list(self.gravity))
+
+
+def _pbf_candidates_torch(p, h):
+    """Candidate pairs (i, j) of one cloud p (n,3): every pair with d < h and more (self pairs included), from a cell
+    list with edge 1.001 h in float64.  Any superset gives the same sums: membership is decided by the canonical d2."""
+    n = p.shape[0]
+    q = p.double()
+    c = torch.floor((q - q.amin(0)) / (1.001 * h)).long() + 1                  # cells from 1: the offsets below stay >= 0
+    dims = c.amax(0) + 2
+    key = (c[:, 2] * dims[1] + c[:, 1]) * dims[0] + c[:, 0]
+    skey, order = torch.sort(key)
+    ii, jj = [], []
+    ar = torch.arange(n, device=p.device)
+    for dz in (-1, 0, 1):
+        for dy in (-1, 0, 1):
+            row = ((c[:, 2] + dz) * dims[1] + (c[:, 1] + dy)) * dims[0] + c[:, 0]       # 3 x-adjacent cells: one run
+            lo, hi = torch.searchsorted(skey, row - 1), torch.searchsorted(skey, row + 1, right=True)
+            cnt = hi - lo
+            i = torch.repeat_interleave(ar, cnt)
+            off = torch.arange(int(cnt.sum()), device=p.device) - torch.repeat_interleave(torch.cumsum(cnt, 0) - cnt, cnt)
+            ii.append(i)
+            jj.append(order[lo[i] + off])
+    return torch.cat(ii), torch.cat(jj)
+
+
+class _PbfPairs:
+    """The pairs of one cloud with d2 < h2 and what the passes share: W, and G where d2 > 0."""
+
+    def __init__(self, p, prm, neighbours):
+        f = lambda v: torch.tensor(v, dtype=torch.float32, device=p.device)      # noqa: E731
+        h, h2 = f(prm.h), f(radius_sq(prm.h))
+        i, j = neighbours(p, prm.h)
+        d = p[i] - p[j]
+        d2 = (d[:, 0] * d[:, 0] + d[:, 1] * d[:, 1]) + d[:, 2] * d[:, 2]
+        keep = d2 < h2
+        self.n = p.shape[0]
+        self.i, self.j, d, d2 = i[keep], j[keep], d[keep], d2[keep]
+        u = (h2 - d2) / h2
+        self.W = (u * u) * u
+        self.off = d2 != 0                                                        # pairs that have a gradient
+        # sqrtf of the rule is correctly rounded; torch's fp32 sqrt on the CPU goes to a vector maths library that is an
+        # ulp off now and then.  The float64 root rounded once IS the correctly rounded fp32 root (53 >= 2 * 24 + 2 bits).
+        dist = torch.sqrt(d2[self.off].double()).float()
+        t = (h - dist) / h
+        self.G = (t * t).unsqueeze(1) * (d[self.off] / dist.unsqueeze(1))
+        self.gi, self.gj = self.i[self.off], self.j[self.off]
+
+    def total(self, index, terms):
+        """sum of int64 `terms` (m,) or (m,3) per particle."""
+        return torch.zeros((self.n,) + terms.shape[1:], dtype=torch.int64, device=terms.device).index_add_(0, index, terms)
+
+
+_PBF_U32, _PBF_U30 = 4294967296.0, 1073741824.0
+
+
+def _pbf_fix30(t):
+    return (t.clamp(-1024.0, 1024.0) * _PBF_U30).to(torch.int64)
+
+
+def _pbf_clamp(p, lo, hi, a):
+    lo_c, hi_c = lo + a, hi - a
+    p = torch.where(p < lo_c, lo_c, p)
+    return torch.where(p > hi_c, hi_c, p)
+
+
+def _pbf_lambda_torch(p, prm, neighbours=_pbf_candidates_torch):
+    """The lambda pass for one cloud (n,3) -> (lambda (n,), C (n,), pairs)."""
+    pr = _PbfPairs(p, prm, neighbours)
+    n = pr.total(pr.i, (pr.W * _PBF_U32).to(torch.int64)).to(torch.float32) * (1.0 / _PBF_U32)
+    g2 = (pr.G[:, 0] * pr.G[:, 0] + pr.G[:, 1] * pr.G[:, 1]) + pr.G[:, 2] * pr.G[:, 2]
+    sg2 = pr.total(pr.gi, (g2 * _PBF_U32).to(torch.int64)).to(torch.float32) * (1.0 / _PBF_U32)
+    S = pr.total(pr.gi, (pr.G * _PBF_U32).to(torch.int64)).to(torch.float32) * (1.0 / _PBF_U32)
+    C = n / torch.tensor(prm.S0, dtype=torch.float32, device=p.device) - 1.0
+    C = torch.where(C > 0, C, torch.zeros_like(C))
+    eps = torch.tensor(prm.eps, dtype=torch.float32, device=p.device)
+    lam = -(C / ((sg2 + ((S[:, 0] * S[:, 0] + S[:, 1] * S[:, 1]) + S[:, 2] * S[:, 2])) + eps))
+    return lam, C, pr
+
+
+def _pbf_dp_torch(p, lam, pr, lo, hi, prm):
+    """The dp pass for one cloud on the pairs of its lambda pass -> (clamped p + dp, dp)."""
+    f = lambda v: torch.tensor(v, dtype=torch.float32, device=p.device)          # noqa: E731
+    r = pr.W[pr.off] / f(prm.wq)
+    r2 = r * r
+    co = (lam[pr.gi] + lam[pr.gj]) + -(f(prm.k) * (r2 * r2))
+    acc = pr.total(pr.gi, _pbf_fix30(co.unsqueeze(1) * pr.G))
+    dp = f(prm.dp_scale) * (acc.to(torch.float32) * (1.0 / _PBF_U30))
+    return _pbf_clamp(p + dp, lo, hi, f(prm.radius)), dp
+
+
+def _pbf_finish_torch(p, x, dt, prm, neighbours=_pbf_candidates_torch):
+    """Velocity and XSPH for one cloud -> v."""
+    f = lambda v: torch.tensor(v, dtype=torch.float32, device=p.device)          # noqa: E731
+    pr = _PbfPairs(p, prm, neighbours)
+    v = (p - x) / f(dt)
+    acc = pr.total(pr.i, _pbf_fix30((v[pr.j] - v[pr.i]) * pr.W.unsqueeze(1)))
+    return v + f(prm.cs) * (acc.to(torch.float32) * (1.0 / _PBF_U30))
+
+
+def _pbf_substep_torch(x, v, lengths, box, dt, prm, neighbours=_pbf_candidates_torch):
+    """`pbf_substep` composed of torch ops, scene by scene: the same fp32 operations in the same order and the same
+    fixed-point sums as csrc/pbf.hip (the rule: include/tpgan_ops.h), so the results are EQUAL to the kernels'.
+    `neighbours(p, h) -> (i, j)` supplies candidate pairs (any superset of the pairs within h)."""
+    B, N, _ = x.shape
+    x_out, v_out = x.clone(), v.clone()
+    lens = [N] * B if lengths is None else [min(max(int(n), 0), N) for n in lengths.tolist()]
+    f = lambda s: torch.tensor(s, dtype=torch.float32, device=x.device)          # noqa: E731
+    for b in range(B):
+        n = lens[b]
+        if n == 0:
+            continue
+        lo, hi = torch.from_numpy(box[b, :3].copy()).to(x.device), torch.from_numpy(box[b, 3:].copy()).to(x.device)
+        xb = x[b, :n]
+        vb = v[b, :n] + f(dt) * torch.tensor(prm.gravity, dtype=torch.float32, device=x.device)
+        p = _pbf_clamp(xb + f(dt) * vb, lo, hi, f(prm.radius))
+        for _ in range(prm.iters):
+            lam, _, pr = _pbf_lambda_torch(p, prm, neighbours)
+            p, _ = _pbf_dp_torch(p, lam, pr, lo, hi, prm)
+        v_out[b, :n] = _pbf_finish_torch(p, xb, dt, prm, neighbours)
+        x_out[b, :n] = p
+    return x_out, v_out
+
+
+def pbf_box(box_lo, box_hi, B):
+    """box_lo, box_hi: 3 values shared by the batch, or (B,3) -> the host table (B,6) fp32 of include/tpgan_ops.h."""
+    lo = np.broadcast_to(np.asarray(box_lo, dtype=np.float32).reshape(-1, 3), (B, 3))
+    hi = np.broadcast_to(np.asarray(box_hi, dtype=np.float32).reshape(-1, 3), (B, 3))
+    box = np.ascontiguousarray(np.concatenate([lo, hi], 1))
+    _need(bool(np.isfinite(box).all()) and bool((box[:, :3] < box[:, 3:]).all()), "the box needs finite lo < hi on every axis")
+    return box
+
+
+def pbf_substep(x, v, lengths, box_lo, box_hi, dt, params=None):
+    """One substep of the particle fluid simulator (Position Based Fluids, Jacobi, gather form; csrc/pbf.hip, the rule
+    in full: include/tpgan_ops.h) for every scene of a ragged batch.
+
+    x, v (B,N,3) fp32; lengths (B,) or None: rows at or beyond lengths[b] are never read and come back unchanged;
+    box_lo, box_hi: HOST values, 3 shared by the batch or (B,3); dt > 0; params: a `PbfParams` (None: the defaults).
+    -> (x, v) new tensors.  Bit-identical from run to run, at every batch position, and equal to `_pbf_substep_torch`,
+    which backends without the kernels run (CPU tensors need a registered checker, as everywhere).  No gradient."""
+    _check_float(x, "x", 3)
+    _check_float(v, "v", 3)
+    _need(x.shape[2] == 3 and v.shape == x.shape, "x and v must be (B,N,3)")
+    _same_device(x, v)
+    B, N, _ = x.shape
+    _need(B <= 65535 and N <= PBF_MAX_N, f"at most 65535 scenes of {PBF_MAX_N} particles")
+    prm = PbfParams() if params is None else params
+    dt = float(_F32(dt))
+    _need(np.isfinite(dt) and dt > 0.0, "dt must be positive and finite")
+    box = pbf_box(box_lo, box_hi, B)
+    lengths = _lengths(lengths, B, N, x.device)
+    be = backend_for(x)
+    with torch.no_grad():
+        if hasattr(be, "pbf_substep"):
+            return be.pbf_substep(x.detach(), v.detach(), lengths, box, dt, prm, x.clone(), v.clone())
+        return _pbf_substep_torch(x.detach(), v.detach(), lengths, box, dt, prm)
 
 
 def cubic_interpolation(query_pos, field, pos, cutoff):
