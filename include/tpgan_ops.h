@@ -834,7 +834,11 @@ int tpg_surface_shade_f32(const float *depth, const int32_t *winner, const float
  * eps, k or cs negative or not finite, a NULL output, x_out == x, a workspace that is NULL or not 256-byte aligned
  * (when B, N > 0).  Then B == 0 or N == 0: TPG_OK, nothing written.  Then B > 65535 or N > 2^22: TPG_ERR_UNSUPPORTED;
  * another NULL pointer, a box that is not finite or has lo >= hi on an axis: TPG_ERR_ARG.  ws: tpg_pbf_workspace_bytes(B,
- * N) bytes; lambda, dp and finish read the grid the last tpg_pbf_grid_f32 with the same B, N left there. */
+ * N) bytes; lambda, dp and finish read the grid the last tpg_pbf_grid_f32 with the same B, N left there.
+ * lengths are device values and are NOT checked (that would be a host read): every entry, the grid build included, takes
+ * lengths[b] as min(max(lengths[b], 0), N) computed on the 64-bit value, before any narrowing -- N + 7 and 2^32 + 5 are
+ * N, -3 is 0 -- so that all launches of a substep agree on a scene's particle count; NULL is N everywhere.  Rows that
+ * such a length brings in are read like any other: finite values there are the caller's business. */
 size_t tpg_pbf_workspace_bytes(int B, int N);
 int tpg_pbf_predict_f32(const float *x, const float *v, const int64_t *lengths, const float *box, int B, int N, float dt,
                         float a, const float *gravity, float *p_out, float *v_out, void *stream);

@@ -29,11 +29,17 @@ __device__ __forceinline__ int cell_axis(float p, float lo, float inv_h) {
     return (int)floorf((p - lo) * inv_h);
 }
 
+// points of cloud b that the grid holds: lengths[b] clamped into [0, P2] in 64 bits, BEFORE the narrowing (2^32 + 5 is
+// P2 points, not 5), the same for every launch of the build and for whoever walks the grid with lengths of its own
+__device__ __forceinline__ int fg_len(const int64_t *__restrict__ len2, int b, int P2) {
+    return len2 ? (int)min(max(len2[b], (int64_t)0), (int64_t)P2) : P2;
+}
+
 __global__ __launch_bounds__(1024) void fg_bbox_kernel(const float *__restrict__ p2, const int64_t *__restrict__ len2,
                                                        int P2, float r, int knn_k, GridParams *__restrict__ gp) {
     __shared__ float red[6][16];
     const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int n2 = len2 ? min((int)len2[b], P2) : P2;
+    const int n2 = fg_len(len2, b, P2);
     const float *x = p2 + (size_t)b * P2 * 3;
     float mn[3] = {3.0e38f, 3.0e38f, 3.0e38f}, mx[3] = {-3.0e38f, -3.0e38f, -3.0e38f};
     for (int i = tid; i < n2; i += 1024)
@@ -106,7 +112,7 @@ __global__ __launch_bounds__(256) void fg_count_kernel(const float *__restrict__
                                                        int P2, const GridParams *__restrict__ gp, int cstride,
                                                        int *__restrict__ counts, int *__restrict__ cellid) {
     const int b = blockIdx.y, i = blockIdx.x * 256 + threadIdx.x;
-    const int n2 = len2 ? min((int)len2[b], P2) : P2;
+    const int n2 = fg_len(len2, b, P2);
     if (i >= n2) return;
     const GridParams g = gp[b];
     const float *x = p2 + ((size_t)b * P2 + i) * 3;
@@ -161,7 +167,7 @@ __global__ __launch_bounds__(256) void fg_fill_kernel(const float *__restrict__ 
                                                       const int *__restrict__ start, int *__restrict__ cursor,
                                                       float4 *__restrict__ sorted) {
     const int b = blockIdx.y, i = blockIdx.x * 256 + threadIdx.x;
-    const int n2 = len2 ? min((int)len2[b], P2) : P2;
+    const int n2 = fg_len(len2, b, P2);
     if (i >= n2) return;
     const int c = cellid[(size_t)b * P2 + i];
     const int pos = start[(size_t)b * (cstride + 1) + c] + atomicAdd(&cursor[(size_t)b * cstride + c], 1);

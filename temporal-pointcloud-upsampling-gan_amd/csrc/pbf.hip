@@ -36,9 +36,8 @@ constexpr float PBF_TERM_MAX = 1024.0f;
 
 struct PbfBoxes { float c[PBF_BOX_CHUNK][6]; };      // lo xyz, hi xyz per scene of the chunk
 
-__device__ __forceinline__ int pbf_len(const int64_t *lengths, int b, int N) {
-    return lengths ? (int)min(max(lengths[b], (int64_t)0), (int64_t)N) : N;
-}
+// the grid build's own clamp (64-bit, into [0, N]): every launch kind and the grid agree on a scene's particle count
+__device__ __forceinline__ int pbf_len(const int64_t *lengths, int b, int N) { return fg_len(lengths, b, N); }
 
 __device__ __forceinline__ float pbf_clamp(float p, float lo, float hi) {
     p = p < lo ? lo : p;

@@ -2157,7 +2157,8 @@ def pbf_substep(x, v, lengths, box_lo, box_hi, dt, params=None):
     """One substep of the particle fluid simulator (Position Based Fluids, Jacobi, gather form; csrc/pbf.hip, the rule
     in full: include/tpgan_ops.h) for every scene of a ragged batch.
 
-    x, v (B,N,3) fp32; lengths (B,) or None: rows at or beyond lengths[b] are never read and come back unchanged;
+    x, v (B,N,3) fp32; lengths (B,) or None: rows at or beyond lengths[b] are never read and come back unchanged
+    (the values stay on the device and are not checked: each counts as min(max(lengths[b], 0), N) of the int64 it is);
     box_lo, box_hi: HOST values, 3 shared by the batch or (B,3); dt > 0; params: a `PbfParams` (None: the defaults).
     -> (x, v) new tensors.  Bit-identical from run to run, at every batch position, and equal to `_pbf_substep_torch`,
     which backends without the kernels run (CPU tensors need a registered checker, as everywhere).  No gradient."""

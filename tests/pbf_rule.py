@@ -50,9 +50,13 @@ def _fix32(term, mask, signed):
     return q.sum(1, dtype=q.dtype).astype(F32) * INV_U32
 
 
-def _fix30(term, mask):
+def _fix30(term, mask, count=None):
     with np.errstate(all="ignore"):
         t = np.where(mask, term, F32(0))
+        if count is not None:                   # what the clamp below met (a dict; the sums do not depend on it)
+            count["over"] = count.get("over", 0) + int((np.abs(t) > TERM_MAX).sum())
+            count["nan"] = count.get("nan", 0) + int(np.isnan(t).sum())
+            count["max"] = max(count.get("max", 0.0), float(np.nanmax(np.abs(t), initial=0.0)))
         t = np.where(t < -TERM_MAX, -TERM_MAX, t)
         t = np.where(t > TERM_MAX, TERM_MAX, t)
         q = (t * U30).astype(np.int64)
@@ -87,25 +91,26 @@ def lambda_rule(p, prm):
     return lam, C
 
 
-def dp_rule(p, lam, lo, hi, prm):
-    """-> (clamped p + dp, dp)."""
+def dp_rule(p, lam, lo, hi, prm, count=None):
+    """-> (clamped p + dp, dp).  count: a dict that gains, summed over the three axes, how many terms lay beyond the
+    term clamp ("over"), how many were NaN ("nan") and the largest magnitude ("max")."""
     p = np.asarray(p, F32)
     pr = Pairs(p, prm)
-    r = pr.W / F32(prm.wq)
-    r2 = r * r
-    co = (lam[:, None] + lam[None, :]) + -(F32(prm.k) * (r2 * r2))
-    with np.errstate(all="ignore"):
-        dp = np.stack([F32(prm.dp_scale) * _fix30(co * g, pr.grad) for g in pr.G], 1)
+    with np.errstate(all="ignore"):             # pairs far beyond the support overflow r2 * r2; the mask drops them
+        r = pr.W / F32(prm.wq)
+        r2 = r * r
+        co = (lam[:, None] + lam[None, :]) + -(F32(prm.k) * (r2 * r2))
+        dp = np.stack([F32(prm.dp_scale) * _fix30(co * g, pr.grad, count) for g in pr.G], 1)
     assert dp.dtype == F32
     return clamp_rule(p + dp, lo, hi, prm), dp
 
 
-def finish_rule(p, x, dt, prm):
-    """-> v after XSPH (x becomes p)."""
+def finish_rule(p, x, dt, prm, count=None):
+    """-> v after XSPH (x becomes p).  count: as in dp_rule."""
     p, x, dt = np.asarray(p, F32), np.asarray(x, F32), F32(dt)
     pr = Pairs(p, prm)
     v = (p - x) / dt
-    out = np.stack([v[:, a] + F32(prm.cs) * _fix30((v[None, :, a] - v[:, None, a]) * pr.W, pr.near) for a in range(3)], 1)
+    out = np.stack([v[:, a] + F32(prm.cs) * _fix30((v[None, :, a] - v[:, None, a]) * pr.W, pr.near, count) for a in range(3)], 1)
     assert out.dtype == F32
     return out
 

@@ -77,6 +77,136 @@ def test_torch_statement_equals_the_numpy_rule_bit_for_bit():
     assert dup.sum() >= 10                                                       # duplicates that no wall separated
 
 
+NEW_CASES = ("chunk", "wide", "flat", "clamp")
+
+
+@pytest.fixture(scope="module")
+def cases():
+    """name -> (the batch, its parameters, its dt, the rule's substep per scene); built once, never modified."""
+    out = {}
+    for name in NEW_CASES + ("small",):
+        batch, prm, dt = pbf_cases.CASES[name][0](), pbf_cases.params(name), pbf_cases.CASES[name][2]
+        out[name] = (batch, prm, dt, _rule_substeps(batch, dt, prm))
+    return out
+
+
+def _rule_substeps(batch, dt, prm, box_row=lambda b: b):
+    x, v, lengths, lo, hi = batch
+    return [P.substep_rule(x[b, :n], v[b, :n], lo[box_row(b)], hi[box_row(b)], dt, prm)
+            for b, n in enumerate(lengths.tolist())]
+
+
+def _statement_equals(batch, dt, prm, want, lengths="own"):
+    from tpgan_amd import ops
+    x, v, own, lo, hi = batch
+    L = None if lengths is None else _t(own)
+    xt, vt = ops._pbf_substep_torch(_t(x), _t(v), L, ops.pbf_box(lo, hi, x.shape[0]), dt, prm)
+    for b, (xr, vr) in enumerate(want):
+        n = len(xr)
+        assert np.array_equal(xt[b, :n].numpy(), xr) and np.array_equal(vt[b, :n].numpy(), vr), b
+        for got, given in ((xt, x), (vt, v)):                                   # rows beyond the length come back as given
+            assert np.array_equal(got[b, n:].numpy(), given[b, n:], equal_nan=True)
+        assert np.isfinite(xr).all() and np.isfinite(vr).all()
+
+
+@pytest.mark.parametrize("name", NEW_CASES)
+def test_torch_statement_equals_the_rule_at_the_batch_grid_and_clamp_edges(cases, name):
+    batch, prm, dt, want = cases[name]
+    _statement_equals(batch, dt, prm, want)
+
+
+@pytest.mark.parametrize("variant", sorted(pbf_cases.VARIANTS))
+def test_torch_statement_equals_the_rule_with_other_parameters(cases, variant):
+    from tpgan_amd import ops
+    batch, _, dt, shipped = cases["small"]
+    prm = ops.PbfParams(**pbf_cases.VARIANTS[variant])
+    want = _rule_substeps(batch, dt, prm)
+    assert not np.array_equal(want[0][1], shipped[0][1])                        # the parameter reaches the result
+    _statement_equals(batch, dt, prm, want)
+
+
+def test_torch_statement_without_lengths_and_with_lengths_outside_0_N(cases):
+    """lengths = None is N; a length is clamped into [0, N] as the 64-bit value it is: N + 7 and 2^32 + 5 are N, -3 is 0."""
+    from tpgan_amd import ops
+    _, prm, dt, _ = cases["small"]
+    full = pbf_cases.full_small()
+    x, v, _, lo, hi = full
+    want = _rule_substeps(full, dt, prm)
+    _statement_equals(full, dt, prm, want, lengths=None)
+    for given, means in pbf_cases.odd_lengths(700):
+        xt, vt = ops._pbf_substep_torch(_t(x), _t(v), torch.tensor(given), ops.pbf_box(lo, hi, 2), dt, prm)
+        for b, n in enumerate(means):
+            assert np.array_equal(xt[b].numpy(), want[b][0] if n else x[b]), (given, b)
+            assert np.array_equal(vt[b].numpy(), want[b][1] if n else v[b]), (given, b)
+
+
+# ---- planted defects: each case sees the defect it is for ------------------------------------------------------------
+def _differs(got, want):
+    return not (np.array_equal(got[0], want[0]) and np.array_equal(got[1], want[1]))
+
+
+def test_chunk_case_sees_another_chunks_box_row(cases):
+    batch, prm, dt, want = cases["chunk"]
+    wrong = _rule_substeps(batch, dt, prm, box_row=lambda b: b % 64)            # box.c[blockIdx.y] without b0, in one launch
+    lengths = batch[2]
+    assert all(not _differs(wrong[b], want[b]) for b in range(64))
+    assert all(_differs(wrong[b], want[b]) for b in range(64, 130) if lengths[b] > 0)
+    assert (lengths[64:] > 0).sum() >= 60 and lengths[128] > 0 and lengths[129] > 0
+
+
+@pytest.mark.parametrize("defect", ["none", "after_conversion"])
+def test_clamp_case_sees_a_missing_and_a_late_term_clamp(cases, monkeypatch, defect):
+    batch, prm, dt, want = cases["clamp"]
+    bound = np.int64(1024) << 30
+
+    def fix30(term, mask, count=None):
+        with np.errstate(all="ignore"):
+            q = (np.where(mask, term, F32(0)) * P.U30).astype(np.int64)
+            if defect == "after_conversion":                                    # clamps what the conversion left of the term
+                q = np.clip(q, -bound, bound)
+        return q.sum(1, dtype=np.int64).astype(F32) * P.INV_U30
+    monkeypatch.setattr(P, "_fix30", fix30)
+    wrong = _rule_substeps(batch, dt, prm)
+    if defect == "none":
+        assert all(_differs(wrong[b], want[b]) for b in range(2))
+    else:
+        assert _differs(wrong[1], want[1])                                      # scene 1 has the terms beyond 2^33
+
+
+def _walk_pairs(keep):
+    """pbf_rule.Pairs restricted to the candidates `keep(grid)` lists per particle."""
+    class Walked(P.Pairs):
+        def __init__(self, p, prm):
+            super().__init__(p, prm)
+            seen = np.zeros(self.near.shape, bool)
+            for i, cand in enumerate(keep(pbf_cases.Grid(p, prm.h))):
+                seen[i, cand] = True
+            self.near, self.grad = self.near & seen, self.grad & seen
+    return Walked
+
+
+@pytest.mark.parametrize("name", ["wide", "flat"])
+def test_the_grid_walk_stated_in_numpy_reaches_every_neighbour(cases, monkeypatch, name):
+    """The walk of tests/pbf_cases.py is what the planted defects below alter: unaltered, it changes nothing."""
+    batch, prm, dt, want = cases[name]
+    monkeypatch.setattr(P, "Pairs", _walk_pairs(lambda g: g.walks()))
+    assert not any(_differs(a, b) for a, b in zip(_rule_substeps(batch, dt, prm), want))
+
+
+def test_wide_case_sees_a_walk_that_stops_after_64_candidates(cases, monkeypatch):
+    batch, prm, dt, want = cases["wide"]
+    monkeypatch.setattr(P, "Pairs", _walk_pairs(lambda g: [w[:64] for w in g.walks()]))
+    wrong = _rule_substeps(batch, dt, prm)
+    assert all(_differs(wrong[b], want[b]) for b in range(2))
+
+
+def test_flat_case_sees_a_wrong_bound_on_an_axis_of_one_cell(cases, monkeypatch):
+    batch, prm, dt, want = cases["flat"]
+    monkeypatch.setattr(P, "Pairs", _walk_pairs(lambda g: g.walks(lower_strict=True)))      # yy > 0 for yy >= 0
+    wrong = _rule_substeps(batch, dt, prm)
+    assert all(_differs(wrong[b], want[b]) for b in range(2))
+
+
 def test_substep_validates_and_refuses_cpu_tensors_without_a_checker():
     from tpgan_amd import ops
     ops.unregister_backend("cpu")
