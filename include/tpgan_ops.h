@@ -850,6 +850,61 @@ int tpg_pbf_dp_f32(const float *p, const float *lam, const int64_t *lengths, con
 int tpg_pbf_finish_f32(const float *p, const float *x, const int64_t *lengths, int B, int N, float h, float dt, float cs,
                        const void *ws, float *x_out, float *v_out, void *stream);
 
+/* ---- isosurfaces (csrc/isosurface.hip) ------------------------------------------------------------------------------
+ * The surface field >= iso of a scalar field on a regular lattice as an indexed triangle mesh: marching tetrahedra on
+ * the Kuhn (Freudenthal) split of every lattice cube into six tetrahedra.  (The reference ends its demo by handing
+ * every frame to an external tool that reconstructs the fluid's surface; this mesher is this project's own and no parity
+ * with any such tool is claimed.)  Everything is fp32, each operation rounded on its own (no FMA), only + - * / and
+ * sqrtf; comparisons and selections are exact.
+ *
+ * Lattice: nx x ny x nz nodes, origin 3 HOST floats, step s > 0; field a contiguous (nx,ny,nz) array, node (i,j,k) has
+ * the id n = (i*ny + j)*nz + k and the position origin[a] + (float)index_a * s on axis a.
+ * Inside: a node is inside iff field[n] >= iso (NaN is outside).
+ * Edges: seven per node, to the node at offset D[d], d = 0..6,
+ *     D = (1,0,0), (0,1,0), (0,0,1), (1,1,0), (0,1,1), (1,0,1), (1,1,1),
+ * where that node is in the lattice; an edge is ACTIVE iff exactly one of its ends is inside.
+ * Vertices: one per active edge, numbered in ascending order of 7*n + d.  With a the owning node, b the far one, fa, fb
+ * their values and pa, pb their positions:  t = (iso - fa) / (fb - fa);  x = pa + t * (pb - pa) per axis.
+ * Normals: at a node g_a = field[index_a + 1] - field[index_a - 1] on each axis a, both indices clamped into the
+ * lattice;  G = ga + t * (gb - ga) per axis;  len = sqrtf((Gx*Gx + Gy*Gy) + Gz*Gz);  normal = (-Gx/len, -Gy/len,
+ * -Gz/len), outward (towards lower values), and (0,0,0) for len == 0.
+ * Cells: addressed by their base node, whose id is the cell's id.  The six tetrahedra come from the permutations of the
+ * axes in the order xyz, xzy, yxz, yzx, zxy, zyx: for a permutation pi the path v0 = base, v1 = v0 + e_pi1,
+ * v2 = v1 + e_pi2, v3 = v2 + e_pi3.  All six share the cube's main diagonal, and every edge (va, vb), a < b, of a
+ * tetrahedron is the edge of direction vb - va of the node va.
+ * Triangles of a tetrahedron, by the inside flags of v0..v3:
+ *     one corner s alone on its side (one inside or one outside): one triangle on the three edges at s, the other
+ *     corners in ascending path position;
+ *     two inside a < b, two outside c < d (path positions): (ac, ad, bd) and (ac, bd, bc).
+ * Winding: every triangle's geometric normal points from the inside corners to the outside corners.  Whether the listed
+ * order is kept or its last two vertices are exchanged is a table of 16 cases x 6 tetrahedra that the host GENERATES in
+ * exact integer arithmetic: every edge vertex at its midpoint in doubled lattice coordinates, the sign of
+ * (q-p) x (r-p) . (sum of the outside corners - sum of the inside corners).  No tetrahedron is degenerate, so the sign
+ * does not depend on t in (0,1).
+ * Faces: in ascending order of (cell id, tetrahedron, triangle), int32 vertex numbers.  Zero-area triangles occur where
+ * t is 0 (a value equal to iso) and are kept: the surface stays closed with them.  Where every boundary node of the
+ * lattice is outside, the mesh is a closed, consistently oriented 2-manifold (the Kuhn split is invariant under
+ * translation and compatible across cube faces).
+ * Non-finite values are the caller's business: they may give non-finite vertices, never an index out of range, since
+ * every index depends on the values only through the inside flags.
+ *
+ * tpg_iso_count_f32: per node the 7-bit mask of its active edges and per cell its number of triangles (0..12) into ws,
+ * their exclusive prefix sums over the G = nx*ny*nz ids, the totals [V, F] into counts (device, int64).
+ * tpg_iso_emit_f32: reads what tpg_iso_count_f32 left in ws for the same field, dimensions and iso and writes vertices
+ * (V,3), normals (V,3) or NULL, faces (F,3); nothing is written at or beyond V_cap vertices / F_cap faces (a short
+ * buffer is truncated, never overrun).  The same bits, order included, on every run.
+ *
+ * Checks, all before anything is launched.  TPG_ERR_ARG: a negative dimension or cap, iso not finite, step not positive
+ * and finite, a NULL counts / origin or an origin that is not finite, NULL vertices with V_cap > 0 or NULL faces with
+ * F_cap > 0, a workspace that is NULL or not 256-byte aligned (when every dimension is >= 2).  Then a dimension below 2
+ * (no cells): TPG_OK with V = F = 0, nothing else written.  Then G > 2^27: TPG_ERR_UNSUPPORTED; a NULL field:
+ * TPG_ERR_ARG.  ws: tpg_iso_workspace_bytes(nx, ny, nz) bytes (0 where there are no cells or G > 2^27). */
+size_t tpg_iso_workspace_bytes(int nx, int ny, int nz);
+int tpg_iso_count_f32(const float *field, int nx, int ny, int nz, float iso, void *ws, int64_t *counts, void *stream);
+int tpg_iso_emit_f32(const float *field, int nx, int ny, int nz, const float *origin, float step, float iso,
+                     const void *ws, long long V_cap, long long F_cap, float *vertices, float *normals, int32_t *faces,
+                     void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -91,9 +91,11 @@ SIGNATURES = {
     "tpg_pbf_lambda_f32": [_P, _P, _I, _I, _F, _F, _F, _P, _P, _P, _P],
     "tpg_pbf_dp_f32": [_P, _P, _P, _P, _I, _I, _F, _F, _F, _F, _F, _P, _P, _P, _P],
     "tpg_pbf_finish_f32": [_P, _P, _P, _I, _I, _F, _F, _F, _P, _P, _P, _P],
+    "tpg_iso_count_f32": [_P, _I, _I, _I, _F, _P, _P, _P],
+    "tpg_iso_emit_f32": [_P, _I, _I, _I, _P, _F, _F, _P, _L, _L, _P, _P, _P, _P],
 }
 SIZE_GETTERS = ("tpg_rowbn_workspace_bytes", "tpg_mlp_workspace_bytes", "tpg_context_expand_workspace_bytes",
-                "tpg_emd_workspace_bytes", "tpg_pbf_workspace_bytes")
+                "tpg_emd_workspace_bytes", "tpg_pbf_workspace_bytes", "tpg_iso_workspace_bytes")
 OTHER_GETTERS = ("tpg_spectral_norm_multi_stride", "tpg_spectral_norm_multi_bwd_scratch",
                  "tpg_mlp_wgrad_workspace_bytes", "tpg_frnn_grid_workspace_bytes", "tpg_small_tail_workspace_bytes",
                  "tpg_chamfer_bwd_workspace_bytes", "tpg_rowlinear_wgrad_workspace_bytes", "tpg_rowlinear_supported",
@@ -129,6 +131,7 @@ def load():
     for name in SIZE_GETTERS:
         getattr(lib, name).argtypes = [C.c_int, C.c_int]
         getattr(lib, name).restype = C.c_size_t
+    lib.tpg_iso_workspace_bytes.argtypes = [C.c_int, C.c_int, C.c_int]          # a lattice: three extents
     lib.tpg_spectral_norm_multi_stride.argtypes = [C.c_int, C.c_int]
     lib.tpg_spectral_norm_multi_stride.restype = C.c_longlong
     lib.tpg_spectral_norm_multi_bwd_scratch.argtypes = [C.c_int, C.c_int]

@@ -417,6 +417,34 @@ class HipBackend:
         self.pbf_finish(p, x, lengths, dt, prm, ws, x_out, v_out)
         return x_out, v_out
 
+    # ---- isosurfaces (csrc/isosurface.hip; the rule: include/tpgan_ops.h)
+    def iso_count(self, field, iso):
+        """Masks, triangle counts and their prefix sums into the per-stream workspace -> (ws, V, F): the ONE host read."""
+        nx, ny, nz = field.shape
+        ws = self._workspace("iso", field, self.lib.tpg_iso_workspace_bytes(nx, ny, nz), dtype=torch.uint8)
+        counts = torch.empty(2, dtype=torch.int64, device=field.device)
+        self._call("tpg_iso_count_f32", "iso_count", 14 * field.numel(), field, _ptr(field), nx, ny, nz, iso, _ptr(ws),
+                   _ptr(counts))
+        V, F = counts.tolist()
+        return ws, int(V), int(F)
+
+    def iso_emit(self, field, origin, step, iso, ws, V_cap, F_cap, vertices, normals, faces):
+        """Vertices, normals (or None) and faces of the field `iso_count` has just classified; nothing is written at or
+        beyond V_cap vertices / F_cap faces."""
+        nx, ny, nz = field.shape
+        self._call("tpg_iso_emit_f32", "iso_emit", 14 * field.numel() + 12 * (2 * V_cap + F_cap), field, _ptr(field), nx,
+                   ny, nz, C.c_void_p(origin.ctypes.data), step, iso, _ptr(ws), int(V_cap), int(F_cap), _ptr(vertices),
+                   _ptr(normals), _ptr(faces))
+
+    def iso_surface(self, field, origin, step, iso, normals):
+        ws, V, F = self.iso_count(field, iso)
+        vertices = torch.empty((V, 3), dtype=torch.float32, device=field.device)
+        faces = torch.empty((F, 3), dtype=torch.int32, device=field.device)
+        nrm = torch.empty((V, 3), dtype=torch.float32, device=field.device) if normals else None
+        if V > 0:
+            self.iso_emit(field, origin, step, iso, ws, V, F, vertices, nrm, faces)
+        return vertices, faces, nrm
+
     def chamfer_fwd(self, src, tgt):
         B, N, _ = src.shape
         M = tgt.shape[1]
@@ -2178,6 +2206,183 @@ def pbf_substep(x, v, lengths, box_lo, box_hi, dt, params=None):
         if hasattr(be, "pbf_substep"):
             return be.pbf_substep(x.detach(), v.detach(), lengths, box, dt, prm, x.clone(), v.clone())
         return _pbf_substep_torch(x.detach(), v.detach(), lengths, box, dt, prm)
+
+
+# ------------------------------------------------------------------------ isosurfaces (csrc/isosurface.hip)
+ISO_DIRECTIONS = ((1, 0, 0), (0, 1, 0), (0, 0, 1), (1, 1, 0), (0, 1, 1), (1, 0, 1), (1, 1, 1))
+ISO_PERMUTATIONS = ((0, 1, 2), (0, 2, 1), (1, 0, 2), (1, 2, 0), (2, 0, 1), (2, 1, 0))
+ISO_MAX_NODES = 1 << 27
+
+
+def iso_tetrahedra():
+    """The corner offsets v0..v3 of the six tetrahedra of the Kuhn split: [p][a] = (dx, dy, dz)."""
+    out = []
+    for perm in ISO_PERMUTATIONS:
+        v, path = [0, 0, 0], [(0, 0, 0)]
+        for axis in perm:
+            v[axis] += 1
+            path.append(tuple(v))
+        out.append(path)
+    return out
+
+
+def iso_case_triangles(case):
+    """The triangles of a tetrahedron whose corner at path position a is inside iff bit a of `case` is set, in the
+    rule's listed order, before winding: each three edges (lo, hi) of path positions."""
+    ins = [a for a in range(4) if case >> a & 1]
+    outs = [a for a in range(4) if not case >> a & 1]
+    if len(ins) == 1 or len(outs) == 1:
+        s = ins[0] if len(ins) == 1 else outs[0]
+        return [[(min(s, o), max(s, o)) for o in range(4) if o != s]]
+    if len(ins) == 2:
+        (a, b), (c, d) = ins, outs
+        e = lambda u, v: (min(u, v), max(u, v))  # noqa: E731
+        return [[e(a, c), e(a, d), e(b, d)], [e(a, c), e(b, d), e(b, c)]]
+    return []
+
+
+def iso_winding_table():
+    """flip[p][case]: the triangles of that case of tetrahedron p are listed with their last two vertices exchanged.
+    Generated in exact integer arithmetic (include/tpgan_ops.h): every edge vertex at its midpoint in doubled lattice
+    coordinates, the sign of (q-p) x (r-p) . (sum of outside corners - sum of inside corners)."""
+    flip = []
+    for path in iso_tetrahedra():
+        row = [False] * 16
+        for case in range(1, 15):
+            for tri in iso_case_triangles(case):
+                p, q, r = ([path[a][x] + path[b][x] for x in range(3)] for a, b in tri)
+                u, v = [q[x] - p[x] for x in range(3)], [r[x] - p[x] for x in range(3)]
+                n = (u[1] * v[2] - u[2] * v[1], u[2] * v[0] - u[0] * v[2], u[0] * v[1] - u[1] * v[0])
+                side = [sum((-2 if case >> a & 1 else 2) * path[a][x] for a in range(4)) for x in range(3)]
+                s = sum(n[x] * side[x] for x in range(3))
+                _need(s != 0, "a degenerate tetrahedron")
+                row[case] = s < 0
+        flip.append(row)
+    return flip
+
+
+def _iso_surface_torch(field, origin, step, iso, normals=True):
+    """The isosurface rule as vectorised torch ops (fp32, one rounding per operation): what backends without the
+    kernels run.  field (nx,ny,nz) f32 with every extent >= 2, origin 3 host floats, step and iso fp32-exact floats."""
+    f, dev = field, field.device
+    nx, ny, nz = f.shape
+    inside = f >= iso                                                        # NaN: outside
+    active = torch.zeros((nx, ny, nz, 7), dtype=torch.bool, device=dev)
+    for d, (dx, dy, dz) in enumerate(ISO_DIRECTIONS):
+        active[:nx - dx, :ny - dy, :nz - dz, d] = inside[:nx - dx, :ny - dy, :nz - dz] != inside[dx:, dy:, dz:]
+    flat = active.reshape(-1)
+    vid = (torch.cumsum(flat, 0) - flat.long()).view(nx, ny, nz, 7)          # the vertex number of edge 7 n + d
+    keys = torch.nonzero(flat).squeeze(1)
+    node, d = torch.div(keys, 7, rounding_mode="floor"), keys % 7
+    ij = torch.div(node, nz, rounding_mode="floor")
+    ia = torch.stack([torch.div(ij, ny, rounding_mode="floor"), ij % ny, node % nz], 1)
+    ib = ia + torch.tensor(ISO_DIRECTIONS, dtype=torch.int64, device=dev)[d]
+
+    def at(table, idx):
+        return table[idx[:, 0], idx[:, 1], idx[:, 2]]
+    fa, fb = at(f, ia), at(f, ib)
+    t = ((iso - fa) / (fb - fa)).unsqueeze(1)
+    org = torch.from_numpy(np.asarray(origin, dtype=np.float32)).to(dev).view(1, 3)
+    pa, pb = org + ia.float() * step, org + ib.float() * step
+    vertices = pa + t * (pb - pa)
+    nrm = None
+    if normals:
+        g = []
+        for a, n in enumerate((nx, ny, nz)):
+            idx = torch.arange(n, device=dev)
+            g.append(f.index_select(a, (idx + 1).clamp(max=n - 1)) - f.index_select(a, (idx - 1).clamp(min=0)))
+        g = torch.stack(g, -1)
+        ga, gb = at(g, ia), at(g, ib)
+        gv = ga + t * (gb - ga)
+        # (sqrtf of the rule is correctly rounded, torch's fp32 sqrt on the CPU is not always: through float64, as the
+        # simulator's statement does)
+        sq = (gv[:, 0] * gv[:, 0] + gv[:, 1] * gv[:, 1]) + gv[:, 2] * gv[:, 2]
+        length = torch.sqrt(sq.double()).float().unsqueeze(1)
+        nrm = torch.where(length == 0, torch.zeros_like(gv), -gv / length)
+
+    paths, flip = iso_tetrahedra(), iso_winding_table()
+    cx, cy, cz = nx - 1, ny - 1, nz - 1
+    cells = torch.arange(nx * ny * nz, device=dev).view(nx, ny, nz)[:cx, :cy, :cz]
+    faces, order = [], []
+    for p, path in enumerate(paths):
+        corner = [inside[o[0]:o[0] + cx, o[1]:o[1] + cy, o[2]:o[2] + cz] for o in path]
+        case = sum(corner[a].long() << a for a in range(4))
+        for c in range(1, 15):
+            where = torch.nonzero(case == c)
+            if where.shape[0] == 0:
+                continue
+            for number, tri in enumerate(iso_case_triangles(c)):
+                if flip[p][c]:
+                    tri = [tri[0], tri[2], tri[1]]
+                cols = []
+                for a, b in tri:
+                    direction = ISO_DIRECTIONS.index(tuple(path[b][x] - path[a][x] for x in range(3)))
+                    owner = where + torch.tensor(path[a], dtype=torch.int64, device=dev)
+                    cols.append(vid[owner[:, 0], owner[:, 1], owner[:, 2], direction])
+                faces.append(torch.stack(cols, 1))
+                order.append((at(cells, where) * 6 + p) * 2 + number)
+    if not faces:
+        return vertices, torch.zeros((0, 3), dtype=torch.int32, device=dev), nrm
+    faces = torch.cat(faces)[torch.argsort(torch.cat(order))]               # the keys are distinct
+    return vertices, faces.to(torch.int32), nrm
+
+
+def iso_surface(field, origin, step, iso, normals=True):
+    """The surface field >= iso of a scalar field on a regular lattice as a triangle mesh: marching tetrahedra on the Kuhn
+    split of every lattice cube (csrc/isosurface.hip; the rule in full: include/tpgan_ops.h).  This project's own mesher:
+    no parity with any external reconstruction tool is claimed.
+
+    field (nx,ny,nz) fp32, node (i,j,k) at origin + (i,j,k) * step; origin: 3 HOST floats; step > 0; iso finite.
+    -> (vertices (V,3) f32, faces (F,3) int32 wound so that the normals point to lower values, normals (V,3) f32 from
+    the field's central differences, or None).  Where every boundary node is below iso the mesh is closed and
+    consistently oriented.  One host read (the two counts) between the two launches' groups.  At most 2^27 nodes; an
+    extent below 2 gives an empty mesh.  Bit-identical from run to run, order included, and equal to
+    `_iso_surface_torch`, which backends without the kernels run (CPU tensors need a registered checker).  No gradient."""
+    _check_float(field, "field", 3)
+    origin = np.ascontiguousarray(np.asarray(origin, dtype=np.float32).reshape(-1))
+    _need(origin.shape == (3,) and bool(np.isfinite(origin).all()), "origin must be 3 finite values")
+    step, iso = float(_F32(step)), float(_F32(iso))
+    _need(np.isfinite(step) and step > 0.0, "step must be positive and finite")
+    _need(np.isfinite(iso), "iso must be finite")
+    nx, ny, nz = field.shape
+    _need(nx * ny * nz <= ISO_MAX_NODES, f"a lattice holds at most 2^27 nodes, got {nx} x {ny} x {nz}")
+    be = backend_for(field)
+    dev = field.device
+    if min(nx, ny, nz) < 2:
+        return (torch.zeros((0, 3), dtype=torch.float32, device=dev), torch.zeros((0, 3), dtype=torch.int32, device=dev),
+                torch.zeros((0, 3), dtype=torch.float32, device=dev) if normals else None)
+    with torch.no_grad():
+        if hasattr(be, "iso_surface"):
+            return be.iso_surface(field.detach(), origin, step, iso, bool(normals))
+        return _iso_surface_torch(field.detach(), origin, step, iso, bool(normals))
+
+
+def _radius_cubic_sums_torch(query, pos, r, pairs_per_chunk=1 << 24):
+    """`radius_reduce(query, pos, r, "cubic")[1]` for one cloud as torch ops, the same bits: the canonical fp32 distance,
+    members d2 <= r2, every term truncated to 64-bit fixed point (unit 2^-32), integer sums, one conversion back
+    (csrc/radius_reduce.hip).  query (Nq,3), pos (Np,3) fp32 -> (Nq,) fp32.  What backends without the kernel run."""
+    r32 = float(_F32(r))
+    r2 = float(_F32(r32) * _F32(r32))
+    out = torch.zeros(query.shape[0], dtype=torch.float32, device=query.device)
+    if pos.shape[0] == 0 or query.shape[0] == 0:
+        return out
+    rows = max(1, pairs_per_chunk // pos.shape[0])
+    px, py, pz = pos[:, 0].unsqueeze(0), pos[:, 1].unsqueeze(0), pos[:, 2].unsqueeze(0)
+    for a in range(0, query.shape[0], rows):
+        q = query[a:a + rows]
+        dx, dy, dz = q[:, 0:1] - px, q[:, 1:2] - py, q[:, 2:3] - pz
+        d2 = dx * dx
+        d2 = d2 + dy * dy
+        d2 = d2 + dz * dz
+        u = torch.clamp(torch.sqrt(d2.double()).float() / r32, max=1.0)      # a correctly rounded fp32 sqrt
+        u2 = u * u
+        near = 6.0 * (u2 * u - u2) + 1.0
+        v = 1.0 - u
+        far = 2.0 * (v * v * v)
+        w = torch.clamp(torch.where(u <= 0.5, near, far), min=0.0)
+        units = torch.where(d2 <= r2, (w * 4294967296.0).to(torch.int64), torch.zeros((), dtype=torch.int64, device=w.device))
+        out[a:a + rows] = units.sum(1).to(torch.float32) * 2.3283064365386963e-10
+    return out
 
 
 def cubic_interpolation(query_pos, field, pos, cutoff):

@@ -13,9 +13,11 @@ neighbours in the 6-D feature space (this project's `SRNet.forward_with_context`
     python -m tpgan_amd.rollout --checkpoint X.ckpt --frames 'dir/data_{i}.npz' --count 800 [--in-feats 6] --out DIR
         [--render PNGDIR --size 3 --width 768 --height 768 --mode pinhole --color depth --direction 0 0 -1
          --style points|surface --particle_radius 0.025 --smooth_iters 3 --smooth_half_width 2]
+        [--mesh MESHDIR --format ply|obj --spacing 0.025 --support 0.05 --step 0.0125 --iso 0.5]
 
 --render writes one picture per frame (render.SequenceRenderer) from each chunk's outputs while they are still on the
-device; the camera is fitted to the first chunk.
+device; the camera is fitted to the first chunk.  --mesh writes one surface mesh per frame (mesh.SequenceMesher) in the
+same way.
 """
 import argparse
 import os
@@ -23,7 +25,7 @@ import os
 import numpy as np
 import torch
 
-from . import ops, render
+from . import mesh, ops, render
 
 # Default chunk: this many low-resolution points per chunk (T = CHUNK_POINTS // N frames, 1 <= T <= MAX_CHUNK), from
 # tools/rollout_chunks.py on MI355X (profiles/rollout_chunks.txt, DESIGN.md "Sequence upsampling").
@@ -139,6 +141,8 @@ def main(argv=None):
     ap.add_argument("--device", default="cuda")
     ap.add_argument("--render", default=None, metavar="PNGDIR", help="also write pcd_{i:04d}.png pictures there")
     render.add_render_options(ap)
+    ap.add_argument("--mesh", default=None, metavar="MESHDIR", help="also write pcd_{i:04d}.ply surface meshes there")
+    mesh.add_mesh_options(ap)
     a = ap.parse_args(argv)
     if "{i}" not in a.frames:
         ap.error("--frames must contain '{i}'")
@@ -146,6 +150,7 @@ def main(argv=None):
     net = load_generator(a.checkpoint, a.in_feats, dev)
     os.makedirs(a.out, exist_ok=True)
     pictures = render.renderer_from(a, a.render, dev) if a.render else None
+    meshes = mesh.mesher_from(a, a.mesh, dev) if a.mesh else None
     up = SequenceUpsampler(net, a.chunk)
     step = a.chunk
     i = 0
@@ -155,9 +160,12 @@ def main(argv=None):
         idx = range(i, min(i + step, a.count))
         feats, poss, cents, hs = load_frames(a.frames, idx, a.in_feats)
         outs = up.push(feats.to(dev), poss.to(dev))
-        if pictures is not None:    # the frames' own coordinates, as the .npy files below hold them
-            pictures.push([out[0] * float(hs[j - i]) + torch.from_numpy(cents[j - i]).to(dev)
-                           for j, out in zip(idx, outs)], i)
+        if pictures is not None or meshes is not None:     # the frames' own coordinates, as the .npy files below hold them
+            own = [out[0] * float(hs[j - i]) + torch.from_numpy(cents[j - i]).to(dev) for j, out in zip(idx, outs)]
+            if pictures is not None:
+                pictures.push(own, i)
+            if meshes is not None:
+                meshes.push(own, i)
         for j, out in zip(idx, outs):
             pcd = out[0].cpu().numpy()
             pcd *= hs[j - i]
