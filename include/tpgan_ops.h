@@ -74,6 +74,18 @@ int tpg_knn_mfma_f32(const float *p1, const float *p2, const int64_t *len1,
                      const int64_t *len2, int B, int P1, int P2, int D, int K,
                      float *dist, int64_t *idx, int redo, void *stream);
 
+/* The same search on SMALL clouds (P2 <= 1024; D = 32 / 64, 2 <= K <= 24, 16-byte aligned rows): the path
+ * tpg_knn_f32 takes by itself for the generator's (24, 512, 32 / 64) feature-space searches
+ * (gcn_lib/pointnet/gcn.py:38,258 at cfg2 / cfg4).  One sweep of the same split-operand Gram products, every
+ * approximate distance of a workgroup's 32 queries in LDS, the candidates within twice the rounding bound of the
+ * K-th approximate distance re-ranked with the canonical distance; queries with more than 64 candidates, a
+ * non-finite bound or a cloud of fewer than 64 valid points are redone by the exhaustive kernel.  The output
+ * equals tpg_knn_f32's bit for bit.  redo = 0 (diagnostic) skips that last launch and leaves
+ * idx[b][i][0] = -2 on the unsettled queries. */
+int tpg_knn_small_f32(const float *p1, const float *p2, const int64_t *len1,
+                      const int64_t *len2, int B, int P1, int P2, int D, int K,
+                      float *dist, int64_t *idx, int redo, void *stream);
+
 /* The same radius search (r > 0, D = 3, K <= 64) on a UNIFORM GRID, for clouds where the exhaustive
  * kernel stops being free (loss.py:256-265 at 16384 points per cloud; the 10^4..10^5-point rollout,
  * upsampling_network.py:159-174): cells of edge max(r, extent/64), points counting-sorted by cell,

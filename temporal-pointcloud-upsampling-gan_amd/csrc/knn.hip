@@ -304,6 +304,39 @@ int knn_mfma_launch(const float *p1, const float *p2, const int64_t *len1, const
     return knn_mfma_launch_m<D_T, 16>(p1, p2, len1, len2, B, P1, P2, K, dist, idx, redo, st);
 }
 
+#include "knn_small.hpp"
+
+// Dispatch bounds of the one-sweep filter: MIN <= P2 < MAX.  Measured (tools/tune_knn_small.py, profiles/knn_small.txt,
+// B = 24): at 512 and 1024 points it beats the tiled kernel for every D and K (1.24-1.88x, 1.63-2.05x); at 256 points
+// only for D = 64 (D = 32: 0.85x at K = 4), at 128 points it loses (its fixed cost is ~18 us whatever the cloud).
+#ifndef TPG_KNN_SMALL_MIN_POINTS
+#define TPG_KNN_SMALL_MIN_POINTS 512
+#endif
+#ifndef TPG_KNN_SMALL_MAX_POINTS
+#define TPG_KNN_SMALL_MAX_POINTS 1025
+#endif
+static_assert(TPG_KNN_SMALL_MAX_POINTS <= KS_MAX_P2 + 1, "the distance matrix of knn_small_kernel must fit the LDS");
+
+// the one-sweep filter kernel, then (redo) the exhaustive kernel on the queries it marked
+template <int D_T>
+int knn_small_launch(const float *p1, const float *p2, const int64_t *len1, const int64_t *len2, int B, int P1, int P2,
+                     int K, float *dist, int64_t *idx, bool redo, hipStream_t st) {
+    if (P2 > KS_MAX_P2) return TPG_ERR_UNSUPPORTED;
+    if (!tpg_allow_dynamic_lds<&knn_small_kernel<D_T>>((int)ks_smem_bytes<D_T>(KS_MAX_P2))) return TPG_ERR_LAUNCH;
+    const int gx = (P1 + KS_Q - 1) / KS_Q;
+    const long long total = (long long)gx * B;
+    if (total > (1ll << 30)) return TPG_ERR_ARG;
+    hipLaunchKernelGGL((knn_small_kernel<D_T>), dim3((unsigned)total), dim3(KS_WAVES * 64), ks_smem_bytes<D_T>(P2), st, p1, p2,
+                       len1, len2, P1, P2, K, gx, dist, idx);
+    TPG_RETURN_IF_LAUNCH_FAILED();
+    if (redo) {
+        const dim3 rg((unsigned)((P1 + KNN_WAVES - 1) / KNN_WAVES), (unsigned)B);
+        hipLaunchKernelGGL((knn_redo_kernel<D_T>), rg, dim3(KNN_WAVES * 64), 0, st, p1, p2, len1, len2, P1, P2, K, dist, idx);
+        TPG_RETURN_IF_LAUNCH_FAILED();
+    }
+    return TPG_OK;
+}
+
 template <bool RADIUS>
 int knn_launch(const float *p1, const float *p2, const int64_t *len1, const int64_t *len2, int B,
                int P1, int P2, int D, int K, float r2, float *dist, int64_t *idx,
@@ -321,6 +354,16 @@ int knn_launch(const float *p1, const float *p2, const int64_t *len1, const int6
     if (mfma_on && !RADIUS && al && K > 1 && K <= KM_MAX_K && (D == 32 || D == 64) && P2 >= TPG_KNN_MFMA_MIN_POINTS) {
         if (D == 32) return knn_mfma_launch<32>(p1, p2, len1, len2, B, P1, P2, K, dist, idx, true, st);
         return knn_mfma_launch<64>(p1, p2, len1, len2, B, P1, P2, K, dist, idx, true, st);
+    }
+#endif
+#ifndef TPG_KNN_NO_SMALL
+    // small feature-space clouds (the generator's (24, 512, 32 / 64) searches): the same filter in one sweep, every
+    // approximate distance of a workgroup's queries in LDS (knn_small.hpp)
+    static const bool small_on = [] { const char *e = getenv("TPG_KNN_SMALL"); return !(e && e[0] == '0'); }();   // A/B switch
+    if (small_on && !RADIUS && al && K > 1 && K <= KM_MAX_K && (D == 32 || D == 64) && P2 >= TPG_KNN_SMALL_MIN_POINTS &&
+        P2 < TPG_KNN_SMALL_MAX_POINTS) {
+        if (D == 32) return knn_small_launch<32>(p1, p2, len1, len2, B, P1, P2, K, dist, idx, true, st);
+        return knn_small_launch<64>(p1, p2, len1, len2, B, P1, P2, K, dist, idx, true, st);
     }
 #endif
     // feature-space searches with several neighbours: the query-tiled kernel
@@ -422,6 +465,17 @@ extern "C" int tpg_knn_mfma_f32(const float *p1, const float *p2, const int64_t 
     if ((reinterpret_cast<uintptr_t>(p1) | reinterpret_cast<uintptr_t>(p2)) & 15) return TPG_ERR_ARG;
     if (D == 32) return knn_mfma_launch<32>(p1, p2, len1, len2, B, P1, P2, K, dist, idx, redo != 0, tpg_stream(stream));
     return knn_mfma_launch<64>(p1, p2, len1, len2, B, P1, P2, K, dist, idx, redo != 0, tpg_stream(stream));
+}
+
+extern "C" int tpg_knn_small_f32(const float *p1, const float *p2, const int64_t *len1, const int64_t *len2, int B, int P1,
+                                 int P2, int D, int K, float *dist, int64_t *idx, int redo, void *stream) {
+    if (B < 0 || P1 < 0 || P2 < 0 || K <= 1) return TPG_ERR_ARG;
+    if ((D != 32 && D != 64) || K > KM_MAX_K || P2 > KS_MAX_P2) return TPG_ERR_UNSUPPORTED;
+    if ((long long)B * P1 == 0) return TPG_OK;
+    if (!p1 || !p2 || !dist || !idx || B > 65535) return TPG_ERR_ARG;
+    if ((reinterpret_cast<uintptr_t>(p1) | reinterpret_cast<uintptr_t>(p2)) & 15) return TPG_ERR_ARG;
+    if (D == 32) return knn_small_launch<32>(p1, p2, len1, len2, B, P1, P2, K, dist, idx, redo != 0, tpg_stream(stream));
+    return knn_small_launch<64>(p1, p2, len1, len2, B, P1, P2, K, dist, idx, redo != 0, tpg_stream(stream));
 }
 
 extern "C" int tpg_chamfer_fwd_f32(const float *src, const float *tgt, int B, int N, int M,

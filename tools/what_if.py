@@ -37,7 +37,7 @@ def free_fps(self, xyz, m, start=None, skip_origin=True):
 _cache = {}
 
 
-def free_knn(self, p1, p2, len1, len2, K, r2):
+def free_knn(self, p1, p2, len1, len2, K, r2, r=None):
     B, P1, D = p1.shape
     key = (B, P1, p2.shape[1], K)
     if key not in _cache:
