@@ -34,6 +34,24 @@ namespace {
 
 constexpr int KNN_WAVES = 4;  // waves (= queries) per workgroup
 
+// The canonical distance sum, t = q - p; acc = acc + t * t in dimension order (no FMA), between the wave's query (LDS,
+// broadcast reads) and a row held in registers: its arithmetic is what makes every list equal the oracle's bit for bit.
+template <int D_T>
+__device__ __forceinline__ float knn_dist_row(const float *qs, const float4 (&row)[D_T / 4]) {
+    const float4 *q4 = reinterpret_cast<const float4 *>(qs);
+    float acc = 0.0f;
+#pragma unroll
+    for (int d = 0; d < D_T / 4; ++d) {
+        const float4 qv = q4[d];
+        float t;
+        t = qv.x - row[d].x; acc = acc + t * t;
+        t = qv.y - row[d].y; acc = acc + t * t;
+        t = qv.z - row[d].z; acc = acc + t * t;
+        t = qv.w - row[d].w; acc = acc + t * t;
+    }
+    return acc;
+}
+
 // distance between the wave's query (LDS, broadcast reads) and this lane's row.
 template <int D_T>
 __device__ __forceinline__ float knn_dist(const float *__restrict__ qs,
@@ -64,7 +82,7 @@ __device__ __forceinline__ float knn_dist(const float *__restrict__ qs,
     return acc;
 }
 
-constexpr long long KM_REDO_MARK = -2;   // knn_mfma.hpp: first index slot of a query the filter could not settle
+#include "knn_gram.hpp"
 
 template <int D_T, bool RADIUS>
 __global__ __launch_bounds__(KNN_WAVES * 64) void knn_kernel(
@@ -191,17 +209,7 @@ __global__ __launch_bounds__(KNN_WAVES * 64) void knn_tile_kernel(
             // Q*D of them out of the tile loop into registers (512 VGPRs + scratch); with it each
             // query is re-read from LDS (broadcast ds_read_b128) right before it is used
             asm volatile("" ::: "memory");
-            const float4 *q4 = reinterpret_cast<const float4 *>(qs + qq * D_T);
-            float acc = 0.0f;
-#pragma unroll
-            for (int d = 0; d < D_T / 4; ++d) {
-                const float4 qv = q4[d];
-                float t;
-                t = qv.x - row[d].x; acc = acc + t * t;
-                t = qv.y - row[d].y; acc = acc + t * t;
-                t = qv.z - row[d].z; acc = acc + t * t;
-                t = qv.w - row[d].w; acc = acc + t * t;
-            }
+            const float acc = knn_dist_row<D_T>(qs + qq * D_T, row);
             tpg_u64 key = TPG_KNN_INF;
             if (j < n2 && (!RADIUS || acc < r2)) key = tpg_knn_key(acc, j);
             tpg_knn_merge(best[qq], thr[qq], key, K, lane, slot);
@@ -219,7 +227,7 @@ __global__ __launch_bounds__(KNN_WAVES * 64) void knn_tile_kernel(
     }
 }
 
-// The queries the matrix-core filter left open (first index slot == KM_REDO_MARK), exhaustively: a workgroup looks
+// The queries the matrix-core filter left open (first index slot == KM_REDO), exhaustively: a workgroup looks
 // at 4 consecutive queries and gives EVERY open one all four of its waves -- each wave scans a quarter of the cloud
 // into its own K-best list, wave 0 merges the four lists (4 x 64 keys through the same rank merge).  Open queries
 // are a handful per cloud and sit in different workgroups: the launch lasts one quarter-scan, not one scan.
@@ -240,7 +248,7 @@ __global__ __launch_bounds__(KNN_WAVES * 64) void knn_redo_kernel(
         const int i = blockIdx.x * KNN_WAVES + u;
         if (i >= P1) break;                                            // (uniform over the workgroup)
         const size_t q = (size_t)b * P1 + i;
-        if (idx[q * K] != KM_REDO_MARK) continue;                      // (uniform: every thread reads the same slot)
+        if (idx[q * K] != KM_REDO) continue;                           // (uniform: every thread reads the same slot)
         __syncthreads();                                               // the previous query's LDS is free
         if (threadIdx.x < D_T) qs[threadIdx.x] = p1[q * D_T + threadIdx.x];
         __syncthreads();
@@ -272,17 +280,16 @@ __global__ __launch_bounds__(KNN_WAVES * 64) void knn_redo_kernel(
 #define TPG_KNN_MFMA_MIN_POINTS 2048    // clouds from which the matrix-core filter beats the tiled exhaustive kernel
 #endif
 
-// the filter kernel, then (redo) the exhaustive kernel on the queries it marked
-template <int D_T, int M>
-int knn_mfma_launch_m(const float *p1, const float *p2, const int64_t *len1, const int64_t *len2, int B, int P1, int P2,
-                      int K, float *dist, int64_t *idx, bool redo, hipStream_t st) {
-    if (!tpg_allow_dynamic_lds<&knn_mfma_kernel<D_T, M>>((int)km_smem_bytes<D_T>())) return TPG_ERR_LAUNCH;
-    const int gx = (P1 + KM_Q - 1) / KM_Q;
+// A filter's launch: gx workgroups of QW queries per cloud, the LDS opt-in of KERNEL (lds_max: the most it can ever ask
+// for), the filter kernel (launch(gx, total)), then (redo) the exhaustive kernel on the queries it marked
+template <int D_T, auto KERNEL, typename Launch>
+int knn_filter_launch(int QW, size_t lds_max, const float *p1, const float *p2, const int64_t *len1, const int64_t *len2, int B,
+                      int P1, int P2, int K, float *dist, int64_t *idx, bool redo, hipStream_t st, Launch launch) {
+    if (!tpg_allow_dynamic_lds<KERNEL>((int)lds_max)) return TPG_ERR_LAUNCH;
+    const int gx = (P1 + QW - 1) / QW;
     const long long total = (long long)gx * B;
     if (total > (1ll << 30)) return TPG_ERR_ARG;
-    const unsigned grid = (unsigned)((total + 7) / 8 * 8);
-    hipLaunchKernelGGL((knn_mfma_kernel<D_T, M>), dim3(grid), dim3(KM_WAVES * 64), km_smem_bytes<D_T>(), st, p1, p2, len1, len2,
-                       P1, P2, K, gx, (int)total, dist, idx);
+    launch(gx, (int)total);
     TPG_RETURN_IF_LAUNCH_FAILED();
     if (redo) {
         const dim3 rg((unsigned)((P1 + KNN_WAVES - 1) / KNN_WAVES), (unsigned)B);
@@ -290,6 +297,16 @@ int knn_mfma_launch_m(const float *p1, const float *p2, const int64_t *len1, con
         TPG_RETURN_IF_LAUNCH_FAILED();
     }
     return TPG_OK;
+}
+
+template <int D_T, int M>
+int knn_mfma_launch_m(const float *p1, const float *p2, const int64_t *len1, const int64_t *len2, int B, int P1, int P2,
+                      int K, float *dist, int64_t *idx, bool redo, hipStream_t st) {
+    return knn_filter_launch<D_T, &knn_mfma_kernel<D_T, M>>(
+        KM_Q, km_smem_bytes<D_T>(), p1, p2, len1, len2, B, P1, P2, K, dist, idx, redo, st, [&](int gx, int total) {
+            hipLaunchKernelGGL((knn_mfma_kernel<D_T, M>), dim3((unsigned)((total + 7) / 8 * 8)), dim3(KM_WAVES * 64),
+                               km_smem_bytes<D_T>(), st, p1, p2, len1, len2, P1, P2, K, gx, total, dist, idx);
+        });
 }
 
 // minima kept per lane: 2 M points are guaranteed below the threshold, ~2.4 M expected; K + 8 <= 2 M keeps the
@@ -317,24 +334,15 @@ int knn_mfma_launch(const float *p1, const float *p2, const int64_t *len1, const
 #endif
 static_assert(TPG_KNN_SMALL_MAX_POINTS <= KS_MAX_P2 + 1, "the distance matrix of knn_small_kernel must fit the LDS");
 
-// the one-sweep filter kernel, then (redo) the exhaustive kernel on the queries it marked
 template <int D_T>
 int knn_small_launch(const float *p1, const float *p2, const int64_t *len1, const int64_t *len2, int B, int P1, int P2,
                      int K, float *dist, int64_t *idx, bool redo, hipStream_t st) {
     if (P2 > KS_MAX_P2) return TPG_ERR_UNSUPPORTED;
-    if (!tpg_allow_dynamic_lds<&knn_small_kernel<D_T>>((int)ks_smem_bytes<D_T>(KS_MAX_P2))) return TPG_ERR_LAUNCH;
-    const int gx = (P1 + KS_Q - 1) / KS_Q;
-    const long long total = (long long)gx * B;
-    if (total > (1ll << 30)) return TPG_ERR_ARG;
-    hipLaunchKernelGGL((knn_small_kernel<D_T>), dim3((unsigned)total), dim3(KS_WAVES * 64), ks_smem_bytes<D_T>(P2), st, p1, p2,
-                       len1, len2, P1, P2, K, gx, dist, idx);
-    TPG_RETURN_IF_LAUNCH_FAILED();
-    if (redo) {
-        const dim3 rg((unsigned)((P1 + KNN_WAVES - 1) / KNN_WAVES), (unsigned)B);
-        hipLaunchKernelGGL((knn_redo_kernel<D_T>), rg, dim3(KNN_WAVES * 64), 0, st, p1, p2, len1, len2, P1, P2, K, dist, idx);
-        TPG_RETURN_IF_LAUNCH_FAILED();
-    }
-    return TPG_OK;
+    return knn_filter_launch<D_T, &knn_small_kernel<D_T>>(
+        KS_Q, ks_smem_bytes<D_T>(KS_MAX_P2), p1, p2, len1, len2, B, P1, P2, K, dist, idx, redo, st, [&](int gx, int total) {
+            hipLaunchKernelGGL((knn_small_kernel<D_T>), dim3((unsigned)total), dim3(KS_WAVES * 64), ks_smem_bytes<D_T>(P2), st,
+                               p1, p2, len1, len2, P1, P2, K, gx, dist, idx);
+        });
 }
 
 template <bool RADIUS>
@@ -349,7 +357,7 @@ int knn_launch(const float *p1, const float *p2, const int64_t *len1, const int6
     // the vector path also needs 16-B aligned rows: D % 4 == 0 and aligned bases
     const bool al = ((reinterpret_cast<uintptr_t>(p1) | reinterpret_cast<uintptr_t>(p2)) & 15) == 0;
 #ifndef TPG_KNN_NO_MFMA
-    // large feature-space clouds: Gram filter on the f32 matrix cores + exact re-ranking (knn_mfma.hpp)
+    // large feature-space clouds: Gram filter on the bf16 matrix cores + exact re-ranking (knn_mfma.hpp)
     static const bool mfma_on = [] { const char *e = getenv("TPG_KNN_MFMA"); return !(e && e[0] == '0'); }();   // A/B switch
     if (mfma_on && !RADIUS && al && K > 1 && K <= KM_MAX_K && (D == 32 || D == 64) && P2 >= TPG_KNN_MFMA_MIN_POINTS) {
         if (D == 32) return knn_mfma_launch<32>(p1, p2, len1, len2, B, P1, P2, K, dist, idx, true, st);
@@ -456,24 +464,27 @@ extern "C" int tpg_knn_f32(const float *p1, const float *p2, const int64_t *len1
     return knn_launch<false>(p1, p2, len1, len2, B, P1, P2, D, K, r2, dist, idx, tpg_stream(stream));
 }
 
-extern "C" int tpg_knn_mfma_f32(const float *p1, const float *p2, const int64_t *len1, const int64_t *len2, int B, int P1,
-                                int P2, int D, int K, float *dist, int64_t *idx, int redo, void *stream) {
+// the argument checks of the two diagnostic filter entries (p2_fits: the entry's own bound on P2); > 0: go on
+static int knn_filter_check(const float *p1, const float *p2, int B, int P1, int P2, int D, int K, bool p2_fits,
+                            const float *dist, const int64_t *idx) {
     if (B < 0 || P1 < 0 || P2 < 0 || K <= 1) return TPG_ERR_ARG;
-    if ((D != 32 && D != 64) || K > KM_MAX_K) return TPG_ERR_UNSUPPORTED;
+    if ((D != 32 && D != 64) || K > KM_MAX_K || !p2_fits) return TPG_ERR_UNSUPPORTED;
     if ((long long)B * P1 == 0) return TPG_OK;
     if (!p1 || !p2 || !dist || !idx || B > 65535) return TPG_ERR_ARG;
     if ((reinterpret_cast<uintptr_t>(p1) | reinterpret_cast<uintptr_t>(p2)) & 15) return TPG_ERR_ARG;
+    return 1;
+}
+
+extern "C" int tpg_knn_mfma_f32(const float *p1, const float *p2, const int64_t *len1, const int64_t *len2, int B, int P1,
+                                int P2, int D, int K, float *dist, int64_t *idx, int redo, void *stream) {
+    if (const int rc = knn_filter_check(p1, p2, B, P1, P2, D, K, true, dist, idx); rc <= 0) return rc;
     if (D == 32) return knn_mfma_launch<32>(p1, p2, len1, len2, B, P1, P2, K, dist, idx, redo != 0, tpg_stream(stream));
     return knn_mfma_launch<64>(p1, p2, len1, len2, B, P1, P2, K, dist, idx, redo != 0, tpg_stream(stream));
 }
 
 extern "C" int tpg_knn_small_f32(const float *p1, const float *p2, const int64_t *len1, const int64_t *len2, int B, int P1,
                                  int P2, int D, int K, float *dist, int64_t *idx, int redo, void *stream) {
-    if (B < 0 || P1 < 0 || P2 < 0 || K <= 1) return TPG_ERR_ARG;
-    if ((D != 32 && D != 64) || K > KM_MAX_K || P2 > KS_MAX_P2) return TPG_ERR_UNSUPPORTED;
-    if ((long long)B * P1 == 0) return TPG_OK;
-    if (!p1 || !p2 || !dist || !idx || B > 65535) return TPG_ERR_ARG;
-    if ((reinterpret_cast<uintptr_t>(p1) | reinterpret_cast<uintptr_t>(p2)) & 15) return TPG_ERR_ARG;
+    if (const int rc = knn_filter_check(p1, p2, B, P1, P2, D, K, P2 <= KS_MAX_P2, dist, idx); rc <= 0) return rc;
     if (D == 32) return knn_small_launch<32>(p1, p2, len1, len2, B, P1, P2, K, dist, idx, redo != 0, tpg_stream(stream));
     return knn_small_launch<64>(p1, p2, len1, len2, B, P1, P2, K, dist, idx, redo != 0, tpg_stream(stream));
 }

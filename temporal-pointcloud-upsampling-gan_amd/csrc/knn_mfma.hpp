@@ -3,19 +3,8 @@
 //
 // The exhaustive kernels of knn.hip evaluate the canonical distance sum_d (q_d - p_d)^2 for every pair on
 // the VALU (three instructions per pair and dimension): 4.6 ms per search on cfg5's (40, 4096, 32) clouds,
-// 30 ms on a 65536-point rollout scene (upsampling_network.py:159-174) -- 97 % of a rollout frame.  The
-// neighbour LIST is what must be bit-exact against the oracle, not the way candidates are ruled out:
-//
-//   approximate  d~(q,p) = |y_q|^2 + |y_p|^2 - 2 y_q.y_p ,  y = x - origin (the mean of the cloud's first tile of points)
-//
-// with the product on v_mfma_f32_32x32x16_bf16 from SPLIT operands: t = hi + lo + r, hi = bf16(t),
-// lo = bf16(t - hi), |r| <= 2^-16 |t|; hi.hi + hi.lo + lo.hi leaves out lo.lo and the two residual terms,
-// together <= 6.06 2^-16 |y_q||y_p|.  (A first form on v_mfma_f32_32x32x2_f32 -- exact fp32, five times tighter --
-// was 2-3x slower: the f32 matrix instruction runs at the vector rate and does NOT co-execute with the VALU work
-// of the selection, SQ_VALU_MFMA_COEXEC_CYCLES = 0; the bf16 one costs 7 x 32 cycles per 32 x 32 pairs beside it.)
-// |y_p|^2 enters as a fourth product: three bf16 terms (exact) in the spare words of the LDS row against (1, 1, 1).
-//
-//   |d~ - d_canonical| <= E_q := 2^-13 |y_q| max_p|y_p| + (8 D + 64) 2^-24 (|y_q| + max_p|y_p|)^2
+// 30 ms on a 65536-point rollout scene (upsampling_network.py:159-174) -- 97 % of a rollout frame.  knn_gram.hpp states
+// the approximation d~ (|y_p|^2 from the spare words of the LDS row), its bound E_q and the tail's key: here, the sweeps.
 //
 // One workgroup owns 128 queries (4 waves x 32; the split queries stay in registers as the B operand), two
 // workgroups per CU, and sweeps the cloud TWICE through a double-buffered LDS tile of split -2 y_p rows:
@@ -25,7 +14,7 @@
 //            M = 10 / 14 / 16 by K (K + 8 <= 2 M), 16 from 16384 points;
 //   sweep 2  the same products again; every pair with d~ <= tau_q appends its index to the query's LDS
 //            list (64 slots; ~2.4 M entries expected);
-//   tail     one wave per query: canonical distance of the listed points (the arithmetic of knn_dist), rank
+//   tail     one wave per query: canonical distance of the listed points (km_tail_key: knn_dist_row of knn.hip), rank
 //            by counting over the 64-bit (dist, idx) keys, the first K are the
 //            answer IF  tau_q - E_q > d_K  (every unlisted point has d~ > tau_q, hence a canonical distance
 //            above d_K: it cannot enter or tie).  Otherwise (list overflow, ragged tails, and clouds whose
@@ -35,20 +24,11 @@
 //            kernels' output bit for bit in every case; only the time depends on the data.
 #pragma once
 
-typedef float km_f32x16 __attribute__((ext_vector_type(16)));
-
-#ifndef KM_WAVES_PER_WG
-#define KM_WAVES_PER_WG 4
-#endif
-constexpr int KM_WAVES = KM_WAVES_PER_WG;   // waves per workgroup (4: two workgroups per CU, out of step with each other)
+constexpr int KM_WAVES = 4;             // waves per workgroup (4: two workgroups per CU, out of step with each other)
 constexpr int KM_Q = KM_WAVES * 32;     // queries per workgroup
 template <int D_T>
 constexpr int km_tile_rows() { return D_T == 32 ? 128 : 64; }   // points per staged tile: two workgroups' LDS must fit a CU
-constexpr int KM_CAP = 64;              // candidate slots per query
-constexpr float KM_BIG = 1.0e30f;       // the norm of a padding row / an empty list entry: finite (no 0 x INF in the matrix unit), never a hit
 constexpr int KM_MIN_VALID = 1024;      // fewer valid points than this in a cloud: no filter (32 entries per lane are the floor)
-constexpr int KM_MAX_K = 24;            // 2 M guaranteed candidates (M = 10 / 14 / 16 minima kept per lane) must exceed K with room to spare
-constexpr long long KM_REDO = KM_REDO_MARK;   // first index slot of a query the exhaustive kernel must redo
 
 template <int CTRL>
 __device__ __forceinline__ float km_dpp_f32(float v) {
@@ -62,8 +42,6 @@ constexpr size_t km_smem_bytes() {
            sizeof(tpg_u64) * KM_WAVES * 64;
 }
 
-typedef __bf16 km_bf16x8 __attribute__((ext_vector_type(8)));
-
 // v_min / v_max as they are, for values the compiler's own instructions produced: fminf / fmaxf put a canonicalising
 // v_max x, x, x in front of their operands (quiet-NaN semantics), a third of the sorted-insert chain.  NOT for the
 // accumulators of a matrix instruction: the hazard recogniser does not look inside inline asm, and a v_min issued
@@ -71,16 +49,6 @@ typedef __bf16 km_bf16x8 __attribute__((ext_vector_type(8)));
 // queries overflowed their candidate list).  No NaN reaches these (finite rows, 1e30 on padding).
 __device__ __forceinline__ float km_min(float a, float b) { float r; asm("v_min_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b)); return r; }
 __device__ __forceinline__ float km_max(float a, float b) { float r; asm("v_max_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b)); return r; }
-
-// x = hi + lo + r with hi = bf16(x), lo = bf16(x - hi) (x - hi is exact in fp32): |r| <= 2^-16 |x|
-__device__ __forceinline__ void km_split2(float a, float b, unsigned &hi, unsigned &lo) {
-    const __hip_bfloat16 ha = __float2bfloat16(a), hb = __float2bfloat16(b);
-    const unsigned short ua = *reinterpret_cast<const unsigned short *>(&ha), ub = *reinterpret_cast<const unsigned short *>(&hb);
-    hi = (unsigned)ua | ((unsigned)ub << 16);
-    const float ra = a - __uint_as_float((unsigned)ua << 16), rb = b - __uint_as_float((unsigned)ub << 16);
-    const __hip_bfloat16 la = __float2bfloat16(ra), lb = __float2bfloat16(rb);
-    lo = (unsigned)*reinterpret_cast<const unsigned short *>(&la) | ((unsigned)*reinterpret_cast<const unsigned short *>(&lb) << 16);
-}
 
 template <int D_T, int KM_M>
 __global__ __launch_bounds__(KM_WAVES * 64, 8 / KM_WAVES) void knn_mfma_kernel(
@@ -147,22 +115,8 @@ __global__ __launch_bounds__(KM_WAVES * 64, 8 / KM_WAVES) void knn_mfma_kernel(
     float nq = 0.0f;
 #pragma unroll
     for (int ks = 0; ks < KS; ++ks) {
-        float y[8];
-#pragma unroll
-        for (int v = 0; v < 2; ++v) {
-            float4 x = make_float4(0.f, 0.f, 0.f, 0.f);
-            const float4 o = *reinterpret_cast<const float4 *>(org + 16 * ks + 8 * h + 4 * v);
-            if (qi < P1) {
-                x = *reinterpret_cast<const float4 *>(p1 + ((size_t)b * P1 + qi) * D_T + 16 * ks + 8 * h + 4 * v);
-                x.x -= o.x; x.y -= o.y; x.z -= o.z; x.w -= o.w;
-            }
-            y[4 * v] = x.x; y[4 * v + 1] = x.y; y[4 * v + 2] = x.z; y[4 * v + 3] = x.w;
-            nq += x.x * x.x + x.y * x.y + x.z * x.z + x.w * x.w;
-        }
-        km_split2(y[0], y[1], bqh[ks].x, bql[ks].x);
-        km_split2(y[2], y[3], bqh[ks].y, bql[ks].y);
-        km_split2(y[4], y[5], bqh[ks].z, bql[ks].z);
-        km_split2(y[6], y[7], bqh[ks].w, bql[ks].w);
+        km_centre_split(reinterpret_cast<const float4 *>(p1 + ((size_t)b * P1 + qi) * D_T + 16 * ks + 8 * h), org + 16 * ks + 8 * h,
+                        qi < P1, 1.0f, bqh[ks], bql[ks], nq);
     }
     nq += __shfl_xor(nq, 32);
 
@@ -198,26 +152,15 @@ __global__ __launch_bounds__(KM_WAVES * 64, 8 / KM_WAVES) void knn_mfma_kernel(
             *reinterpret_cast<uint2 *>(tile + row * LD + 2 * sv) = hi;
             *reinterpret_cast<uint2 *>(tile + row * LD + D_T / 2 + 2 * sv) = lo;
             if (sv == 0) {
-                // |y_p|^2 as three bf16 terms (8 + 8 + 8 significant bits: exact) in the row's four spare words:
-                // one more matrix instruction against (1, 1, 1, 0 ...) starts the accumulator at the norm, instead
-                // of four LDS reads and sixteen moves per lane and sub-tile
-                const float nv = pv[p] ? s : KM_BIG;
-                const __hip_bfloat16 n0 = __float2bfloat16(nv);
-                const float r0 = nv - __bfloat162float(n0);
-                const __hip_bfloat16 n1 = __float2bfloat16(r0);
-                const __hip_bfloat16 n2b = __float2bfloat16(r0 - __bfloat162float(n1));
-                const unsigned w0 = (unsigned)*reinterpret_cast<const unsigned short *>(&n0) |
-                                    ((unsigned)*reinterpret_cast<const unsigned short *>(&n1) << 16);
-                const unsigned w1 = (unsigned)*reinterpret_cast<const unsigned short *>(&n2b);
+                unsigned w0, w1;                                       // the norm triplet, into the row's four spare words
+                km_norm_triplet(pv[p] ? s : KM_BIG, w0, w1);
                 *reinterpret_cast<uint4 *>(tile + row * LD + D_T) = make_uint4(w0, w1, 0u, 0u);
             }
             if (pv[p]) mymax = fmaxf(mymax, s);
         }
     };
 
-    // B operand of the norm step: ones at k = 0, 1, 2 (lanes of the lower half), zeros elsewhere
-    const uint4 ones = h == 0 ? make_uint4(0x3f803f80u, 0x00003f80u, 0u, 0u) : make_uint4(0u, 0u, 0u, 0u);
-    const km_f32x16 zero16 = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    const uint4 ones = km_ones(h);
     float lst[KM_M];
 #pragma unroll
     for (int i = 0; i < KM_M; ++i) lst[i] = KM_BIG;
@@ -227,8 +170,7 @@ __global__ __launch_bounds__(KM_WAVES * 64, 8 / KM_WAVES) void knn_mfma_kernel(
     // well over KM_M entries for its KM_M-th smallest to be a tight threshold
     const bool pairs = n2 >= 4096;
 
-    // One sweep over the cloud.  d' = |y_p|^2 - 2 y_p.y_q (the query's own norm is added in the tail): the accumulator
-    // starts from the row norms and takes 3 KS matrix instructions (hi.hi + hi.lo + lo.hi) per 32 x 32 pairs.
+    // One sweep over the cloud: km_gram's d' per 32 x 32 pairs (the query's own norm is added in the tail).
     // The VALU work on sub-tile s-1 (minima / hit mask) sits between the matrix instructions of sub-tile s.
     auto sweep = [&](auto second_tag, int step0, float tauf) {
         constexpr bool SECOND = decltype(second_tag)::value;
@@ -251,15 +193,7 @@ __global__ __launch_bounds__(KM_WAVES * 64, 8 / KM_WAVES) void knn_mfma_kernel(
                         al[ks] = *reinterpret_cast<const uint4 *>(arow + D_T / 2 + 8 * ks);
                     }
                     const uint4 an = *reinterpret_cast<const uint4 *>(tile + (cur * KM_TP + sub * 32 + c) * LD + D_T);
-                    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(km_bf16x8, an), __builtin_bit_cast(km_bf16x8, ones), zero16, 0, 0, 0);
-#pragma unroll
-                    for (int ks = 0; ks < KS; ++ks) {
-                        const km_bf16x8 Ah = __builtin_bit_cast(km_bf16x8, ah[ks]), Al = __builtin_bit_cast(km_bf16x8, al[ks]);
-                        const km_bf16x8 Bh = __builtin_bit_cast(km_bf16x8, bqh[ks]), Bl = __builtin_bit_cast(km_bf16x8, bql[ks]);
-                        acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(Al, Bh, acc, 0, 0, 0);
-                        acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(Ah, Bl, acc, 0, 0, 0);
-                        acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(Ah, Bh, acc, 0, 0, 0);
-                    }
+                    acc = km_gram<KS>(an, ones, ah, al, bqh, bql);
                 }
                 if (sub > 0) {
                     if constexpr (!SECOND) {
@@ -321,13 +255,7 @@ __global__ __launch_bounds__(KM_WAVES * 64, 8 / KM_WAVES) void knn_mfma_kernel(
     __syncthreads();
 
     // ---- tail: exact re-ranking, one wave per query ------------------------------------------------------
-    // |d~ - d_canonical| <= E_q = c1 |y_q| max|y_p| + c2 (|y_q| + max|y_p|)^2 :
-    //   c1 = 2^-13: the three dropped cross terms of the split products, 6.06 2^-16 |y_q||y_p|, with a third to spare;
-    //   c2 = (8 D + 64) 2^-24: fp32 accumulation of the 3 D / 16 matrix steps (taken as 4 ulp each of the running
-    //        magnitude), the two norms, the centring and the canonical sum itself, doubled.
     const float sq_pmax = sqrtf(__uint_as_float(*pmax));
-    constexpr float C1 = 1.220703125e-4f;                                         // 2^-13
-    constexpr float C2 = (float)(8 * D_T + 64) * 5.9604644775390625e-8f;          // (8 D + 64) 2^-24
     float *qs = qrow + wave * D_T;
     tpg_u64 *ks_ = keys + wave * 64;
     const tpg_u64 INF = TPG_KNN_INF;
@@ -357,24 +285,9 @@ __global__ __launch_bounds__(KM_WAVES * 64, 8 / KM_WAVES) void knn_mfma_kernel(
         const float nqq = __uint_as_float((unsigned)__builtin_amdgcn_readlane((int)__float_as_uint(nq), qq));
         const float tq = __uint_as_float((unsigned)__builtin_amdgcn_readlane((int)__float_as_uint(tau), qq)) + nqq;
         const float sqq = sqrtf(nqq);
-        const float eq = C1 * sqq * sq_pmax + C2 * (sqq + sq_pmax) * (sqq + sq_pmax);
+        const float eq = km_bound<D_T>(sqq, sq_pmax);
         if (lane < D_T) qs[lane] = p1[((size_t)b * P1 + i) * D_T + lane];
-        tpg_u64 key = INF;
-        if (j >= 0) {
-            // the canonical sum of knn_dist (knn.hip), the candidate row in registers
-            const float4 *q4 = reinterpret_cast<const float4 *>(qs);
-            float acc = 0.0f;
-#pragma unroll
-            for (int d = 0; d < V4; ++d) {
-                const float4 qv = q4[d];
-                float t;
-                t = qv.x - row[d].x; acc = acc + t * t;
-                t = qv.y - row[d].y; acc = acc + t * t;
-                t = qv.z - row[d].z; acc = acc + t * t;
-                t = qv.w - row[d].w; acc = acc + t * t;
-            }
-            key = tpg_knn_key(acc, j);
-        }
+        const tpg_u64 key = km_tail_key<D_T>(qs, row, j);
         ks_[lane] = key;
         int rank = 0;
         const int nk = n <= KM_CAP ? n : 0;
@@ -386,9 +299,6 @@ __global__ __launch_bounds__(KM_WAVES * 64, 8 / KM_WAVES) void knn_mfma_kernel(
             dk = tpg_knn_key_dist(tpg_readlane_u64(key, __builtin_amdgcn_readfirstlane(__builtin_ctzll(kth))));
             ok = tq - eq > dk;
         }
-#ifdef KM_DEBUG
-        if (!ok && lane == 0) { od[(size_t)i * K] = (float)n; od[(size_t)i * K + 1] = tq; od[(size_t)i * K + 2] = eq; od[(size_t)i * K + 3] = dk; }
-#endif
         if (ok) {
             if (rank < K && key != INF) {
                 od[(size_t)i * K + rank] = tpg_knn_key_dist(key);

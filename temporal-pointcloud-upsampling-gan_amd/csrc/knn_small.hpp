@@ -1,6 +1,7 @@
-// Feature-space kNN (D = 32 / 64) on SMALL clouds (64 .. 1024 valid points): the Gram-matrix filter of knn_mfma.hpp
-// in one sweep, exact re-ranking of the survivors.  Included by knn.hip after knn_mfma.hpp (inside its anonymous
-// namespace); km_split2, the norm triplet, the origin, C1 / C2, KM_BIG, KM_CAP and KM_REDO are that file's.
+// Feature-space kNN (D = 32 / 64) on SMALL clouds (64 .. 1024 valid points): the Gram-matrix filter of knn_gram.hpp
+// in one sweep, exact re-ranking of the survivors.  Included by knn.hip after knn_gram.hpp and knn_mfma.hpp (inside its
+// anonymous namespace); the approximation, its bound, the tail's key, KM_BIG, KM_CAP and KM_REDO are knn_gram.hpp's,
+// the origin's tile (km_tile_rows) is knn_mfma.hpp's.
 //
 // The tiled exhaustive kernel spends three VALU instructions per pair and dimension (-ffp-contract=off): 24 x 512 x 512
 // pairs x 192 instructions is a floor of 31-35 us per search of the generator's (24, 512, 64) clouds, 75-82 us measured,
@@ -13,20 +14,20 @@
 //   sweep      the 32-row sub-tiles of the cloud are dealt to the waves.  A lane (row c = lane & 31, half h = lane >> 5)
 //              reads the half rows it feeds the matrix unit straight from global memory / L2 (the whole cloud is
 //              <= 256 KB), centres and splits them in registers -- the same work per lane as staging a tile in LDS,
-//              without the round trip, and the LDS goes to the distance matrix instead -- and takes the same
-//              1 + 3 D / 16 v_mfma_f32_32x32x16_bf16 products per sub-tile as knn_mfma.hpp (norm triplet, lo.hi, hi.lo,
-//              hi.hi).  d'(q, p) = |y_p|^2 - 2 y_p.y_q goes to the LDS matrix dm[query][point] (the query's own norm
+//              without the round trip, and the LDS goes to the distance matrix instead -- and takes the
+//              1 + 3 D / 16 v_mfma_f32_32x32x16_bf16 products per sub-tile (km_gram of knn_gram.hpp: norm triplet, lo.hi,
+//              hi.lo, hi.hi).  d'(q, p) = |y_p|^2 - 2 y_p.y_q goes to the LDS matrix dm[query][point] (the query's own norm
 //              is the same for every point of a row: it is never added);
 //   select     one wave per query, 4 queries per wave (selection and tail are chains of LDS and L2 latencies per
 //              query: with 4 waves and 8 queries each the kernel took 72 us where the tiled kernel takes 86).
 //              Every lane takes the minimum of its points (j = lane mod 64),
 //              T_q = the K-th smallest of the 64 lane minima (rank by counting): K DISTINCT points have d' <= T_q,
 //              and about K + 1 .. K + 6 in all.  C = {p : d' <= T_q + 2 E_q} is collected into <= KM_CAP = 64 slots;
-//   tail       as knn_mfma.hpp's: canonical distance of the listed rows (the arithmetic of knn_dist), rank by counting
+//   tail       knn_gram.hpp's: canonical distance of the listed rows (km_tail_key: knn_dist_row of knn.hip), rank by counting
 //              over the 64-bit (dist, idx) keys, the first K are written; at D = 32 the rows of the next query are
 //              fetched before the current one is ranked (at D = 64 a second set of rows does not fit 128 VGPRs).
 //
-// Why the first K of C are the answer.  |d~ - d_canonical| <= E_q for every point (knn_mfma.hpp's bound, max|y_p| over
+// Why the first K of C are the answer.  |d~ - d_canonical| <= E_q for every point (km_bound of knn_gram.hpp, max|y_p| over
 // the whole cloud; d~ = d' + |y_q|^2, so differences and thresholds in d' are differences and thresholds in d~):
 //   * the K points with d' <= T_q have a canonical distance <= T_q + E_q, so the true K-th distance d_K <= T_q + E_q;
 //   * every point of the true top K, and every point tying at d_K, has d~ <= d_K + E_q <= T_q + 2 E_q and is in C.
@@ -117,21 +118,8 @@ __global__ __launch_bounds__(KS_WAVES * 64, 4) void knn_small_kernel(
     auto centre_split = [&](const float4 (&x)[NV], bool valid, float scale, uint4 (&hi)[KS], uint4 (&lo)[KS]) {
         float s = 0.0f;
 #pragma unroll
-        for (int ks = 0; ks < KS; ++ks) {
-            float y[8];
-#pragma unroll
-            for (int v = 0; v < 2; ++v) {
-                float4 t = make_float4(0.f, 0.f, 0.f, 0.f);
-                const float4 o = *reinterpret_cast<const float4 *>(org + 16 * ks + 8 * h + 4 * v);   // this lane's dims of the origin
-                if (valid) { t.x = x[2 * ks + v].x - o.x; t.y = x[2 * ks + v].y - o.y; t.z = x[2 * ks + v].z - o.z; t.w = x[2 * ks + v].w - o.w; }
-                y[4 * v] = t.x; y[4 * v + 1] = t.y; y[4 * v + 2] = t.z; y[4 * v + 3] = t.w;
-                s += t.x * t.x + t.y * t.y + t.z * t.z + t.w * t.w;
-            }
-            km_split2(scale * y[0], scale * y[1], hi[ks].x, lo[ks].x);
-            km_split2(scale * y[2], scale * y[3], hi[ks].y, lo[ks].y);
-            km_split2(scale * y[4], scale * y[5], hi[ks].z, lo[ks].z);
-            km_split2(scale * y[6], scale * y[7], hi[ks].w, lo[ks].w);
-        }
+        for (int ks = 0; ks < KS; ++ks)      // (org + ...: this lane's dims of the origin)
+            km_centre_split(x + 2 * ks, org + 16 * ks + 8 * h, valid, scale, hi[ks], lo[ks], s);
         return s + __shfl_xor(s, 32);
     };
 
@@ -146,8 +134,7 @@ __global__ __launch_bounds__(KS_WAVES * 64, 4) void knn_small_kernel(
     }
 
     // ---- the sweep: sub-tile s = wave, wave + 8, ... (16 waves per CU hide the rows' way from L2) ----
-    const uint4 ones = h == 0 ? make_uint4(0x3f803f80u, 0x00003f80u, 0u, 0u) : make_uint4(0u, 0u, 0u, 0u);
-    const km_f32x16 zero16 = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    const uint4 ones = km_ones(h);
     const int NS = (n2 + 31) >> 5;
     float mymax = 0.0f;
     for (int s = wave; s < NS; s += KS_WAVES) {
@@ -156,26 +143,12 @@ __global__ __launch_bounds__(KS_WAVES * 64, 4) void knn_small_kernel(
         load_half(cb + (size_t)min(32 * s + c, n2 - 1) * D_T, valid, cur);
         uint4 ah[KS], al[KS];
         const float ss = centre_split(cur, valid, -2.0f, ah, al);
-        // |y_p|^2 as three bf16 terms (exact) against (1, 1, 1): the accumulator starts at the norm; KM_BIG on padding rows
-        const float nv = valid ? ss : KM_BIG;
-        const __hip_bfloat16 t0 = __float2bfloat16(nv);
-        const float r0 = nv - __bfloat162float(t0);
-        const __hip_bfloat16 t1 = __float2bfloat16(r0);
-        const __hip_bfloat16 t2 = __float2bfloat16(r0 - __bfloat162float(t1));
-        const unsigned w0 = (unsigned)*reinterpret_cast<const unsigned short *>(&t0) |
-                            ((unsigned)*reinterpret_cast<const unsigned short *>(&t1) << 16);
-        const unsigned w1 = (unsigned)*reinterpret_cast<const unsigned short *>(&t2);
+        // the accumulator starts at the row's norm triplet; KM_BIG on padding rows
+        unsigned w0, w1;
+        km_norm_triplet(valid ? ss : KM_BIG, w0, w1);
         const uint4 an = h == 0 ? make_uint4(w0, w1, 0u, 0u) : make_uint4(0u, 0u, 0u, 0u);
         if (valid) mymax = (ss > mymax || ss != ss) ? ss : mymax;      // a NaN norm stays (fmaxf would drop it)
-        km_f32x16 acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(km_bf16x8, an), __builtin_bit_cast(km_bf16x8, ones), zero16, 0, 0, 0);
-#pragma unroll
-        for (int ks = 0; ks < KS; ++ks) {
-            const km_bf16x8 Ah = __builtin_bit_cast(km_bf16x8, ah[ks]), Al = __builtin_bit_cast(km_bf16x8, al[ks]);
-            const km_bf16x8 Bh = __builtin_bit_cast(km_bf16x8, bqh[ks]), Bl = __builtin_bit_cast(km_bf16x8, bql[ks]);
-            acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(Al, Bh, acc, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(Ah, Bl, acc, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(Ah, Bh, acc, 0, 0, 0);
-        }
+        const km_f32x16 acc = km_gram<KS>(an, ones, ah, al, bqh, bql);
         // acc[4 g + r] is (point 32 s + 8 g + 4 h + r, query c)
         float *drow = dm + c * LDQ + 32 * s + 4 * h;
 #pragma unroll
@@ -186,10 +159,7 @@ __global__ __launch_bounds__(KS_WAVES * 64, 4) void knn_small_kernel(
     __syncthreads();
 
     // ---- select: threshold and candidate list of this wave's KS_QW queries --------------------------------
-    // |d~ - d_canonical| <= E_q = c1 |y_q| max|y_p| + c2 (|y_q| + max|y_p|)^2, c1 and c2 as in knn_mfma.hpp
     const float sq_pmax = sqrtf(__uint_as_float(*pmax));
-    constexpr float C1 = 1.220703125e-4f;                                         // 2^-13
-    constexpr float C2 = (float)(8 * D_T + 64) * 5.9604644775390625e-8f;          // (8 D + 64) 2^-24
     const int NT = (n2 + 63) >> 6;
     for (int qq = 0; qq < KS_QW; ++qq) {
         const int ql = wave * KS_QW + qq, i = q0 + ql;
@@ -213,7 +183,7 @@ __global__ __launch_bounds__(KS_WAVES * 64, 4) void knn_small_kernel(
         const float T = __uint_as_float((unsigned)__builtin_amdgcn_readlane(
             (int)__float_as_uint(mn), __builtin_amdgcn_readfirstlane(at ? __builtin_ctzll(at) : 0)));
         const float sqq = sqrtf(nqs[ql]);
-        const float eq = (C1 * sqq * sq_pmax + C2 * (sqq + sq_pmax) * (sqq + sq_pmax)) * 1.001f;
+        const float eq = km_bound<D_T>(sqq, sq_pmax) * 1.001f;
         float thr = T + 2.0f * eq;
         thr = thr + fabsf(thr) * 9.5367431640625e-7f;                  // + 2^-20: upwards, whatever the additions rounded
         int n = 0;
@@ -264,22 +234,7 @@ __global__ __launch_bounds__(KS_WAVES * 64, 4) void knn_small_kernel(
             return;
         }
         if (lane < D_T) qs[lane] = qx;
-        tpg_u64 key = INF;
-        if (j >= 0) {
-            // the canonical sum of knn_dist (knn.hip), the candidate row in registers
-            const float4 *q4 = reinterpret_cast<const float4 *>(qs);
-            float acc = 0.0f;
-#pragma unroll
-            for (int d = 0; d < V4; ++d) {
-                const float4 qv = q4[d];
-                float t;
-                t = qv.x - row[d].x; acc = acc + t * t;
-                t = qv.y - row[d].y; acc = acc + t * t;
-                t = qv.z - row[d].z; acc = acc + t * t;
-                t = qv.w - row[d].w; acc = acc + t * t;
-            }
-            key = tpg_knn_key(acc, j);
-        }
+        const tpg_u64 key = km_tail_key<D_T>(qs, row, j);
         ks_[lane] = key;
         const int nk = (n >= K && n <= KM_CAP) ? n : 0;
         int rank = 0;

@@ -119,6 +119,9 @@ def test_new_entries_reject_bad_arguments_before_any_launch(hip_lib):
     assert hip_lib.tpg_knn_mfma_f32(p, p, None, None, 1, 8, 8, 48, 4, p, p, 1, None) == -3
     assert hip_lib.tpg_knn_mfma_f32(p, p, None, None, 1, 8, 8, 32, 25, p, p, 1, None) == -3
     assert hip_lib.tpg_knn_mfma_f32(p, p, None, None, 1, 8, 8, 32, 1, p, p, 1, None) == -1
+    assert hip_lib.tpg_knn_mfma_f32(p, None, None, None, 1, 8, 8, 32, 4, p, p, 1, None) == -1       # null p2
+    assert hip_lib.tpg_knn_mfma_f32(C.c_void_p(p.value + 4), p, None, None, 1, 8, 8, 32, 4, p, p, 1, None) == -1   # rows not 16-byte aligned
+    assert hip_lib.tpg_knn_mfma_f32(p, p, None, None, 70000, 8, 8, 32, 4, p, p, 1, None) == -1      # B > 65535
     assert hip_lib.tpg_knn_mfma_f32(p, p, None, None, 0, 8, 8, 32, 4, p, p, 1, None) == 0
     # grid searches: K <= 64, workspace required
     assert hip_lib.tpg_knn_grid_f32(p, p, None, None, 1, 8, 8, 65, p, p, p, None) == -1

@@ -3,11 +3,17 @@ distance in LDS, exact re-rank): `hip.knn` takes that path by itself for D = 32 
 SMALL_MIN <= P2 <= 1024, and its output must equal the oracle's bit for bit, indices and distances, (0, 0) padding
 included -- whichever queries the filter handed to the exhaustive kernel.  Every case also calls the path directly
 (`hip.knn_small`, filter + redo): the kernel itself takes any P2 <= 1024, below the dispatch's bound too."""
+import os
+import sys
+
 import numpy as np
 import pytest
 import torch
 
 from oracle import ref_ops as R
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from knn_cases import feature_cloud as _cloud  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -23,24 +29,6 @@ def hip():
 
 def dev(a):
     return torch.from_numpy(np.ascontiguousarray(a)).cuda()
-
-
-def _cloud(rng, B, P, D, kind):
-    """The cloud kinds of test_ops_gpu._feature_cloud, plus `same`: every point identical (everything ties)."""
-    if kind == "manifold":
-        z = rng.standard_normal((B, P, 3)).astype(np.float32)
-        x = np.tanh(z @ rng.standard_normal((3, D)).astype(np.float32)) + 0.05 * rng.standard_normal((B, P, D)).astype(np.float32)
-    else:
-        x = rng.standard_normal((B, P, D)).astype(np.float32)
-    if kind == "lattice":
-        x = rng.integers(0, 3, (B, P, D)).astype(np.float32) * 0.5
-    if kind == "offset":
-        x += 300.0
-    if kind == "dups":
-        x[:, P // 4 * 3:] = x[:, :P - P // 4 * 3]
-    if kind == "same":
-        x[:] = 0.37
-    return np.ascontiguousarray(x.astype(np.float32))
 
 
 def _same_as_oracle(hip, p1, p2, K, l1=None, l2=None):

@@ -3,12 +3,17 @@ oracle on the same seeded inputs.  Neighbour / sample indices must be BIT-EXACT,
 produced by the canonical no-FMA sum must be bit-exact too; scatter-add gradients (LDS /
 global float atomics, order not fixed) are held to 1e-5."""
 import copy
+import os
+import sys
 
 import numpy as np
 import pytest
 import torch
 
 from oracle import ref_ops as R
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from knn_cases import feature_cloud as _feature_cloud  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 TOL = 1e-5  # fp32 feature / gradient tolerance stated by BASELINE.json north_star
@@ -51,32 +56,13 @@ def test_knn_bit_exact(hip, B, P1, P2, D, K):
     assert np.array_equal(d.cpu().numpy(), rd)
 
 
-def _feature_cloud(rng, B, P, D, kind):
-    """Feature-space clouds as the generator's bottleneck layers produce them: a few-dimensional manifold
-    embedded in D dims plus noise ("manifold"), iid normal ("normal"), the same far from the origin
-    ("offset": the Gram form cancels badly unless centred), and a cloud of 1/4 exact duplicates ("dups")."""
-    if kind == "manifold":
-        z = rng.standard_normal((B, P, 3)).astype(np.float32)
-        x = np.tanh(z @ rng.standard_normal((3, D)).astype(np.float32)) + 0.05 * rng.standard_normal((B, P, D)).astype(np.float32)
-    else:
-        x = rng.standard_normal((B, P, D)).astype(np.float32)
-    if kind == "lattice":
-        # small integers: distances are small integers too -- exact ties everywhere, in particular AT the K-th
-        # distance, where only the (dist, idx) order decides and the filter's margin test must give up
-        x = rng.integers(0, 3, (B, P, D)).astype(np.float32) * 0.5
-    if kind == "offset":
-        x += 300.0
-    if kind == "dups":
-        x[:, P // 4 * 3:] = x[:, :P - P // 4 * 3]
-    return np.ascontiguousarray(x.astype(np.float32))
-
-
 @pytest.mark.parametrize("B,P1,P2,D,K,kind", [
     (2, 4096, 4096, 32, 20, "manifold"), (1, 4096, 4096, 64, 12, "manifold"), (1, 2048, 2048, 32, 10, "normal"),
     (1, 3000, 5000, 64, 8, "normal"), (1, 4096, 4096, 32, 20, "offset"), (1, 2500, 2500, 32, 20, "dups"),
-    (1, 700, 16384, 64, 24, "manifold"), (1, 2048, 2048, 32, 20, "lattice"), (1, 600, 4096, 64, 12, "lattice")])
+    (1, 700, 16384, 64, 24, "manifold"), (1, 2048, 2048, 32, 20, "lattice"), (1, 600, 4096, 64, 12, "lattice"),
+    (1, 300, 2048, 32, 24, "normal"), (1, 300, 2048, 64, 16, "manifold")])    # knn_mfma_kernel<32, 16> and <64, 14>
 def test_knn_matrix_core_filter_bit_exact(hip, B, P1, P2, D, K, kind):
-    """tpg_knn_f32 on clouds of >= 2048 points in 32 / 64 dims runs the Gram filter on the f32 matrix cores and
+    """tpg_knn_f32 on clouds of >= 2048 points in 32 / 64 dims runs the Gram filter on the bf16 matrix cores and
     re-ranks the survivors exactly (csrc/knn_mfma.hpp): indices and distances equal the oracle's bit for bit,
     whatever share of the queries fell back to the exhaustive kernel -- and on benign clouds that share is small
     (a wrong operand layout would send every query there and still pass the first assertion)."""
@@ -94,6 +80,19 @@ def test_knn_matrix_core_filter_bit_exact(hip, B, P1, P2, D, K, kind):
     assert np.array_equal(raw[~open_], ri[~open_])           # what the filter settled IS the answer
     if kind in ("manifold", "normal"):
         assert open_.mean() < 0.02
+
+
+def test_knn_matrix_core_filter_at_its_floor(hip):
+    """The filter called directly at its own floor of valid points (KM_MIN_VALID = 1024, below the dispatch's bound)
+    and one below: filter + redo equals the oracle bit for bit; below the floor the filter settles nothing."""
+    for P2 in (1024, 1023):
+        rng = np.random.default_rng(200 + P2 + 32 + 12)
+        p1, p2 = _feature_cloud(rng, 1, 200, 32, "normal"), _feature_cloud(rng, 1, P2, 32, "normal")
+        d, i = hip.knn_mfma(dev(p1), dev(p2), None, None, 12, redo=True)
+        rd, ri = R.knn(p1, p2, 12)
+        assert np.array_equal(i.cpu().numpy(), ri) and np.array_equal(d.cpu().numpy(), rd)
+    _, raw = hip.knn_mfma(dev(p1), dev(p2), None, None, 12, redo=False)
+    assert (raw.cpu().numpy()[:, :, 0] == -2).all()          # 1023 points: every query is the exhaustive kernel's
 
 
 def test_knn_matrix_core_filter_ragged(hip):
