@@ -33,6 +33,10 @@
 #define TPG_ERR_ARG (-1)
 #define TPG_ERR_UNSUPPORTED (-3)
 
+/* the neighbour order on distances: a before b.  A NaN distance ranks after every other (as its bits do in
+ * the kernels' unsigned (dist_bits << 32 | idx) keys), NaN among themselves by index like any tie. */
+static inline int dist_before(float a, float b) { return a < b || (b != b && a == a); }
+
 static inline float sqdist(const float *a, const float *b, int D) {
     float acc = 0.0f;
     for (int d = 0; d < D; ++d) {
@@ -73,9 +77,9 @@ int tpgref_knn_f32(const float *p1, const float *p2, const int64_t *len1,
             for (int j = 0; j < n2; ++j) {
                 const float d = sqdist(q, p2 + ((size_t)b * P2 + j) * D, D);
                 if (radius && !(d < r2)) continue;
-                if (cnt == K && !(d < od[K - 1])) continue; /* ties keep lower idx */
+                if (cnt == K && !dist_before(d, od[K - 1])) continue; /* ties keep lower idx */
                 int pos = cnt < K ? cnt : K - 1;
-                while (pos > 0 && d < od[pos - 1]) { /* strict: equal stays behind */
+                while (pos > 0 && dist_before(d, od[pos - 1])) { /* strict: equal stays behind */
                     od[pos] = od[pos - 1]; oi[pos] = oi[pos - 1]; --pos;
                 }
                 od[pos] = d; oi[pos] = j;

@@ -100,11 +100,20 @@ __device__ __forceinline__ km_f32x16 km_gram(const uint4 &an, const uint4 &ones,
 //   c1 = 2^-13: the three dropped cross terms of the split products, 6.06 2^-16 |y_q||y_p|, with a third to spare;
 //   c2 = (8 D + 64) 2^-24: fp32 accumulation of the 3 D / 16 matrix steps (taken as 4 ulp each of the running
 //        magnitude), the two norms, the centring and the canonical sum itself, doubled.
+// Both terms are RELATIVE: they hold while nothing underflows.  Below the normal range the norm triplet is no longer exact
+// (its terms are bf16 denormals: 2^-133 apart), the lo halves and the products are cut off, and whether the matrix unit
+// keeps or flushes them is not ours to know.  Taking the worst -- every operand and product below 2^-126 lost -- the
+// loss is under 2^-126 (3 D + 6 + 6 D (|y_q| + max|y_p|)), which from max|y_p| >= KM_TINY = 2^-40 on is less than 2^-20 of
+// the c2 term ((8 D + 64) 2^-104 at least) and inside its doubling.  Below KM_TINY, or with a NaN norm, there is no
+// bound: E_q = +Inf, which no threshold of either kernel survives (measured before this rule: a cloud scaled by 2^-70,
+// distances ~2e-41, came back with wrong lists from knn_small_kernel; profiles/knn_bound.txt).
 // The bare bound: how each kernel rounds and uses it is its own.
 constexpr float KM_C1 = 1.220703125e-4f;                                                         // 2^-13
 template <int D_T> constexpr float KM_C2 = (float)(8 * D_T + 64) * 5.9604644775390625e-8f;       // (8 D + 64) 2^-24
+constexpr float KM_TINY = 9.094947017729282e-13f;                                                // 2^-40
 template <int D_T>
 __device__ __forceinline__ float km_bound(float sqq, float sq_pmax) {
+    if (!(sq_pmax >= KM_TINY)) return __builtin_inff();
     return KM_C1 * sqq * sq_pmax + KM_C2<D_T> * (sqq + sq_pmax) * (sqq + sq_pmax);
 }
 

@@ -17,7 +17,8 @@
 //   tail     one wave per query: canonical distance of the listed points (km_tail_key: knn_dist_row of knn.hip), rank
 //            by counting over the 64-bit (dist, idx) keys, the first K are the
 //            answer IF  tau_q - E_q > d_K  (every unlisted point has d~ > tau_q, hence a canonical distance
-//            above d_K: it cannot enter or tie).  Otherwise (list overflow, ragged tails, and clouds whose
+//            above d_K: it cannot enter or tie).  Otherwise (list overflow, ragged tails, E_q = +Inf or NaN on non-finite,
+//            huge or underflowing rows -- km_bound --, and clouds whose
 //            neighbour spacing is below the rounding bound: thousands of points on a 2-D sheet in feature space)
 //            the query's first index slot is set to -2 and knn_redo_kernel (knn.hip: the
 //            exhaustive scan, four waves per flagged query) redoes it.  The output is the exhaustive
@@ -46,7 +47,9 @@ constexpr size_t km_smem_bytes() {
 // v_max x, x, x in front of their operands (quiet-NaN semantics), a third of the sorted-insert chain.  NOT for the
 // accumulators of a matrix instruction: the hazard recogniser does not look inside inline asm, and a v_min issued
 // before the matrix unit has written its result reads the old register (measured: thresholds far too high, 12 % of the
-// queries overflowed their candidate list).  No NaN reaches these (finite rows, 1e30 on padding).
+// queries overflowed their candidate list).  On finite rows no NaN reaches these (1e30 on padding); a NaN query or row leaves
+// whatever threshold it leaves, and the tail's NaN or +Inf bound hands the query to the exhaustive kernel
+// (tests/test_knn_bound_gpu.py, test_nonfinite).
 __device__ __forceinline__ float km_min(float a, float b) { float r; asm("v_min_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b)); return r; }
 __device__ __forceinline__ float km_max(float a, float b) { float r; asm("v_max_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b)); return r; }
 

@@ -35,7 +35,8 @@
 // kernels' list bit for bit.  No verification step is needed; the threshold is rounded UP (E_q x 1.001, the sum
 // + 2^-20 of itself).  A query goes to knn_redo_kernel (first index slot = KM_REDO) when C overflows its 64 slots
 // (ties everywhere, all points identical), when the threshold is not finite and below the padding norm (NaN / Inf /
-// huge inputs: max|y_p| is taken NaN-preserving), or when the cloud has fewer than KS_MIN_VALID valid points (fewer than
+// huge inputs: max|y_p| is taken NaN-preserving; a cloud within 2^-40 of its origin, where products underflow and
+// km_bound gives +Inf), or when the cloud has fewer than KS_MIN_VALID valid points (fewer than
 // one point per lane: the lane minima would not be K distinct points).
 #pragma once
 
