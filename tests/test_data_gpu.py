@@ -9,10 +9,10 @@ import pytest
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from select_rule import patch_rule as rule  # noqa: E402
 from test_data_cpu import _equal, check_golden_items, check_trainer, write_dataset  # noqa: E402
 
 pytestmark = pytest.mark.gpu
-NAN_KEY = 0x7FC00000
 
 
 @pytest.fixture(scope="module")
@@ -20,19 +20,6 @@ def dev():
     if not torch.cuda.is_available():
         pytest.skip("no GPU")
     return torch.device("cuda", 0)
-
-
-def rule(points, seed, K):
-    """The selection rule in numpy: fp32 d2 = (dx*dx + dy*dy) + dz*dz, each operation rounded; the K smallest in
-    ascending (d2, index); a NaN d2 ranks as the bit pattern 0x7FC00000 (after +inf)."""
-    with np.errstate(all="ignore"):
-        d = points - points[seed]
-        d2 = ((d[:, 0] * d[:, 0] + d[:, 1] * d[:, 1]) + d[:, 2] * d[:, 2]).astype(np.float32)
-    index = np.arange(len(d2))
-    if np.isfinite(d2).all():
-        return np.lexsort((index, d2))[:K].astype(np.int32)
-    key = np.where(np.isnan(d2), np.uint32(NAN_KEY), d2.view(np.uint32))
-    return np.lexsort((index, key))[:K].astype(np.int32)
 
 
 def select(dev, scenes, seeds, K):
