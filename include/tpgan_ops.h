@@ -917,6 +917,96 @@ int tpg_iso_emit_f32(const float *field, int nx, int ny, int nz, const float *or
                      const void *ws, long long V_cap, long long F_cap, float *vertices, float *normals, int32_t *faces,
                      void *stream);
 
+/* ---- anisotropic kernels (csrc/aniso.hip) -------------------------------------------------------------------------
+ * The density field of tpgan_amd.mesh with one ellipsoidal kernel per particle, fitted to the particle's neighbourhood
+ * (Yu and Turk, "Reconstructing surfaces of particle-based fluids using anisotropic kernels"), in place of one ball per
+ * particle: flat regions come out flat and thin sheets stay sheets.  (The reference hands its frames to an external
+ * tool for this; the mesher is this project's own and no parity with any such tool is claimed.)  Two stages.
+ *
+ * Parameters, each an fp32 value: rc (neighbourhood radius), lambda in [0,1] (centre smoothing), ks (scale of the
+ * extents), kr >= 1 (largest ratio between a particle's extents), 0 < s_min <= s_max (clamp on the extents), kn (extent
+ * of a particle with few neighbours), n_eps >= 0 (the count at or below which kn applies), R (support of the density
+ * kernel), reach (= fp32(s_max) * fp32(R) as the Python layer calls it).  The host layer's defaults: rc = 2 R,
+ * lambda = 0.9, kr = 4, s_min = 0.125, s_max = 2, kn = 0.5, n_eps = 25, ks = 1 / (the per-axis weighted variance, in
+ * units of rc^2, of a full cubic lattice of the particles' spacing: mesh.lattice_covariance), which makes the kernel of
+ * a particle inside a full lattice the isotropic one.
+ *
+ * Stage A, tpg_aniso_kernels_f32.  pos (B,N,3) f32, lengths (B) int64 or NULL, taken as min(max(lengths[b], 0), N) on
+ * the 64-bit value.  Per particle i < lengths[b] of cloud b:
+ *   members   the rows j < lengths[b] with d2 <= rc*rc (fp32 product), INCLUSIVE, i itself included, d2 the canonical
+ *             fp32 distance of the searches: t = x_i - x_j per axis; d2 = t0*t0; d2 = d2 + t1*t1; d2 = d2 + t2*t2
+ *             (a non-finite coordinate makes d2 NaN: no member)
+ *   per member, fp32, each operation rounded on its own (no FMA):
+ *             d = sqrtf(d2);  rho = fminf(d / rc, 1);  w = 1 - (rho*rho)*rho;  u_a = (x_j[a] - x_i[a]) / rc;
+ *             wu_a = w*u_a;  the ten terms  w | wu_x, wu_y, wu_z | wu_x*u_x, wu_x*u_y, wu_x*u_z, wu_y*u_y, wu_y*u_z,
+ *             wu_z*u_z,  each within [-1, 1], each converted on its own as (int64)(term * 2^32) (truncation towards
+ *             zero, the scaling is exact) and added as integers: S0 | S1_a | S2_ab.  n_i = the number of members.
+ *             Integer sums do not depend on the order of the members, the lane, the batch position or the launch shape.
+ *   finish, float64 (+ - * / sqrt and comparisons only; each int64 sum converted to float64 once):
+ *             m_a = S1_a / S0;  C_ab = S2_ab / S0 - m_a*m_b   (a <= b; n_i = 0, which only a non-finite x_i gives,
+ *             has S0 = 0: m and C are 0 then)
+ *             centre_i[a] = (float)((double)x_i[a] + (lambda*rc) * m_a),  lambda*rc the exact float64 product of the
+ *             two fp32 parameters
+ *   eigen-decomposition of C: A = C, V = I, then 5 sweeps of the rotations (p,q) = (0,1), (0,2), (1,2), r the third
+ *             index, every rotation with the values the one before left:
+ *                 zero = (A_pq == 0);  theta = (A_qq - A_pp) / (zero ? 1 : 2*A_pq);  sg = theta >= 0 ? 1 : -1
+ *                 t = sg / (|theta| + sqrt(theta*theta + 1));  t = zero ? 0 : t       (an overflowing theta gives t = 0)
+ *                 c = 1 / sqrt(t*t + 1);  s = t*c;  h = t*A_pq
+ *                 A_pp = A_pp - h;  A_qq = A_qq + h;  A_pq = 0
+ *                 (A_rp, A_rq) = (c*A_rp - s*A_rq,  s*A_rp + c*A_rq)
+ *                 (V_kp, V_kq) = (c*V_kp - s*V_kq,  s*V_kp + c*V_kq)      for k = 0, 1, 2
+ *             A zero off-diagonal element gives the identity rotation (c = 1, s = 0), carried out like any other.
+ *             sigma_k = A_kk, its eigenvector the column k of V.  With S0 > 0 every quantity is a quotient or a bounded
+ *             combination of finite numbers: nothing non-finite can arise, and S0 = 0 takes the kn branch below.
+ *   extents   top = max(max(sigma_0, sigma_1), sigma_2) (a > b ? a : b).  If n_i <= n_eps or not top > 0:
+ *             G_i = diag(1 / kn), det_i = 1 / ((kn*kn)*kn).  Otherwise
+ *                 e_k = max(sigma_k, top / kr);  e_k = ks*e_k;  e_k = e_k < s_min ? s_min : e_k;
+ *                 e_k = e_k > s_max ? s_max : e_k;  inv_k = 1 / e_k
+ *                 G_ab = ((V_a0*inv_0)*V_b0 + (V_a1*inv_1)*V_b1) + (V_a2*inv_2)*V_b2;  det = 1 / ((e_0*e_1)*e_2)
+ *   outputs   centres (B,N,3) f32, G (B,N,6) f32 in the order xx, xy, xz, yy, yz, zz, det (B,N) f32 (each the float64
+ *             value rounded once), count (B,N) int32 = n_i.  Rows at or beyond lengths[b] get zeros in all four.
+ * Launches: the walk (one wave per particle, the ten sums into ws) and the finish (one lane per particle); `stages`
+ * selects them: 1 the walk, 2 the finish of the sums an earlier walk with the same B, N left in ws, 3 both (what the
+ * host layer calls; 1 and 2 exist so that a timing can tell them apart).  tpg_aniso_kernels_exhaustive_f32: the same with
+ * the lanes striding over the whole cloud instead of the uniform grid; the same bits.
+ *
+ * Stage B, tpg_aniso_field_f32.  query (B,Nq,3), centres (B,Np,3), G (B,Np,6), det (B,Np), lenq, lenp as above.  Per
+ * query x < lenq[b] (others get 0):
+ *   members   the centres j < lenp[b] with canonical fp32 |x - c_j|^2 <= reach*reach (t = x - c_j), inclusive
+ *   per member, fp32, no FMA:
+ *             t = x - c_j;  y_0 = (Gxx*t0 + Gxy*t1) + Gxz*t2;  y_1 = (Gxy*t0 + Gyy*t1) + Gyz*t2;
+ *             y_2 = (Gxz*t0 + Gyz*t1) + Gzz*t2;  q = fminf(sqrtf((y_0*y_0 + y_1*y_1) + y_2*y_2) / R, 1)
+ *             W = q <= 0.5 ? 6*((q*q)*q - q*q) + 1 : 2*((v*v)*v) with v = 1 - q; W = fmaxf(W, 0)   (the cubic of
+ *             tpg_radius_reduce_f32: exactly 0 at q = 1)
+ *             dw = fminf(fmaxf(det_j * W, 0), 512);  term = (uint64)(dw * 2^22)
+ *   result    (float)(sum of the terms) * 2^-22.
+ * Overflow: stage A's det is at most s_min^-3 (512 at the default 0.125) and the clamp holds for any det (a NaN det
+ * or G gives dw = 0 or q = 1): a term is at most 2^31 units, and fewer than 2^31 of them cannot overflow 64 bits.
+ * Membership at the rim does not matter: |G t| >= |t| / s_max, so the ellipsoid q < 1 lies inside the reach ball, and
+ * the term vanishes at the ellipsoid's rim; both launch shapes apply the same test and return the same bits.
+ * tpg_aniso_field_f32 builds the uniform grid over the centres with radius reach in ws (a second build: stage A's is
+ * over the particles, with rc); tpg_aniso_field_exhaustive_f32 needs no workspace.
+ *
+ * Checks, all before anything is launched.  TPG_ERR_ARG: a negative B, N, Nq or Np; rc, ks, s_min, s_max, kn, R or reach
+ * not positive and finite; kr not finite or below 1; lambda outside [0,1]; s_min > s_max; n_eps < 0; stages outside
+ * 1..3; a NULL output; a workspace that is NULL or not 256-byte aligned where one is taken and no size is 0.  Then a
+ * size of 0 among B, N / B, Nq: TPG_OK, nothing written.  Then B > 65535: TPG_ERR_UNSUPPORTED; a NULL pos / query:
+ * TPG_ERR_ARG; Np == 0: zeros, TPG_OK; NULL centres, G or det: TPG_ERR_ARG.  ws: tpg_aniso_workspace_bytes(B, N) bytes
+ * (stage B: of B, Np; it uses the grid's part). */
+size_t tpg_aniso_workspace_bytes(int B, int N);
+int tpg_aniso_kernels_f32(const float *pos, const int64_t *lengths, int B, int N, float rc, float lambda, float ks,
+                          float kr, float s_min, float s_max, float kn, int n_eps, int stages, float *centres, float *G,
+                          float *det, int32_t *count, void *ws, void *stream);
+int tpg_aniso_kernels_exhaustive_f32(const float *pos, const int64_t *lengths, int B, int N, float rc, float lambda,
+                                     float ks, float kr, float s_min, float s_max, float kn, int n_eps, int stages,
+                                     float *centres, float *G, float *det, int32_t *count, void *ws, void *stream);
+int tpg_aniso_field_f32(const float *query, const float *centres, const float *G, const float *det, const int64_t *lenq,
+                        const int64_t *lenp, int B, int Nq, int Np, float support, float reach, float *sum, void *ws,
+                        void *stream);
+int tpg_aniso_field_exhaustive_f32(const float *query, const float *centres, const float *G, const float *det,
+                                   const int64_t *lenq, const int64_t *lenp, int B, int Nq, int Np, float support,
+                                   float reach, float *sum, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -94,9 +94,14 @@ SIGNATURES = {
     "tpg_pbf_finish_f32": [_P, _P, _P, _I, _I, _F, _F, _F, _P, _P, _P, _P],
     "tpg_iso_count_f32": [_P, _I, _I, _I, _F, _P, _P, _P],
     "tpg_iso_emit_f32": [_P, _I, _I, _I, _P, _F, _F, _P, _L, _L, _P, _P, _P, _P],
+    "tpg_aniso_kernels_f32": [_P, _P, _I, _I, _F, _F, _F, _F, _F, _F, _F, _I, _I, _P, _P, _P, _P, _P, _P],
+    "tpg_aniso_kernels_exhaustive_f32": [_P, _P, _I, _I, _F, _F, _F, _F, _F, _F, _F, _I, _I, _P, _P, _P, _P, _P, _P],
+    "tpg_aniso_field_f32": [_P, _P, _P, _P, _P, _P, _I, _I, _I, _F, _F, _P, _P, _P],
+    "tpg_aniso_field_exhaustive_f32": [_P, _P, _P, _P, _P, _P, _I, _I, _I, _F, _F, _P, _P],
 }
 SIZE_GETTERS = ("tpg_rowbn_workspace_bytes", "tpg_mlp_workspace_bytes", "tpg_context_expand_workspace_bytes",
-                "tpg_emd_workspace_bytes", "tpg_pbf_workspace_bytes", "tpg_iso_workspace_bytes")
+                "tpg_emd_workspace_bytes", "tpg_pbf_workspace_bytes", "tpg_iso_workspace_bytes",
+                "tpg_aniso_workspace_bytes")
 OTHER_GETTERS = ("tpg_spectral_norm_multi_stride", "tpg_spectral_norm_multi_bwd_scratch",
                  "tpg_mlp_wgrad_workspace_bytes", "tpg_frnn_grid_workspace_bytes", "tpg_small_tail_workspace_bytes",
                  "tpg_chamfer_bwd_workspace_bytes", "tpg_rowlinear_wgrad_workspace_bytes", "tpg_rowlinear_supported",

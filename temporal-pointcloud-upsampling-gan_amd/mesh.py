@@ -1,7 +1,8 @@
 """Triangle meshes of particle frames on the GPU: the fluid's surface as geometry, with OBJ / PLY export.
 
     python -m tpgan_amd.mesh --frames 'out/pcd_{i}.npy' --count 200 --out meshes [--format ply|obj --spacing 0.025
-        --support 0.05 --step 0.0125 --iso 0.5 --stats stats.npz]
+        --support 0.05 --step 0.0125 --iso 0.5 --stats stats.npz --kernel isotropic|anisotropic --cov_radius 0.1
+        --smooth_lambda 0.9]
 
 The reference ends its demo (train_fluid/demo.ipynb, cell 5) by writing every upsampled frame to a geometry file for an
 external renderer that reconstructs the fluid's surface.  Here the surface is built on the device: the particles' cubic
@@ -9,6 +10,12 @@ kernel density (`ops.radius_reduce`, the reference's particle_dns2grid_dns) is s
 its level set at a fraction of the density inside a full particle lattice is meshed by `ops.iso_surface` (marching
 tetrahedra, csrc/isosurface.hip).  The mesher is this project's own: no parity with any external reconstruction tool is
 claimed.  A mesh also gives the enclosed volume and the surface area of a frame, which `analysis` cannot.
+
+--kernel anisotropic replaces the density of one ball per particle by that of one ellipsoid per particle, fitted to the
+particle's neighbourhood (`ops.anisotropic_kernels` / `ops.anisotropic_field`, csrc/aniso.hip; Yu and Turk): irregular
+particle spacing no longer shows as bumps on flat regions.  Its centre smoothing pulls the surface INWARDS by about one
+particle spacing against the isotropic surface; --smooth_lambda and --iso are the knobs, nothing compensates
+for it silently.
 """
 import argparse
 import collections
@@ -39,18 +46,19 @@ def _valid_rows(points, lengths=None):
     return p[valid].contiguous()
 
 
-def lattice_for(points, support, step, lengths=None):
+def lattice_for(points, support, step, lengths=None, reach=None):
     """The lattice of spacing `step` around the valid rows of `points` (N,3): their bounding box padded by support +
-    2 step on every side, so that the boundary nodes lie beyond every particle's support (field 0 there) and no active
-    edge comes within one node of the boundary: the mesh is closed.  Raises, naming a step that fits, when the lattice
-    would hold more than 2^27 nodes."""
+    2 step on every side (`reach` + 2 step when given: the anisotropic field's kernels extend to s_max * support), so
+    that the boundary nodes lie beyond every particle's support (field 0 there) and no active edge comes within one node
+    of the boundary: the mesh is closed.  Raises, naming a step that fits, when the lattice would hold more than 2^27
+    nodes."""
     support, step = float(support), float(np.float32(step))
     ops._need(np.isfinite(support) and support > 0.0, "support must be positive and finite")
     ops._need(np.isfinite(step) and step > 0.0, "step must be positive and finite")
     p = _valid_rows(points, lengths)
     ops._need(p.shape[0] > 0, "no valid point to build a lattice around")
     lo, hi = p.amin(0).double().cpu().numpy(), p.amax(0).double().cpu().numpy()
-    pad = support + 2.0 * step
+    pad = (support if reach is None else float(reach)) + 2.0 * step
     origin = (lo - pad).astype(np.float32)
     extent = (hi + pad) - origin.astype(np.float64)
     shape = tuple(int(np.ceil(e / step)) + 1 for e in extent)                 # origin + (n - 1) step >= hi + pad
@@ -108,18 +116,71 @@ def lattice_value(spacing, support):
     return float(cubic_kernel(d[d <= support] / support).sum())
 
 
-def surface_mesh(points, spacing=analysis.BASE_RADIUS, support=None, step=None, iso=0.5, lengths=None, normals=True):
+def lattice_covariance(spacing, cov_radius):
+    """The per-axis weighted variance, in units of cov_radius^2, of an infinite cubic lattice of `spacing` seen from one
+    of its points: sum w x^2 / sum w over the lattice points within cov_radius (the particle itself included) with the
+    weights w = 1 - (d / cov_radius)^3 of the anisotropic kernels' stage A, float64.  Its reciprocal is the `ks` that
+    makes the kernel of a particle inside a full lattice the isotropic one (0.150571... at 4 spacings)."""
+    spacing, rc = float(spacing), float(cov_radius)
+    ops._need(np.isfinite(spacing) and spacing > 0.0 and np.isfinite(rc) and rc > 0.0,
+              "spacing and cov_radius must be positive and finite")
+    m = int(np.floor(rc / spacing)) + 1
+    r = np.arange(-m, m + 1, dtype=np.float64) * spacing
+    x = np.broadcast_to(r[:, None, None], (r.shape[0],) * 3)
+    d = np.sqrt((r[:, None, None] ** 2 + r[None, :, None] ** 2) + r[None, None, :] ** 2)
+    inside = d <= rc
+    w = 1.0 - (d[inside] / rc) ** 3
+    return float((w * (x[inside] / rc) ** 2).sum() / w.sum())
+
+
+ANISO_S_MAX = 2.0                       # the clamp on the extents: the anisotropic kernels reach s_max * support
+
+
+def anisotropic_field(points, lattice, spacing, support, cov_radius=None, smooth_lambda=0.9, lengths=None):
+    """(nx,ny,nz) fp32 on the points' device: the anisotropic kernels' density of the valid rows of `points` at every
+    node -- `ops.anisotropic_kernels` at the defaults with cov_radius (default 2 support) and ks = 1 /
+    `lattice_covariance(spacing, cov_radius)`, then `ops.anisotropic_field`, NODES_PER_CALL nodes per call.  Inside a
+    full lattice of `spacing` it is the isotropic `density_field`."""
+    p = _valid_rows(points, lengths)
+    rc = 2.0 * float(support) if cov_radius is None else float(cov_radius)
+    ks = 1.0 / lattice_covariance(spacing, rc)
+    nx, ny, nz = lattice.shape
+    G = nx * ny * nz
+    field = torch.empty(G, dtype=torch.float32, device=p.device)
+    with torch.no_grad():
+        centres, mat, det, _ = ops.anisotropic_kernels(p, rc, ks, smooth_lambda, s_max=ANISO_S_MAX)
+        for first in range(0, G, NODES_PER_CALL):
+            count = min(NODES_PER_CALL, G - first)
+            nodes = lattice_nodes(lattice, first, count, p.device)
+            field[first:first + count] = ops.anisotropic_field(nodes, centres, mat, det, support, ANISO_S_MAX)
+    return field.view(nx, ny, nz)
+
+
+KERNELS = ("isotropic", "anisotropic")
+
+
+def surface_mesh(points, spacing=analysis.BASE_RADIUS, support=None, step=None, iso=0.5, lengths=None, normals=True,
+                 kernel="isotropic", cov_radius=None, smooth_lambda=0.9):
     """The surface of one frame of particles (N,3) as a `Mesh`: the cubic density of width `support` (default 2 spacings)
     on a lattice of `step` (default spacing / 2), meshed at `iso` x the density inside a full particle lattice
     (`lattice_value`; at support = 2 spacings the field inside a full lattice varies by under 0.3 %, so 0.5 leaves no
-    cavities).  vertices (V,3) f32, faces (F,3) int32 wound outward, normals (V,3) f32 or None, on the points' device."""
+    cavities).  vertices (V,3) f32, faces (F,3) int32 wound outward, normals (V,3) f32 or None, on the points' device.
+    kernel="anisotropic": the density of `anisotropic_field` (cov_radius, smooth_lambda) on a lattice padded by
+    s_max * support + 2 step; the level keeps its meaning, since inside a full lattice the two fields agree.  The
+    smoothed centres pull that surface inwards by about one spacing: smooth_lambda and iso are the knobs."""
     spacing = float(spacing)
     ops._need(np.isfinite(spacing) and spacing > 0.0, "spacing must be positive and finite")
     support = 2.0 * spacing if support is None else float(support)
     step = spacing / 2.0 if step is None else float(step)
     ops._need(np.isfinite(iso) and iso > 0.0, "iso must be a positive fraction of the lattice density")
-    lattice = lattice_for(points, support, step, lengths)
-    field = density_field(points, lattice, support, lengths)
+    ops._need(kernel in KERNELS, f"kernel must be one of {KERNELS}")
+    if kernel == "anisotropic":
+        # the centres are convex combinations of the points: the points' bounding box bounds them too
+        lattice = lattice_for(points, support, step, lengths, reach=ANISO_S_MAX * support)
+        field = anisotropic_field(points, lattice, spacing, support, cov_radius, smooth_lambda, lengths)
+    else:
+        lattice = lattice_for(points, support, step, lengths)
+        field = density_field(points, lattice, support, lengths)
     level = float(np.float32(float(iso) * lattice_value(spacing, support)))
     vertices, faces, nrm = ops.iso_surface(field, lattice.origin, lattice.step, level, normals)
     return Mesh(vertices, faces, nrm, lattice, level)
@@ -188,11 +249,15 @@ class SequenceMesher:
     clouds, first = index of the first one -> one record per frame (frame, points, vertices, faces, volume, area), also
     appended to `records`."""
 
-    def __init__(self, out_dir, fmt="ply", spacing=analysis.BASE_RADIUS, support=None, step=None, iso=0.5, device="cuda"):
+    def __init__(self, out_dir, fmt="ply", spacing=analysis.BASE_RADIUS, support=None, step=None, iso=0.5, device="cuda",
+                 kernel="isotropic", cov_radius=None, smooth_lambda=0.9):
         if fmt not in WRITERS:
             raise ValueError(f"format must be one of {sorted(WRITERS)}")
+        if kernel not in KERNELS:
+            raise ValueError(f"kernel must be one of {KERNELS}")
         self.out_dir, self.fmt, self.device = out_dir, fmt, torch.device(device)
         self.spacing, self.support, self.step, self.iso = spacing, support, step, iso
+        self.kernel, self.cov_radius, self.smooth_lambda = kernel, cov_radius, smooth_lambda
         self.records = []
         os.makedirs(out_dir, exist_ok=True)
 
@@ -200,7 +265,8 @@ class SequenceMesher:
         out = []
         for t, frame in enumerate(frames):
             p = torch.as_tensor(frame).detach().float().reshape(-1, 3).to(self.device)
-            m = surface_mesh(p, self.spacing, self.support, self.step, self.iso)
+            m = surface_mesh(p, self.spacing, self.support, self.step, self.iso, kernel=self.kernel,
+                             cov_radius=self.cov_radius, smooth_lambda=self.smooth_lambda)
             WRITERS[self.fmt](os.path.join(self.out_dir, f"pcd_{first + t:04d}.{self.fmt}"), m)
             out.append(dict(frame=first + t, points=int(_valid_rows(p).shape[0]), vertices=int(m.vertices.shape[0]),
                             faces=int(m.faces.shape[0]), volume=volume(m), area=area(m)))
@@ -221,10 +287,17 @@ def add_mesh_options(ap):
     ap.add_argument("--support", type=float, default=None, help="width of the density kernel (default 2 spacings)")
     ap.add_argument("--step", type=float, default=None, help="lattice step (default spacing / 2)")
     ap.add_argument("--iso", type=float, default=0.5, help="level, as a fraction of a full lattice's density")
+    ap.add_argument("--kernel", choices=KERNELS, default="isotropic",
+                    help="one ball per particle, or one ellipsoid fitted to its neighbourhood (smoother; sits further in)")
+    ap.add_argument("--cov_radius", type=float, default=None,
+                    help="anisotropic: neighbourhood radius of the fit (default 2 supports)")
+    ap.add_argument("--smooth_lambda", type=float, default=0.9,
+                    help="anisotropic: how far a kernel's centre moves toward its neighbours' weighted mean, 0..1")
 
 
 def mesher_from(a, out_dir, device):
-    return SequenceMesher(out_dir, a.format, a.spacing, a.support, a.step, a.iso, device)
+    return SequenceMesher(out_dir, a.format, a.spacing, a.support, a.step, a.iso, device, a.kernel, a.cov_radius,
+                          a.smooth_lambda)
 
 
 def main(argv=None):

@@ -452,6 +452,44 @@ class HipBackend:
             self.iso_emit(field, origin, step, iso, ws, V, F, vertices, nrm, faces)
         return vertices, faces, nrm
 
+    # ---- anisotropic kernels (csrc/aniso.hip; the rule: include/tpgan_ops.h)
+    def _aniso_ws(self, ref, B, N):
+        return self._workspace("aniso", ref, max(int(self.lib.tpg_aniso_workspace_bytes(B, N)), 1), dtype=torch.uint8)
+
+    def aniso_kernels(self, pos, lengths, prm, grid=None, stages=3, out=None):
+        """Stage A -> (centres (B,N,3), G (B,N,6), det (B,N), count (B,N) int32).  The grid from the sizes of the radius
+        search's switch on, the exhaustive shape below (same bits; `grid` forces one).  stages / out: the walk (1) and
+        the finish (2) as calls of their own into the tensors of an earlier call, for timing."""
+        B, N, _ = pos.shape
+        rc, lam, ks, kr, s_min, s_max, kn, n_eps = prm
+        if out is None:
+            out = (torch.empty((B, N, 3), dtype=torch.float32, device=pos.device),
+                   torch.empty((B, N, 6), dtype=torch.float32, device=pos.device),
+                   torch.empty((B, N), dtype=torch.float32, device=pos.device),
+                   torch.empty((B, N), dtype=torch.int32, device=pos.device))
+        if grid is None:
+            grid = N >= self.GRID_MIN_POINTS and float(B) * N * N >= self.GRID_MIN_PAIRS
+        symbol = "tpg_aniso_kernels_f32" if grid else "tpg_aniso_kernels_exhaustive_f32"
+        self._call(symbol, "aniso_kernels", 12 * B * N + 44 * B * N, pos, _ptr(pos), _ptr(lengths), B, N, rc, lam, ks, kr,
+                   s_min, s_max, kn, int(n_eps), int(stages), *[_ptr(t) for t in out], _ptr(self._aniso_ws(pos, B, N)))
+        return out
+
+    def aniso_field(self, query, centres, G, det, lenq, lenp, support, reach, grid=None):
+        """Stage B -> sum (B,Nq) f32; the launch shapes as for `aniso_kernels`."""
+        B, Nq, _ = query.shape
+        Np = centres.shape[1]
+        total = torch.empty((B, Nq), dtype=torch.float32, device=query.device)
+        if grid is None:
+            grid = Np >= self.GRID_MIN_POINTS and float(B) * Nq * Np >= self.GRID_MIN_PAIRS
+        args = (_ptr(query), _ptr(centres), _ptr(G), _ptr(det), _ptr(lenq), _ptr(lenp), B, Nq, Np, support, reach,
+                _ptr(total))
+        nbytes = 12 * B * Nq + 44 * B * Np + 4 * B * Nq
+        if grid and B > 0 and Nq > 0 and Np > 0:
+            self._call("tpg_aniso_field_f32", "aniso_field_grid", nbytes, query, *args, _ptr(self._aniso_ws(query, B, Np)))
+        else:
+            self._call("tpg_aniso_field_exhaustive_f32", "aniso_field", nbytes, query, *args)
+        return total
+
     def chamfer_fwd(self, src, tgt):
         B, N, _ = src.shape
         M = tgt.shape[1]
@@ -2390,6 +2428,235 @@ def _radius_cubic_sums_torch(query, pos, r, pairs_per_chunk=1 << 24):
         units = torch.where(d2 <= r2, (w * 4294967296.0).to(torch.int64), torch.zeros((), dtype=torch.int64, device=w.device))
         out[a:a + rows] = units.sum(1).to(torch.float32) * 2.3283064365386963e-10
     return out
+
+
+# ------------------------------------------------- anisotropic kernels (csrc/aniso.hip; the rule: include/tpgan_ops.h)
+def _aniso_params(cov_radius, ks, smooth_lambda, kr, s_min, s_max, kn, n_eps):
+    """The stage-A parameters, validated and each rounded to fp32 once -> (rc, lambda, ks, kr, s_min, s_max, kn, n_eps)."""
+    vals = [float(_F32(v)) for v in (cov_radius, smooth_lambda, ks, kr, s_min, s_max, kn)]
+    rc, lam, ks, kr, s_min, s_max, kn = vals
+    for name, v in (("cov_radius", rc), ("ks", ks), ("s_min", s_min), ("s_max", s_max), ("kn", kn)):
+        _need(np.isfinite(v) and v > 0.0, f"{name} must be positive and finite")
+    _need(np.isfinite(kr) and kr >= 1.0, "kr must be finite and at least 1")
+    _need(0.0 <= lam <= 1.0, "smooth_lambda must lie in [0, 1]")
+    _need(s_min <= s_max, "s_min must not exceed s_max")
+    _need(int(n_eps) == n_eps and n_eps >= 0, "n_eps must be a non-negative integer")
+    return rc, lam, ks, kr, s_min, s_max, kn, int(n_eps)
+
+
+def _sqrt64(t):
+    """A correctly rounded float64 square root of a float64 tensor: torch's own on the CPU is not (about one value in
+    150 is an ulp off), numpy's is, and the statements below must give the device's bits.  Through host memory: the
+    statements serve checkers, not a hot path."""
+    return torch.from_numpy(np.sqrt(t.detach().cpu().numpy())).to(t.device)
+
+
+def _aniso_rotate_torch(app, aqq, apq, arp, arq, vp, vq):
+    """One Jacobi rotation of the rule, float64, on every particle at once."""
+    zero = apq == 0.0
+    theta = (aqq - app) / torch.where(zero, torch.ones_like(apq), 2.0 * apq)
+    sg = torch.where(theta >= 0.0, 1.0, -1.0).to(theta.dtype)
+    t = sg / (theta.abs() + _sqrt64(theta * theta + 1.0))
+    t = torch.where(zero, torch.zeros_like(t), t)
+    c = 1.0 / _sqrt64(t * t + 1.0)
+    s = t * c
+    h = t * apq
+    new_vp = [c * a - s * e for a, e in zip(vp, vq)]
+    new_vq = [s * a + c * e for a, e in zip(vp, vq)]
+    return app - h, aqq + h, torch.zeros_like(apq), c * arp - s * arq, s * arp + c * arq, new_vp, new_vq
+
+
+def _aniso_kernels_torch(points, prm, pairs_per_chunk=1 << 22):
+    """Stage A of the anisotropic kernels for one cloud as torch ops, the same bits as the kernels: points (N,3) fp32 ->
+    (centres (N,3), G (N,6), det (N,) fp32, count (N,) int32).  What backends without the kernels run."""
+    rc, lam, ks, kr, s_min, s_max, kn, n_eps = prm
+    N, dev = points.shape[0], points.device
+    rc2 = float(_F32(rc) * _F32(rc))
+    S = torch.zeros((10, N), dtype=torch.int64, device=dev)
+    count = torch.zeros(N, dtype=torch.int32, device=dev)
+    px, py, pz = points[:, 0].unsqueeze(0), points[:, 1].unsqueeze(0), points[:, 2].unsqueeze(0)
+    rows = max(1, pairs_per_chunk // max(N, 1))
+    for a in range(0, N, rows):
+        qx, qy, qz = points[a:a + rows, 0:1], points[a:a + rows, 1:2], points[a:a + rows, 2:3]
+        dx, dy, dz = qx - px, qy - py, qz - pz
+        d2 = dx * dx
+        d2 = d2 + dy * dy
+        d2 = d2 + dz * dz
+        member = d2 <= rc2
+        d = torch.sqrt(d2.double()).float()                                   # a correctly rounded fp32 sqrt
+        rho = torch.fmin(d / rc, torch.ones((), dtype=torch.float32, device=dev))
+        w = 1.0 - (rho * rho) * rho
+        ux, uy, uz = (px - qx) / rc, (py - qy) / rc, (pz - qz) / rc
+        wx, wy, wz = w * ux, w * uy, w * uz
+        terms = (w, wx, wy, wz, wx * ux, wx * uy, wx * uz, wy * uy, wy * uz, wz * uz)
+        for k, term in enumerate(terms):
+            units = (torch.where(member, term, torch.zeros_like(term)) * 4294967296.0).to(torch.int64)
+            S[k, a:a + rows] = units.sum(1)
+        count[a:a + rows] = member.sum(1).to(torch.int32)
+    Sd = S.double()
+    S0 = torch.where(Sd[0] > 0.0, Sd[0], torch.ones_like(Sd[0]))
+    m = [Sd[1] / S0, Sd[2] / S0, Sd[3] / S0]
+    lr = float(np.float64(_F32(lam)) * np.float64(_F32(rc)))
+    centres = torch.stack([(points[:, a].double() + lr * m[a]).float() for a in range(3)], 1)
+    a00, a01, a02 = Sd[4] / S0 - m[0] * m[0], Sd[5] / S0 - m[0] * m[1], Sd[6] / S0 - m[0] * m[2]
+    a11, a12, a22 = Sd[7] / S0 - m[1] * m[1], Sd[8] / S0 - m[1] * m[2], Sd[9] / S0 - m[2] * m[2]
+    one, nil = torch.ones_like(a00), torch.zeros_like(a00)
+    V = [[one, nil, nil], [nil, one, nil], [nil, nil, one]]                   # V[k][column]
+
+    def col(j):
+        return [V[0][j], V[1][j], V[2][j]]
+
+    def put(j, v):
+        for k in range(3):
+            V[k][j] = v[k]
+    for _ in range(5):
+        a00, a11, a01, a02, a12, vp, vq = _aniso_rotate_torch(a00, a11, a01, a02, a12, col(0), col(1))
+        put(0, vp), put(1, vq)
+        a00, a22, a02, a01, a12, vp, vq = _aniso_rotate_torch(a00, a22, a02, a01, a12, col(0), col(2))
+        put(0, vp), put(2, vq)
+        a11, a22, a12, a01, a02, vp, vq = _aniso_rotate_torch(a11, a22, a12, a01, a02, col(1), col(2))
+        put(1, vp), put(2, vq)
+    top = torch.where(a00 > a11, a00, a11)
+    top = torch.where(top > a22, top, a22)
+    few = (count <= n_eps) | ~(top > 0.0)
+    fl = top / kr
+    e = []
+    for sig in (a00, a11, a22):
+        x = ks * torch.where(sig > fl, sig, fl)
+        x = torch.where(x < s_min, torch.full_like(x, s_min), x)
+        e.append(torch.where(x > s_max, torch.full_like(x, s_max), x))
+    inv = [1.0 / x for x in e]
+    inv_kn = 1.0 / np.float64(kn)
+    G = []
+    for a, b in ((0, 0), (0, 1), (0, 2), (1, 1), (1, 2), (2, 2)):
+        g = ((V[a][0] * inv[0]) * V[b][0] + (V[a][1] * inv[1]) * V[b][1]) + (V[a][2] * inv[2]) * V[b][2]
+        G.append(torch.where(few, torch.full_like(g, float(inv_kn) if a == b else 0.0), g).float())
+    det = 1.0 / ((e[0] * e[1]) * e[2])
+    det = torch.where(few, torch.full_like(det, float(1.0 / ((np.float64(kn) * kn) * kn))), det).float()
+    return centres, torch.stack(G, 1), det, count
+
+
+def _aniso_field_torch(query, centres, G, det, support, reach, pairs_per_chunk=1 << 22, query_rows=8192):
+    """Stage B of the anisotropic kernels for one cloud as torch ops, the same bits as the kernels: query (Nq,3), centres
+    (Np,3), G (Np,6), det (Np,) fp32 -> (Nq,) fp32.  A chunk of queries meets only the centres within reach of its
+    bounding box (with a margin): every other centre is no member and would add exactly 0."""
+    R, reach = float(_F32(support)), float(_F32(reach))
+    reach2 = float(_F32(reach) * _F32(reach))
+    dev = query.device
+    out = torch.zeros(query.shape[0], dtype=torch.float32, device=dev)
+    if centres.shape[0] == 0 or query.shape[0] == 0:
+        return out
+    one = torch.ones((), dtype=torch.float32, device=dev)
+    nil = torch.zeros((), dtype=torch.float32, device=dev)
+    for first in range(0, query.shape[0], query_rows):
+        chunk = query[first:first + query_rows]
+        finite = torch.isfinite(chunk).all(1)
+        if not bool(finite.any()):
+            continue
+        lo, hi = chunk[finite].amin(0) - 1.001 * reach, chunk[finite].amax(0) + 1.001 * reach
+        keep = ((centres >= lo) & (centres <= hi)).all(1)
+        c, g, dt = centres[keep], G[keep], det[keep].unsqueeze(0)
+        if c.shape[0] == 0:
+            continue
+        cx, cy, cz = c[:, 0].unsqueeze(0), c[:, 1].unsqueeze(0), c[:, 2].unsqueeze(0)
+        g = [g[:, k].unsqueeze(0) for k in range(6)]
+        rows = max(1, pairs_per_chunk // c.shape[0])
+        for a in range(0, chunk.shape[0], rows):
+            q = chunk[a:a + rows]
+            t0, t1, t2 = q[:, 0:1] - cx, q[:, 1:2] - cy, q[:, 2:3] - cz
+            d2 = t0 * t0
+            d2 = d2 + t1 * t1
+            d2 = d2 + t2 * t2
+            y0 = (g[0] * t0 + g[1] * t1) + g[2] * t2
+            y1 = (g[1] * t0 + g[3] * t1) + g[4] * t2
+            y2 = (g[2] * t0 + g[4] * t1) + g[5] * t2
+            yy = (y0 * y0 + y1 * y1) + y2 * y2
+            u = torch.fmin(torch.sqrt(yy.double()).float() / R, one)
+            u2 = u * u
+            near = 6.0 * (u2 * u - u2) + 1.0
+            v = 1.0 - u
+            far = 2.0 * (v * v * v)
+            w = torch.fmax(torch.where(u <= 0.5, near, far), nil)
+            dw = torch.fmin(torch.fmax(dt * w, nil), 512.0 * one)
+            units = torch.where(d2 <= reach2, (dw * 4194304.0).to(torch.int64),
+                                torch.zeros((), dtype=torch.int64, device=dev))
+            out[first + a:first + a + q.shape[0]] = units.sum(1).to(torch.float32) * 2.384185791015625e-7
+    return out
+
+
+def anisotropic_kernels(points, cov_radius, ks, smooth_lambda=0.9, kr=4.0, s_min=0.125, s_max=2.0, kn=0.5, n_eps=25,
+                        lengths=None, _grid=None):
+    """Stage A of the anisotropic surface kernels (Yu and Turk; csrc/aniso.hip, the rule in full: include/tpgan_ops.h):
+    per particle the smoothed centre and the symmetric matrix G = V diag(1/s) V^T of the ellipsoid fitted to the weighted
+    covariance of its neighbours within `cov_radius` -> (centres (B,N,3) f32, G (B,N,6) f32 as xx xy xz yy yz zz,
+    det (B,N) f32 = 1 / (s0 s1 s2), count (B,N) int32, the neighbours within cov_radius, the particle included).
+
+    points (B,N,3) float tensor on the GPU, or unbatched (N,3); lengths (B,) or None (rows beyond get zeros).  ks scales
+    the extents (1 / `mesh.lattice_covariance` makes a full lattice's kernel the isotropic one); a particle with at most
+    n_eps neighbours is a ball of extent kn.  Deterministic: the same bits from run to run, at every batch position and
+    from both launch shapes, and equal to `_aniso_kernels_torch`, which backends without the kernels run (CPU tensors
+    need a registered checker).  No gradient."""
+    _need(isinstance(points, torch.Tensor) and points.is_floating_point(), "points must be a float tensor")
+    squeeze = points.dim() == 2
+    if squeeze:
+        points = points.unsqueeze(0)
+    _need(points.dim() == 3 and points.shape[2] == 3, "points must be (B,N,3) or (N,3)")
+    prm = _aniso_params(cov_radius, ks, smooth_lambda, kr, s_min, s_max, kn, n_eps)
+    p = points.detach().float().contiguous()
+    be = backend_for(p)
+    B, N = p.shape[:2]
+    ln = _lengths(lengths, B, N, p.device)
+    with torch.no_grad():
+        if hasattr(be, "aniso_kernels"):
+            out = be.aniso_kernels(p, ln, prm, _grid)
+        else:
+            out = (torch.zeros((B, N, 3)), torch.zeros((B, N, 6)), torch.zeros((B, N)), torch.zeros((B, N), dtype=torch.int32))
+            out = tuple(t.to(p.device) for t in out)
+            for b in range(B):
+                n = N if ln is None else min(max(int(ln[b]), 0), N)
+                for dst, src in zip(out, _aniso_kernels_torch(p[b, :n], prm)):
+                    dst[b, :n] = src
+    return tuple(t[0] for t in out) if squeeze else out
+
+
+def anisotropic_field(query, centres, G, det, support, s_max=2.0, lengths_q=None, lengths_p=None, _grid=None):
+    """Stage B of the anisotropic surface kernels: at every query the sum over the centres within s_max * support of
+    det_j * W(|G_j (x - centre_j)| / support), W the cubic kernel of `radius_reduce` -> (B,Nq) f32.
+
+    query (B,Nq,3), centres (B,Np,3), G (B,Np,6), det (B,Np) float tensors on the GPU (what `anisotropic_kernels`
+    returned), or all unbatched; lengths as in `radius_reduce`.  Deterministic like stage A and equal to
+    `_aniso_field_torch`.  No gradient."""
+    tensors = (query, centres, G, det)
+    _need(all(isinstance(t, torch.Tensor) and t.is_floating_point() for t in tensors),
+          "query, centres, G and det must be float tensors")
+    squeeze = query.dim() == 2
+    if squeeze:
+        _need(centres.dim() == 2 and G.dim() == 2 and det.dim() == 1, "query (Nq,3) needs centres (Np,3), G (Np,6), det (Np,)")
+        query, centres, G, det = (t.unsqueeze(0) for t in tensors)
+    _need(query.dim() == 3 and query.shape[2] == 3 and centres.dim() == 3 and centres.shape[2] == 3,
+          "query (B,Nq,3), centres (B,Np,3)")
+    B, Np = centres.shape[:2]
+    _need(query.shape[0] == B and tuple(G.shape) == (B, Np, 6) and tuple(det.shape) == (B, Np),
+          "centres (B,Np,3) need G (B,Np,6) and det (B,Np)")
+    _same_device(query, centres, G, det)
+    support32, smax32 = float(_F32(support)), float(_F32(s_max))
+    _need(np.isfinite(support32) and support32 > 0.0, "support must be positive and finite")
+    _need(np.isfinite(smax32) and smax32 > 0.0, "s_max must be positive and finite")
+    reach = float(_F32(smax32) * _F32(support32))
+    q, c, g, d = (t.detach().float().contiguous() for t in (query, centres, G, det))
+    be = backend_for(q)
+    Nq = q.shape[1]
+    lq, lp = _lengths(lengths_q, B, Nq, q.device), _lengths(lengths_p, B, Np, q.device)
+    with torch.no_grad():
+        if hasattr(be, "aniso_field"):
+            total = be.aniso_field(q, c, g, d, lq, lp, support32, reach, _grid)
+        else:
+            total = torch.zeros((B, Nq), dtype=torch.float32, device=q.device)
+            for b in range(B):
+                nq = Nq if lq is None else min(max(int(lq[b]), 0), Nq)
+                n = Np if lp is None else min(max(int(lp[b]), 0), Np)
+                total[b, :nq] = _aniso_field_torch(q[b, :nq], c[b, :n], g[b, :n], d[b, :n], support32, reach)
+    return total[0] if squeeze else total
 
 
 def cubic_interpolation(query_pos, field, pos, cutoff):

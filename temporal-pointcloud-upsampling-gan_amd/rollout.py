@@ -13,7 +13,8 @@ neighbours in the 6-D feature space (this project's `SRNet.forward_with_context`
     python -m tpgan_amd.rollout --checkpoint X.ckpt --frames 'dir/data_{i}.npz' --count 800 [--in-feats 6] --out DIR
         [--render PNGDIR --size 3 --width 768 --height 768 --mode pinhole --color depth --direction 0 0 -1
          --style points|surface --particle_radius 0.025 --smooth_iters 3 --smooth_half_width 2]
-        [--mesh MESHDIR --format ply|obj --spacing 0.025 --support 0.05 --step 0.0125 --iso 0.5]
+        [--mesh MESHDIR --format ply|obj --spacing 0.025 --support 0.05 --step 0.0125 --iso 0.5
+         --kernel isotropic|anisotropic --cov_radius 0.1 --smooth_lambda 0.9]
 
 --render writes one picture per frame (render.SequenceRenderer) from each chunk's outputs while they are still on the
 device; the camera is fitted to the first chunk.  --mesh writes one surface mesh per frame (mesh.SequenceMesher) in the
