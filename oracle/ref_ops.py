@@ -634,3 +634,105 @@ def err_ratio(got, ref, bound):
     bound = _f64(bound, err)
     r = torch.where(err == 0, torch.zeros_like(err), err / bound)
     return float(r.max()) if r.numel() else 0.0
+
+
+# ---- the 16 -> 16 -> 32 small tails (csrc/mlp_small.hip): restatements and derived per-element bounds ---------------
+# out[n] = max_j lrelu_s2(W2 . lrelu_s1(W1 . h[n, j])) and its backward, exact in float64 on any device.  The kernels
+# compute in fp32 on v_mfma_f32_16x16x4_f32 (fmaf chains) whatever the row type, so every bound below is a first-order
+# running-error bound in u = U32, propagated through the magnitudes |W| . |x|; SMALL_SAFETY = 2 covers the second-order
+# terms, once, by doubling u everywhere (the z1-sign threshold included).  Nothing here is measured on a kernel.
+SMALL_SAFETY = 2.0
+
+
+def slope32(s):
+    """A LeakyReLU slope as the launch receives it: a C float."""
+    return float(np.float32(s))
+
+
+def small_tail_geometry(P):
+    """(tiles, workgroups) of tpg_small_tail_bwd (small_bwd_blocks): 16 points per tile, 4 waves per workgroup, at
+    most 1024 workgroups; a wave takes tiles wave, wave + 4 * workgroups, ..."""
+    tiles = -(-P // 16)
+    return tiles, max(1, min(1024, -(-tiles // 4)))
+
+
+def small_tail_depth(P, K):
+    """h_w, the deepest fp32 chain of a weight-gradient element: a wave's trips x 16 k-steps per edge slot x K into one
+    accumulator, the reduce kernel's strided groups of slabs, the 16 group sums."""
+    tiles, blocks = small_tail_geometry(P)
+    return -(-tiles // (4 * blocks)) * 16 * K + -(-(4 * blocks) // 16) + 16
+
+
+def _small_hidden(h, W1, s1, u):
+    z1 = h @ W1.t()
+    a1 = torch.where(z1 > 0, z1, z1 * s1)
+    M1 = h.abs() @ W1.abs().t()
+    E1 = 16 * u * M1                               # a 16-term fmaf chain
+    return z1, a1, M1, E1, E1 + u * a1.abs()       # lrelu is 1-Lipschitz for slopes in [0, 1]; z1 * s1 rounds once
+
+
+def small_tail_fwd_ref(h, W1, W2, s1, s2, K):
+    """h (P*K, 16), W1 (16, 16), W2 (32, 16) -> dict of float64 tensors: the exact z1, a1 (P*K, 16), z2 (P*K, 32),
+    best = max_j z2, out = lrelu_s2(best) before the store's rounding (P, 32), arg (P, 32) uint8 = the FIRST maximum
+    (lowest j); the magnitudes M1 = |W1| . |h|, M2 = |W2| . |a1| and the bounds
+        E1 = 16u M1,  Ea1 = E1 + u |a1|,  E2 = |W2| . Ea1 + 16u M2,  E2max = max_j E2,  Eout = E2max + u |out|
+    (max over j and lrelu are 1-Lipschitz; a bf16 store: small_stored_bound)."""
+    h = _f64(h)
+    W1, W2 = _f64(W1, h), _f64(W2, h)
+    s1, s2, u = slope32(s1), slope32(s2), SMALL_SAFETY * U32
+    P = h.shape[0] // K
+    z1, a1, M1, E1, Ea1 = _small_hidden(h, W1, s1, u)
+    z2 = a1 @ W2.t()
+    M2 = a1.abs() @ W2.abs().t()
+    E2 = Ea1 @ W2.abs().t() + 16 * u * M2
+    z2v = z2.view(P, K, W2.shape[0])
+    best = z2v.max(1)[0]
+    ks = torch.arange(K, device=h.device)[None, :, None]
+    arg = torch.where(z2v == best[:, None], ks, K).min(1)[0]
+    out = torch.where(best > 0, best, best * s2)
+    E2max = E2.view(P, K, W2.shape[0]).max(1)[0]
+    return dict(z1=z1, a1=a1, z2=z2, best=best, out=out, arg=arg.to(torch.uint8), M1=M1, M2=M2, E1=E1, Ea1=Ea1, E2=E2,
+                E2max=E2max, Eout=E2max + u * out.abs())
+
+
+def small_tail_bwd_ref(h, out_sign, gout, arg, W1, W2, s1, s2, K, h_w=None):
+    """The backward as the kernel defines it, `arg` (P, 32) and the sign of `out` (any tensor positive where out is)
+    taken as given, exactly as the kernel reads them back:
+        gp = out > 0 ? gout : gout s2,  gz2[n, j, c] = (arg[n, c] == j) gp[n, c],  ga1 = W2^T gz2,
+        gz1 = ga1 (z1 > 0 ? 1 : s1),  gh = W1^T gz1,  dW1 = sum_edges gz1 (x) h,  dW2 = sum_edges gz2 (x) a1.
+    -> dict: the exact float64 values, the magnitude sums S1 / S2 of the weight gradients' terms, and the bounds
+        Egz2 = u |gz2|                                               (gout s2 rounds once)
+        Ega1 = 32u |W2|^T |gz2| + |W2|^T Egz2                        (a 32-term chain)
+        Egz1 = Ega1 lrelu'(z1) + u |gz1|; where |z1| <= E1 (`flip`: the recomputed sign may differ there)
+               Ega1 + u |gz1| + (1 - s1) |ga1|
+        Egh  = |W1|^T Egz1 + 16u |W1|^T |gz1|                        (a bf16 store: small_stored_bound)
+        EdW1 = h_w u S1 + sum Egz1 (x) |h|,   EdW2 = h_w u S2 + sum (Egz2 (x) |a1| + |gz2| (x) Ea1)
+    with h_w = small_tail_depth(P, K) unless given."""
+    h = _f64(h)
+    W1, W2, gout = _f64(W1, h), _f64(W2, h), _f64(gout, h)
+    s1, s2, u = slope32(s1), slope32(s2), SMALL_SAFETY * U32
+    P = h.shape[0] // K
+    h_w = small_tail_depth(P, K) if h_w is None else h_w
+    z1, a1, _, E1, Ea1 = _small_hidden(h, W1, s1, u)
+    gp = torch.where(out_sign.to(h.device) > 0, gout, gout * s2)
+    hit = arg.to(h.device).long()[:, None, :] == torch.arange(K, device=h.device)[None, :, None]
+    gz2 = torch.where(hit, gp[:, None, :], torch.zeros_like(gp[:, None, :])).reshape(P * K, W2.shape[0])
+    Egz2 = u * gz2.abs()
+    ga1 = gz2 @ W2
+    Ega1 = 32 * u * (gz2.abs() @ W2.abs()) + Egz2 @ W2.abs()
+    dz1 = torch.where(z1 > 0, torch.ones_like(z1), torch.full_like(z1, s1))
+    gz1 = ga1 * dz1
+    flip = z1.abs() <= E1
+    Egz1 = Ega1 * torch.where(flip, torch.ones_like(dz1), dz1) + u * gz1.abs() + \
+        torch.where(flip, (1.0 - s1) * ga1.abs(), torch.zeros_like(ga1))
+    gh = gz1 @ W1
+    Egh = Egz1 @ W1.abs() + 16 * u * (gz1.abs() @ W1.abs())
+    S1, S2 = gz1.abs().t() @ h.abs(), gz2.abs().t() @ a1.abs()
+    return dict(z1=z1, a1=a1, gz2=gz2, ga1=ga1, gz1=gz1, gh=gh, dW1=gz1.t() @ h, dW2=gz2.t() @ a1, S1=S1, S2=S2,
+                flip=flip, Egz1=Egz1, Egh=Egh, h_w=h_w, EdW1=h_w * u * S1 + Egz1.t() @ h.abs(),
+                EdW2=h_w * u * S2 + Egz2.t() @ a1.abs() + gz2.abs().t() @ Ea1)
+
+
+def small_stored_bound(ref, E, bf16):
+    """A stored row value: within E of ref in fp32, then one round-to-nearest-even to bf16 of that value."""
+    return E + BF16_REL * (ref.abs() + E) if bf16 else E

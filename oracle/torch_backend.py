@@ -165,6 +165,15 @@ class OracleBackend:
         return torch.cat(dxs, 0).to(x.dtype), (dg if need_affine else None), (db if need_affine else None)
 
 
+    # ---- the 16 -> 16 -> 32 small tails (float64 inside, stored as the kernels store) ------
+    def small_tail_fwd(self, h, W1, W2, s1, s2, K):
+        f = R.small_tail_fwd_ref(h.detach(), W1.detach(), W2.detach(), s1, s2, int(K))
+        return f["out"].to(torch.float32).to(h.dtype), f["arg"]
+
+    def small_tail_bwd(self, h, out, gout, arg, W1, W2, s1, s2, K):
+        b = R.small_tail_bwd_ref(h.detach(), out.detach(), gout.detach(), arg, W1.detach(), W2.detach(), s1, s2, int(K))
+        return b["gh"].to(torch.float32).to(h.dtype), b["dW1"].to(torch.float32), b["dW2"].to(torch.float32)
+
     # ---- fused spectral norm ------------------------------------------------------------
     def spectral_norm_fwd(self, W, u, v, iterate, eps):
         Wsn, u2, v2, sigma = R.spectral_norm_fwd(_np(W), _np(u), _np(v), iterate, eps)
