@@ -862,6 +862,57 @@ int tpg_pbf_dp_f32(const float *p, const float *lam, const int64_t *lengths, con
 int tpg_pbf_finish_f32(const float *p, const float *x, const int64_t *lengths, int B, int N, float h, float dt, float cs,
                        const void *ws, float *x_out, float *v_out, void *stream);
 
+/* ---- solid obstacles in the particle fluid simulator (csrc/pbf.hip) ----------------------------------------------
+ * Static solids in the way of the fluid: the three shapes the fluid bodies use, each in a rotated frame of its own.  A
+ * scene has up to PBF_MAX_OBSTACLES = 8 of them, in a DEVICE table obstacles (B,M,16) f32, one row per obstacle:
+ *     kind, cx, cy, cz, R00 R01 R02 R10 R11 R12 R20 R21 R22 (row-major), s0, s1, s2
+ *     kind 1  ball      radius s0
+ *     kind 2  box       half extents s0, s1, s2
+ *     kind 3  cylinder  along the local y axis: radius s0, half height s1
+ * The world position of a local point q is c + R q.  A row is SKIPPED when its kind is none of 1.0f, 2.0f, 3.0f (padding
+ * rows have kind 0) or when any of its 15 other values is not finite (|v| <= FLT_MAX is false: NaN, +-inf), so a row with
+ * a non-finite number never tests "inside".  Like lengths, the table's values sit on the device and are not checked by
+ * the entry; no address depends on a table value, so a bad row cannot fault.  (ops.pbf_obstacles validates on the host:
+ * finite values, positive sizes, R orthonormal.)
+ *
+ * collide(p), per particle, over the obstacles o = 0 .. M-1 IN INDEX ORDER, each acting on the position the previous one
+ * left.  fp32, only + - * / and sqrtf, each operation rounded on its own (no FMA); comparisons, |.| and selections are
+ * exact.  With a the particle radius:
+ *   local frame   dx = px - cx, dy = py - cy, dz = pz - cz;  q_k = (dx*R[0][k] + dy*R[1][k]) + dz*R[2][k],  k = x, y, z
+ *   ball          E = s0 + a;  d2 = (qx*qx + qy*qy) + qz*qz;  inside iff d2 < E*E (STRICT).
+ *                 d2 == 0: q = (0, E, 0);  otherwise d = sqrtf(d2), q_k = (q_k / d) * E
+ *   box           E_k = s_k + a;  inside iff |q_k| < E_k on all three axes.  pen_k = E_k - |q_k|; the axis with the
+ *                 smallest pen, ties to the lowest k (k = 0; pen_1 < pen_0: k = 1; pen_2 < pen_k: k = 2); on that axis
+ *                 q_k = q_k < 0 ? -E_k : E_k
+ *   cylinder      Er = s0 + a, Eh = s1 + a, r2 = qx*qx + qz*qz;  inside iff r2 < Er*Er and |qy| < Eh.
+ *                 r = sqrtf(r2);  pen_r = Er - r;  pen_h = Eh - |qy|.
+ *                 pen_h <= pen_r: onto the cap, qy = qy < 0 ? -Eh : Eh;
+ *                 otherwise radially: (qx, qz) = ((qx / r) * Er, (qz / r) * Er), or (Er, 0) when r2 == 0
+ *   back          ONLY a particle that was inside is written back: p_k = c_k + ((R[k][0]*qx + R[k][1]*qy) + R[k][2]*qz).
+ *                 A particle that was not inside keeps its bits for that obstacle: no round trip through the local frame.
+ *   at the end    the scene's box clamp of the rule above, clamp(p, lo + a, hi - a): the clamp wins over an obstacle
+ *                 that leans on a wall.
+ * One substep with obstacles is the substep above with collide applied once to the output of predict and once to the
+ * output of every dp pass (each of which has already been clamped: the clamp is idempotent).  Velocities need nothing
+ * more: finish takes v = (p - x) / dt.  The solid is a position constraint only, exactly as the walls are: no boundary
+ * particles, no friction.  Consequences:
+ *   - density is deficient at an obstacle's skin, as at a wall (nothing fills the solid's side of the neighbourhood);
+ *   - a particle that moves more than an obstacle's half thickness in one substep can come out on the far side (it is
+ *     projected to the nearest face, or is never seen inside): keep obstacles several particle spacings thick;
+ *   - an obstacle that overlaps a wall can pin particles in the wedge: the obstacle pushes them through the wall, the
+ *     clamp puts them back inside the obstacle.
+ *
+ * tpg_pbf_collide_f32: p_out = collide(p) for every scene; p_out may be p (a thread touches its own row only).  hit_out
+ * (B,N) int32 or NULL: bit o is set iff obstacle o moved the particle (it tested inside).  box is the HOST table of
+ * tpg_pbf_predict_f32.  One thread per particle, scenes in chunks of 64 per launch like predict.  Rows at or beyond
+ * lengths[b] are never read and never written.  Checks, all before anything is launched.  TPG_ERR_ARG: negative B, N or
+ * M, a not positive and finite, a NULL p_out.  Then B == 0 or N == 0: TPG_OK, nothing written.  Then B > 65535, N > 2^22
+ * or M > PBF_MAX_OBSTACLES: TPG_ERR_UNSUPPORTED.  Then a NULL p or box, a box that is not finite or has lo >= hi on an
+ * axis, a NULL obstacles with M > 0: TPG_ERR_ARG.  M == 0 is legal and applies the clamp alone. */
+#define PBF_MAX_OBSTACLES 8
+int tpg_pbf_collide_f32(const float *p, const int64_t *lengths, const float *box, const float *obstacles, int B, int N,
+                        int M, float a, float *p_out, int32_t *hit_out, void *stream);
+
 /* ---- isosurfaces (csrc/isosurface.hip) ------------------------------------------------------------------------------
  * The surface field >= iso of a scalar field on a regular lattice as an indexed triangle mesh: marching tetrahedra on
  * the Kuhn (Freudenthal) split of every lattice cube into six tetrahedra.  (The reference ends its demo by handing

@@ -92,6 +92,7 @@ SIGNATURES = {
     "tpg_pbf_lambda_f32": [_P, _P, _I, _I, _F, _F, _F, _P, _P, _P, _P],
     "tpg_pbf_dp_f32": [_P, _P, _P, _P, _I, _I, _F, _F, _F, _F, _F, _P, _P, _P, _P],
     "tpg_pbf_finish_f32": [_P, _P, _P, _I, _I, _F, _F, _F, _P, _P, _P, _P],
+    "tpg_pbf_collide_f32": [_P, _P, _P, _P, _I, _I, _I, _F, _P, _P, _P],
     "tpg_iso_count_f32": [_P, _I, _I, _I, _F, _P, _P, _P],
     "tpg_iso_emit_f32": [_P, _I, _I, _I, _P, _F, _F, _P, _L, _L, _P, _P, _P, _P],
     "tpg_aniso_kernels_f32": [_P, _P, _I, _I, _F, _F, _F, _F, _F, _F, _F, _I, _I, _P, _P, _P, _P, _P, _P],

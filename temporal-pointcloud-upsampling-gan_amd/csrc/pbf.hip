@@ -345,3 +345,107 @@ extern "C" int tpg_pbf_finish_f32(const float *p, const float *x, const int64_t 
     TPG_RETURN_IF_LAUNCH_FAILED();
     return TPG_OK;
 }
+
+// ---- static solid obstacles (the rule in full: include/tpgan_ops.h, "solid obstacles"; the numpy statement:
+// tests/pbf_obstacle_rule.py).  collide is a launch kind of its own, after predict and after every dp: one thread per
+// particle, streaming like predict (12 bytes in, 12 or 16 out).  The M rows of a scene sit at an address that depends on
+// blockIdx.y alone and are read before the kernel's only stores, so they travel through the scalar cache into scalar
+// registers, and every branch on a row's kind or on its finiteness is uniform over the workgroup.  No address depends on a
+// table value.  No LDS, no atomics.
+namespace {
+
+constexpr int PBF_OBSTACLE_FLOATS = 16;     // PBF_MAX_OBSTACLES: include/tpgan_ops.h
+
+__device__ __forceinline__ bool pbf_finite(float v) { return fabsf(v) <= 3.4028234663852886e38f; }      // false for NaN
+
+// p = collide(p): the obstacles in index order, then the box clamp         grid (ceil(N/256), chunk of scenes)
+// p_out may be p (a thread reads and writes its own row only), hence no __restrict__ on the two
+__global__ __launch_bounds__(256) void pbf_collide_kernel(const float *p, const int64_t *__restrict__ lengths, PbfBoxes box,
+                                                          const float *__restrict__ obstacles, int b0, int N, int M,
+                                                          float a, float *p_out, int32_t *__restrict__ hit_out) {
+    const int b = b0 + blockIdx.y, i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= pbf_len(lengths, b, N)) return;
+    const size_t at = (size_t)b * N + i;
+    float px = p[at * 3], py = p[at * 3 + 1], pz = p[at * 3 + 2];
+    const float *__restrict__ row = obstacles + (size_t)b * M * PBF_OBSTACLE_FLOATS;
+    int hit = 0;
+    for (int o = 0; o < M; ++o, row += PBF_OBSTACLE_FLOATS) {
+        float t[PBF_OBSTACLE_FLOATS];
+#pragma unroll
+        for (int j = 0; j < PBF_OBSTACLE_FLOATS; ++j) t[j] = row[j];
+        const float kind = t[0];
+        bool ok = kind == 1.0f || kind == 2.0f || kind == 3.0f;
+#pragma unroll
+        for (int j = 1; j < PBF_OBSTACLE_FLOATS; ++j) ok = ok && pbf_finite(t[j]);
+        if (!ok) continue;
+        const float dx = px - t[1], dy = py - t[2], dz = pz - t[3];
+        float qx = (dx * t[4] + dy * t[7]) + dz * t[10];
+        float qy = (dx * t[5] + dy * t[8]) + dz * t[11];
+        float qz = (dx * t[6] + dy * t[9]) + dz * t[12];
+        bool inside;
+        if (kind == 1.0f) {
+            const float E = t[13] + a, d2 = (qx * qx + qy * qy) + qz * qz;
+            inside = d2 < E * E;
+            if (d2 == 0.0f) {
+                qx = 0.0f, qy = E, qz = 0.0f;
+            } else {
+                const float d = sqrtf(d2);
+                qx = (qx / d) * E, qy = (qy / d) * E, qz = (qz / d) * E;
+            }
+        } else if (kind == 2.0f) {
+            const float Ex = t[13] + a, Ey = t[14] + a, Ez = t[15] + a;
+            const float ax = fabsf(qx), ay = fabsf(qy), az = fabsf(qz);
+            inside = ax < Ex && ay < Ey && az < Ez;
+            const float p0 = Ex - ax, p1 = Ey - ay, p2 = Ez - az;
+            int k = 0;
+            float pk = p0;
+            if (p1 < pk) k = 1, pk = p1;
+            if (p2 < pk) k = 2;
+            if (k == 0) qx = qx < 0.0f ? -Ex : Ex;
+            if (k == 1) qy = qy < 0.0f ? -Ey : Ey;
+            if (k == 2) qz = qz < 0.0f ? -Ez : Ez;
+        } else {
+            const float Er = t[13] + a, Eh = t[14] + a, r2 = qx * qx + qz * qz;
+            inside = r2 < Er * Er && fabsf(qy) < Eh;
+            const float r = sqrtf(r2), pen_r = Er - r, pen_h = Eh - fabsf(qy);
+            if (pen_h <= pen_r) {
+                qy = qy < 0.0f ? -Eh : Eh;
+            } else if (r2 == 0.0f) {
+                qx = Er, qz = 0.0f;
+            } else {
+                qx = (qx / r) * Er, qz = (qz / r) * Er;
+            }
+        }
+        if (inside) {
+            px = t[1] + ((t[4] * qx + t[5] * qy) + t[6] * qz);
+            py = t[2] + ((t[7] * qx + t[8] * qy) + t[9] * qz);
+            pz = t[3] + ((t[10] * qx + t[11] * qy) + t[12] * qz);
+            hit |= 1 << o;
+        }
+    }
+    p_out[at * 3] = pbf_clamp(px, box.c[blockIdx.y][0] + a, box.c[blockIdx.y][3] - a);
+    p_out[at * 3 + 1] = pbf_clamp(py, box.c[blockIdx.y][1] + a, box.c[blockIdx.y][4] - a);
+    p_out[at * 3 + 2] = pbf_clamp(pz, box.c[blockIdx.y][2] + a, box.c[blockIdx.y][5] - a);
+    if (hit_out) hit_out[at] = hit;
+}
+
+}  // namespace
+
+extern "C" int tpg_pbf_collide_f32(const float *p, const int64_t *lengths, const float *box, const float *obstacles, int B,
+                                   int N, int M, float a, float *p_out, int32_t *hit_out, void *stream) {
+    if (M < 0 || !pbf_pos(a) || !p_out) return TPG_ERR_ARG;
+    const int chk = pbf_shape(B, N);
+    if (chk && chk != TPG_ERR_UNSUPPORTED) return chk > 0 ? TPG_OK : chk;
+    if (chk || M > PBF_MAX_OBSTACLES) return TPG_ERR_UNSUPPORTED;
+    if (!p || !box || !pbf_box_ok(box, B) || (M > 0 && !obstacles)) return TPG_ERR_ARG;
+    hipStream_t st = tpg_stream(stream);
+    for (int b0 = 0; b0 < B; b0 += PBF_BOX_CHUNK) {
+        const int nb = min(PBF_BOX_CHUNK, B - b0);
+        PbfBoxes bx;
+        pbf_fill_boxes(bx, box, b0, nb);
+        hipLaunchKernelGGL(pbf_collide_kernel, dim3((N + 255) / 256, nb), dim3(256), 0, st, p, lengths, bx, obstacles, b0, N,
+                           M, a, p_out, hit_out);
+    }
+    TPG_RETURN_IF_LAUNCH_FAILED();
+    return TPG_OK;
+}

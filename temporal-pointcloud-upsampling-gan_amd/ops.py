@@ -408,18 +408,30 @@ class HipBackend:
         self._call("tpg_pbf_finish_f32", "pbf_finish", 48 * B * N, p, _ptr(p), _ptr(x), _ptr(lengths), B, N, prm.h, dt,
                    prm.cs, _ptr(ws), _ptr(x_out), _ptr(v_out))
 
-    def pbf_substep(self, x, v, lengths, box, dt, prm, x_out, v_out):
+    def pbf_collide(self, p, lengths, box, obstacles, prm, p_out, hit_out=None):
+        """p_out = collide(p) (p_out may be p): the obstacles (B,M,16) in index order, then the box clamp."""
+        B, N, _ = p.shape
+        self._call("tpg_pbf_collide_f32", "pbf_collide", (24 + (4 if hit_out is not None else 0)) * B * N, p, _ptr(p),
+                   _ptr(lengths), box.ctypes.data, _ptr(obstacles), B, N, obstacles.shape[1], prm.radius, _ptr(p_out),
+                   _ptr(hit_out))
+
+    def pbf_substep(self, x, v, lengths, box, dt, prm, x_out, v_out, obstacles=None):
         """One substep of every scene: predict | iters x (grid | lambda | dp) | grid | finish.  x_out / v_out receive the
-        rows below lengths; p and lambda are per-stream workspaces, the dp pass updates p in place."""
+        rows below lengths; p and lambda are per-stream workspaces, the dp pass updates p in place.  obstacles (B,M,16):
+        a collide launch in place after predict and after every dp; None: no such launch."""
         B, N, _ = x.shape
         ws = self.pbf_ws(x, B, N)
         p = self._workspace("pbf_p", x, B * N * 3)[:B * N * 3].view(B, N, 3)
         lam = self._workspace("pbf_lam", x, B * N)
         self.pbf_predict(x, v, lengths, box, dt, prm, p, v_out)
+        if obstacles is not None:
+            self.pbf_collide(p, lengths, box, obstacles, prm, p)
         for _ in range(prm.iters):
             self.pbf_grid(p, lengths, prm, ws)
             self.pbf_lambda(p, lengths, prm, ws, lam)
             self.pbf_dp(p, lam, lengths, box, prm, ws, p)
+            if obstacles is not None:
+                self.pbf_collide(p, lengths, box, obstacles, prm, p)
         self.pbf_grid(p, lengths, prm, ws)
         self.pbf_finish(p, x, lengths, dt, prm, ws, x_out, v_out)
         return x_out, v_out
@@ -2193,10 +2205,59 @@ def _pbf_finish_torch(p, x, dt, prm, neighbours=_pbf_candidates_torch):
     return v + f(prm.cs) * (acc.to(torch.float32) * (1.0 / _PBF_U30))
 
 
-def _pbf_substep_torch(x, v, lengths, box, dt, prm, neighbours=_pbf_candidates_torch):
+def _pbf_collide_torch(p, lo, hi, table, prm, hit=None):
+    """collide of include/tpgan_ops.h ("solid obstacles") for one cloud p (n,3) against the rows of table (M,16), in
+    torch ops: the same fp32 operations in the same order as pbf_collide_kernel, so the results are EQUAL to its.
+    hit: an int32 (n,) tensor that gains bit o for the particles obstacle o moved -> the new p."""
+    f = lambda s: torch.tensor(s, dtype=torch.float32, device=p.device)          # noqa: E731
+    root = lambda t: torch.sqrt(t.double()).float()                               # noqa: E731  (see _PbfPairs)
+    a = f(prm.radius)
+    side = lambda q, E: torch.where(q < 0, -E, E)                                 # noqa: E731
+    P = [p[:, 0], p[:, 1], p[:, 2]]
+    for o in range(table.shape[0]):
+        row = table[o].to(device=p.device, dtype=torch.float32)
+        kind = float(row[0])
+        if kind not in (1.0, 2.0, 3.0) or not bool(torch.isfinite(row[1:]).all()):
+            continue
+        c, R, s = row[1:4], row[4:13].view(3, 3), row[13:16]
+        d = [P[0] - c[0], P[1] - c[1], P[2] - c[2]]
+        q = [(d[0] * R[0, k] + d[1] * R[1, k]) + d[2] * R[2, k] for k in range(3)]
+        zeros = torch.zeros_like(q[0])
+        if kind == 1.0:
+            E = s[0] + a
+            d2 = (q[0] * q[0] + q[1] * q[1]) + q[2] * q[2]
+            inside = d2 < E * E
+            dist = root(d2)
+            new = [torch.where(d2 == 0, E if k == 1 else zeros, (q[k] / dist) * E) for k in range(3)]
+        elif kind == 2.0:
+            E = [s[k] + a for k in range(3)]
+            mag = [q[k].abs() for k in range(3)]
+            inside = (mag[0] < E[0]) & (mag[1] < E[1]) & (mag[2] < E[2])
+            pen = [E[k] - mag[k] for k in range(3)]
+            k1 = pen[1] < pen[0]
+            k2 = pen[2] < torch.where(k1, pen[1], pen[0])
+            axis = torch.where(k2, 2, torch.where(k1, 1, 0))
+            new = [torch.where(axis == k, side(q[k], E[k]), q[k]) for k in range(3)]
+        else:
+            Er, Eh = s[0] + a, s[1] + a
+            r2 = q[0] * q[0] + q[2] * q[2]
+            inside = (r2 < Er * Er) & (q[1].abs() < Eh)
+            r = root(r2)
+            cap = (Eh - q[1].abs()) <= (Er - r)
+            new = [torch.where(cap, q[0], torch.where(r2 == 0, Er, (q[0] / r) * Er)),
+                   torch.where(cap, side(q[1], Eh), q[1]),
+                   torch.where(cap, q[2], torch.where(r2 == 0, zeros, (q[2] / r) * Er))]
+        P = [torch.where(inside, c[k] + ((R[k, 0] * new[0] + R[k, 1] * new[1]) + R[k, 2] * new[2]), P[k]) for k in range(3)]
+        if hit is not None:
+            hit |= inside.to(torch.int32) << o
+    return _pbf_clamp(torch.stack(P, 1), lo, hi, a)
+
+
+def _pbf_substep_torch(x, v, lengths, box, dt, prm, neighbours=_pbf_candidates_torch, obstacles=None):
     """`pbf_substep` composed of torch ops, scene by scene: the same fp32 operations in the same order and the same
     fixed-point sums as csrc/pbf.hip (the rule: include/tpgan_ops.h), so the results are EQUAL to the kernels'.
-    `neighbours(p, h) -> (i, j)` supplies candidate pairs (any superset of the pairs within h)."""
+    `neighbours(p, h) -> (i, j)` supplies candidate pairs (any superset of the pairs within h).  obstacles (B,M,16) or
+    None: collide after predict and after every dp."""
     B, N, _ = x.shape
     x_out, v_out = x.clone(), v.clone()
     lens = [N] * B if lengths is None else [min(max(int(n), 0), N) for n in lengths.tolist()]
@@ -2209,9 +2270,13 @@ def _pbf_substep_torch(x, v, lengths, box, dt, prm, neighbours=_pbf_candidates_t
         xb = x[b, :n]
         vb = v[b, :n] + f(dt) * torch.tensor(prm.gravity, dtype=torch.float32, device=x.device)
         p = _pbf_clamp(xb + f(dt) * vb, lo, hi, f(prm.radius))
+        if obstacles is not None:
+            p = _pbf_collide_torch(p, lo, hi, obstacles[b], prm)
         for _ in range(prm.iters):
             lam, _, pr = _pbf_lambda_torch(p, prm, neighbours)
             p, _ = _pbf_dp_torch(p, lam, pr, lo, hi, prm)
+            if obstacles is not None:
+                p = _pbf_collide_torch(p, lo, hi, obstacles[b], prm)
         v_out[b, :n] = _pbf_finish_torch(p, xb, dt, prm, neighbours)
         x_out[b, :n] = p
     return x_out, v_out
@@ -2226,13 +2291,100 @@ def pbf_box(box_lo, box_hi, B):
     return box
 
 
-def pbf_substep(x, v, lengths, box_lo, box_hi, dt, params=None):
+PBF_MAX_OBSTACLES = 8                  # obstacles per scene (include/tpgan_ops.h)
+PBF_OBSTACLE_KINDS = {"ball": 1, "box": 2, "cylinder": 3}
+_PBF_OBSTACLE_SIZES = {"ball": 1, "box": 3, "cylinder": 2}
+
+
+def _pbf_obstacle_row(ob):
+    """One validated table row (16 float32) of an obstacle dict."""
+    _need(isinstance(ob, dict) and ob.get("shape") in PBF_OBSTACLE_KINDS,
+          f"an obstacle is a dict whose shape is one of {sorted(PBF_OBSTACLE_KINDS)}")
+    _need("centre" in ob and "size" in ob, "an obstacle needs a centre and a size")
+    shape = ob["shape"]
+    centre = np.asarray(ob["centre"], dtype=np.float64).reshape(-1)
+    rot = np.asarray(ob.get("rotation", np.eye(3)), dtype=np.float64).reshape(-1)
+    size = np.asarray(ob["size"], dtype=np.float64).reshape(-1)
+    _need(centre.size == 3 and rot.size == 9, "an obstacle's centre has 3 values, its rotation 9")
+    _need(size.size == _PBF_OBSTACLE_SIZES[shape], f"a {shape}'s size has {_PBF_OBSTACLE_SIZES[shape]} value(s)")
+    row = np.zeros(16, np.float32)
+    row[0], row[1:4], row[4:13], row[13:13 + size.size] = PBF_OBSTACLE_KINDS[shape], centre, rot, size
+    _need(bool(np.isfinite(row).all()), "an obstacle's centre, rotation and size must be finite")
+    _need(bool((row[13:13 + size.size] > 0).all()), "an obstacle's sizes must be positive")
+    R = rot.reshape(3, 3)
+    _need(float(np.abs(R @ R.T - np.eye(3)).max()) <= 1e-5, "an obstacle's rotation must be orthonormal within 1e-5")
+    return row
+
+
+def pbf_obstacles(obstacles, B=None, device="cuda"):
+    """The device table (B,M,16) fp32 of include/tpgan_ops.h ("solid obstacles") from obstacle dicts, validated on the
+    host: `shape` ("ball" | "box" | "cylinder"), `centre` (3), `rotation` (9 values, row-major, default the identity) and
+    `size`: a radius for a ball, 3 half extents for a box, (radius, half height) for a cylinder along its local y axis.
+
+    obstacles: one list of dicts shared by the batch (B: how many scenes, default 1), or one list per scene (B: their
+    number), padded to the longest with kind-0 rows; None: no obstacles (M = 0).  Raises on a non-finite value, a size
+    that is not positive, more than PBF_MAX_OBSTACLES per scene, a rotation that is not orthonormal within 1e-5."""
+    obstacles = [] if obstacles is None else list(obstacles)
+    if all(isinstance(o, dict) for o in obstacles):
+        per_scene = [obstacles] * (1 if B is None else int(B))
+    else:
+        per_scene = [[] if o is None else list(o) for o in obstacles]
+        _need(B is None or int(B) == len(per_scene), "one obstacle list per scene")
+    M = max([len(s) for s in per_scene] + [0])
+    _need(M <= PBF_MAX_OBSTACLES, f"at most {PBF_MAX_OBSTACLES} obstacles per scene")
+    table = np.zeros((len(per_scene), M, 16), np.float32)
+    for b, scene in enumerate(per_scene):
+        for o, ob in enumerate(scene):
+            table[b, o] = _pbf_obstacle_row(ob)
+    return torch.from_numpy(table).to(device)
+
+
+def _pbf_check_obstacles(obstacles, ref, B):
+    _check_float(obstacles, "obstacles", 3)
+    _need(obstacles.shape[0] == B and obstacles.shape[2] == 16, "obstacles must be (B,M,16)")
+    _need(obstacles.shape[1] <= PBF_MAX_OBSTACLES, f"at most {PBF_MAX_OBSTACLES} obstacles per scene")
+    _same_device(ref, obstacles)
+
+
+def pbf_collide(p, lengths, box_lo, box_hi, obstacles, params=None, return_hit=False):
+    """The simulator's collide launch kind on its own (include/tpgan_ops.h, "solid obstacles"): every particle projected
+    out of the obstacles of its scene in index order, then clamped into the box.
+
+    p (B,N,3) fp32; lengths, box_lo, box_hi as in `pbf_substep`; obstacles: the DEVICE table (B,M,16) of `pbf_obstacles`
+    (its values are not checked here; M = 0 applies the clamp alone); params: a `PbfParams` for the particle radius.
+    -> p (a new tensor; rows at or beyond lengths[b] come back unchanged), and with return_hit an int32 (B,N) whose bit o
+    is set iff obstacle o moved the particle (0 beyond the lengths).  Equal to `_pbf_collide_torch`.  No gradient."""
+    _check_float(p, "p", 3)
+    _need(p.shape[2] == 3, "p must be (B,N,3)")
+    B, N, _ = p.shape
+    _need(B <= 65535 and N <= PBF_MAX_N, f"at most 65535 scenes of {PBF_MAX_N} particles")
+    _pbf_check_obstacles(obstacles, p, B)
+    prm = PbfParams() if params is None else params
+    box = pbf_box(box_lo, box_hi, B)
+    lengths = _lengths(lengths, B, N, p.device)
+    be = backend_for(p)
+    with torch.no_grad():
+        out = p.detach().clone()
+        hit = torch.zeros((B, N), dtype=torch.int32, device=p.device) if return_hit else None
+        if hasattr(be, "pbf_collide"):
+            be.pbf_collide(p.detach(), lengths, box, obstacles.detach(), prm, out, hit)
+        else:
+            lens = [N] * B if lengths is None else [min(max(int(n), 0), N) for n in lengths.tolist()]
+            for b, n in enumerate(lens):
+                lo, hi = torch.from_numpy(box[b, :3].copy()).to(p.device), torch.from_numpy(box[b, 3:].copy()).to(p.device)
+                out[b, :n] = _pbf_collide_torch(p[b, :n].detach(), lo, hi, obstacles[b], prm, None if hit is None else hit[b, :n])
+    return (out, hit) if return_hit else out
+
+
+def pbf_substep(x, v, lengths, box_lo, box_hi, dt, params=None, obstacles=None):
     """One substep of the particle fluid simulator (Position Based Fluids, Jacobi, gather form; csrc/pbf.hip, the rule
     in full: include/tpgan_ops.h) for every scene of a ragged batch.
 
     x, v (B,N,3) fp32; lengths (B,) or None: rows at or beyond lengths[b] are never read and come back unchanged
     (the values stay on the device and are not checked: each counts as min(max(lengths[b], 0), N) of the int64 it is);
-    box_lo, box_hi: HOST values, 3 shared by the batch or (B,3); dt > 0; params: a `PbfParams` (None: the defaults).
+    box_lo, box_hi: HOST values, 3 shared by the batch or (B,3); dt > 0; params: a `PbfParams` (None: the defaults);
+    obstacles: the device table (B,M,16) of `pbf_obstacles`: static solids, applied after predict and after every dp
+    pass (None: no obstacles, and no launch for them).
     -> (x, v) new tensors.  Bit-identical from run to run, at every batch position, and equal to `_pbf_substep_torch`,
     which backends without the kernels run (CPU tensors need a registered checker, as everywhere).  No gradient."""
     _check_float(x, "x", 3)
@@ -2241,6 +2393,9 @@ def pbf_substep(x, v, lengths, box_lo, box_hi, dt, params=None):
     _same_device(x, v)
     B, N, _ = x.shape
     _need(B <= 65535 and N <= PBF_MAX_N, f"at most 65535 scenes of {PBF_MAX_N} particles")
+    if obstacles is not None:
+        _pbf_check_obstacles(obstacles, x, B)
+        obstacles = obstacles.detach()
     prm = PbfParams() if params is None else params
     dt = float(_F32(dt))
     _need(np.isfinite(dt) and dt > 0.0, "dt must be positive and finite")
@@ -2249,8 +2404,8 @@ def pbf_substep(x, v, lengths, box_lo, box_hi, dt, params=None):
     be = backend_for(x)
     with torch.no_grad():
         if hasattr(be, "pbf_substep"):
-            return be.pbf_substep(x.detach(), v.detach(), lengths, box, dt, prm, x.clone(), v.clone())
-        return _pbf_substep_torch(x.detach(), v.detach(), lengths, box, dt, prm)
+            return be.pbf_substep(x.detach(), v.detach(), lengths, box, dt, prm, x.clone(), v.clone(), obstacles)
+        return _pbf_substep_torch(x.detach(), v.detach(), lengths, box, dt, prm, obstacles=obstacles)
 
 
 # ------------------------------------------------------------------------ isosurfaces (csrc/isosurface.hip)

@@ -2,9 +2,13 @@
 
     python -m tpgan_amd.simulate --out DATA --cases 20 --frames 200 --seed 1 [--test_out TEST --test_cases 4]
         [--particle_radius 0.0125 --substeps 4 --iters 4 --box 3 2.5 3 --body_size 0.68 --batch 8 --device cuda]
+        [--obstacles 2 --obstacle_size 0.3 0.6]
 
 writes `DATA/case{c}/data_{s}.npz` (`pos`, `vel`: float32 (N,3)) for c = 1.., s = 0.., the layout `data.FluidSequences`
 and `python -m tpgan_amd.train --train_dataset_path DATA` read, and `DATA/case{c}/scene.json` beside them.
+--obstacles K puts K static solids (ball, box, cylinder; `ops.pbf_collide`, the rule: include/tpgan_ops.h, "solid
+obstacles") into the lower half of every scene; `scene.json` records them and `DATA/case{c}/obstacles.ply` is their
+surface (`obstacle_mesh`), to be loaded beside the fluid's meshes.
 
 The reference makes these directories with an external solver (fluid_data_generation/ drives SPlisHSPlasH's DFSPH on
 scenes from create_physics_scenes.py, with models it does not ship).  Here the solver is the project's own: Position
@@ -32,16 +36,21 @@ DEFAULT_BOX = (3.0, 2.5, 3.0)          # with BODY_SIZE: roughly 20k-120k partic
 BODY_SIZE = 0.68                       # edge of the unscaled box body in metres (a ball / cylinder of about its volume)
 COUNT_RANGE = (20000, 120000)
 SHAPES = ("box", "ball", "cylinder")
+OBSTACLE_SIZE = (0.3, 0.6)             # range of an obstacle's largest extent (edge, diameter, height) in metres
+MAX_RANDOM_OBSTACLES = 3
+MIN_OBSTACLE_SPACINGS = 4.0            # no obstacle thinner than this many particle spacings (tunnelling: tpgan_ops.h)
 
 
 class Scene:
     """A box and the fluid in it at t = 0.  `bodies`: dicts of shape, size (the scaled edge), rotation (3x3, row-major),
-    centre and velocity, from which `particles()` rebuilds the same points; or explicit `pos` / `vel` (n,3)."""
+    centre and velocity, from which `particles()` rebuilds the same points; or explicit `pos` / `vel` (n,3).
+    `obstacles`: the static solids in the box, dicts as `ops.pbf_obstacles` takes them (shape, centre, rotation, size)."""
 
-    def __init__(self, box_lo, box_hi, bodies=(), seed=None, radius=ops.PBF_RADIUS, pos=None, vel=None):
+    def __init__(self, box_lo, box_hi, bodies=(), seed=None, radius=ops.PBF_RADIUS, pos=None, vel=None, obstacles=()):
         self.box_lo = [float(v) for v in box_lo]
         self.box_hi = [float(v) for v in box_hi]
         self.bodies, self.seed, self.radius = list(bodies), seed, float(radius)
+        self.obstacles = list(obstacles)
         self._pos = None if pos is None else np.ascontiguousarray(pos, dtype=np.float32).reshape(-1, 3)
         self._vel = None if vel is None else np.ascontiguousarray(vel, dtype=np.float32).reshape(-1, 3)
 
@@ -57,12 +66,15 @@ class Scene:
         return self._pos, self._vel
 
     def to_json(self):
-        return {"seed": self.seed, "box_lo": self.box_lo, "box_hi": self.box_hi, "particle_radius": self.radius,
-                "bodies": self.bodies}
+        d = {"seed": self.seed, "box_lo": self.box_lo, "box_hi": self.box_hi, "particle_radius": self.radius,
+             "bodies": self.bodies}
+        if self.obstacles:                                   # a scene without obstacles is written as it always was
+            d["obstacles"] = self.obstacles
+        return d
 
     @classmethod
     def from_json(cls, d):
-        return cls(d["box_lo"], d["box_hi"], d["bodies"], d["seed"], d["particle_radius"])
+        return cls(d["box_lo"], d["box_hi"], d["bodies"], d["seed"], d["particle_radius"], obstacles=d.get("obstacles", ()))
 
 
 def body_half_extent(shape, size):
@@ -94,18 +106,62 @@ def _random_rotation(rng):
                      [2 * (x * z - y * w), 2 * (y * z + x * w), 1 - 2 * (x * x + y * y)]])
 
 
-def random_scene(seed, box=DEFAULT_BOX, radius=ops.PBF_RADIUS, body_size=BODY_SIZE, count_range=None, max_tries=1000):
+def obstacle_bound(ob):
+    """The radius of an obstacle's bounding sphere about its centre."""
+    size = np.atleast_1d(np.asarray(ob["size"], np.float64))
+    return float(size[0]) if ob["shape"] == "ball" else float(np.linalg.norm(size))
+
+
+def random_obstacles(rng, count, box, spacing, size_range=OBSTACLE_SIZE, max_tries=1000):
+    """`count` obstacle dicts drawn from `rng`: a ball, box or cylinder whose largest extent is U(size_range) metres (a
+    ball's diameter; a box's longest edge, the others U(0.6, 1) of it; a cylinder's height, its diameter U(0.6, 1) of it),
+    rotated at random, the centre in the lower half of the box [0, box] and at least a bounding radius from the walls, no
+    two bounding spheres overlapping.  An obstacle thinner than MIN_OBSTACLE_SPACINGS particle spacings is never drawn."""
+    out, spheres = [], []
+    for _ in range(max_tries):
+        if len(out) == count:
+            return out
+        shape = SHAPES[int(rng.integers(0, 3))]
+        half = 0.5 * float(rng.uniform(*size_range))
+        thin = [float(t) for t in rng.uniform(0.6, 1.0, 2)]
+        rot = _random_rotation(rng)
+        size = {"ball": half, "box": [half, half * thin[0], half * thin[1]], "cylinder": [half * thin[0], half]}[shape]
+        ob = {"shape": shape, "size": size, "rotation": rot.reshape(-1).tolist()}
+        bound = obstacle_bound(ob)
+        top = np.array([box[0] - bound, 0.5 * box[1], box[2] - bound])
+        if 2.0 * float(np.min(size)) < MIN_OBSTACLE_SPACINGS * spacing or (top < bound).any():
+            continue
+        centre = rng.uniform(bound, top)
+        if all(np.linalg.norm(centre - c) >= bound + b for c, b in spheres):
+            spheres.append((centre, bound))
+            out.append(dict(ob, centre=centre.tolist()))
+    if len(out) == count:
+        return out
+    raise RuntimeError(f"no room for {count} obstacles of {size_range} m in the lower half of the box {box.tolist()}")
+
+
+def random_scene(seed, box=DEFAULT_BOX, radius=ops.PBF_RADIUS, body_size=BODY_SIZE, count_range=None, max_tries=1000,
+                 obstacles=0, obstacle_size=OBSTACLE_SIZE):
     """The scene of `seed` (an int or a sequence of ints), everything drawn from numpy.random.default_rng(seed): one to
     three bodies, each a box, ball or upright cylinder of `body_size` scaled by U(0.5, 1.5) and rotated at random, placed
     by rejection so that the bodies' bounding spheres stay a particle spacing apart and inside the box, thrown with a
     start velocity of U(-2, 2) in x and z and U(-0.5, 0.5) in y.  The box is [0, box].  count_range (lo, hi): redraw
     (from the same generator) until the particle count lies in it; None: COUNT_RANGE for the default box and body size,
-    no condition otherwise."""
+    no condition otherwise.  obstacles: 0 to 3 static solids (`random_obstacles`), drawn first and from a generator of
+    their OWN (the seed's sequence with spawn key 1), so that the fluid's draws are those of the scene without obstacles;
+    a body is then also rejected unless its bounding sphere stays a spacing clear of every obstacle's."""
+    if not 0 <= int(obstacles) <= MAX_RANDOM_OBSTACLES:
+        raise ValueError(f"obstacles must be 0 .. {MAX_RANDOM_OBSTACLES}")
     rng = np.random.default_rng(seed)
     box = np.asarray(box, np.float64).reshape(3)
     if count_range is None and tuple(box) == DEFAULT_BOX and body_size == BODY_SIZE and radius == ops.PBF_RADIUS:
         count_range = COUNT_RANGE
     spacing = 2.0 * radius
+    solids = []
+    if obstacles:
+        own = np.random.default_rng(np.random.SeedSequence(seed, spawn_key=(1,)))
+        solids = random_obstacles(own, int(obstacles), box, spacing, obstacle_size)
+    keep_out = [(np.asarray(o["centre"]), obstacle_bound(o)) for o in solids]
     for _ in range(max_tries):
         bodies, spheres = [], []
         for _ in range(int(rng.integers(1, 4))):
@@ -118,13 +174,13 @@ def random_scene(seed, box=DEFAULT_BOX, radius=ops.PBF_RADIUS, body_size=BODY_SI
                 if (2 * bound >= box).any():
                     break
                 centre = rng.uniform(bound, box - bound)
-                if all(np.linalg.norm(centre - c) >= bound + b for c, b in spheres):
+                if all(np.linalg.norm(centre - c) >= bound + b for c, b in spheres + keep_out):
                     spheres.append((centre, bound))
                     bodies.append({"shape": shape, "size": size, "rotation": rot.reshape(-1).tolist(),
                                    "centre": centre.tolist(), "velocity": velocity})
                     break
         seed_out = seed if isinstance(seed, (int, np.integer)) else [int(s) for s in seed]
-        scene = Scene([0.0, 0.0, 0.0], box.tolist(), bodies, seed_out, radius)
+        scene = Scene([0.0, 0.0, 0.0], box.tolist(), bodies, seed_out, radius, obstacles=solids)
         n = scene.particles()[0].shape[0]
         if bodies and (count_range is None or count_range[0] <= n <= count_range[1]):
             return scene
@@ -144,24 +200,79 @@ def pack(scenes, device):
     return torch.from_numpy(x).to(device), torch.from_numpy(v).to(device), lengths.to(device), lo, hi
 
 
+def obstacle_table(scenes, device):
+    """The batch's device table (B,M,16) of `ops.pbf_obstacles`, validated on the host; None when no scene has an
+    obstacle (the substeps then launch nothing for them)."""
+    if not any(s.obstacles for s in scenes):
+        return None
+    return ops.pbf_obstacles([s.obstacles for s in scenes], len(scenes), device)
+
+
 def simulate(scenes, frames, substeps=SUBSTEPS, iters=ops.PBF_ITERS, params=None, device="cuda"):
     """`frames` exported frames of every scene, frame 0 being the start state and each further one 1/40 s later, made of
     `substeps` substeps of dt = 1 / (40 * substeps).  All scenes advance in the same launches; the frames stay on the
     device.  params: an `ops.PbfParams` (its `iters` wins); None: the defaults with `iters`, at the first scene's radius.
+    The scenes' obstacles go into one table, built once and passed to every substep.
     -> pos, vel (B, frames, N, 3) fp32, lengths (B,) int64 (rows beyond a scene's length are 0)."""
     if frames < 1 or substeps < 1:
         raise ValueError("frames and substeps must be >= 1")
     prm = params if params is not None else ops.PbfParams(radius=scenes[0].radius if scenes else ops.PBF_RADIUS, iters=iters)
     x, v, lengths, lo, hi = pack(scenes, torch.device(device))
+    table = obstacle_table(scenes, torch.device(device))
     B, N, _ = x.shape
     pos, vel = x.new_zeros((B, frames, N, 3)), x.new_zeros((B, frames, N, 3))
     dt = 1.0 / (FPS * substeps)
     for f in range(frames):
         if f:
             for _ in range(substeps):
-                x, v = ops.pbf_substep(x, v, lengths, lo, hi, dt, prm)
+                x, v = ops.pbf_substep(x, v, lengths, lo, hi, dt, prm, table)
         pos[:, f], vel[:, f] = x, v
     return pos, vel, lengths
+
+
+def obstacle_distance(obstacles, points):
+    """The signed distance (negative inside) of points (n,3) to the union of the obstacle dicts, exact per shape, in
+    the points' dtype on their device -> (n,)."""
+    best = torch.full(points.shape[:1], float("inf"), dtype=points.dtype, device=points.device)
+    for ob in obstacles:
+        t = lambda v: torch.tensor(v, dtype=points.dtype, device=points.device)  # noqa: E731
+        R = t(ob.get("rotation", np.eye(3).reshape(-1).tolist())).view(3, 3)
+        q = (points - t(ob["centre"])) @ R                                       # q_k = sum_i d_i R[i][k]
+        size = t(ob["size"]).reshape(-1)
+        if ob["shape"] == "ball":
+            d = q.norm(dim=1) - size[0]
+        else:
+            if ob["shape"] == "box":
+                e = q.abs() - size
+            else:
+                e = torch.stack([q[:, [0, 2]].norm(dim=1) - size[0], q[:, 1].abs() - size[1]], 1)
+            d = e.clamp(min=0).norm(dim=1) + e.amax(dim=1).clamp(max=0)
+        best = torch.minimum(best, d)
+    return best
+
+
+def obstacle_mesh(scene, step=None, device="cuda"):
+    """The surface of a scene's obstacles as a `mesh.Mesh` wound outward, to be loaded beside the fluid's meshes: the
+    union's signed distance, negated so that inside is positive, sampled on a lattice of `step` (default one particle
+    spacing) around the obstacles and meshed at level 0 by `ops.iso_surface`.  Linear interpolation of a distance field
+    puts the surface within one step of the true one; edges and corners are rounded at that scale."""
+    from . import mesh
+    ops._need(len(scene.obstacles) > 0, "the scene has no obstacles")
+    step = float(np.float32(2.0 * scene.radius if step is None else step))
+    ops._need(np.isfinite(step) and step > 0.0, "step must be positive and finite")
+    centres = np.array([o["centre"] for o in scene.obstacles], np.float64)
+    bounds = np.array([obstacle_bound(o) for o in scene.obstacles])[:, None]
+    lo, hi = (centres - bounds).min(0) - 2.0 * step, (centres + bounds).max(0) + 2.0 * step
+    shape = tuple(int(n) for n in np.ceil((hi - lo) / step).astype(np.int64) + 1)
+    ops._need(shape[0] * shape[1] * shape[2] <= mesh.MAX_NODES, f"a lattice of {shape} nodes is too large: raise step")
+    lattice = mesh.Lattice(lo.astype(np.float32), step, shape)
+    dev = torch.device(device)
+    axes = [torch.from_numpy(lattice.origin[a] + np.arange(shape[a], dtype=np.float32) * np.float32(step)).to(dev)
+            for a in range(3)]
+    nodes = torch.stack(torch.meshgrid(*axes, indexing="ij"), -1).reshape(-1, 3)
+    field = (-obstacle_distance(scene.obstacles, nodes)).reshape(shape).contiguous()
+    vertices, faces, nrm = ops.iso_surface(field, lattice.origin, step, 0.0, True)
+    return mesh.Mesh(vertices, faces, nrm, lattice, 0.0)
 
 
 def write_cases(out, scenes, first_case, frames, substeps, prm, device, settings):
@@ -178,6 +289,9 @@ def write_cases(out, scenes, first_case, frames, substeps, prm, device, settings
             np.savez(os.path.join(case, f"data_{s}.npz"), pos=pos[b, s, :n], vel=vel[b, s, :n])
         with open(os.path.join(case, "scene.json"), "w") as f:
             json.dump(dict(scene.to_json(), frames=frames, substeps=substeps, fps=FPS, params=prm.as_dict(), **settings), f)
+        if scene.obstacles:
+            from . import mesh
+            mesh.write_ply(os.path.join(case, "obstacles.ply"), obstacle_mesh(scene, device=device))
         print(json.dumps({"case": first_case + b, "dir": case, "particles": n, "frames": frames,
                           "seconds": round(seconds / len(scenes), 3), "batch": len(scenes)}), flush=True)
 
@@ -198,15 +312,23 @@ def main(argv=None):
     ap.add_argument("--body_size", type=float, default=BODY_SIZE, help="edge of the unscaled box body")
     ap.add_argument("--batch", type=int, default=8, help="scenes simulated together")
     ap.add_argument("--device", type=str, default="cuda")
+    ap.add_argument("--obstacles", type=int, default=0, help="static solids per scene (0 .. 3), in the lower half of the box")
+    ap.add_argument("--obstacle_size", type=float, nargs=2, default=list(OBSTACLE_SIZE),
+                    help="range of an obstacle's largest extent in metres")
     a = ap.parse_args(argv)
     if a.cases < 0 or a.test_cases < 0 or a.frames < 1 or a.batch < 1 or a.substeps < 1 or a.iters < 0:
         ap.error("--cases, --test_cases, --iters >= 0; --frames, --batch, --substeps >= 1")
+    if not 0 <= a.obstacles <= MAX_RANDOM_OBSTACLES or not 0 < a.obstacle_size[0] <= a.obstacle_size[1]:
+        ap.error(f"--obstacles 0 .. {MAX_RANDOM_OBSTACLES}; --obstacle_size 0 < LO <= HI")
     prm = ops.PbfParams(radius=a.particle_radius, iters=a.iters)
     settings = {"box": list(a.box), "body_size": a.body_size}
+    if a.obstacles:                                          # without obstacles scene.json holds what it always held
+        settings["obstacle_size"] = list(a.obstacle_size)
     # split 0: training, 1: held out -- the seed sequences (seed, split, case) can never coincide
     for split, (out, cases) in enumerate(((a.out, a.cases), (a.test_out, a.test_cases if a.test_out else 0))):
         for c0 in range(0, cases, a.batch):
-            scenes = [random_scene([a.seed, split, c], tuple(a.box), a.particle_radius, a.body_size)
+            scenes = [random_scene([a.seed, split, c], tuple(a.box), a.particle_radius, a.body_size, obstacles=a.obstacles,
+                                   obstacle_size=tuple(a.obstacle_size))
                       for c in range(c0, min(c0 + a.batch, cases))]
             write_cases(out, scenes, c0 + 1, a.frames, a.substeps, prm, a.device, settings)
     return 0
