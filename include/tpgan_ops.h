@@ -1058,6 +1058,109 @@ int tpg_aniso_field_exhaustive_f32(const float *query, const float *centres, con
                                    const int64_t *lenq, const int64_t *lenp, int B, int Nq, int Np, float support,
                                    float reach, float *sum, void *stream);
 
+/* ---- signed distance to a triangle mesh (csrc/mesh_sdf.hip) -------------------------------------------------------
+ * query (Q,3) f32, vertices (V,3) f32, faces (F,3) int32 -> dist (Q) f32, negative inside, and face (Q) int32, the
+ * nearest triangle.  Brute force over all triangles; no acceleration structure.  box: 6 HOST floats, lo xyz then hi xyz
+ * of the vertices' bounding box; inv_unit: 1 / unit, unit a power of two with unit >= (largest extent of the box) / 2^16
+ * (ops.mesh_sdf computes both from the vertices; the smallest such unit, 1 for a box of no extent).
+ * Every vertex index is clamped into [0, V-1] before use (faces are device values the entry cannot check).
+ *
+ * Skipped triangles.  With u = b - a, v = c - a per axis in fp32, a triangle whose fp32 normal
+ * (uy*vz - uz*vy, uz*vx - ux*vz, ux*vy - uy*vx) is exactly (0, 0, 0) is skipped, for the magnitude and for the sign.
+ *
+ * Magnitude.  fp32, each operation rounded on its own (no FMA), only + - * / and sqrtf; comparisons and selections are
+ * exact; dot(s, t) = (sx*tx + sy*ty) + sz*tz.  Per triangle (a, b, c) and query p, the closest point in region form:
+ *     ab = b - a, ac = c - a, ap = p - a, bp = p - b, cp = p - c
+ *     d1 = dot(ab, ap), d2 = dot(ac, ap), d3 = dot(ab, bp), d4 = dot(ac, bp), d5 = dot(ab, cp), d6 = dot(ac, cp)
+ *     vc = d1*d4 - d3*d2, vb = d5*d2 - d1*d6, va = d3*d6 - d5*d4, e43 = d4 - d3, e56 = d5 - d6
+ *   the closest point is a + v*ab + w*ac with (v, w) from the FIRST of these that holds:
+ *     vertex a   d1 <= 0 and d2 <= 0                      (0, 0)
+ *     vertex b   d3 >= 0 and d4 <= d3                     (1, 0)
+ *     edge ab    vc <= 0 and d1 >= 0 and d3 <= 0          (d1 / (d1 - d3), 0)
+ *     vertex c   d6 >= 0 and d5 <= d6                     (0, 1)
+ *     edge ac    vb <= 0 and d2 >= 0 and d6 <= 0          (0, d2 / (d2 - d6))
+ *     edge bc    va <= 0 and e43 >= 0 and e56 >= 0        t = e43 / (e43 + e56): (1 - t, t)
+ *     face       otherwise                                s = (va + vb) + vc: (vb / s, vc / s)
+ *   r_k = ap_k - (v*ab_k + w*ac_k) per axis;  dd = (rx*rx + ry*ry) + rz*rz.
+ * The result takes the smallest dd over the triangles that are not skipped, ties to the LOWEST face index (a NaN dd is
+ * never smaller), and dist = sqrtf(dd) once.  A (value, index) minimum does not depend on the order of execution: the
+ * same bits for any tiling.  No such triangle (all skipped, or every dd NaN): dist = +inf, face = -1.
+ *
+ * Sign, in exact integer arithmetic.  snap(x, axis) = floor((x - lo[axis]) * inv_unit + 0.5) in fp32, then clamped into
+ * [0, 2^16] (NaN: 0; the clamp changes nothing when box is the vertices' box), converted to an integer.
+ *   - A query is IN THE BOX iff lo <= p <= hi on every axis (a NaN coordinate is not); a query not in the box is outside.
+ *   - Otherwise Q = snap(p) and, per triangle that is not skipped, A, B, C = snap of its corners.
+ *     area = (By-Ay)*(Cz-Az) - (Bz-Az)*(Cy-Ay), the doubled area of the projection on the yz plane.  area == 0: the
+ *     triangle counts nothing.  area < 0: B and C are exchanged (the integer corners only), so that area > 0 below.
+ *     edge(U, V) = (Vy-Uy)*(Qz-Uz) - (Vz-Uz)*(Qy-Uy) for the edges (B,C), (C,A), (A,B).  The projection COVERS the query
+ *     iff for each edge:  edge > 0,  or edge == 0 and the edge owns its points: Vy-Uy > 0, or Vy-Uy == 0 and Vz-Uz > 0
+ *     (a half-open rule: of two triangles on opposite sides of a shared edge exactly one owns a point on it, two on the
+ *     same side both or neither; it is the coverage of the query moved by an infinitesimal (-eps^2, +eps) in (y, z)).
+ *     n = (B-A) x (C-A) in integers (nx = area);  det = (nx*(Qx-Ax) + ny*(Qy-Ay)) + nz*(Qz-Az).  The crossing lies strictly
+ *     AHEAD of the query in +x iff det < 0.
+ *     The triangle counts one iff it covers the query and lies ahead.  Coordinates are within [0, 2^16], so an edge
+ *     function is below 2^33 and det below 6 * 2^48: 64-bit integers (or float64) are exact.
+ *   - inside iff the count is odd;  dist = inside ? -sqrtf(dd) : sqrtf(dd).
+ * The sign is that of the SNAPPED query against the SNAPPED mesh and is meaningful for a closed mesh (every edge shared
+ * by two triangles; the orientation does not matter: parity).  Within about a unit of the surface it may differ from the
+ * sign in real coordinates; a query exactly on the surface gets whatever the rule above gives.
+ *
+ * Launch: one thread per query, 256 per workgroup, the triangles staged through LDS in tiles of 256.  Checks, all before
+ * the launch.  TPG_ERR_ARG: a NULL pointer, a negative Q, V or F, inv_unit not positive and finite, a box that is not
+ * finite or has lo > hi on an axis.  Then Q == 0: TPG_OK, nothing written.  Then F == 0, V == 0, or Q, V or F above
+ * 2^30: TPG_ERR_UNSUPPORTED. */
+int tpg_mesh_sdf_f32(const float *query, const float *vertices, const int32_t *faces, int Q, int V, int F,
+                     const float *box, float inv_unit, float *dist, int32_t *face, void *stream);
+
+/* ---- mesh obstacles in the particle fluid simulator (csrc/pbf.hip) --------------------------------------------------
+ * A static solid of any shape as a SAMPLED DISTANCE FIELD in the obstacle's own frame: a lattice of nx x ny x nz nodes,
+ * node (i,j,k) at origin + (i,j,k) * step, its value (signed distance, negative inside) at fields[offset +
+ * (i*ny + j)*nz + k].  One device buffer `fields` of fields_len floats holds every field; rows of any scene may share
+ * one at different poses.  A scene has up to PBF_MAX_SDF_OBSTACLES = 4 rows in a DEVICE table (B,M,24) of 32-bit words:
+ *     words 0..16   f32: kind (4.0f), cx, cy, cz, R00 .. R22 (row-major), ox, oy, oz (lattice origin), step
+ *     words 17..19  int32: nx, ny, nz
+ *     words 20..21  int64 (low word first): offset
+ *     words 22..23  unused
+ * The world position of a local point q is c + R q.  A row is SKIPPED unless ALL of these hold: kind == 4.0f; words
+ * 1..16 finite (|v| <= FLT_MAX); step > 0; 2 <= nx, ny, nz <= PBF_SDF_MAX_DIM = 4096; offset >= 0; offset + nx*ny*nz <=
+ * fields_len, evaluated in 64 bits as offset <= fields_len and nx*ny*nz <= fields_len - offset (nothing can wrap).  The
+ * table sits on the device and is not checked by the entry; every address derived from a table value is checked in the
+ * kernel before use, and the test is uniform over a workgroup.  (ops.pbf_sdf_obstacles validates on the host.)
+ *
+ * collide_sdf(p), per particle, the rows o = 0 .. M-1 IN INDEX ORDER, each on the position the one before left.  fp32,
+ * only + - * / and sqrtf, each rounded on its own (no FMA); with a the particle radius:
+ *   local frame   as collide: d = p - c;  q_k = (dx*R[0][k] + dy*R[1][k]) + dz*R[2][k]
+ *   lattice       g_k = (q_k - o_k) / step.  Unless 0 <= g_k <= (float)(n_k - 1) on all three axes the particle keeps
+ *                 its bits for this row (NaN included).
+ *   cell          i_k = min((int)floor(g_k), n_k - 2);  t_k = g_k - (float)i_k  (in [0, 1]; 1 on the last face)
+ *   trilinear     f_abc the value at node (ix+a, iy+b, iz+c):
+ *                 x_bc = f_1bc - f_0bc;  c_bc = f_0bc + tx*x_bc                      (bc = 00, 10, 01, 11)
+ *                 y_c = c_1c - c_0c;     c_c = c_0c + ty*y_c                         (c = 0, 1)
+ *                 gz = c_1 - c_0;        phi = c_0 + tz*gz
+ *   gradient      of the interpolant, in lattice units:
+ *                 gx_c = x_0c + ty*(x_1c - x_0c);  gx = gx_0 + tz*(gx_1 - gx_0);  gy = y_0 + tz*(y_1 - y_0)
+ *                 n2 = (gx*gx + gy*gy) + gz*gz
+ *   moved         iff phi < a (STRICT) and 0 < n2 <= FLT_MAX (a zero gradient leaves the particle):
+ *                 len = sqrtf(n2);  s = a - phi;  q_k = q_k + s*(g_k / len)     (g the gradient)
+ *   back          only a particle that moved: p_k = c_k + ((R[k][0]*qx + R[k][1]*qy) + R[k][2]*qz); bit o of hit.
+ *   at the end    the scene's box clamp, clamp(p, lo + a, hi - a), as collide.
+ * In a substep it is applied where collide is (after predict and after every dp), behind collide when both are given.
+ * Consequences: one Newton step on an interpolated field leaves a particle within the interpolation error of the skin
+ * phi = a, not on it; a particle outside the lattice is not seen, so the lattice must reach a beyond the surface; the
+ * thinness and wedge caveats of collide apply unchanged.
+ *
+ * tpg_pbf_collide_sdf_f32: p_out = collide_sdf(p); p_out may be p.  hit_out (B,N) int32 or NULL.  box: the HOST table of
+ * tpg_pbf_predict_f32.  One thread per particle, scenes in chunks of 64 per launch.  Rows at or beyond lengths[b] (taken
+ * as everywhere: min(max(lengths[b], 0), N)) are never read and never written.  Checks, all before anything is launched.
+ * TPG_ERR_ARG: negative B, N, M or fields_len, a not positive and finite, a NULL p_out.  Then B == 0 or N == 0: TPG_OK.
+ * Then B > 65535, N > 2^22 or M > PBF_MAX_SDF_OBSTACLES: TPG_ERR_UNSUPPORTED.  Then a NULL p or box, a bad box, a NULL
+ * table with M > 0, NULL fields with fields_len > 0: TPG_ERR_ARG.  M == 0 applies the clamp alone. */
+#define PBF_MAX_SDF_OBSTACLES 4
+#define PBF_SDF_MAX_DIM 4096
+int tpg_pbf_collide_sdf_f32(const float *p, const int64_t *lengths, const float *box, const float *table,
+                            const float *fields, long long fields_len, int B, int N, int M, float a, float *p_out,
+                            int32_t *hit_out, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

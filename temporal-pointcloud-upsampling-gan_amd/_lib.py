@@ -93,6 +93,8 @@ SIGNATURES = {
     "tpg_pbf_dp_f32": [_P, _P, _P, _P, _I, _I, _F, _F, _F, _F, _F, _P, _P, _P, _P],
     "tpg_pbf_finish_f32": [_P, _P, _P, _I, _I, _F, _F, _F, _P, _P, _P, _P],
     "tpg_pbf_collide_f32": [_P, _P, _P, _P, _I, _I, _I, _F, _P, _P, _P],
+    "tpg_pbf_collide_sdf_f32": [_P, _P, _P, _P, _P, _L, _I, _I, _I, _F, _P, _P, _P],
+    "tpg_mesh_sdf_f32": [_P, _P, _P, _I, _I, _I, _P, _F, _P, _P, _P],
     "tpg_iso_count_f32": [_P, _I, _I, _I, _F, _P, _P, _P],
     "tpg_iso_emit_f32": [_P, _I, _I, _I, _P, _F, _F, _P, _L, _L, _P, _P, _P, _P],
     "tpg_aniso_kernels_f32": [_P, _P, _I, _I, _F, _F, _F, _F, _F, _F, _F, _I, _I, _P, _P, _P, _P, _P, _P],

@@ -449,3 +449,101 @@ extern "C" int tpg_pbf_collide_f32(const float *p, const int64_t *lengths, const
     TPG_RETURN_IF_LAUNCH_FAILED();
     return TPG_OK;
 }
+
+// ---- mesh obstacles: sampled distance fields (the rule in full: include/tpgan_ops.h, "mesh obstacles"; the numpy
+// statement: tests/pbf_sdf_rule.py).  A launch kind of its own with collide's shape: one thread per particle, the M rows
+// of a scene at an address that depends on blockIdx.y alone, read before the kernel's only stores, so every branch on a
+// row is uniform over the workgroup.  Unlike collide, addresses DO depend on table values here (the field's offset and
+// dims): a row is used only after offset >= 0 and offset + nx*ny*nz <= fields_len have been checked in 64 bits, and a
+// particle reads its cell only after it has tested inside the lattice, so every index lies in [offset, offset + nx*ny*nz).
+// Eight gathered loads per particle and obstacle; no LDS, no atomics.
+namespace {
+
+constexpr int PBF_SDF_WORDS = 24;           // PBF_MAX_SDF_OBSTACLES, PBF_SDF_MAX_DIM: include/tpgan_ops.h
+
+__global__ __launch_bounds__(256) void pbf_collide_sdf_kernel(const float *p, const int64_t *__restrict__ lengths,
+                                                              PbfBoxes box, const float *__restrict__ table,
+                                                              const float *__restrict__ fields, long long fields_len,
+                                                              int b0, int N, int M, float a, float *p_out,
+                                                              int32_t *__restrict__ hit_out) {
+    const int b = b0 + blockIdx.y, i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= pbf_len(lengths, b, N)) return;
+    const size_t at = (size_t)b * N + i;
+    float px = p[at * 3], py = p[at * 3 + 1], pz = p[at * 3 + 2];
+    const float *__restrict__ row = table + (size_t)b * M * PBF_SDF_WORDS;
+    int hit = 0;
+    for (int o = 0; o < M; ++o, row += PBF_SDF_WORDS) {
+        float t[17];
+#pragma unroll
+        for (int j = 0; j < 17; ++j) t[j] = row[j];
+        const int nx = __float_as_int(row[17]), ny = __float_as_int(row[18]), nz = __float_as_int(row[19]);
+        const long long off = (long long)(((tpg_u64)(unsigned)__float_as_int(row[21]) << 32) |
+                                          (unsigned)__float_as_int(row[20]));
+        bool ok = t[0] == 4.0f && t[16] > 0.0f;
+#pragma unroll
+        for (int j = 1; j < 17; ++j) ok = ok && pbf_finite(t[j]);
+        ok = ok && nx >= 2 && ny >= 2 && nz >= 2 && nx <= PBF_SDF_MAX_DIM && ny <= PBF_SDF_MAX_DIM && nz <= PBF_SDF_MAX_DIM;
+        const long long cells = ok ? ((long long)nx * ny) * nz : 0;          // <= 2^36
+        ok = ok && off >= 0 && off <= fields_len && cells <= fields_len - off;
+        if (!ok) continue;
+        const float dx = px - t[1], dy = py - t[2], dz = pz - t[3];
+        float qx = (dx * t[4] + dy * t[7]) + dz * t[10];
+        float qy = (dx * t[5] + dy * t[8]) + dz * t[11];
+        float qz = (dx * t[6] + dy * t[9]) + dz * t[12];
+        const float gx = (qx - t[13]) / t[16], gy = (qy - t[14]) / t[16], gz = (qz - t[15]) / t[16];
+        const bool in = gx >= 0.0f && gx <= (float)(nx - 1) && gy >= 0.0f && gy <= (float)(ny - 1) && gz >= 0.0f &&
+                        gz <= (float)(nz - 1);
+        if (!in) continue;
+        const int ix = min((int)floorf(gx), nx - 2), iy = min((int)floorf(gy), ny - 2), iz = min((int)floorf(gz), nz - 2);
+        const float tx = gx - (float)ix, ty = gy - (float)iy, tz = gz - (float)iz;
+        const float *__restrict__ f = fields + off + ((long long)ix * ny + iy) * nz + iz;
+        const long long sx = (long long)ny * nz;
+        const float f000 = f[0], f001 = f[1], f010 = f[nz], f011 = f[nz + 1];
+        const float f100 = f[sx], f101 = f[sx + 1], f110 = f[sx + nz], f111 = f[sx + nz + 1];
+        const float x00 = f100 - f000, x10 = f110 - f010, x01 = f101 - f001, x11 = f111 - f011;
+        const float c00 = f000 + tx * x00, c10 = f010 + tx * x10, c01 = f001 + tx * x01, c11 = f011 + tx * x11;
+        const float y0 = c10 - c00, y1 = c11 - c01;
+        const float c0 = c00 + ty * y0, c1 = c01 + ty * y1;
+        const float gradz = c1 - c0;
+        const float phi = c0 + tz * gradz;
+        const float gradx0 = x00 + ty * (x10 - x00), gradx1 = x01 + ty * (x11 - x01);
+        const float gradx = gradx0 + tz * (gradx1 - gradx0);
+        const float grady = y0 + tz * (y1 - y0);
+        const float n2 = (gradx * gradx + grady * grady) + gradz * gradz;
+        const bool moved = phi < a && n2 > 0.0f && pbf_finite(n2);
+        if (moved) {
+            const float len = sqrtf(n2), s = a - phi;
+            qx = qx + s * (gradx / len), qy = qy + s * (grady / len), qz = qz + s * (gradz / len);
+            px = t[1] + ((t[4] * qx + t[5] * qy) + t[6] * qz);
+            py = t[2] + ((t[7] * qx + t[8] * qy) + t[9] * qz);
+            pz = t[3] + ((t[10] * qx + t[11] * qy) + t[12] * qz);
+            hit |= 1 << o;
+        }
+    }
+    p_out[at * 3] = pbf_clamp(px, box.c[blockIdx.y][0] + a, box.c[blockIdx.y][3] - a);
+    p_out[at * 3 + 1] = pbf_clamp(py, box.c[blockIdx.y][1] + a, box.c[blockIdx.y][4] - a);
+    p_out[at * 3 + 2] = pbf_clamp(pz, box.c[blockIdx.y][2] + a, box.c[blockIdx.y][5] - a);
+    if (hit_out) hit_out[at] = hit;
+}
+
+}  // namespace
+
+extern "C" int tpg_pbf_collide_sdf_f32(const float *p, const int64_t *lengths, const float *box, const float *table,
+                                       const float *fields, long long fields_len, int B, int N, int M, float a,
+                                       float *p_out, int32_t *hit_out, void *stream) {
+    if (M < 0 || fields_len < 0 || !pbf_pos(a) || !p_out) return TPG_ERR_ARG;
+    const int chk = pbf_shape(B, N);
+    if (chk && chk != TPG_ERR_UNSUPPORTED) return chk > 0 ? TPG_OK : chk;
+    if (chk || M > PBF_MAX_SDF_OBSTACLES) return TPG_ERR_UNSUPPORTED;
+    if (!p || !box || !pbf_box_ok(box, B) || (M > 0 && !table) || (fields_len > 0 && !fields)) return TPG_ERR_ARG;
+    hipStream_t st = tpg_stream(stream);
+    for (int b0 = 0; b0 < B; b0 += PBF_BOX_CHUNK) {
+        const int nb = min(PBF_BOX_CHUNK, B - b0);
+        PbfBoxes bx;
+        pbf_fill_boxes(bx, box, b0, nb);
+        hipLaunchKernelGGL(pbf_collide_sdf_kernel, dim3((N + 255) / 256, nb), dim3(256), 0, st, p, lengths, bx, table, fields,
+                           fields_len, b0, N, M, a, p_out, hit_out);
+    }
+    TPG_RETURN_IF_LAUNCH_FAILED();
+    return TPG_OK;
+}

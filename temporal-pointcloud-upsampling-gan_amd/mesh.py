@@ -210,14 +210,22 @@ def _host(mesh):
     return v, f, n
 
 
-def write_ply(path, mesh):
-    """Binary little-endian PLY: vertices x y z [nx ny nz] float, faces as `list uchar int`.  Standard library and numpy."""
+def write_ply(path, mesh, ascii=False):
+    """Binary little-endian PLY: vertices x y z [nx ny nz] float, faces as `list uchar int`.  Standard library and numpy.
+    ascii: the same file as text, nine significant digits, so that fp32 values read back unchanged."""
     v, f, n = _host(mesh)
     props = ["x", "y", "z"] + ([] if n is None else ["nx", "ny", "nz"])
-    header = ["ply", "format binary_little_endian 1.0", "comment tpgan_amd.mesh", f"element vertex {v.shape[0]}"]
+    header = ["ply", "format %s 1.0" % ("ascii" if ascii else "binary_little_endian"), "comment tpgan_amd.mesh",
+              f"element vertex {v.shape[0]}"]
     header += [f"property float {name}" for name in props]
     header += [f"element face {f.shape[0]}", "property list uchar int vertex_indices", "end_header"]
     rows = v if n is None else np.concatenate([v, n], axis=1)
+    if ascii:
+        with open(path, "w") as out:
+            out.write("\n".join(header) + "\n")
+            out.writelines(" ".join("%.9g" % x for x in row) + "\n" for row in rows.tolist())
+            out.writelines("3 %d %d %d\n" % tuple(row) for row in f.tolist())
+        return
     faces = np.empty(f.shape[0], dtype=[("count", "u1"), ("index", "<i4", (3,))])
     faces["count"] = 3
     faces["index"] = f
@@ -242,6 +250,159 @@ def write_obj(path, mesh):
 
 
 WRITERS = {"ply": write_ply, "obj": write_obj}
+
+
+# ---- meshes in: readers, a closedness check and two generators (what `ops.mesh_sdf` and `simulate` take) ------------
+def _obj_index(token, count):
+    i = int(token.split("/")[0])                             # v, v/vt, v//vn, v/vt/vn
+    return i - 1 if i > 0 else count + i                     # negative: relative to the vertices read so far
+
+
+def read_obj(path):
+    """Wavefront OBJ -> (vertices (V,3) float32, faces (F,3) int32): the `v` and `f` lines, everything else ignored.
+    Polygons are fanned about their first corner; `v/vt/vn` forms and negative (relative) indices are accepted."""
+    vertices, faces = [], []
+    with open(path) as src:
+        for line in src:
+            parts = line.split()
+            if not parts:
+                continue
+            if parts[0] == "v":
+                vertices.append([float(x) for x in parts[1:4]])
+            elif parts[0] == "f":
+                idx = [_obj_index(t, len(vertices)) for t in parts[1:]]
+                faces += [[idx[0], idx[k], idx[k + 1]] for k in range(1, len(idx) - 1)]
+    v = np.asarray(vertices, dtype=np.float32).reshape(-1, 3)
+    f = np.asarray(faces, dtype=np.int64).reshape(-1, 3)
+    ops._need(f.size == 0 or (int(f.min()) >= 0 and int(f.max()) < v.shape[0]), f"{path}: a face names a missing vertex")
+    return v, f.astype(np.int32)
+
+
+def read_ply(path):
+    """The triangle PLY files `write_ply` writes, binary little-endian or ASCII -> (vertices (V,3) float32, faces (F,3)
+    int32, normals (V,3) float32 or None): float vertex properties of which x y z [nx ny nz] are taken, faces as
+    `list uchar int` of three indices each."""
+    with open(path, "rb") as src:
+        ops._need(src.readline().strip() == b"ply", f"{path}: not a PLY file")
+        fmt, elements = None, []
+        while True:
+            line = src.readline()
+            ops._need(len(line) > 0, f"{path}: no end_header")
+            parts = line.decode("ascii").split()
+            if not parts or parts[0] in ("comment", "obj_info"):
+                continue
+            if parts[0] == "format":
+                fmt = parts[1]
+            elif parts[0] == "element":
+                elements.append((parts[1], int(parts[2]), []))
+            elif parts[0] == "property":
+                elements[-1][2].append(parts[1:])
+            elif parts[0] == "end_header":
+                break
+        ops._need(fmt in ("ascii", "binary_little_endian"), f"{path}: format {fmt} is not read")
+        ops._need([e[0] for e in elements] == ["vertex", "face"], f"{path}: expected the elements vertex, face")
+        (_, V, vprops), (_, F, fprops) = elements
+        ops._need(all(len(q) == 2 and q[0] in ("float", "float32") for q in vprops), f"{path}: vertex properties must be float")
+        ops._need(len(fprops) == 1 and fprops[0][:3] in (["list", "uchar", "int"], ["list", "uint8", "int32"]),
+                  f"{path}: faces must be `list uchar int`")
+        names = [q[1] for q in vprops]
+        if fmt == "ascii":
+            tokens = src.read().split()
+            rows = np.array(tokens[:V * len(names)], dtype=np.float64).astype(np.float32).reshape(V, len(names))
+            rest = np.array(tokens[V * len(names):V * len(names) + 4 * F], dtype=np.int64).reshape(F, 4)
+            counts, faces = rest[:, 0], rest[:, 1:]
+        else:
+            rows = np.frombuffer(src.read(4 * V * len(names)), dtype="<f4").reshape(V, len(names))
+            rec = np.frombuffer(src.read(13 * F), dtype=[("count", "u1"), ("index", "<i4", (3,))])
+            counts, faces = rec["count"], rec["index"]
+        ops._need(bool((np.asarray(counts) == 3).all()), f"{path}: every face must be a triangle")
+    col = lambda *want: np.ascontiguousarray(rows[:, [names.index(w) for w in want]], dtype=np.float32)  # noqa: E731
+    normals = col("nx", "ny", "nz") if all(w in names for w in ("nx", "ny", "nz")) else None
+    return col("x", "y", "z"), np.ascontiguousarray(faces, dtype=np.int32), normals
+
+
+def check_closed(vertices, faces):
+    """Counts that say whether `ops.mesh_sdf`'s sign means anything for a mesh -> dict:
+        boundary_edges      undirected edges used by exactly one face          (the sign needs 0)
+        nonmanifold_edges   undirected edges used by more than two faces       (the sign needs 0)
+        zero_normal_faces   faces whose fp32 normal is exactly zero            (skipped by the op; reported)
+        inconsistent_pairs  edges whose two faces run along them in the SAME direction (reported; parity does not care)"""
+    v = np.asarray(vertices, dtype=np.float32).reshape(-1, 3)
+    f = np.asarray(faces, dtype=np.int64).reshape(-1, 3)
+    e = np.concatenate([f[:, [0, 1]], f[:, [1, 2]], f[:, [2, 0]]])
+    key = np.minimum(e[:, 0], e[:, 1]) * (int(f.max(initial=0)) + 1) + np.maximum(e[:, 0], e[:, 1])
+    forward = (e[:, 0] < e[:, 1]).astype(np.int64)
+    uniq, inverse, counts = np.unique(key, return_inverse=True, return_counts=True)
+    fwd = np.bincount(inverse.reshape(-1), weights=forward, minlength=len(uniq))
+    u, w = v[f[:, 1]] - v[f[:, 0]], v[f[:, 2]] - v[f[:, 0]]
+    n = np.stack([u[:, 1] * w[:, 2] - u[:, 2] * w[:, 1], u[:, 2] * w[:, 0] - u[:, 0] * w[:, 2],
+                  u[:, 0] * w[:, 1] - u[:, 1] * w[:, 0]], 1)
+    return {"boundary_edges": int((counts == 1).sum()), "nonmanifold_edges": int((counts > 2).sum()),
+            "zero_normal_faces": int((n == 0).all(1).sum()),
+            "inconsistent_pairs": int(((counts == 2) & (fwd != 1)).sum())}
+
+
+def make_icosphere(subdivisions=2, radius=1.0):
+    """A closed sphere of 20 * 4^subdivisions triangles wound outward: the icosahedron, every triangle split in four and
+    the new vertices pushed onto the sphere -> (vertices (V,3) float32, faces (F,3) int32)."""
+    ops._need(0 <= int(subdivisions) <= 7, "subdivisions must be 0 .. 7")
+    t = (1.0 + 5.0 ** 0.5) / 2.0
+    v = [(-1, t, 0), (1, t, 0), (-1, -t, 0), (1, -t, 0), (0, -1, t), (0, 1, t), (0, -1, -t), (0, 1, -t), (t, 0, -1),
+         (t, 0, 1), (-t, 0, -1), (-t, 0, 1)]
+    v = [tuple(np.asarray(p, np.float64) / np.linalg.norm(p)) for p in v]
+    f = [(0, 11, 5), (0, 5, 1), (0, 1, 7), (0, 7, 10), (0, 10, 11), (1, 5, 9), (5, 11, 4), (11, 10, 2), (10, 7, 6),
+         (7, 1, 8), (3, 9, 4), (3, 4, 2), (3, 2, 6), (3, 6, 8), (3, 8, 9), (4, 9, 5), (2, 4, 11), (6, 2, 10), (8, 6, 7),
+         (9, 8, 1)]
+    for _ in range(int(subdivisions)):
+        mid, out = {}, []
+
+        def middle(a, b):
+            k = (min(a, b), max(a, b))
+            if k not in mid:
+                m = np.asarray(v[a]) + np.asarray(v[b])
+                v.append(tuple(m / np.linalg.norm(m)))
+                mid[k] = len(v) - 1
+            return mid[k]
+        for a, b, c in f:
+            ab, bc, ca = middle(a, b), middle(b, c), middle(c, a)
+            out += [(a, ab, ca), (b, bc, ab), (c, ca, bc), (ab, bc, ca)]
+        f = out
+    return (np.asarray(v, np.float64) * float(radius)).astype(np.float32), np.asarray(f, dtype=np.int32)
+
+
+def make_torus(R=0.5, r=0.2, nu=48, nv=24):
+    """A closed torus about the y axis, wound outward: centre circle of radius R in the xz plane, tube radius r, nu
+    segments around the axis and nv around the tube, 2 nu nv triangles -> (vertices (nu*nv,3) float32, faces int32)."""
+    ops._need(int(nu) >= 3 and int(nv) >= 3 and 0.0 < float(r) < float(R), "a torus needs nu, nv >= 3 and 0 < r < R")
+    nu, nv = int(nu), int(nv)
+    u = 2.0 * np.pi * np.arange(nu) / nu
+    w = 2.0 * np.pi * np.arange(nv) / nv
+    ring = R + r * np.cos(w)[None, :]
+    v = np.stack([ring * np.cos(u)[:, None], np.broadcast_to(r * np.sin(w)[None, :], (nu, nv)), ring * np.sin(u)[:, None]],
+                 -1).reshape(-1, 3)
+    i, j = np.meshgrid(np.arange(nu), np.arange(nv), indexing="ij")
+    a, b = i * nv + j, ((i + 1) % nu) * nv + j
+    c, d = ((i + 1) % nu) * nv + (j + 1) % nv, i * nv + (j + 1) % nv
+    f = np.concatenate([np.stack([a, d, c], -1).reshape(-1, 3), np.stack([a, c, b], -1).reshape(-1, 3)])
+    return v.astype(np.float32), f.astype(np.int32)
+
+
+def load_spec(spec):
+    """A mesh from a SPEC: a path to an .obj or .ply file, `icosphere:SUBDIVISIONS` or `torus:R,r,nu,nv` ->
+    (vertices (V,3) float32, faces (F,3) int32)."""
+    spec = str(spec)
+    kind, _, args = spec.partition(":")
+    if kind == "icosphere" and not os.path.exists(spec):
+        return make_icosphere(int(args) if args else 2)
+    if kind == "torus" and not os.path.exists(spec):
+        a = [x for x in args.split(",") if x]
+        ops._need(len(a) in (0, 4), "torus:R,r,nu,nv")
+        return make_torus(*((float(a[0]), float(a[1]), int(a[2]), int(a[3])) if a else ()))
+    ops._need(os.path.exists(spec), f"mesh spec {spec!r}: no such file, and not icosphere:N or torus:R,r,nu,nv")
+    if spec.lower().endswith(".obj"):
+        return read_obj(spec)
+    v, f, _ = read_ply(spec)
+    return v, f
 
 
 class SequenceMesher:

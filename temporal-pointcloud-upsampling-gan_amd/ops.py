@@ -415,26 +415,47 @@ class HipBackend:
                    _ptr(lengths), box.ctypes.data, _ptr(obstacles), B, N, obstacles.shape[1], prm.radius, _ptr(p_out),
                    _ptr(hit_out))
 
-    def pbf_substep(self, x, v, lengths, box, dt, prm, x_out, v_out, obstacles=None):
+    def pbf_collide_sdf(self, p, lengths, box, table, fields, prm, p_out, hit_out=None):
+        """p_out = collide_sdf(p) (p_out may be p): the mesh obstacles (B,M,24) in index order, then the box clamp."""
+        B, N, _ = p.shape
+        self._call("tpg_pbf_collide_sdf_f32", "pbf_collide_sdf", (24 + (4 if hit_out is not None else 0)) * B * N, p,
+                   _ptr(p), _ptr(lengths), box.ctypes.data, _ptr(table), _ptr(fields), fields.numel(), B, N, table.shape[1],
+                   prm.radius, _ptr(p_out), _ptr(hit_out))
+
+    def pbf_substep(self, x, v, lengths, box, dt, prm, x_out, v_out, obstacles=None, sdf_obstacles=None):
         """One substep of every scene: predict | iters x (grid | lambda | dp) | grid | finish.  x_out / v_out receive the
         rows below lengths; p and lambda are per-stream workspaces, the dp pass updates p in place.  obstacles (B,M,16):
-        a collide launch in place after predict and after every dp; None: no such launch."""
+        a collide launch in place after predict and after every dp; None: no such launch.  sdf_obstacles (table, fields):
+        a collide_sdf launch in the same places, behind collide; None: no such launch."""
         B, N, _ = x.shape
         ws = self.pbf_ws(x, B, N)
         p = self._workspace("pbf_p", x, B * N * 3)[:B * N * 3].view(B, N, 3)
         lam = self._workspace("pbf_lam", x, B * N)
+
+        def solids():
+            if obstacles is not None:
+                self.pbf_collide(p, lengths, box, obstacles, prm, p)
+            if sdf_obstacles is not None:
+                self.pbf_collide_sdf(p, lengths, box, sdf_obstacles[0], sdf_obstacles[1], prm, p)
         self.pbf_predict(x, v, lengths, box, dt, prm, p, v_out)
-        if obstacles is not None:
-            self.pbf_collide(p, lengths, box, obstacles, prm, p)
+        solids()
         for _ in range(prm.iters):
             self.pbf_grid(p, lengths, prm, ws)
             self.pbf_lambda(p, lengths, prm, ws, lam)
             self.pbf_dp(p, lam, lengths, box, prm, ws, p)
-            if obstacles is not None:
-                self.pbf_collide(p, lengths, box, obstacles, prm, p)
+            solids()
         self.pbf_grid(p, lengths, prm, ws)
         self.pbf_finish(p, x, lengths, dt, prm, ws, x_out, v_out)
         return x_out, v_out
+
+    # ---- signed distance to a triangle mesh (csrc/mesh_sdf.hip; the rule: include/tpgan_ops.h)
+    def mesh_sdf(self, query, vertices, faces, box, inv_unit):
+        Q, V, F = query.shape[0], vertices.shape[0], faces.shape[0]
+        dist = torch.empty(Q, dtype=torch.float32, device=query.device)
+        face = torch.empty(Q, dtype=torch.int32, device=query.device)
+        self._call("tpg_mesh_sdf_f32", "mesh_sdf", 20 * Q + 12 * (V + F), query, _ptr(query), _ptr(vertices), _ptr(faces),
+                   Q, V, F, box.ctypes.data, inv_unit, _ptr(dist), _ptr(face), flops=150 * Q * F)
+        return dist, face
 
     # ---- isosurfaces (csrc/isosurface.hip; the rule: include/tpgan_ops.h)
     def iso_count(self, field, iso):
@@ -2253,11 +2274,13 @@ def _pbf_collide_torch(p, lo, hi, table, prm, hit=None):
     return _pbf_clamp(torch.stack(P, 1), lo, hi, a)
 
 
-def _pbf_substep_torch(x, v, lengths, box, dt, prm, neighbours=_pbf_candidates_torch, obstacles=None):
+def _pbf_substep_torch(x, v, lengths, box, dt, prm, neighbours=_pbf_candidates_torch, obstacles=None,
+                       sdf_obstacles=None):
     """`pbf_substep` composed of torch ops, scene by scene: the same fp32 operations in the same order and the same
     fixed-point sums as csrc/pbf.hip (the rule: include/tpgan_ops.h), so the results are EQUAL to the kernels'.
     `neighbours(p, h) -> (i, j)` supplies candidate pairs (any superset of the pairs within h).  obstacles (B,M,16) or
-    None: collide after predict and after every dp."""
+    None: collide after predict and after every dp; sdf_obstacles (table (B,M,24), fields) or None: collide_sdf in the
+    same places, behind collide."""
     B, N, _ = x.shape
     x_out, v_out = x.clone(), v.clone()
     lens = [N] * B if lengths is None else [min(max(int(n), 0), N) for n in lengths.tolist()]
@@ -2269,14 +2292,17 @@ def _pbf_substep_torch(x, v, lengths, box, dt, prm, neighbours=_pbf_candidates_t
         lo, hi = torch.from_numpy(box[b, :3].copy()).to(x.device), torch.from_numpy(box[b, 3:].copy()).to(x.device)
         xb = x[b, :n]
         vb = v[b, :n] + f(dt) * torch.tensor(prm.gravity, dtype=torch.float32, device=x.device)
-        p = _pbf_clamp(xb + f(dt) * vb, lo, hi, f(prm.radius))
-        if obstacles is not None:
-            p = _pbf_collide_torch(p, lo, hi, obstacles[b], prm)
+        def solids(p):
+            if obstacles is not None:
+                p = _pbf_collide_torch(p, lo, hi, obstacles[b], prm)
+            if sdf_obstacles is not None:
+                p = _pbf_collide_sdf_torch(p, lo, hi, sdf_obstacles[0][b], sdf_obstacles[1], prm)
+            return p
+        p = solids(_pbf_clamp(xb + f(dt) * vb, lo, hi, f(prm.radius)))
         for _ in range(prm.iters):
             lam, _, pr = _pbf_lambda_torch(p, prm, neighbours)
             p, _ = _pbf_dp_torch(p, lam, pr, lo, hi, prm)
-            if obstacles is not None:
-                p = _pbf_collide_torch(p, lo, hi, obstacles[b], prm)
+            p = solids(p)
         v_out[b, :n] = _pbf_finish_torch(p, xb, dt, prm, neighbours)
         x_out[b, :n] = p
     return x_out, v_out
@@ -2376,7 +2402,7 @@ def pbf_collide(p, lengths, box_lo, box_hi, obstacles, params=None, return_hit=F
     return (out, hit) if return_hit else out
 
 
-def pbf_substep(x, v, lengths, box_lo, box_hi, dt, params=None, obstacles=None):
+def pbf_substep(x, v, lengths, box_lo, box_hi, dt, params=None, obstacles=None, sdf_obstacles=None):
     """One substep of the particle fluid simulator (Position Based Fluids, Jacobi, gather form; csrc/pbf.hip, the rule
     in full: include/tpgan_ops.h) for every scene of a ragged batch.
 
@@ -2384,7 +2410,8 @@ def pbf_substep(x, v, lengths, box_lo, box_hi, dt, params=None, obstacles=None):
     (the values stay on the device and are not checked: each counts as min(max(lengths[b], 0), N) of the int64 it is);
     box_lo, box_hi: HOST values, 3 shared by the batch or (B,3); dt > 0; params: a `PbfParams` (None: the defaults);
     obstacles: the device table (B,M,16) of `pbf_obstacles`: static solids, applied after predict and after every dp
-    pass (None: no obstacles, and no launch for them).
+    pass (None: no obstacles, and no launch for them); sdf_obstacles: the (table, fields) pair of `pbf_sdf_obstacles`:
+    mesh obstacles as sampled distance fields, applied in the same places behind the analytic ones (None: no launch).
     -> (x, v) new tensors.  Bit-identical from run to run, at every batch position, and equal to `_pbf_substep_torch`,
     which backends without the kernels run (CPU tensors need a registered checker, as everywhere).  No gradient."""
     _check_float(x, "x", 3)
@@ -2396,6 +2423,8 @@ def pbf_substep(x, v, lengths, box_lo, box_hi, dt, params=None, obstacles=None):
     if obstacles is not None:
         _pbf_check_obstacles(obstacles, x, B)
         obstacles = obstacles.detach()
+    if sdf_obstacles is not None:
+        sdf_obstacles = _pbf_check_sdf_obstacles(sdf_obstacles, x, B)
     prm = PbfParams() if params is None else params
     dt = float(_F32(dt))
     _need(np.isfinite(dt) and dt > 0.0, "dt must be positive and finite")
@@ -2403,9 +2432,331 @@ def pbf_substep(x, v, lengths, box_lo, box_hi, dt, params=None, obstacles=None):
     lengths = _lengths(lengths, B, N, x.device)
     be = backend_for(x)
     with torch.no_grad():
-        if hasattr(be, "pbf_substep"):
-            return be.pbf_substep(x.detach(), v.detach(), lengths, box, dt, prm, x.clone(), v.clone(), obstacles)
-        return _pbf_substep_torch(x.detach(), v.detach(), lengths, box, dt, prm, obstacles=obstacles)
+        if sdf_obstacles is None:                       # the calls of before, argument for argument
+            if hasattr(be, "pbf_substep"):
+                return be.pbf_substep(x.detach(), v.detach(), lengths, box, dt, prm, x.clone(), v.clone(), obstacles)
+            return _pbf_substep_torch(x.detach(), v.detach(), lengths, box, dt, prm, obstacles=obstacles)
+        if hasattr(be, "pbf_collide_sdf"):
+            return be.pbf_substep(x.detach(), v.detach(), lengths, box, dt, prm, x.clone(), v.clone(), obstacles,
+                                  sdf_obstacles)
+        # a backend without the new launch kind (the CPU checker): the whole substep as torch ops, with the backend's own
+        # neighbour search where it has one
+        return _pbf_substep_torch(x.detach(), v.detach(), lengths, box, dt, prm, obstacles=obstacles,
+                                  sdf_obstacles=sdf_obstacles)
+
+
+# ------------------------------------------------------------------------ mesh obstacles (csrc/pbf.hip)
+PBF_MAX_SDF_OBSTACLES = 4              # include/tpgan_ops.h
+PBF_SDF_MAX_DIM = 4096
+PBF_SDF_KIND = 4
+_PBF_SDF_WORDS = 24
+
+
+def _pbf_sdf_row_host(row):
+    """One table row (24 words, a float32 array) -> (floats[17], (nx, ny, nz), offset) with the integer words decoded."""
+    row = np.ascontiguousarray(row, dtype=np.float32)
+    words = row.view(np.int32)
+    offset = (int(words[21]) << 32) | (int(words[20]) & 0xFFFFFFFF)
+    return row[:17], (int(words[17]), int(words[18]), int(words[19])), offset
+
+
+def _pbf_sdf_row_ok(fl, dims, offset, fields_len):
+    with np.errstate(all="ignore"):
+        ok = float(fl[0]) == float(PBF_SDF_KIND) and bool((np.abs(fl[1:]) <= np.finfo(np.float32).max).all())
+    ok = ok and float(fl[16]) > 0.0 and all(2 <= n <= PBF_SDF_MAX_DIM for n in dims)
+    return ok and 0 <= offset <= fields_len and dims[0] * dims[1] * dims[2] <= fields_len - offset
+
+
+def _pbf_collide_sdf_torch(p, lo, hi, table, fields, prm, hit=None):
+    """collide_sdf of include/tpgan_ops.h ("mesh obstacles") for one cloud p (n,3) against the rows of table (M,24) and
+    the buffer fields (L,), in torch ops: the same fp32 operations in the same order as pbf_collide_sdf_kernel, so the
+    results are EQUAL to its.  hit: an int32 (n,) tensor that gains bit o for the particles row o moved -> the new p."""
+    f = lambda s: torch.tensor(s, dtype=torch.float32, device=p.device)          # noqa: E731
+    a = f(prm.radius)
+    rows = table.detach().cpu().numpy().reshape(-1, _PBF_SDF_WORDS)
+    fields = fields.reshape(-1)
+    P = [p[:, 0].clone(), p[:, 1].clone(), p[:, 2].clone()]
+    for o in range(rows.shape[0]):
+        fl, (nx, ny, nz), off = _pbf_sdf_row_host(rows[o])
+        if not _pbf_sdf_row_ok(fl, (nx, ny, nz), off, fields.numel()):
+            continue
+        t = torch.from_numpy(fl.copy()).to(p.device)
+        c, R, org, step = t[1:4], t[4:13].view(3, 3), t[13:16], t[16]
+        d = [P[0] - c[0], P[1] - c[1], P[2] - c[2]]
+        q = [(d[0] * R[0, k] + d[1] * R[1, k]) + d[2] * R[2, k] for k in range(3)]
+        g = [(q[k] - org[k]) / step for k in range(3)]
+        n = (nx, ny, nz)
+        inl = torch.ones_like(g[0], dtype=torch.bool)
+        for k in range(3):
+            inl &= (g[k] >= 0) & (g[k] <= float(n[k] - 1))
+        sel = torch.nonzero(inl).squeeze(1)
+        if sel.numel() == 0:
+            continue
+        q, g = [v[sel] for v in q], [v[sel] for v in g]
+        i = [torch.clamp(torch.floor(g[k]).long(), max=n[k] - 2) for k in range(3)]
+        tx, ty, tz = (g[k] - i[k].to(torch.float32) for k in range(3))
+        base = off + (i[0] * ny + i[1]) * nz + i[2]
+        F = lambda da, db, dc: fields[base + (da * ny + db) * nz + dc]             # noqa: E731
+        x00, x10, x01, x11 = F(1, 0, 0) - F(0, 0, 0), F(1, 1, 0) - F(0, 1, 0), F(1, 0, 1) - F(0, 0, 1), F(1, 1, 1) - F(0, 1, 1)
+        c00, c10, c01, c11 = F(0, 0, 0) + tx * x00, F(0, 1, 0) + tx * x10, F(0, 0, 1) + tx * x01, F(0, 1, 1) + tx * x11
+        y0, y1 = c10 - c00, c11 - c01
+        c0, c1 = c00 + ty * y0, c01 + ty * y1
+        gz = c1 - c0
+        phi = c0 + tz * gz
+        gx0, gx1 = x00 + ty * (x10 - x00), x01 + ty * (x11 - x01)
+        gx = gx0 + tz * (gx1 - gx0)
+        gy = y0 + tz * (y1 - y0)
+        n2 = (gx * gx + gy * gy) + gz * gz
+        moved = (phi < a) & (n2 > 0) & torch.isfinite(n2)
+        length = torch.sqrt(n2.double()).float()                                  # correctly rounded (see _PbfPairs)
+        s = a - phi
+        new = [q[0] + s * (gx / length), q[1] + s * (gy / length), q[2] + s * (gz / length)]
+        for k in range(3):
+            world = c[k] + ((R[k, 0] * new[0] + R[k, 1] * new[1]) + R[k, 2] * new[2])
+            P[k][sel] = torch.where(moved, world, P[k][sel])
+        if hit is not None:
+            hit[sel] |= moved.to(torch.int32) << o
+    return _pbf_clamp(torch.stack(P, 1), lo, hi, a)
+
+
+def _pbf_sdf_obstacle_row(ob, offsets, chunks, total):
+    _need(isinstance(ob, dict) and all(k in ob for k in ("field", "origin", "step", "centre")),
+          "a mesh obstacle is a dict with field, origin, step and centre")
+    field = ob["field"]
+    key = id(field)
+    if key not in offsets:
+        arr = field.detach().cpu().numpy() if isinstance(field, torch.Tensor) else np.asarray(field)
+        _need(arr.ndim == 3 and arr.dtype == np.float32, "a field is a float32 (nx,ny,nz) lattice")
+        _need(all(2 <= n <= PBF_SDF_MAX_DIM for n in arr.shape), f"a field has 2 .. {PBF_SDF_MAX_DIM} nodes per axis")
+        _need(bool(np.isfinite(arr).all()), "a field must be finite")
+        offsets[key] = (total[0], arr.shape)
+        chunks.append(np.ascontiguousarray(arr).reshape(-1))
+        total[0] += arr.size
+    offset, dims = offsets[key]
+    centre = np.asarray(ob["centre"], dtype=np.float64).reshape(-1)
+    rot = np.asarray(ob.get("rotation", np.eye(3)), dtype=np.float64).reshape(-1)
+    origin = np.asarray(ob["origin"], dtype=np.float64).reshape(-1)
+    _need(centre.size == 3 and rot.size == 9 and origin.size == 3, "centre and origin have 3 values, rotation 9")
+    row = np.zeros(_PBF_SDF_WORDS, np.float32)
+    row[0], row[1:4], row[4:13], row[13:16], row[16] = PBF_SDF_KIND, centre, rot, origin, ob["step"]
+    _need(bool(np.isfinite(row[:17]).all()) and row[16] > 0, "a mesh obstacle's values must be finite, its step positive")
+    R = rot.reshape(3, 3)
+    _need(float(np.abs(R @ R.T - np.eye(3)).max()) <= 1e-5, "an obstacle's rotation must be orthonormal within 1e-5")
+    words = row.view(np.int32)
+    words[17:20] = dims
+    words[20:22] = np.array([offset], dtype=np.int64).view(np.int32)
+    return row
+
+
+def pbf_sdf_obstacles(obstacles, B=None, device="cuda"):
+    """The device pair (table (B,M,24), fields (L,)) of include/tpgan_ops.h ("mesh obstacles") from obstacle dicts,
+    validated on the host: `field` (a float32 (nx,ny,nz) lattice of signed distances in the obstacle's frame, negative
+    inside: `mesh_sdf` at the nodes), `origin` (3: the position of node (0,0,0) in that frame), `step`, `centre` (3) and
+    `rotation` (9 values, row-major, default the identity).  Dicts that hold the SAME field object share one copy in
+    `fields`, at any number of poses.
+
+    obstacles: one list shared by the batch (B scenes, default 1) or one list per scene, padded with kind-0 rows; None:
+    M = 0.  Raises on a non-finite value, a step that is not positive, an extent outside 2 .. 4096, more than
+    PBF_MAX_SDF_OBSTACLES per scene, a rotation that is not orthonormal within 1e-5."""
+    obstacles = [] if obstacles is None else list(obstacles)
+    if all(isinstance(o, dict) for o in obstacles):
+        per_scene = [obstacles] * (1 if B is None else int(B))
+    else:
+        per_scene = [[] if o is None else list(o) for o in obstacles]
+        _need(B is None or int(B) == len(per_scene), "one obstacle list per scene")
+    M = max([len(s) for s in per_scene] + [0])
+    _need(M <= PBF_MAX_SDF_OBSTACLES, f"at most {PBF_MAX_SDF_OBSTACLES} mesh obstacles per scene")
+    table = np.zeros((len(per_scene), M, _PBF_SDF_WORDS), np.float32)
+    offsets, chunks, total = {}, [], [0]
+    for b, scene in enumerate(per_scene):
+        for o, ob in enumerate(scene):
+            table[b, o] = _pbf_sdf_obstacle_row(ob, offsets, chunks, total)
+    fields = np.concatenate(chunks) if chunks else np.zeros(0, np.float32)
+    return torch.from_numpy(table).to(device), torch.from_numpy(fields).to(device)
+
+
+def _pbf_check_sdf_obstacles(sdf_obstacles, ref, B):
+    _need(isinstance(sdf_obstacles, (tuple, list)) and len(sdf_obstacles) == 2, "sdf_obstacles is the pair (table, fields)")
+    table, fields = sdf_obstacles
+    _check_float(table, "table", 3)
+    _check_float(fields, "fields", 1)
+    _need(table.shape[0] == B and table.shape[2] == _PBF_SDF_WORDS, f"the table must be (B,M,{_PBF_SDF_WORDS})")
+    _need(table.shape[1] <= PBF_MAX_SDF_OBSTACLES, f"at most {PBF_MAX_SDF_OBSTACLES} mesh obstacles per scene")
+    _same_device(ref, table, fields)
+    return table.detach(), fields.detach()
+
+
+def pbf_collide_sdf(p, lengths, box_lo, box_hi, table, fields, params=None, return_hit=False):
+    """The simulator's collide_sdf launch kind on its own (include/tpgan_ops.h, "mesh obstacles"): every particle pushed
+    out of the sampled distance fields of its scene in index order, then clamped into the box.
+
+    p (B,N,3) fp32; lengths, box_lo, box_hi as in `pbf_substep`; table (B,M,24), fields (L,): the DEVICE pair of
+    `pbf_sdf_obstacles` (the values are not checked here: a row that fails the rule's tests is skipped in the kernel;
+    M = 0 applies the clamp alone); params: a `PbfParams` for the particle radius.
+    -> p (a new tensor; rows at or beyond lengths[b] come back unchanged), and with return_hit an int32 (B,N) whose bit o
+    is set iff row o moved the particle.  Equal to `_pbf_collide_sdf_torch`, which backends without the kernel run.  No
+    gradient."""
+    _check_float(p, "p", 3)
+    _need(p.shape[2] == 3, "p must be (B,N,3)")
+    B, N, _ = p.shape
+    _need(B <= 65535 and N <= PBF_MAX_N, f"at most 65535 scenes of {PBF_MAX_N} particles")
+    table, fields = _pbf_check_sdf_obstacles((table, fields), p, B)
+    prm = PbfParams() if params is None else params
+    box = pbf_box(box_lo, box_hi, B)
+    lengths = _lengths(lengths, B, N, p.device)
+    be = backend_for(p)
+    with torch.no_grad():
+        out = p.detach().clone()
+        hit = torch.zeros((B, N), dtype=torch.int32, device=p.device) if return_hit else None
+        if hasattr(be, "pbf_collide_sdf"):
+            be.pbf_collide_sdf(p.detach(), lengths, box, table, fields, prm, out, hit)
+        else:
+            lens = [N] * B if lengths is None else [min(max(int(n), 0), N) for n in lengths.tolist()]
+            for b, n in enumerate(lens):
+                lo, hi = torch.from_numpy(box[b, :3].copy()).to(p.device), torch.from_numpy(box[b, 3:].copy()).to(p.device)
+                out[b, :n] = _pbf_collide_sdf_torch(p[b, :n].detach(), lo, hi, table[b], fields, prm,
+                                                    None if hit is None else hit[b, :n])
+    return (out, hit) if return_hit else out
+
+
+# ------------------------------------------------------------------------ signed distance to a mesh (csrc/mesh_sdf.hip)
+MESH_SDF_GRID = 65536
+MESH_SDF_MAX = 1 << 30
+
+
+def mesh_sdf_grid(vertices):
+    """The snap grid of the sign (include/tpgan_ops.h) of HOST vertices (V,3) float32 -> (box (6,) float32: lo, hi;
+    inv_unit): unit the smallest power of two with unit >= largest extent / 2^16 (1 where the box has no extent)."""
+    v = np.asarray(vertices, dtype=np.float32).reshape(-1, 3)
+    _need(v.shape[0] > 0 and bool(np.isfinite(v).all()), "vertices must be finite and at least one")
+    lo, hi = v.min(0), v.max(0)
+    ext = float((hi.astype(np.float64) - lo.astype(np.float64)).max())
+    if ext == 0.0:
+        unit = 1.0
+    else:
+        m, e = np.frexp(ext / MESH_SDF_GRID)                 # ext / 2^16 = m * 2^e, 0.5 <= m < 1
+        unit = float(np.ldexp(1.0, int(e) - 1 if m == 0.5 else int(e)))
+    _need(2.0 ** -100 <= unit <= 2.0 ** 100, "the mesh's extent is outside what the snap grid holds")
+    return np.ascontiguousarray(np.concatenate([lo, hi]).astype(np.float32)), float(1.0 / unit)
+
+
+def _mesh_sdf_torch(query, vertices, faces, box, inv_unit, pairs_per_chunk=1 << 20):
+    """`mesh_sdf` as vectorised torch ops: the same fp32 operations in the same order and the same integer sign as
+    csrc/mesh_sdf.hip (the rule: include/tpgan_ops.h), so the results are EQUAL to the kernel's."""
+    dev = query.device
+    Q, F = query.shape[0], faces.shape[0]
+    V = vertices.shape[0]
+    lo = torch.from_numpy(np.asarray(box[:3], dtype=np.float32).copy()).to(dev)
+    hi = torch.from_numpy(np.asarray(box[3:], dtype=np.float32).copy()).to(dev)
+    iu = torch.tensor(inv_unit, dtype=torch.float32, device=dev)
+
+    def snap(x):                                            # (..., 3) f32 -> int64
+        t = torch.floor((x - lo) * iu + 0.5)
+        t = torch.where(t >= 0, t, torch.zeros_like(t))
+        t = torch.where(t <= float(MESH_SDF_GRID), t, torch.full_like(t, float(MESH_SDF_GRID)))
+        return t.long()
+
+    def dot(s, t):
+        return (s[..., 0] * t[..., 0] + s[..., 1] * t[..., 1]) + s[..., 2] * t[..., 2]
+    inbox = ((query >= lo) & (query <= hi)).all(1)
+    qi = torch.where(inbox.unsqueeze(1), snap(torch.where(inbox.unsqueeze(1), query, lo.expand_as(query))),
+                     torch.zeros((Q, 3), dtype=torch.int64, device=dev))
+    best = torch.full((Q,), float("inf"), dtype=torch.float32, device=dev)
+    best_f = torch.full((Q,), -1, dtype=torch.int64, device=dev)
+    count = torch.zeros((Q,), dtype=torch.int64, device=dev)
+    step = max(1, int(pairs_per_chunk) // max(Q, 1))
+    inf = torch.tensor(float("inf"), dtype=torch.float32, device=dev)
+    zero, one = torch.zeros((), dtype=torch.float32, device=dev), torch.ones((), dtype=torch.float32, device=dev)
+    P = query.unsqueeze(1)                                  # (Q,1,3)
+    for f0 in range(0, F, step):
+        fc = faces[f0:f0 + step].long().clamp(0, V - 1)
+        a, b, c = vertices[fc[:, 0]], vertices[fc[:, 1]], vertices[fc[:, 2]]            # (Fc,3)
+        u, w_ = b - a, c - a
+        valid = ~((u[:, 1] * w_[:, 2] - u[:, 2] * w_[:, 1] == 0) & (u[:, 2] * w_[:, 0] - u[:, 0] * w_[:, 2] == 0)
+                  & (u[:, 0] * w_[:, 1] - u[:, 1] * w_[:, 0] == 0))
+        # ---- the sign
+        A, B_, C_ = snap(a), snap(b), snap(c)
+        area = (B_[:, 1] - A[:, 1]) * (C_[:, 2] - A[:, 2]) - (B_[:, 2] - A[:, 2]) * (C_[:, 1] - A[:, 1])
+        swap = (area < 0).unsqueeze(1)
+        B_, C_ = torch.where(swap, C_, B_), torch.where(swap, B_, C_)
+        e1, e2 = B_ - A, C_ - A
+        nx = e1[:, 1] * e2[:, 2] - e1[:, 2] * e2[:, 1]
+        ny = e1[:, 2] * e2[:, 0] - e1[:, 0] * e2[:, 2]
+        nz = e1[:, 0] * e2[:, 1] - e1[:, 1] * e2[:, 0]
+        counts = valid & (area != 0)
+        qy, qz = qi[:, 1:2], qi[:, 2:3]                     # (Q,1)
+        covers = torch.ones((Q, fc.shape[0]), dtype=torch.bool, device=dev)
+        for U, W in ((B_, C_), (C_, A), (A, B_)):
+            dy, dz = W[:, 1] - U[:, 1], W[:, 2] - U[:, 2]
+            e = dy * (qz - U[:, 2]) - dz * (qy - U[:, 1])
+            own = (dy > 0) | ((dy == 0) & (dz > 0))
+            covers &= (e > 0) | ((e == 0) & own)
+        det = (nx * (qi[:, 0:1] - A[:, 0]) + ny * (qy - A[:, 1])) + nz * (qz - A[:, 2])
+        count += (covers & (det < 0) & counts & inbox.unsqueeze(1)).sum(1)
+        # ---- the magnitude
+        ab, ac = (b - a).unsqueeze(0), (c - a).unsqueeze(0)                 # (1,Fc,3)
+        ap, bp, cp = P - a, P - b, P - c                                    # (Q,Fc,3)
+        d1, d2, d3, d4, d5, d6 = dot(ab, ap), dot(ac, ap), dot(ab, bp), dot(ac, bp), dot(ab, cp), dot(ac, cp)
+        vc, vb, va = d1 * d4 - d3 * d2, d5 * d2 - d1 * d6, d3 * d6 - d5 * d4
+        e43, e56 = d4 - d3, d5 - d6
+        sm = (va + vb) + vc
+        v, w = vb / sm, vc / sm
+        rbc = (va <= 0) & (e43 >= 0) & (e56 >= 0)
+        wbc = e43 / (e43 + e56)
+        v, w = torch.where(rbc, one - wbc, v), torch.where(rbc, wbc, w)
+        rac = (vb <= 0) & (d2 >= 0) & (d6 <= 0)
+        v, w = torch.where(rac, zero, v), torch.where(rac, d2 / (d2 - d6), w)
+        rc = (d6 >= 0) & (d5 <= d6)
+        v, w = torch.where(rc, zero, v), torch.where(rc, one, w)
+        rab = (vc <= 0) & (d1 >= 0) & (d3 <= 0)
+        v, w = torch.where(rab, d1 / (d1 - d3), v), torch.where(rab, zero, w)
+        rb = (d3 >= 0) & (d4 <= d3)
+        v, w = torch.where(rb, one, v), torch.where(rb, zero, w)
+        ra = (d1 <= 0) & (d2 <= 0)
+        v, w = torch.where(ra, zero, v), torch.where(ra, zero, w)
+        r = ap - (v.unsqueeze(2) * ab + w.unsqueeze(2) * ac)
+        dd = dot(r, r)
+        dd = torch.where(valid.unsqueeze(0) & ~torch.isnan(dd), dd, inf)
+        val = dd.amin(1)
+        ids = torch.arange(f0, f0 + fc.shape[0], device=dev)
+        first = torch.where(dd == val.unsqueeze(1), ids.unsqueeze(0), torch.full_like(ids, F).unsqueeze(0)).amin(1)
+        better = val < best
+        best, best_f = torch.where(better, val, best), torch.where(better, first, best_f)
+    d = torch.sqrt(best.double()).float()                   # correctly rounded (see _PbfPairs)
+    return torch.where(count % 2 == 1, -d, d), best_f.to(torch.int32)
+
+
+def mesh_sdf(query, vertices, faces):
+    """The signed distance from every query point to a triangle mesh, brute force over all triangles (csrc/mesh_sdf.hip;
+    the rule in full: include/tpgan_ops.h): the exact closest point on every triangle in fp32, the sign by ray parity in
+    exact integer arithmetic on a 2^16 snap grid over the mesh's box.
+
+    query (Q,3) f32, vertices (V,3) f32, faces (F,3) int32, one device.  -> (dist (Q,) f32, negative inside;
+    face (Q,) int32, the nearest triangle, ties to the lowest).  The sign needs a CLOSED mesh (`mesh.check_closed`); its
+    orientation does not matter.  Triangles whose fp32 normal is exactly zero are skipped; if all are, dist = +inf and
+    face = -1.  One host read (the mesh: faces in range, finite vertices, the bounding box): the op is meant to be called
+    once per mesh, not per frame.  Equal to `_mesh_sdf_torch`, which backends without the kernel run (CPU tensors need a
+    registered checker).  No gradient."""
+    _check_float(query, "query", 2)
+    _check_float(vertices, "vertices", 2)
+    _check_int(faces, "faces", 2)
+    _need(query.shape[1] == 3 and vertices.shape[1] == 3 and faces.shape[1] == 3, "query, vertices and faces are (., 3)")
+    _same_device(query, vertices, faces)
+    Q, V, F = query.shape[0], vertices.shape[0], faces.shape[0]
+    _need(V > 0 and F > 0, "a mesh needs vertices and faces")
+    _need(max(Q, V, F) <= MESH_SDF_MAX, "at most 2^30 queries, vertices or faces")
+    be = backend_for(query)
+    vh, fh = vertices.detach().cpu().numpy(), faces.detach().cpu().numpy()
+    _need(bool(np.isfinite(vh).all()), "vertices must be finite")
+    _need(int(fh.min()) >= 0 and int(fh.max()) < V, "a face names a vertex that does not exist")
+    box, inv_unit = mesh_sdf_grid(vh)
+    if Q == 0:
+        return (torch.zeros(0, dtype=torch.float32, device=query.device),
+                torch.zeros(0, dtype=torch.int32, device=query.device))
+    with torch.no_grad():
+        if hasattr(be, "mesh_sdf"):
+            return be.mesh_sdf(query.detach(), vertices.detach(), faces.detach(), box, inv_unit)
+        return _mesh_sdf_torch(query.detach(), vertices.detach(), faces.detach(), box, inv_unit)
 
 
 # ------------------------------------------------------------------------ isosurfaces (csrc/isosurface.hip)

@@ -3,12 +3,16 @@
     python -m tpgan_amd.simulate --out DATA --cases 20 --frames 200 --seed 1 [--test_out TEST --test_cases 4]
         [--particle_radius 0.0125 --substeps 4 --iters 4 --box 3 2.5 3 --body_size 0.68 --batch 8 --device cuda]
         [--obstacles 2 --obstacle_size 0.3 0.6]
+        [--fluid_mesh SPEC ... --obstacle_mesh SPEC ...]          SPEC: a .obj / .ply path, icosphere:3, torus:0.5,0.2,48,24
 
 writes `DATA/case{c}/data_{s}.npz` (`pos`, `vel`: float32 (N,3)) for c = 1.., s = 0.., the layout `data.FluidSequences`
 and `python -m tpgan_amd.train --train_dataset_path DATA` read, and `DATA/case{c}/scene.json` beside them.
 --obstacles K puts K static solids (ball, box, cylinder; `ops.pbf_collide`, the rule: include/tpgan_ops.h, "solid
 obstacles") into the lower half of every scene; `scene.json` records them and `DATA/case{c}/obstacles.ply` is their
-surface (`obstacle_mesh`), to be loaded beside the fluid's meshes.
+surface (`obstacle_mesh`), to be loaded beside the fluid's meshes.  --fluid_mesh / --obstacle_mesh add closed triangle
+meshes to the shapes the bodies / the obstacles are drawn from: a mesh body is filled with the lattice nodes at least a
+particle radius inside it (`ops.mesh_sdf`), a mesh obstacle is its distance field sampled once per batch
+(`ops.pbf_sdf_obstacles`, the rule: include/tpgan_ops.h, "mesh obstacles").
 
 The reference makes these directories with an external solver (fluid_data_generation/ drives SPlisHSPlasH's DFSPH on
 scenes from create_physics_scenes.py, with models it does not ship).  Here the solver is the project's own: Position
@@ -39,12 +43,47 @@ SHAPES = ("box", "ball", "cylinder")
 OBSTACLE_SIZE = (0.3, 0.6)             # range of an obstacle's largest extent (edge, diameter, height) in metres
 MAX_RANDOM_OBSTACLES = 3
 MIN_OBSTACLE_SPACINGS = 4.0            # no obstacle thinner than this many particle spacings (tunnelling: tpgan_ops.h)
+MESH = "mesh"                          # the shape of a body or obstacle given by a triangle mesh (its "mesh": a SPEC)
+_MESHES = {}                           # SPEC -> (vertices centred on their box, faces, extents): read and checked once
+
+
+def mesh_geometry(spec, size):
+    """The closed mesh of `spec` (`mesh.load_spec`) in its own frame: its bounding box centred on the origin and scaled so
+    that the box's largest extent is `size` -> (vertices (V,3) float32, faces (F,3) int32, half extents (3,) float64).
+    Raises on a mesh with boundary or non-manifold edges: the distance's sign needs a closed one."""
+    from . import mesh
+    if spec not in _MESHES:
+        v, f = mesh.load_spec(spec)
+        ops._need(v.shape[0] > 0 and f.shape[0] > 0, f"mesh {spec!r} is empty")
+        report = mesh.check_closed(v, f)
+        ops._need(report["boundary_edges"] == 0 and report["nonmanifold_edges"] == 0,
+                  f"mesh {spec!r} is not closed: {report}")
+        lo, hi = v.astype(np.float64).min(0), v.astype(np.float64).max(0)
+        ops._need(float((hi - lo).max()) > 0.0, f"mesh {spec!r} has no extent")
+        _MESHES[spec] = (v.astype(np.float64) - 0.5 * (lo + hi), f, hi - lo)
+    v, f, extent = _MESHES[spec]
+    scale = float(size) / float(extent.max())
+    return (v * scale).astype(np.float32), f, 0.5 * extent * scale
+
+
+def _scene_device(device=None):
+    return torch.device(device if device is not None else ("cuda" if torch.cuda.is_available() else "cpu"))
+
+
+def mesh_distance(spec, size, points, device=None):
+    """`ops.mesh_sdf` of local points (n,3) against the mesh of `mesh_geometry(spec, size)` -> (n,) float32 tensor on
+    `device` (default: the GPU when there is one; CPU tensors need a registered checker, as everywhere)."""
+    dev = _scene_device(device)
+    v, f, _ = mesh_geometry(spec, size)
+    q = torch.as_tensor(points, dtype=torch.float32).to(dev).contiguous()
+    return ops.mesh_sdf(q, torch.from_numpy(v).to(dev), torch.from_numpy(f).to(dev))[0]
 
 
 class Scene:
     """A box and the fluid in it at t = 0.  `bodies`: dicts of shape, size (the scaled edge), rotation (3x3, row-major),
     centre and velocity, from which `particles()` rebuilds the same points; or explicit `pos` / `vel` (n,3).
-    `obstacles`: the static solids in the box, dicts as `ops.pbf_obstacles` takes them (shape, centre, rotation, size)."""
+    `obstacles`: the static solids in the box, dicts as `ops.pbf_obstacles` takes them (shape, centre, rotation, size).
+    A body or obstacle of shape "mesh" names its triangle mesh in "mesh" (a SPEC); its size is the largest extent."""
 
     def __init__(self, box_lo, box_hi, bodies=(), seed=None, radius=ops.PBF_RADIUS, pos=None, vel=None, obstacles=()):
         self.box_lo = [float(v) for v in box_lo]
@@ -77,8 +116,11 @@ class Scene:
         return cls(d["box_lo"], d["box_hi"], d["bodies"], d["seed"], d["particle_radius"], obstacles=d.get("obstacles", ()))
 
 
-def body_half_extent(shape, size):
-    """Half extents of the body's own frame (x, y, z); ball and cylinder have about the box's volume."""
+def body_half_extent(shape, size, spec=None):
+    """Half extents of the body's own frame (x, y, z); ball and cylinder have about the box's volume; a mesh (spec: its
+    SPEC) has its bounding box's."""
+    if shape == MESH:
+        return mesh_geometry(spec, size)[2]
     if shape == "box":
         return np.array([size / 2, size / 2, size / 2])
     if shape == "ball":
@@ -86,12 +128,17 @@ def body_half_extent(shape, size):
     return np.array([0.5 * size, 0.64 * size, 0.5 * size])     # cylinder: radius, half height, radius
 
 
-def body_points(body, spacing):
-    """The lattice points of spacing `spacing` inside the body, rotated and moved to its centre -> (n,3) float64."""
-    half = body_half_extent(body["shape"], body["size"])
+def body_points(body, spacing, device=None):
+    """The lattice points of spacing `spacing` inside the body, rotated and moved to its centre -> (n,3) float64.  Of a
+    mesh body: the nodes in the mesh's box whose signed distance (`ops.mesh_sdf`, on `device`) is <= -spacing / 2, so that
+    every particle's sphere lies inside the mesh."""
+    half = body_half_extent(body["shape"], body["size"], body.get("mesh"))
     axes = [np.arange(-np.floor(e / spacing), np.floor(e / spacing) + 1) * spacing for e in half]
     g = np.stack(np.meshgrid(*axes, indexing="ij"), -1).reshape(-1, 3)
-    if body["shape"] == "ball":
+    if body["shape"] == MESH:
+        d = mesh_distance(body["mesh"], body["size"], g, device).cpu().numpy()
+        g = g[d <= -np.float32(0.5 * spacing)]
+    elif body["shape"] == "ball":
         g = g[(g ** 2).sum(1) <= half[0] ** 2]
     elif body["shape"] == "cylinder":
         g = g[g[:, 0] ** 2 + g[:, 2] ** 2 <= half[0] ** 2]
@@ -107,16 +154,20 @@ def _random_rotation(rng):
 
 
 def obstacle_bound(ob):
-    """The radius of an obstacle's bounding sphere about its centre."""
+    """The radius of an obstacle's bounding sphere about its centre (a mesh: of its bounding box)."""
+    if ob["shape"] == MESH:
+        return float(np.linalg.norm(mesh_geometry(ob["mesh"], ob["size"])[2]))
     size = np.atleast_1d(np.asarray(ob["size"], np.float64))
     return float(size[0]) if ob["shape"] == "ball" else float(np.linalg.norm(size))
 
 
-def random_obstacles(rng, count, box, spacing, size_range=OBSTACLE_SIZE, max_tries=1000):
+def random_obstacles(rng, count, box, spacing, size_range=OBSTACLE_SIZE, max_tries=1000, meshes=(), mesh_rng=None):
     """`count` obstacle dicts drawn from `rng`: a ball, box or cylinder whose largest extent is U(size_range) metres (a
     ball's diameter; a box's longest edge, the others U(0.6, 1) of it; a cylinder's height, its diameter U(0.6, 1) of it),
     rotated at random, the centre in the lower half of the box [0, box] and at least a bounding radius from the walls, no
-    two bounding spheres overlapping.  An obstacle thinner than MIN_OBSTACLE_SPACINGS particle spacings is never drawn."""
+    two bounding spheres overlapping.  An obstacle thinner than MIN_OBSTACLE_SPACINGS particle spacings is never drawn.
+    meshes: SPECs that join the three shapes; whether a draw becomes one of them is decided by `mesh_rng`, a generator of
+    its own, AFTER the draw's values have been taken from `rng`: without meshes `rng` gives what it always gave."""
     out, spheres = [], []
     for _ in range(max_tries):
         if len(out) == count:
@@ -127,9 +178,15 @@ def random_obstacles(rng, count, box, spacing, size_range=OBSTACLE_SIZE, max_tri
         rot = _random_rotation(rng)
         size = {"ball": half, "box": [half, half * thin[0], half * thin[1]], "cylinder": [half * thin[0], half]}[shape]
         ob = {"shape": shape, "size": size, "rotation": rot.reshape(-1).tolist()}
+        thinnest = 2.0 * float(np.min(size))
+        if meshes:
+            k = int(mesh_rng.integers(0, len(SHAPES) + len(meshes)))
+            if k >= len(SHAPES):
+                ob = {"shape": MESH, "mesh": meshes[k - len(SHAPES)], "size": 2.0 * half, "rotation": rot.reshape(-1).tolist()}
+                thinnest = 2.0 * float(mesh_geometry(ob["mesh"], ob["size"])[2].min())
         bound = obstacle_bound(ob)
         top = np.array([box[0] - bound, 0.5 * box[1], box[2] - bound])
-        if 2.0 * float(np.min(size)) < MIN_OBSTACLE_SPACINGS * spacing or (top < bound).any():
+        if thinnest < MIN_OBSTACLE_SPACINGS * spacing or (top < bound).any():
             continue
         centre = rng.uniform(bound, top)
         if all(np.linalg.norm(centre - c) >= bound + b for c, b in spheres):
@@ -141,7 +198,7 @@ def random_obstacles(rng, count, box, spacing, size_range=OBSTACLE_SIZE, max_tri
 
 
 def random_scene(seed, box=DEFAULT_BOX, radius=ops.PBF_RADIUS, body_size=BODY_SIZE, count_range=None, max_tries=1000,
-                 obstacles=0, obstacle_size=OBSTACLE_SIZE):
+                 obstacles=0, obstacle_size=OBSTACLE_SIZE, fluid_meshes=(), obstacle_meshes=()):
     """The scene of `seed` (an int or a sequence of ints), everything drawn from numpy.random.default_rng(seed): one to
     three bodies, each a box, ball or upright cylinder of `body_size` scaled by U(0.5, 1.5) and rotated at random, placed
     by rejection so that the bodies' bounding spheres stay a particle spacing apart and inside the box, thrown with a
@@ -149,7 +206,11 @@ def random_scene(seed, box=DEFAULT_BOX, radius=ops.PBF_RADIUS, body_size=BODY_SI
     (from the same generator) until the particle count lies in it; None: COUNT_RANGE for the default box and body size,
     no condition otherwise.  obstacles: 0 to 3 static solids (`random_obstacles`), drawn first and from a generator of
     their OWN (the seed's sequence with spawn key 1), so that the fluid's draws are those of the scene without obstacles;
-    a body is then also rejected unless its bounding sphere stays a spacing clear of every obstacle's."""
+    a body is then also rejected unless its bounding sphere stays a spacing clear of every obstacle's.
+    fluid_meshes / obstacle_meshes: SPECs of closed triangle meshes that join the shapes bodies / obstacles are drawn from.
+    Which draw becomes a mesh is decided by generators of their own (spawn keys 2 and 3) after the draw has taken its
+    values, so that without these options every seed gives the scene it gave, draw for draw."""
+    fluid_meshes, obstacle_meshes = [str(m) for m in fluid_meshes], [str(m) for m in obstacle_meshes]
     if not 0 <= int(obstacles) <= MAX_RANDOM_OBSTACLES:
         raise ValueError(f"obstacles must be 0 .. {MAX_RANDOM_OBSTACLES}")
     rng = np.random.default_rng(seed)
@@ -160,15 +221,22 @@ def random_scene(seed, box=DEFAULT_BOX, radius=ops.PBF_RADIUS, body_size=BODY_SI
     solids = []
     if obstacles:
         own = np.random.default_rng(np.random.SeedSequence(seed, spawn_key=(1,)))
-        solids = random_obstacles(own, int(obstacles), box, spacing, obstacle_size)
+        pick = np.random.default_rng(np.random.SeedSequence(seed, spawn_key=(3,))) if obstacle_meshes else None
+        solids = random_obstacles(own, int(obstacles), box, spacing, obstacle_size, meshes=obstacle_meshes, mesh_rng=pick)
     keep_out = [(np.asarray(o["centre"]), obstacle_bound(o)) for o in solids]
+    pick = np.random.default_rng(np.random.SeedSequence(seed, spawn_key=(2,))) if fluid_meshes else None
     for _ in range(max_tries):
         bodies, spheres = [], []
         for _ in range(int(rng.integers(1, 4))):
             shape = SHAPES[int(rng.integers(0, 3))]
             size = float(body_size * rng.uniform(0.5, 1.5))
             rot = _random_rotation(rng)
-            bound = float(np.linalg.norm(body_half_extent(shape, size))) + spacing
+            spec = None
+            if fluid_meshes:
+                k = int(pick.integers(0, len(SHAPES) + len(fluid_meshes)))
+                if k >= len(SHAPES):
+                    shape, spec = MESH, fluid_meshes[k - len(SHAPES)]
+            bound = float(np.linalg.norm(body_half_extent(shape, size, spec))) + spacing
             velocity = [float(rng.uniform(-2, 2)), float(rng.uniform(-0.5, 0.5)), float(rng.uniform(-2, 2))]
             for _ in range(100):
                 if (2 * bound >= box).any():
@@ -178,6 +246,8 @@ def random_scene(seed, box=DEFAULT_BOX, radius=ops.PBF_RADIUS, body_size=BODY_SI
                     spheres.append((centre, bound))
                     bodies.append({"shape": shape, "size": size, "rotation": rot.reshape(-1).tolist(),
                                    "centre": centre.tolist(), "velocity": velocity})
+                    if spec is not None:
+                        bodies[-1]["mesh"] = spec
                     break
         seed_out = seed if isinstance(seed, (int, np.integer)) else [int(s) for s in seed]
         scene = Scene([0.0, 0.0, 0.0], box.tolist(), bodies, seed_out, radius, obstacles=solids)
@@ -203,41 +273,80 @@ def pack(scenes, device):
 def obstacle_table(scenes, device):
     """The batch's device table (B,M,16) of `ops.pbf_obstacles`, validated on the host; None when no scene has an
     obstacle (the substeps then launch nothing for them)."""
-    if not any(s.obstacles for s in scenes):
+    analytic = [[o for o in s.obstacles if o["shape"] != MESH] for s in scenes]
+    if not any(analytic):
         return None
-    return ops.pbf_obstacles([s.obstacles for s in scenes], len(scenes), device)
+    return ops.pbf_obstacles(analytic, len(scenes), device)
+
+
+def sdf_obstacle_table(scenes, device, step=None):
+    """The batch's mesh obstacles as the device pair (table (B,M,24), fields) of `ops.pbf_sdf_obstacles`; None when no
+    scene has one.  Every distinct (mesh, size) is sampled ONCE, by `ops.mesh_sdf` at the nodes of a lattice of `step`
+    (default: the particle radius) that reaches a radius and two steps beyond the mesh's box, and shared by every
+    obstacle of the batch that uses it, at any pose."""
+    if not any(o["shape"] == MESH for s in scenes for o in s.obstacles):
+        return None
+    dev = torch.device(device)
+    fields, per_scene = {}, []
+    for s in scenes:
+        rows = []
+        for o in s.obstacles:
+            if o["shape"] != MESH:
+                continue
+            h = float(np.float32(s.radius if step is None else step))
+            key = (o["mesh"], float(o["size"]), h, float(s.radius))
+            if key not in fields:
+                half = mesh_geometry(o["mesh"], o["size"])[2]
+                reach = half + (s.radius + 2.0 * h)
+                origin = (-reach).astype(np.float32)
+                dims = tuple(int(n) for n in np.ceil((reach - origin.astype(np.float64)) / h).astype(np.int64) + 1)
+                axes = [torch.from_numpy(origin[a] + np.arange(dims[a], dtype=np.float32) * np.float32(h)).to(dev)
+                        for a in range(3)]
+                nodes = torch.stack(torch.meshgrid(*axes, indexing="ij"), -1).reshape(-1, 3).contiguous()
+                fields[key] = (mesh_distance(o["mesh"], o["size"], nodes, dev).view(dims), origin, h)
+            field, origin, h = fields[key]
+            rows.append({"field": field, "origin": origin, "step": h, "centre": o["centre"],
+                         "rotation": o.get("rotation", np.eye(3).reshape(-1).tolist())})
+        per_scene.append(rows)
+    return ops.pbf_sdf_obstacles(per_scene, len(scenes), dev)
 
 
 def simulate(scenes, frames, substeps=SUBSTEPS, iters=ops.PBF_ITERS, params=None, device="cuda"):
     """`frames` exported frames of every scene, frame 0 being the start state and each further one 1/40 s later, made of
     `substeps` substeps of dt = 1 / (40 * substeps).  All scenes advance in the same launches; the frames stay on the
     device.  params: an `ops.PbfParams` (its `iters` wins); None: the defaults with `iters`, at the first scene's radius.
-    The scenes' obstacles go into one table, built once and passed to every substep.
+    The scenes' obstacles go into one table, built once and passed to every substep; mesh obstacles into a table and a
+    field buffer of their own (`sdf_obstacle_table`), also built once.
     -> pos, vel (B, frames, N, 3) fp32, lengths (B,) int64 (rows beyond a scene's length are 0)."""
     if frames < 1 or substeps < 1:
         raise ValueError("frames and substeps must be >= 1")
     prm = params if params is not None else ops.PbfParams(radius=scenes[0].radius if scenes else ops.PBF_RADIUS, iters=iters)
     x, v, lengths, lo, hi = pack(scenes, torch.device(device))
     table = obstacle_table(scenes, torch.device(device))
+    sdf = sdf_obstacle_table(scenes, torch.device(device))
+    extra = {} if sdf is None else {"sdf_obstacles": sdf}    # without mesh obstacles: the call of before
     B, N, _ = x.shape
     pos, vel = x.new_zeros((B, frames, N, 3)), x.new_zeros((B, frames, N, 3))
     dt = 1.0 / (FPS * substeps)
     for f in range(frames):
         if f:
             for _ in range(substeps):
-                x, v = ops.pbf_substep(x, v, lengths, lo, hi, dt, prm, table)
+                x, v = ops.pbf_substep(x, v, lengths, lo, hi, dt, prm, table, **extra)
         pos[:, f], vel[:, f] = x, v
     return pos, vel, lengths
 
 
 def obstacle_distance(obstacles, points):
     """The signed distance (negative inside) of points (n,3) to the union of the obstacle dicts, exact per shape, in
-    the points' dtype on their device -> (n,)."""
+    the points' dtype on their device -> (n,).  A mesh obstacle's is `ops.mesh_sdf` of the points in its frame (fp32)."""
     best = torch.full(points.shape[:1], float("inf"), dtype=points.dtype, device=points.device)
     for ob in obstacles:
         t = lambda v: torch.tensor(v, dtype=points.dtype, device=points.device)  # noqa: E731
         R = t(ob.get("rotation", np.eye(3).reshape(-1).tolist())).view(3, 3)
         q = (points - t(ob["centre"])) @ R                                       # q_k = sum_i d_i R[i][k]
+        if ob["shape"] == MESH:
+            best = torch.minimum(best, mesh_distance(ob["mesh"], ob["size"], q.float(), points.device).to(points.dtype))
+            continue
         size = t(ob["size"]).reshape(-1)
         if ob["shape"] == "ball":
             d = q.norm(dim=1) - size[0]
@@ -315,7 +424,13 @@ def main(argv=None):
     ap.add_argument("--obstacles", type=int, default=0, help="static solids per scene (0 .. 3), in the lower half of the box")
     ap.add_argument("--obstacle_size", type=float, nargs=2, default=list(OBSTACLE_SIZE),
                     help="range of an obstacle's largest extent in metres")
+    ap.add_argument("--fluid_mesh", type=str, nargs="*", default=[], metavar="SPEC",
+                    help="closed meshes that join the shapes bodies are drawn from: a .obj/.ply path, icosphere:N, torus:R,r,nu,nv")
+    ap.add_argument("--obstacle_mesh", type=str, nargs="*", default=[], metavar="SPEC",
+                    help="closed meshes that join the shapes obstacles are drawn from (needs --obstacles >= 1)")
     a = ap.parse_args(argv)
+    if a.obstacle_mesh and not a.obstacles:
+        ap.error("--obstacle_mesh adds shapes to the obstacles' draw: give --obstacles 1 .. 3 as well")
     if a.cases < 0 or a.test_cases < 0 or a.frames < 1 or a.batch < 1 or a.substeps < 1 or a.iters < 0:
         ap.error("--cases, --test_cases, --iters >= 0; --frames, --batch, --substeps >= 1")
     if not 0 <= a.obstacles <= MAX_RANDOM_OBSTACLES or not 0 < a.obstacle_size[0] <= a.obstacle_size[1]:
@@ -324,11 +439,16 @@ def main(argv=None):
     settings = {"box": list(a.box), "body_size": a.body_size}
     if a.obstacles:                                          # without obstacles scene.json holds what it always held
         settings["obstacle_size"] = list(a.obstacle_size)
+    if a.fluid_mesh:
+        settings["fluid_mesh"] = list(a.fluid_mesh)
+    if a.obstacle_mesh:
+        settings["obstacle_mesh"] = list(a.obstacle_mesh)
     # split 0: training, 1: held out -- the seed sequences (seed, split, case) can never coincide
     for split, (out, cases) in enumerate(((a.out, a.cases), (a.test_out, a.test_cases if a.test_out else 0))):
         for c0 in range(0, cases, a.batch):
             scenes = [random_scene([a.seed, split, c], tuple(a.box), a.particle_radius, a.body_size, obstacles=a.obstacles,
-                                   obstacle_size=tuple(a.obstacle_size))
+                                   obstacle_size=tuple(a.obstacle_size), fluid_meshes=a.fluid_mesh,
+                                   obstacle_meshes=a.obstacle_mesh)
                       for c in range(c0, min(c0 + a.batch, cases))]
             write_cases(out, scenes, c0 + 1, a.frames, a.substeps, prm, a.device, settings)
     return 0
