@@ -736,3 +736,389 @@ def small_tail_bwd_ref(h, out_sign, gout, arg, W1, W2, s1, s2, K, h_w=None):
 def small_stored_bound(ref, E, bf16):
     """A stored row value: within E of ref in fp32, then one round-to-nearest-even to bf16 of that value."""
     return E + BF16_REL * (ref.abs() + E) if bf16 else E
+
+
+# ---- fused BatchNorm + LeakyReLU (+ max over K) on rows (csrc/rowbn.hip): geometry, per-launch restatements, bounds --
+# The launcher's tunables, copied: a retuned constant must be copied here too, and tests/test_rowbn_cpu.py then
+# re-asserts which launch edge each case of tests/rowbn_cases.py still reaches.
+TPG_BN_THREADS = 256          # csrc/rowbn.hip, BN_THREADS
+TPG_BN_MAX_BLOCKS = 256       # csrc/rowbn.hip
+TPG_BN_STATS_ROWS = 8         # csrc/rowbn.hip
+TPG_BN_YRED_ROWS = 4          # csrc/rowbn.hip
+TPG_BN_STATS_U = 8            # csrc/rowbn.hip
+TPG_BN_APPLY_CAP = 256        # csrc/rowbn.hip
+TPG_BN_APPLY_ROWS = 8         # csrc/rowbn.hip
+TPG_BN_GROUP_CAP = 512        # csrc/rowbn.hip
+TPG_BN_UNROLL = 4             # csrc/rowbn.hip
+TPG_BN_BWD_U = 2              # csrc/rowbn.hip
+TPG_BN_SEG_DIV = 4            # csrc/rowbn.hip
+TPG_BN_FIN_R = 8              # csrc/tpg_bn_finalize.hpp, FIN_R
+ROWBN_SAFETY = 2.0            # second-order terms of the first-order bounds below, once (as SMALL_SAFETY)
+
+
+def _bn_row_blocks(rows, rpi, per_thread, cap):
+    return max(1, min(cap, -(-rows // (rpi * per_thread))))
+
+
+def _bn_seg_blocks(blocks, nseg):
+    return max(1, -(-blocks // min(nseg, TPG_BN_SEG_DIV)))
+
+
+def _bn_group_cap(nseg, cap_div):
+    return (2 * TPG_BN_GROUP_CAP if nseg <= 3 else TPG_BN_GROUP_CAP) // cap_div
+
+
+def _bn_group_unroll(K):
+    return 4 if K % 4 == 0 else (2 if K % 2 == 0 else 1)
+
+
+def _bn_group_runs(Gp, K, cpr, nseg, room):
+    L = 1
+    while K % (2 * L) == 0 and (K // (2 * L)) % 4 == 0 and Gp * L * cpr * nseg < 65536 and \
+            (room == 0 or Gp * 2 * L <= room):
+        L *= 2
+    return L
+
+
+def _bn_split(nseg):
+    sp = 1
+    while sp < nseg and sp < 64:
+        sp <<= 1
+    return sp, 64 // sp
+
+
+def _is_bf16(dt):
+    return dt in (torch.bfloat16, "bf16")
+
+
+def rowbn_geometry(P, K, C, dtype_in, dtype_other, nseg=1):
+    """The integer decisions of tpg_rowbn_fwd / tpg_rowbn_bwd (csrc/rowbn.hip: row_blocks, stats_blocks, seg_blocks,
+    group_cap, group_unroll, group_runs with the forward's `room`; csrc/tpg_bn_finalize.hpp: split, pair_sums) for P
+    rows per segment.  dtype_other: the output's type for the forward, the arriving gradient's for the backward.
+    -> dict: *_stats the statistics walk (the INPUT type's vector width), the others the apply / backward walks:
+    ne, cpr (chunks per row), rpi (rows per workgroup iteration), idle (threads of a workgroup without a column chunk),
+    G_stats / G_bwd (workgroups = partials per segment of the reductions), fin_L (lanes per segment of a finalize
+    wave) and fin_blocks_* (trips of pair_sums' outer loop), L_* (runs per group), U_* (rows per pipeline stage),
+    grid_* (workgroups per segment of the streaming launch), per_* = (fewest, most) rows (K = 0: statistics, apply,
+    reduce), groups (max-variant reduce) or runs (max-variant apply) a thread that has any walks."""
+    bf_in, bf_any = _is_bf16(dtype_in), _is_bf16(dtype_in) or _is_bf16(dtype_other)
+    ne_s, ne = (8 if bf_in else 4), (8 if bf_any else 4)
+    assert C > 0 and C % ne == 0 and C // 4 <= TPG_BN_THREADS and 0 <= K <= 256 and (K == 0 or P % K == 0)
+    cpr_s, cpr = C // ne_s, C // ne
+    rpi_s, rpi = TPG_BN_THREADS // cpr_s, TPG_BN_THREADS // cpr
+    cap_div = min(nseg, TPG_BN_SEG_DIV)
+    sp, fl = _bn_split(nseg)
+
+    def per(rows, threads):
+        return (rows // threads if rows >= threads else 1, -(-rows // threads))
+    G_stats = _bn_seg_blocks(_bn_row_blocks(P, rpi_s, TPG_BN_STATS_ROWS, TPG_BN_MAX_BLOCKS), nseg)
+    rows_g = P // K if K else P
+    G_bwd = _bn_seg_blocks(_bn_row_blocks(rows_g, rpi, TPG_BN_YRED_ROWS if K else TPG_BN_STATS_ROWS,
+                                          TPG_BN_MAX_BLOCKS), nseg)
+    if K:
+        L_fwd = _bn_group_runs(rows_g, K, cpr, nseg, TPG_BN_MAX_BLOCKS * 8 // 5)
+        L_bwd = _bn_group_runs(rows_g, K, cpr, nseg, 0)
+        grid_fwd = _bn_row_blocks(rows_g * L_fwd, rpi, 1, _bn_group_cap(nseg, cap_div))
+        grid_bwd = _bn_row_blocks(rows_g * L_bwd, rpi, 1, _bn_group_cap(nseg, cap_div))
+        U_fwd, U_bwd = _bn_group_unroll(K // L_fwd), _bn_group_unroll(K // L_bwd)
+        per_fwd, per_bwd = per(rows_g * L_fwd, grid_fwd * rpi), per(rows_g * L_bwd, grid_bwd * rpi)
+    else:
+        L_fwd = L_bwd = 1
+        grid_fwd = grid_bwd = _bn_row_blocks(P, rpi, TPG_BN_APPLY_ROWS, TPG_BN_APPLY_CAP // cap_div)
+        U_fwd, U_bwd = TPG_BN_UNROLL, TPG_BN_BWD_U
+        per_fwd = per_bwd = per(P, grid_fwd * rpi)
+    return dict(P=P, K=K, C=C, nseg=nseg, ne_stats=ne_s, cpr_stats=cpr_s, rpi_stats=rpi_s,
+                idle_stats=TPG_BN_THREADS - cpr_s * rpi_s, G_stats=G_stats, per_stats=per(P, G_stats * rpi_s),
+                fin_SP=sp, fin_L=fl, fin_blocks_stats=-(-G_stats // (fl * TPG_BN_FIN_R)),
+                ne=ne, cpr=cpr, rpi=rpi, idle=TPG_BN_THREADS - cpr * rpi, G_bwd=G_bwd,
+                per_reduce=per(rows_g, G_bwd * rpi), fin_blocks_bwd=-(-G_bwd // (fl * TPG_BN_FIN_R)),
+                L_fwd=L_fwd, L_bwd=L_bwd, U_fwd=U_fwd, U_bwd=U_bwd, grid_fwd=grid_fwd, grid_bwd=grid_bwd,
+                per_fwd=per_fwd, per_bwd=per_bwd)
+
+
+def _bn_partials(t, G, rpi, ar):
+    """Per-workgroup partial column sums of the rows t (n, C) as the reduction kernels take them: thread (workgroup b,
+    rsub) adds its rows b*rpi + rsub + j*G*rpi in ascending order into one fp32 accumulator, block_column_reduce adds
+    the rpi accumulators of a column in ascending rsub -> (G, C).  (A missing row adds +0: exact.)"""
+    n, C = t.shape
+    step = G * rpi
+    J = -(-n // step)
+    if J * step != n:
+        t = torch.cat([t, torch.zeros(J * step - n, C, dtype=t.dtype, device=t.device)])
+    t = t.view(J, G, rpi, C)
+    acc = torch.zeros_like(t[0])
+    for j in range(J):
+        acc = ar.add(acc, t[j])
+    s = torch.zeros_like(acc[:, 0])
+    for r in range(rpi):
+        s = ar.add(s, acc[:, r])
+    return s
+
+
+def _bn_consts(C, nseg, mean, rstd, gamma, beta, like):
+    """mean / rstd (nseg or 1, C) or None, gamma / beta (C) or None -> float64 mu, rs (nseg, C), gm, b (C): absent
+    constants read as the kernels' ld_consts defaults (0, 1, 1, 0)."""
+    mu = torch.zeros(1, C, dtype=torch.float64, device=like.device) if mean is None else _f64(mean, like).reshape(-1, C)
+    rs = torch.ones(1, C, dtype=torch.float64, device=like.device) if rstd is None else _f64(rstd, like).reshape(-1, C)
+    gm = torch.ones(C, dtype=torch.float64, device=like.device) if gamma is None else _f64(gamma, like)
+    b = torch.zeros(C, dtype=torch.float64, device=like.device) if beta is None else _f64(beta, like)
+    return mu.expand(nseg, C), rs.expand(nseg, C), gm, b
+
+
+def rowbn_stats_ref(x, nseg, eps, momentum, dtype_in, running_mean=None, running_var=None, num_batches_tracked=None,
+                    mean_shift=None, ar=FP32):
+    """rowbn_stats_kernel + rowbn_stats_finalize_kernel: x (nseg*P, C) -> dict(mean, rstd (nseg, C), running_mean,
+    running_var (C) after the chain over the segments in call order, num_batches_tracked, and per segment the
+    magnitudes S1 = sum |d|, S2 = sum d^2, m = sum d / P, var of the bound).  d = x - pivot (the segment's first row)
+    and d*d round once each, the sums are _bn_partials, everything from the partials on is fp64 as in the kernel
+    (the ORDER of the fp64 additions is not restated: 2^-53 relative), mean = fp32(pivot + m),
+    rstd = fp32(1 / sqrt(var + eps)), running = fp32((1 - momentum) * running + momentum * new) with the unbiased
+    variance for P > 1.  ar = FP64: the same algebra, no rounding.  eps and momentum are the launch's C floats."""
+    x = _f64(x)
+    N, C = x.shape
+    P = N // nseg
+    geo = rowbn_geometry(P, 0, C, dtype_in, dtype_in, nseg)
+    G, rpi = geo["G_stats"], geo["rpi_stats"]
+    eps, mom = slope32(eps), slope32(momentum)
+    rm = None if running_mean is None else _f64(running_mean, x).clone()
+    rv = None if running_var is None else _f64(running_var, x).clone()
+    sh = 0.0 if mean_shift is None else _f64(mean_shift, x)
+    out = {k: [] for k in ("mean", "rstd", "S1", "S2", "m", "var", "mean64")}
+    for s in range(nseg):
+        xs = x[s * P:(s + 1) * P]
+        piv = xs[0]
+        d = ar.sub(xs, piv[None])
+        dd = ar.mul(d, d)
+        p0, p1 = _bn_partials(d, G, rpi, ar), _bn_partials(dd, G, rpi, ar)
+        m = p0.sum(0) / P
+        var = (p1.sum(0) / P - m * m).clamp_min(0.0)
+        pm = piv + m
+        out["mean"].append(ar.r(pm))
+        out["rstd"].append(ar.r(1.0 / torch.sqrt(var + eps)))
+        out["mean64"].append(pm)
+        out["S1"].append(d.abs().sum(0))
+        out["S2"].append(dd.sum(0))
+        out["m"].append(m)
+        out["var"].append(var)
+        if rm is not None:
+            unbiased = var * P / (P - 1) if P > 1 else var
+            rm = ar.r((1.0 - mom) * rm + mom * (pm + sh))
+            rv = ar.r((1.0 - mom) * rv + mom * unbiased)
+    out = {k: torch.stack(v) for k, v in out.items()}
+    out.update(running_mean=rm, running_var=rv, geo=geo, P=P, eps=eps, momentum=mom,
+               num_batches_tracked=None if num_batches_tracked is None else int(num_batches_tracked) + nseg)
+    return out
+
+
+def rowbn_stats_bound(ref, running_mean=None, running_var=None):
+    """|kernel - FP64 twin| of mean, rstd (nseg, C) and the running statistics (C), from the twin `ref` =
+    rowbn_stats_ref(..., ar=FP64) alone.  h = rows per thread + rpi LDS additions (_bn_partials' chain), fp64 after.
+      sum d   : each d rounds once (u |d|), the chain adds h u sum |d|                  -> Em = (h + 1) u S1 / P
+      sum d^2 : d's rounding twice, the product once, the chain                        -> Ess = (h + 3) u S2 / P
+      var = ss/P - m^2                                                                 -> Ev = Ess + 2 |m| Em
+      mean = fp32(pivot + m): Em + u |mean|;  rstd is monotone in var: the larger one-sided change of
+      (var +- Ev + eps)^-1/2 (var - Ev clamped at 0, as the kernel clamps), + u rstd for its rounding
+      running' = fp32((1 - mom) running + mom new): E' = (1 - mom) E + mom E_new + u |running'| along the chain, the
+      unbiased variance scaling Ev by P / (P - 1).
+    u = ROWBN_SAFETY * 2^-24."""
+    geo, P, eps, mom = ref["geo"], ref["P"], ref["eps"], ref["momentum"]
+    u = ROWBN_SAFETY * U32
+    h = geo["per_stats"][1] + geo["rpi_stats"]
+    Em = (h + 1) * u * ref["S1"] / P
+    Ev = (h + 3) * u * ref["S2"] / P + 2.0 * ref["m"].abs() * Em
+    var, rstd = ref["var"], ref["rstd"]
+    up = 1.0 / torch.sqrt((var - Ev).clamp_min(0.0) + eps) - rstd
+    dn = rstd - 1.0 / torch.sqrt(var + Ev + eps)
+    out = dict(mean=Em + u * ref["mean"].abs(), rstd=torch.maximum(up, dn) + u * rstd, h=h)
+    if running_mean is not None:
+        rm, rv = _f64(running_mean, var), _f64(running_var, var)
+        sc = P / (P - 1) if P > 1 else 1.0
+        Erm, Erv = torch.zeros_like(rm), torch.zeros_like(rv)
+        for s in range(var.shape[0]):
+            rm = (1.0 - mom) * rm + mom * ref["mean64"][s]          # magnitudes only: mean_shift moves no bound
+            rv = (1.0 - mom) * rv + mom * var[s] * sc
+            Erm = (1.0 - mom) * Erm + mom * Em[s] + u * (rm.abs() + Erm)
+            Erv = (1.0 - mom) * Erv + mom * Ev[s] * sc + u * (rv.abs() + Erv)
+        out.update(running_mean=Erm, running_var=Erv)
+    return out
+
+
+def _bn_z(xs, mu, a, b, ar):
+    """bn_z of csrc/rowbn.hip: (v - mu) * a + beta, each operation rounded once."""
+    return ar.add(ar.mul(ar.sub(xs, mu), a), b)
+
+
+def rowbn_apply_ref(x, K, mean, rstd, gamma, beta, slope, nseg=1, ar=FP32):
+    """rowbn_apply_kernel / rowbn_apply_max_kernel (+ rowbn_max_combine_kernel) with GIVEN statistics: a = gamma * rstd,
+    z = bn_z, v = z > 0 ? z : z * slope, all (nseg*P, C); K > 0: y = max over each group of K rows, arg = the FIRST
+    maximum (lowest k; the runs of a cut group and the first-run-wins combine define the same) -> dict(z, v, y, arg):
+    y before the store's rounding (rowbn_stored).  The slope is the launch's C float."""
+    x = _f64(x)
+    N, C = x.shape
+    P = N // nseg
+    mu, rs, gm, b = _bn_consts(C, nseg, mean, rstd, gamma, beta, x)
+    a = ar.mul(gm[None], rs)
+    z = _bn_z(x, _rows(mu, P), _rows(a, P), b[None], ar)
+    s = slope32(slope)
+    v = torch.where(z > 0, z, ar.mul(z, s))
+    if not K:
+        return dict(z=z, v=v, y=v, arg=None, a=a)
+    vk = v.view(N // K, K, C)
+    y = vk.max(1)[0]
+    ks = torch.arange(K, device=x.device)[None, :, None]
+    arg = torch.where(vk == y[:, None], ks, K).min(1)[0].to(torch.uint8)
+    return dict(z=z, v=v, y=y, arg=arg, a=a)
+
+
+def rowbn_stored(v, bf16):
+    """A row element as the kernels store it: fp32, or one round-to-nearest-even of that fp32 value to bf16."""
+    return rbf16(r32(v)) if bf16 else r32(v)
+
+
+def rowbn_guard(gamma, beta, C, like, fixed=True):
+    """The per-channel choice of rowbn_bwd_reduce_max_kernel's (gy, y) form: |beta| <= 4 |gamma| in fp32 and (fixed) a
+    finite non-zero fp32 1 / gamma -> (inv (C) bool, ig = fp32(1 / gamma), float64; 0 where not inv)."""
+    gm = torch.ones(C, dtype=torch.float64, device=like.device) if gamma is None else _f64(gamma, like)
+    b = torch.zeros(C, dtype=torch.float64, device=like.device) if beta is None else _f64(beta, like)
+    inv = b.abs() <= r32(4.0 * gm.abs())
+    ig = r32(1.0 / gm)
+    if fixed:
+        inv = inv & torch.isfinite(ig) & (ig != 0)
+    return inv, torch.where(inv, ig, torch.zeros_like(ig))
+
+
+def rowbn_bwd_sums_ref(gy, x, arg, y, K, mean, rstd, gamma, beta, slope, nseg, dtype_in, dtype_g, training=True,
+                       ar=FP32, fixed_guard=True):
+    """The backward reductions + rowbn_bwd_finalize_kernel, per segment of P rows.
+    K == 0 (rowbn_bwd_reduce_kernel) and the gather form of K > 0 (rowbn_bwd_reduce_max_kernel, y None or the guard
+    false: x read at the arg-max row): gg = bn_z(v) > 0 ? g : g * slope, xhat = (v - mu) * rstd, terms gg | gg * xhat.
+    Stored-output form (y given, channels where rowbn_guard holds): pos = y > 0, gg = pos ? g : g * slope,
+    z = pos ? y : y * fp32(1 / slope) (slope 0: * 0), xhat = (z - beta) * fp32(1 / gamma).
+    Sums: _bn_partials over the rows (K == 0) or the groups, then fp64: c12 (nseg, 2, C) = fp32(s / P | sx / P) with P
+    the ROWS of a segment (zero in eval mode), dbeta = fp32(sum over segments of s), dgamma = of sx.
+    ar = FP64: the same algebra without rounding (the guard and 1 / gamma stay those of the kernel's fp32 inputs).
+    -> dict(c12, dgamma, dbeta, inv, and for the bounds S0 = sum |gg|, S1 = sum |gg xhat|, gg, xhat per summed row)."""
+    x, gy = _f64(x), _f64(gy)
+    N, C = x.shape
+    P = N // nseg
+    geo = rowbn_geometry(P, K, C, dtype_in, dtype_g, nseg)
+    G, rpi = geo["G_bwd"], geo["rpi"]
+    mu, rs, gm, b = _bn_consts(C, nseg, mean, rstd, gamma, beta, x)
+    a = ar.mul(gm[None], rs)
+    s = slope32(slope)
+    rows = P // K if K else P
+    if K:
+        v = x.view(-1, K, C).gather(1, arg.to(x.device).long()[:, None])[:, 0]
+    else:
+        v = x
+    z = _bn_z(v, _rows(mu, rows), _rows(a, rows), b[None], ar)
+    gg = torch.where(z > 0, gy, ar.mul(gy, s))
+    xh = ar.mul(ar.sub(v, _rows(mu, rows)), _rows(rs, rows))
+    inv = torch.zeros(C, dtype=torch.bool, device=x.device)
+    if K and y is not None:
+        y = _f64(y, x)
+        inv, ig = rowbn_guard(gamma, beta, C, x, fixed_guard)
+        isl = (float(np.float32(1.0) / np.float32(s)) if ar.emulate else 1.0 / s) if s != 0.0 else 0.0
+        igv = ig if ar.emulate else torch.where(inv, 1.0 / gm, ig)
+        pos = y > 0
+        gg_y = torch.where(pos, gy, ar.mul(gy, s))
+        zz = torch.where(pos, y, ar.mul(y, isl))
+        xh_y = ar.mul(ar.sub(zz, b[None]), igv[None])
+        gg, xh = torch.where(inv[None], gg_y, gg), torch.where(inv[None], xh_y, xh)
+    t1 = ar.mul(gg, xh)
+    s0 = torch.stack([_bn_partials(gg[i * rows:(i + 1) * rows], G, rpi, ar).sum(0) for i in range(nseg)])
+    s1 = torch.stack([_bn_partials(t1[i * rows:(i + 1) * rows], G, rpi, ar).sum(0) for i in range(nseg)])
+    c12 = ar.r(torch.stack([s0 / P, s1 / P], 1)) if training else torch.zeros(nseg, 2, C, dtype=torch.float64, device=x.device)
+    return dict(c12=c12, dbeta=ar.r(s0.sum(0)), dgamma=ar.r(s1.sum(0)), inv=inv, geo=geo, P=P, gg=gg, xhat=xh, g=gy, z=z,
+                S0=gg.abs().view(nseg, rows, C).sum(1), S1=t1.abs().view(nseg, rows, C).sum(1))
+
+
+def rowbn_kink(ref_apply, x, mean, nseg):
+    """Where the FP64 twin's pre-activation z is too close to 0 for its sign to be the fp32 one: |z| <= the first-order
+    error of bn_z, u (3 |(x - mu) a| + |z|) with u = ROWBN_SAFETY * 2^-24 (a's, the difference's and the product's
+    rounding, the sum's) -> bool (N, C)."""
+    x = _f64(x)
+    P = x.shape[0] // nseg
+    mu = _f64(mean, x).reshape(-1, x.shape[1]).expand(nseg, -1) if mean is not None else \
+        torch.zeros(nseg, x.shape[1], dtype=torch.float64, device=x.device)
+    t = ((x - _rows(mu, P)) * _rows(ref_apply["a"], P)).abs()
+    return ref_apply["z"].abs() <= ROWBN_SAFETY * U32 * (3.0 * t + ref_apply["z"].abs())
+
+
+def rowbn_bwd_sums_bound(ref, slope, flip=None, stored=None):
+    """|kernel - FP64 twin| of the gather-form sums, from the twin `ref` = rowbn_bwd_sums_ref(..., y=None, ar=FP64):
+    h = rows (groups) per thread + rpi LDS additions; gg rounds once (g * slope), xhat twice, their product once:
+      s  : (h + 1) u S0,   sx : (h + 4) u S1,   then dbeta / dgamma sum them over the segments and round once,
+      c1 = fp32(s / P), c2 = fp32(sx / P) round once.
+    flip (rows, C) bool: summed rows whose lrelu' the fp32 sign of z may take from the other side (rowbn_kink at the
+    summed rows): each allows (1 - slope) |g| resp. (1 - slope) |g xhat| more.
+    stored = dict(gamma, beta, bf16): the stored-output form, judged against the SAME gather-form twin.  On the
+    channels of rowbn_guard xhat is recovered from the stored y instead: z' = y or y * fp32(1/slope) carries y's own
+    distance from the exact z (the forward's fp32 bn_z, 3u (|z - beta| + |z|) generously, its bf16 store 2^-8 |z| as in
+    tests/test_autograd_ops.py::_stored_y_allowance) plus 3u |z| for the two roundings of the inversion, z' - beta
+    rounds once and 1 / gamma once more (3u |z - beta|): Exhat = (6u |z - beta| + (6u [+ 2^-8]) |z|) / |gamma|, and
+    sx allows sum |gg| Exhat more (the guard |beta| <= 4 |gamma| keeps |z| / |gamma| within |xhat| / rstd + 4)."""
+    geo, P = ref["geo"], ref["P"]
+    u = ROWBN_SAFETY * U32
+    h = geo["per_reduce"][1] + geo["rpi"]
+    nseg, C = ref["S0"].shape
+    E0, E1 = (h + 1) * u * ref["S0"], (h + 4) * u * ref["S1"]
+    s = slope32(slope)
+    if flip is not None:
+        f = flip.to(torch.float64) * abs(1.0 - s) * ref["g"].abs()
+        E0 = E0 + f.view(nseg, -1, C).sum(1)
+        E1 = E1 + (f * ref["xhat"].abs()).view(nseg, -1, C).sum(1)
+    if stored is not None:
+        gmv = torch.ones(C, dtype=torch.float64) if stored["gamma"] is None else _f64(stored["gamma"])
+        bv = torch.zeros(C, dtype=torch.float64) if stored["beta"] is None else _f64(stored["beta"])
+        zt = ref["z"]                                               # the twin's z at the summed rows
+        rel = 6.0 * u + (BF16_REL if stored["bf16"] else 0.0)
+        Ex = (6.0 * u * (zt - bv[None]).abs() + rel * zt.abs()) / gmv.abs()[None]
+        inv = rowbn_guard(stored["gamma"], stored["beta"], C, zt)[0]
+        Ex = torch.where(inv[None], Ex, torch.zeros_like(Ex))
+        E1 = E1 + (ref["gg"].abs() * Ex).view(nseg, -1, C).sum(1)
+    c12 = torch.stack([E0 / P, E1 / P], 1)
+    c12 = c12 + u * (ref["c12"].abs() + c12)
+    Eb, Eg = E0.sum(0), E1.sum(0)
+    return dict(c12=c12, dbeta=Eb + u * (ref["dbeta"].abs() + Eb), dgamma=Eg + u * (ref["dgamma"].abs() + Eg), h=h)
+
+
+def rowbn_bwd_apply_ref(gy, x, arg, K, mean, rstd, gamma, beta, slope, c12, nseg, ar=FP32):
+    """rowbn_bwd_apply_kernel / rowbn_bwd_apply_max_kernel: a = gamma * rstd, gg = bn_z(x) > 0 ? g : g * slope (K > 0:
+    only on the row k == arg of its group, else 0), dx = a * ((gg - c1) - ((x - mu) * rstd) * c2), c12 (nseg, 2, C) or
+    None (absent constants read as zero) -> dict(dx before the store's rounding, and E: the first-order bound of
+    |fp32 - FP64 twin| per element, u |a| (|gg| + 2 |gg - c1| + 4 |xhat c2| + 2 |inner|) with u = ROWBN_SAFETY * 2^-24:
+    g * slope, the difference twice counted through the outer one, xhat's two roundings, its product, the product
+    with a and a's own rounding)."""
+    x, gy = _f64(x), _f64(gy)
+    N, C = x.shape
+    P = N // nseg
+    mu, rs, gm, b = _bn_consts(C, nseg, mean, rstd, gamma, beta, x)
+    a = ar.mul(gm[None], rs)
+    s = slope32(slope)
+    c12 = torch.zeros(nseg, 2, C, dtype=torch.float64, device=x.device) if c12 is None else _f64(c12, x)
+    z = _bn_z(x, _rows(mu, P), _rows(a, P), b[None], ar)
+    if K:
+        rows = torch.arange(N, device=x.device)
+        hit = arg.to(x.device).long()[rows // K] == (rows % K)[:, None]
+        g = torch.where(hit, gy[rows // K], torch.zeros_like(x))
+    else:
+        g = gy
+    gg = torch.where(z > 0, g, ar.mul(g, s))
+    xh = ar.mul(ar.sub(x, _rows(mu, P)), _rows(rs, P))
+    t = ar.mul(xh, _rows(c12[:, 1], P))
+    e = ar.sub(gg, _rows(c12[:, 0], P))
+    inner = ar.sub(e, t)
+    dx = ar.mul(_rows(a, P), inner)
+    E = ROWBN_SAFETY * U32 * _rows(a, P).abs() * (gg.abs() + 2.0 * e.abs() + 4.0 * t.abs() + 2.0 * inner.abs())
+    E = E + 2.0 ** -149 * (1.0 + inner.abs())        # a denormal a (gamma 2^-130) and a denormal product round absolutely
+    return dict(dx=dx, E=E, a=a, xhat=xh, gg=gg, z=z)
+
+
+def rowbn_dx_bound(ref, Ec12, nseg, bf16):
+    """dx of one tpg_rowbn_bwd call (reduce + apply): the apply's own bound E plus what the kernel's c12 (within Ec12 of
+    the twin's, rowbn_bwd_sums_bound) moves it, |a| (Ec1 + |xhat| Ec2); a bf16 store on top (small_stored_bound)."""
+    P = ref["dx"].shape[0] // nseg
+    E = ref["E"] if Ec12 is None else \
+        ref["E"] + _rows(ref["a"], P).abs() * (_rows(Ec12[:, 0], P) + ref["xhat"].abs() * _rows(Ec12[:, 1], P))
+    return small_stored_bound(ref["dx"], E, bf16) + (2.0 ** -134 if bf16 else 0.0)    # half a bf16 denormal step

@@ -164,6 +164,36 @@ class OracleBackend:
             dg, db = dg + _t(g_), db + _t(b_)
         return torch.cat(dxs, 0).to(x.dtype), (dg if need_affine else None), (db if need_affine else None)
 
+    # the phase entries, by the per-launch restatements of csrc/rowbn.hip (ref_ops.rowbn_*_ref, the kernels' fp32)
+    def rowbn_stats(self, x, eps, momentum, running_mean, running_var, num_batches_tracked, nseg, mean_shift,
+                    consts=None):
+        s = R.rowbn_stats_ref(x.detach(), nseg, eps, momentum, x.dtype, running_mean, running_var,
+                              None if num_batches_tracked is None else int(num_batches_tracked), mean_shift)
+        with torch.no_grad():
+            if running_mean is not None:
+                running_mean.copy_(s["running_mean"].float())
+                running_var.copy_(s["running_var"].float())
+            if num_batches_tracked is not None:
+                num_batches_tracked.fill_(s["num_batches_tracked"])
+        mean, rstd = s["mean"].float(), s["rstd"].float()
+        if consts is not None:
+            return mean, rstd, R.mlp_consts(mean, rstd, consts[0], consts[1], None)[0].float()
+        return mean, rstd
+
+    def rowbn_apply_max(self, x, K, mean, rstd, gamma, beta, slope, out_dtype, nseg):
+        f = R.rowbn_apply_ref(x.detach(), K, mean, rstd, gamma, beta, slope, nseg)
+        return f["y"].float().to(out_dtype), f["arg"]
+
+    def rowbn_bwd_sums(self, gy, x, arg, y, K, mean, rstd, gamma, beta, slope, need_affine, nseg, want_cb=False):
+        if want_cb:
+            raise NotImplementedError("the oracle backend has no cb / ag by-products")
+        if y is not None and (not K or y.dtype != gy.dtype):
+            y = None
+        b = R.rowbn_bwd_sums_ref(gy.detach(), x.detach(), arg, y, K, mean, rstd, gamma, beta, slope, nseg, x.dtype,
+                                 gy.dtype)
+        return (b["c12"].float(), b["dgamma"].float() if need_affine else None,
+                b["dbeta"].float() if need_affine else None)
+
 
     # ---- the 16 -> 16 -> 32 small tails (float64 inside, stored as the kernels store) ------
     def small_tail_fwd(self, h, W1, W2, s1, s2, K):

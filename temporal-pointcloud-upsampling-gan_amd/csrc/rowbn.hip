@@ -519,7 +519,8 @@ __global__ __launch_bounds__(BN_THREADS) void rowbn_bwd_reduce_kernel(
 // With the forward's output y (stored like gy) the arg-max row's pre-activation is
 // z = y > 0 ? y : y / slope and xhat = (z - beta) / gamma: two small streaming reads instead of
 // one scattered 2/4-byte load of x per (group, channel).  Per-channel guard: the inversion is
-// used only where it is well conditioned (|beta| <= 4|gamma|); y == nullptr: always gather.
+// used only where it is well conditioned (|beta| <= 4|gamma|, 1/gamma finite and non-zero: a zero-initialised or
+// denormal gamma gathers); y == nullptr: always gather.
 template <typename TI, typename TG>
 __global__ __launch_bounds__(BN_THREADS) void rowbn_bwd_reduce_max_kernel(
     const TG *__restrict__ gy, const TG *__restrict__ y, const TI *__restrict__ x,
@@ -552,8 +553,9 @@ __global__ __launch_bounds__(BN_THREADS) void rowbn_bwd_reduce_max_kernel(
         ld_consts<NE>(gamma, col, 1.0f, a);
 #pragma unroll
         for (int i = 0; i < NE; ++i) {
-            inv[i] = y != nullptr && fabsf(b[i]) <= 4.0f * fabsf(a[i]);
-            ig[i] = inv[i] ? 1.0f / a[i] : 0.0f;
+            const float g1 = 1.0f / a[i];          // gamma zero or denormal: inf, and (z - beta) * inf is NaN or inf
+            inv[i] = y != nullptr && fabsf(b[i]) <= 4.0f * fabsf(a[i]) && g1 != 0.0f && fabsf(g1) < INFINITY;
+            ig[i] = inv[i] ? g1 : 0.0f;
             a[i] = a[i] * rs[i];
         }
         for (long long r = (long long)blockIdx.x * rpi + rsub; r < Gp; r += (long long)gridDim.x * rpi) {
