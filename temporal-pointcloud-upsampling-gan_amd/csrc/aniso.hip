@@ -4,10 +4,10 @@
 // full, operation by operation: include/tpgan_ops.h, "anisotropic kernels".  The mesher that uses it is this project's
 // own (tpgan_amd.mesh); the reference hands its frames to an external reconstruction tool.
 //
-// Both stages follow radius_reduce.hip: one wave per particle / query, the 27 cells of the uniform grid of
-// frnn_grid_build.hpp around it as 9 runs of the cell-sorted array (or, exhaustive shape, the lanes stride over the whole
-// cloud), every sum in 64-bit fixed point with integer butterflies for the wave totals, so that the result does not
-// depend on the order in which the grid hands out the neighbours nor on the launch shape.
+// Both stages follow radius_reduce.hip: one wave per particle / query, its candidates from fg_candidates of
+// frnn_grid_build.hpp (the walk over the 27 cells of the uniform grid around it or, exhaustive shape, the lanes stride
+// over the whole cloud), every sum in 64-bit fixed point with tpg_wave_add_u64 for the wave totals, so that the result
+// does not depend on the order in which the grid hands out the neighbours nor on the launch shape.
 //
 // Stage A is TWO launches.  The walk leaves the ten sums of a particle in the workspace (ten planes of int64, one value
 // per particle) and its member count in `count`; the finish takes ONE LANE per particle and runs the float64 part: the
@@ -27,57 +27,6 @@ struct AnParams {
     float rc, lambda, ks, kr, s_min, s_max, kn;
     int n_eps;
 };
-
-// rr_cell of radius_reduce.hip: a query may lie anywhere; outside [-2, FG_MAXDIM + 2) (and NaN) nothing is selected
-__device__ __forceinline__ int an_cell(float p, float lo, float inv_h) {
-    return (int)floorf(fminf(fmaxf((p - lo) * inv_h, -2.0f), (float)(FG_MAXDIM + 2)));
-}
-
-// f(x, y, z, row) for every candidate of the query (qx, qy, qz): the points of the 27 cells around it, 64 per step,
-// or every stored row below np
-template <bool GRID, typename F>
-__device__ __forceinline__ void an_walk(float qx, float qy, float qz, const GridParams *__restrict__ gp, int b,
-                                        int cstride, const int *__restrict__ start, const float4 *__restrict__ sorted,
-                                        const float *__restrict__ pos, int np, int Np, int lane, F &&f) {
-    if (GRID) {
-        const GridParams g = gp[b];
-        const int cx = an_cell(qx, g.lo[0], g.inv_h), cy = an_cell(qy, g.lo[1], g.inv_h);
-        const int cz = an_cell(qz, g.lo[2], g.inv_h);
-        const int x0 = max(cx - 1, 0), x1 = min(cx + 1, g.dim[0] - 1);
-        const int *st = start + (size_t)b * (cstride + 1);
-        const float4 *pts = sorted + (size_t)b * Np;
-        int rb[9], re[9], total = 0;
-#pragma unroll
-        for (int t = 0; t < 9; ++t) {
-            const int zz = cz + t / 3 - 1, yy = cy + t % 3 - 1;
-            int bgn = 0, end = 0;
-            if (x0 <= x1 && zz >= 0 && zz < g.dim[2] && yy >= 0 && yy < g.dim[1]) {
-                const int row = (zz * g.dim[1] + yy) * g.dim[0];
-                bgn = st[row + x0];
-                end = st[row + x1 + 1];
-            }
-            rb[t] = bgn;
-            re[t] = end;
-            total += end - bgn;
-        }
-        for (int base = 0; base < total; base += 64) {
-            int c = base + lane, at = -1;
-#pragma unroll
-            for (int t = 0; t < 9; ++t) {
-                const int n = re[t] - rb[t];
-                if (at < 0 && c < n) at = rb[t] + c;
-                c -= (at < 0) ? n : 0;
-            }
-            if (at >= 0 && base + lane < total) {
-                const float4 p = pts[at];
-                f(p.x, p.y, p.z, __float_as_int(p.w));
-            }
-        }
-    } else {
-        const float *x = pos + (size_t)b * Np * 3;
-        for (int j = lane; j < np; j += 64) f(x[(size_t)j * 3], x[(size_t)j * 3 + 1], x[(size_t)j * 3 + 2], j);
-    }
-}
 
 __device__ __forceinline__ long long an_fix32(float term) { return (long long)(term * 4294967296.0f); }
 
@@ -101,36 +50,34 @@ __global__ __launch_bounds__(FG_WAVES * 64) void an_sums_kernel(
     for (int k = 0; k < 10; ++k) s[k] = 0;
     if (i < n) {
         const float qx = pos[q * 3], qy = pos[q * 3 + 1], qz = pos[q * 3 + 2];
-        an_walk<GRID>(qx, qy, qz, gp, b, cstride, start, sorted, pos, n, N, lane,
-                      [&](float px, float py, float pz, int) {
-                          const float d2 = tpg_sq3(qx, qy, qz, px, py, pz);
-                          if (d2 <= rc2) {
-                              ++cnt;
-                              const float d = sqrtf(d2);
-                              const float rho = fminf(d / rc, 1.0f);
-                              const float w = 1.0f - (rho * rho) * rho;
-                              const float ux = (px - qx) / rc, uy = (py - qy) / rc, uz = (pz - qz) / rc;
-                              const float wx = w * ux, wy = w * uy, wz = w * uz;
-                              s[0] += an_fix32(w);
-                              s[1] += an_fix32(wx);
-                              s[2] += an_fix32(wy);
-                              s[3] += an_fix32(wz);
-                              s[4] += an_fix32(wx * ux);
-                              s[5] += an_fix32(wx * uy);
-                              s[6] += an_fix32(wx * uz);
-                              s[7] += an_fix32(wy * uy);
-                              s[8] += an_fix32(wy * uz);
-                              s[9] += an_fix32(wz * uz);
-                          }
-                      });
+        fg_candidates<GRID>(qx, qy, qz, gp, b, cstride, start, sorted, pos, n, N, lane,
+                            [&](float px, float py, float pz, int) {
+                                const float d2 = tpg_sq3(qx, qy, qz, px, py, pz);
+                                if (d2 <= rc2) {
+                                    ++cnt;
+                                    const float d = sqrtf(d2);
+                                    const float rho = fminf(d / rc, 1.0f);
+                                    const float w = 1.0f - (rho * rho) * rho;
+                                    const float ux = (px - qx) / rc, uy = (py - qy) / rc, uz = (pz - qz) / rc;
+                                    const float wx = w * ux, wy = w * uy, wz = w * uz;
+                                    s[0] += an_fix32(w);
+                                    s[1] += an_fix32(wx);
+                                    s[2] += an_fix32(wy);
+                                    s[3] += an_fix32(wz);
+                                    s[4] += an_fix32(wx * ux);
+                                    s[5] += an_fix32(wx * uy);
+                                    s[6] += an_fix32(wx * uz);
+                                    s[7] += an_fix32(wy * uy);
+                                    s[8] += an_fix32(wy * uz);
+                                    s[9] += an_fix32(wz * uz);
+                                }
+                            });
     }
-    // wave totals: xor butterflies of integer additions (the whole wave is here: every branch above is wave-uniform)
+    // wave totals (the whole wave is here: every branch above is wave-uniform)
 #pragma unroll
-    for (int d = 32; d > 0; d >>= 1) {
-        cnt += __shfl_xor(cnt, d);
+    for (int d = 32; d > 0; d >>= 1) cnt += __shfl_xor(cnt, d);
 #pragma unroll
-        for (int k = 0; k < 10; ++k) s[k] += __shfl_xor(s[k], d);
-    }
+    for (int k = 0; k < 10; ++k) s[k] = tpg_wave_add_u64(s[k]);
     if (lane == 0) {
         count[q] = cnt;
 #pragma unroll
@@ -250,31 +197,22 @@ __global__ __launch_bounds__(FG_WAVES * 64) void an_field_kernel(
     if (i < fg_len(lenq, b, Nq)) {
         const float qx = query[q * 3], qy = query[q * 3 + 1], qz = query[q * 3 + 2];
         const float *Gb = G + (size_t)b * Np * 6, *db = det + (size_t)b * Np;
-        an_walk<GRID>(qx, qy, qz, gp, b, cstride, start, sorted, centres, fg_len(lenp, b, Np), Np, lane,
-                      [&](float px, float py, float pz, int j) {
-                          if (!(tpg_sq3(qx, qy, qz, px, py, pz) <= reach2)) return;
-                          const float *g = Gb + (size_t)j * 6;
-                          const float t0 = qx - px, t1 = qy - py, t2 = qz - pz;
-                          const float y0 = (g[0] * t0 + g[1] * t1) + g[2] * t2;
-                          const float y1 = (g[1] * t0 + g[3] * t1) + g[4] * t2;
-                          const float y2 = (g[2] * t0 + g[4] * t1) + g[5] * t2;
-                          const float u = fminf(sqrtf((y0 * y0 + y1 * y1) + y2 * y2) / R, 1.0f);
-                          float w;
-                          if (u <= 0.5f) {
-                              const float u2 = u * u;
-                              w = 6.0f * (u2 * u - u2) + 1.0f;
-                          } else {
-                              const float v = 1.0f - u;
-                              w = 2.0f * (v * v * v);
-                          }
-                          w = fmaxf(w, 0.0f);
-                          // clamped into [0, 512] whatever det holds (NaN -> 0): a term is at most 2^31 units
-                          const float dw = fminf(fmaxf(db[j] * w, 0.0f), 512.0f);
-                          acc += (tpg_u64)(dw * 4194304.0f);
-                      });
+        fg_candidates<GRID>(qx, qy, qz, gp, b, cstride, start, sorted, centres, fg_len(lenp, b, Np), Np, lane,
+                            [&](float px, float py, float pz, int j) {
+                                if (!(tpg_sq3(qx, qy, qz, px, py, pz) <= reach2)) return;
+                                const float *g = Gb + (size_t)j * 6;
+                                const float t0 = qx - px, t1 = qy - py, t2 = qz - pz;
+                                const float y0 = (g[0] * t0 + g[1] * t1) + g[2] * t2;
+                                const float y1 = (g[1] * t0 + g[3] * t1) + g[4] * t2;
+                                const float y2 = (g[2] * t0 + g[4] * t1) + g[5] * t2;
+                                const float u = fminf(sqrtf((y0 * y0 + y1 * y1) + y2 * y2) / R, 1.0f);
+                                const float w = tpg_cubic_spline_w(u);
+                                // clamped into [0, 512] whatever det holds (NaN -> 0): a term is at most 2^31 units
+                                const float dw = fminf(fmaxf(db[j] * w, 0.0f), 512.0f);
+                                acc += (tpg_u64)(dw * 4194304.0f);
+                            });
     }
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) acc += __shfl_xor(acc, d);
+    acc = tpg_wave_add_u64(acc);
     if (lane == 0) sum[q] = (float)acc * 2.384185791015625e-7f;
 }
 
@@ -297,11 +235,11 @@ int an_kernels(bool grid, const float *pos, const int64_t *lengths, int B, int N
     long long *sums = reinterpret_cast<long long *>(static_cast<unsigned char *>(ws) + fg_workspace_bytes(B, N));
     if (stages & 1) {
         if (grid) {
-            GridParams *gp; int *start; float4 *sorted;
-            const int rcode = fg_build(pos, lengths, B, N, rc, 0, ws, st, &gp, &start, &sorted);
+            GridView v;
+            const int rcode = fg_build(pos, lengths, B, N, rc, 0, ws, st, &v);
             if (rcode) return rcode;
             hipLaunchKernelGGL(an_sums_kernel<true>, dim3(fg_query_blocks(N), B), dim3(FG_WAVES * 64), 0, st, pos,
-                               lengths, N, gp, FG_CELLS, start, sorted, rc, rc * rc, sums, count);
+                               lengths, N, v.gp, FG_CELLS, v.start, v.sorted, rc, rc * rc, sums, count);
         } else {
             hipLaunchKernelGGL(an_sums_kernel<false>, dim3(fg_query_blocks(N), B), dim3(FG_WAVES * 64), 0, st, pos,
                                lengths, N, (const GridParams *)nullptr, 0, (const int *)nullptr, (const float4 *)nullptr,
@@ -330,11 +268,12 @@ int an_field(bool grid, const float *query, const float *centres, const float *G
         return hipMemsetAsync(sum, 0, sizeof(float) * (size_t)B * Nq, st) == hipSuccess ? TPG_OK : TPG_ERR_LAUNCH;
     if (!centres || !G || !det) return TPG_ERR_ARG;
     if (grid) {
-        GridParams *gp; int *start; float4 *sorted;
-        const int rcode = fg_build(centres, lenp, B, Np, reach, 0, ws, st, &gp, &start, &sorted);
+        GridView v;
+        const int rcode = fg_build(centres, lenp, B, Np, reach, 0, ws, st, &v);
         if (rcode) return rcode;
         hipLaunchKernelGGL(an_field_kernel<true>, dim3(fg_query_blocks(Nq), B), dim3(FG_WAVES * 64), 0, st, query,
-                           centres, G, det, lenq, lenp, Nq, Np, gp, FG_CELLS, start, sorted, support, reach * reach, sum);
+                           centres, G, det, lenq, lenp, Nq, Np, v.gp, FG_CELLS, v.start, v.sorted, support,
+                           reach * reach, sum);
     } else {
         hipLaunchKernelGGL(an_field_kernel<false>, dim3(fg_query_blocks(Nq), B), dim3(FG_WAVES * 64), 0, st, query,
                            centres, G, det, lenq, lenp, Nq, Np, (const GridParams *)nullptr, 0, (const int *)nullptr,

@@ -12,20 +12,178 @@
 //   cell edge  h = max(r, extent / 64) * (1 + 1e-4)     (>= r with a margin far above fp32 rounding)
 //   cell(p)    = floor((p - lo) / h) per axis, the same expression for stored points and queries
 //
-// Build (four small launches per call, all clouds at once):
-//   bbox   per cloud: lo, 1/h, grid dims (<= 64 per axis)            one workgroup per cloud
-//   count  cell of every point, int atomics on the cell counters     (deterministic totals)
-//   scan   exclusive prefix of the counters                          one workgroup per cloud
-//   fill   points copied into cell order as (x, y, z, original index)
-// Query: one WAVE per query (as knn.hip): the 27 neighbour cells are 9 runs of 3 x-adjacent cells,
-// each a contiguous range of the cell-sorted array; the lanes take 64 candidates of the concatenated
-// ranges per step and the survivors (d < r^2) enter the wave's K-best list by rank merge
+// Build: fg_build below, the four small launches frnn_grid_build.hpp describes, all clouds at once; the library's other
+// files that query the grid call it too.
+// Query: one WAVE per query (as knn.hip): the walk of frnn_grid_build.hpp over the 27 neighbour cells,
+// 64 candidates per trip; the survivors (d < r^2) enter the wave's K-best list by rank merge
 // (knn_select.hpp).  At the particle spacing of the fluid clips a query meets ~75 candidates instead
-// of 16384.
+// of 16384.  A query may lie anywhere (fg_cell_any): far from the cloud, infinite or NaN, it meets no cell.
 #include "frnn_grid_build.hpp"
 #include "knn_select.hpp"
 #include "tpg_common.hpp"
 
+// ---- the build: the four launches frnn_grid_build.hpp describes, compiled here alone, and fg_build, the entry the
+// library's other translation units call before they query the grid
+namespace {
+
+__global__ __launch_bounds__(1024) void fg_bbox_kernel(const float *__restrict__ p2, const int64_t *__restrict__ len2,
+                                                       int P2, float r, int knn_k, GridParams *__restrict__ gp) {
+    __shared__ float red[6][16];
+    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int n2 = fg_len(len2, b, P2);
+    const float *x = p2 + (size_t)b * P2 * 3;
+    float mn[3] = {3.0e38f, 3.0e38f, 3.0e38f}, mx[3] = {-3.0e38f, -3.0e38f, -3.0e38f};
+    for (int i = tid; i < n2; i += 1024)
+#pragma unroll
+        for (int d = 0; d < 3; ++d) {
+            const float v = x[(size_t)i * 3 + d];
+            mn[d] = fminf(mn[d], v);
+            mx[d] = fmaxf(mx[d], v);
+        }
+#pragma unroll
+    for (int d = 0; d < 3; ++d) {
+#pragma unroll
+        for (int s = 32; s > 0; s >>= 1) {
+            mn[d] = fminf(mn[d], __shfl_xor(mn[d], s));
+            mx[d] = fmaxf(mx[d], __shfl_xor(mx[d], s));
+        }
+        if (lane == 0) { red[d][wave] = mn[d]; red[3 + d][wave] = mx[d]; }
+    }
+    __syncthreads();
+    if (tid == 0) {
+        float ext = 0.0f;
+        float lo[3];
+        for (int d = 0; d < 3; ++d) {
+            float a = red[d][0], c = red[3 + d][0];
+            for (int w = 1; w < 16; ++w) { a = fminf(a, red[d][w]); c = fmaxf(c, red[3 + d][w]); }
+            lo[d] = n2 > 0 ? a : 0.0f;
+            ext = fmaxf(ext, n2 > 0 ? c - a : 0.0f);
+        }
+        float h = fmaxf(r, ext / (float)FG_MAXDIM) * 1.0001f;
+        if (knn_k > 0) {
+            // kNN form: ~K/2 points per cell (flat directions count as one cell edge of the coarsest grid), so that the
+            // ball inscribed in the 27 cells around a query's cell holds ~2 K points and one pass usually settles it
+            float vol = 1.0f;
+            for (int d = 0; d < 3; ++d) {
+                float a = red[d][0], c = red[3 + d][0];
+                for (int w = 1; w < 16; ++w) { a = fminf(a, red[d][w]); c = fmaxf(c, red[3 + d][w]); }
+                vol *= fmaxf(n2 > 0 ? c - a : 0.0f, ext / (float)FG_MAXDIM);
+            }
+            const float want = cbrtf(vol * 0.5f * (float)max(knn_k, 8) / (float)max(n2, 1));
+            h = fmaxf(want, ext / (float)FG_MAXDIM) * 1.0001f;
+            if (!(h > 0.0f)) h = 1.0f;                      // a cloud of identical points: one cell
+        }
+        GridParams g;
+        g.inv_h = 1.0f / h;
+        int nc = 1;
+        for (int d = 0; d < 3; ++d) {
+            g.lo[d] = lo[d];
+            float c = red[3 + d][0];
+            for (int w = 1; w < 16; ++w) c = fmaxf(c, red[3 + d][w]);
+            int n = n2 > 0 ? cell_axis(c, lo[d], g.inv_h) + 1 : 1;
+            n = n < 1 ? 1 : (n > FG_MAXDIM ? FG_MAXDIM : n);
+            g.dim[d] = n;
+            nc *= n;
+        }
+        g.ncell = nc;
+        gp[b] = g;
+    }
+}
+
+// counts[b][cell] += 1; cellid[b][i] = cell        grid (ceil(P2/256), B)
+__global__ __launch_bounds__(256) void fg_count_kernel(const float *__restrict__ p2, const int64_t *__restrict__ len2,
+                                                       int P2, const GridParams *__restrict__ gp, int cstride,
+                                                       int *__restrict__ counts, int *__restrict__ cellid) {
+    const int b = blockIdx.y, i = blockIdx.x * 256 + threadIdx.x;
+    const int n2 = fg_len(len2, b, P2);
+    if (i >= n2) return;
+    const GridParams g = gp[b];
+    const float *x = p2 + ((size_t)b * P2 + i) * 3;
+    const int c = cell_of(g, x[0], x[1], x[2]);
+    cellid[(size_t)b * P2 + i] = c;
+    atomicAdd(&counts[(size_t)b * cstride + c], 1);
+}
+
+// start[b][c] = exclusive prefix of counts (start has ncell + 1 entries); counts are zeroed again to
+// serve as the fill cursors.                          grid (B)
+__global__ __launch_bounds__(1024) void fg_scan_kernel(const GridParams *__restrict__ gp, int cstride,
+                                                       int *__restrict__ counts, int *__restrict__ start) {
+    __shared__ int wsum[32];
+    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int nc = gp[b].ncell;
+    int *cnt = counts + (size_t)b * cstride, *st = start + (size_t)b * (cstride + 1);
+    const int per = (nc + 1023) / 1024;
+    const int lo = min(tid * per, nc), hi = min(lo + per, nc);
+    int local = 0;
+    for (int c = lo; c < hi; ++c) local += cnt[c];
+    int incl = local;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        const int o = __shfl_up(incl, d);
+        if (lane >= d) incl += o;
+    }
+    if (lane == 63) wsum[wave] = incl;
+    __syncthreads();
+    if (wave == 0) {
+        int w = lane < 16 ? wsum[lane] : 0;
+#pragma unroll
+        for (int d = 1; d < 16; d <<= 1) {
+            const int o = __shfl_up(w, d);
+            if (lane >= d) w += o;
+        }
+        if (lane < 16) wsum[16 + lane] = w;
+    }
+    __syncthreads();
+    int run = incl - local + (wave ? wsum[16 + wave - 1] : 0);
+    for (int c = lo; c < hi; ++c) {
+        const int n = cnt[c];
+        st[c] = run;
+        cnt[c] = 0;
+        run += n;
+    }
+    if (tid == 0) st[nc] = wsum[16 + 15];
+}
+
+// sorted[b][start[cell] + k] = (x, y, z, bits of i)      grid (ceil(P2/256), B)
+__global__ __launch_bounds__(256) void fg_fill_kernel(const float *__restrict__ p2, const int64_t *__restrict__ len2,
+                                                      int P2, int cstride, const int *__restrict__ cellid,
+                                                      const int *__restrict__ start, int *__restrict__ cursor,
+                                                      float4 *__restrict__ sorted) {
+    const int b = blockIdx.y, i = blockIdx.x * 256 + threadIdx.x;
+    const int n2 = fg_len(len2, b, P2);
+    if (i >= n2) return;
+    const int c = cellid[(size_t)b * P2 + i];
+    const int pos = start[(size_t)b * (cstride + 1) + c] + atomicAdd(&cursor[(size_t)b * cstride + c], 1);
+    const float *x = p2 + ((size_t)b * P2 + i) * 3;
+    sorted[(size_t)b * P2 + pos] = make_float4(x[0], x[1], x[2], __int_as_float(i));
+}
+
+}  // namespace
+
+int fg_build(const float *p2, const int64_t *len2, int B, int P2, float r, int knn_k, void *ws, hipStream_t st,
+             GridView *view) {
+    // the workspace, region by region (fg_workspace_bytes; fg_view finds gp, start and sorted the same way)
+    unsigned char *w = static_cast<unsigned char *>(ws);
+    GridParams *gp = reinterpret_cast<GridParams *>(w);
+    w += align256(sizeof(GridParams) * (size_t)B);
+    int *counts = reinterpret_cast<int *>(w);
+    w += align256(sizeof(int) * (size_t)B * FG_CELLS);
+    int *start = reinterpret_cast<int *>(w);
+    w += align256(sizeof(int) * (size_t)B * (FG_CELLS + 1));
+    int *cellid = reinterpret_cast<int *>(w);
+    w += align256(sizeof(int) * (size_t)B * P2);
+    float4 *sorted = reinterpret_cast<float4 *>(w);
+    *view = GridView{gp, start, sorted};
+    if (hipMemsetAsync(counts, 0, sizeof(int) * (size_t)B * FG_CELLS, st) != hipSuccess) return TPG_ERR_LAUNCH;
+    const dim3 pg((P2 + 255) / 256, B);
+    hipLaunchKernelGGL(fg_bbox_kernel, dim3(B), dim3(1024), 0, st, p2, len2, P2, r, knn_k, gp);
+    hipLaunchKernelGGL(fg_count_kernel, pg, dim3(256), 0, st, p2, len2, P2, gp, FG_CELLS, counts, cellid);
+    hipLaunchKernelGGL(fg_scan_kernel, dim3(B), dim3(1024), 0, st, gp, FG_CELLS, counts, start);
+    hipLaunchKernelGGL(fg_fill_kernel, pg, dim3(256), 0, st, p2, len2, P2, FG_CELLS, cellid, start, counts, sorted);
+    return TPG_OK;
+}
+
+// ---- the searches
 namespace {
 
 // one wave per query: the K nearest stored points with d < r2, ascending (dist, idx); -1 / -1 padding
@@ -50,44 +208,20 @@ __global__ __launch_bounds__(FG_WAVES * 64) void fg_query_kernel(
     }
     const GridParams g = gp[b];
     const float qx = p1[q * 3], qy = p1[q * 3 + 1], qz = p1[q * 3 + 2];
-    const int cx = cell_axis(qx, g.lo[0], g.inv_h), cy = cell_axis(qy, g.lo[1], g.inv_h), cz = cell_axis(qz, g.lo[2], g.inv_h);
-    const int x0 = max(cx - 1, 0), x1 = min(cx + 1, g.dim[0] - 1);
-    const int *st = start + (size_t)b * (cstride + 1);
     const float4 *pts = sorted + (size_t)b * P2;
-    // the 9 (dz, dy) runs: [begin, end) of the cell-sorted array, and their running total
-    int rb[9], re[9], total = 0;
-#pragma unroll
-    for (int t = 0; t < 9; ++t) {
-        const int zz = cz + t / 3 - 1, yy = cy + t % 3 - 1;
-        int bgn = 0, end = 0;
-        if (x0 <= x1 && zz >= 0 && zz < g.dim[2] && yy >= 0 && yy < g.dim[1]) {
-            const int row = (zz * g.dim[1] + yy) * g.dim[0];
-            bgn = st[row + x0];
-            end = st[row + x1 + 1];
-        }
-        rb[t] = bgn;
-        re[t] = end;
-        total += end - bgn;
-    }
     tpg_u64 best = TPG_KNN_INF, thr = TPG_KNN_INF;
-    for (int base = 0; base < total; base += 64) {
-        // candidate number base + lane of the concatenated runs
-        int c = base + lane, pos = -1;
-#pragma unroll
-        for (int t = 0; t < 9; ++t) {
-            const int n = re[t] - rb[t];
-            if (pos < 0 && c < n) pos = rb[t] + c;
-            c -= (pos < 0) ? n : 0;
-        }
-        tpg_u64 key = TPG_KNN_INF;
-        if (pos >= 0 && base + lane < total) {
-            const float4 p = pts[pos];
-            const float d = tpg_sq3(qx, qy, qz, p.x, p.y, p.z);
-            if (d < r2) key = tpg_knn_key(d, __float_as_int(p.w));
-        }
-        if (K == 1) best = key < best ? key : best;
-        else tpg_knn_merge(best, thr, key, K, lane, slot);
-    }
+    // every lane takes part in the merge, with or without a candidate
+    fg_walk_at(g, start + (size_t)b * (cstride + 1), fg_cell_any(qx, g.lo[0], g.inv_h), fg_cell_any(qy, g.lo[1], g.inv_h),
+               fg_cell_any(qz, g.lo[2], g.inv_h), lane, [&](int pos, bool has) {
+                   tpg_u64 key = TPG_KNN_INF;
+                   if (has) {
+                       const float4 p = pts[pos];
+                       const float d = tpg_sq3(qx, qy, qz, p.x, p.y, p.z);
+                       if (d < r2) key = tpg_knn_key(d, __float_as_int(p.w));
+                   }
+                   if (K == 1) best = key < best ? key : best;
+                   else tpg_knn_merge(best, thr, key, K, lane, slot);
+               });
     if (K == 1) {
         best = tpg_wave_min_u64(best);
         if (lane == 0) {
@@ -183,17 +317,17 @@ int fg_search(bool radius, const float *p1, const float *p2, const int64_t *len1
     if (!p1 || !dist || !idx) return TPG_ERR_ARG;
     if (P2 == 0) return TPG_ERR_UNSUPPORTED;             // (the exhaustive entry pads an empty search)
     if (!p2 || !fg_workspace_ok(ws)) return TPG_ERR_ARG;
-    GridParams *gp; int *start; float4 *sorted;
-    const int rc = fg_build(p2, len2, B, P2, radius ? r : 0.0f, radius ? 0 : K, ws, st, &gp, &start, &sorted);
+    GridView v;
+    const int rc = fg_build(p2, len2, B, P2, radius ? r : 0.0f, radius ? 0 : K, ws, st, &v);
     if (rc) return rc;
     const dim3 grid(fg_query_blocks(P1), B), block(FG_WAVES * 64);
     if (radius) {
         const float r2 = r * r;     // fp32(r) * fp32(r), the value the exhaustive entry is given
-        hipLaunchKernelGGL(fg_query_kernel, grid, block, 0, st, p1, len1, P1, P2, gp, FG_CELLS, start, sorted, K, r2,
-                           dist, idx);
+        hipLaunchKernelGGL(fg_query_kernel, grid, block, 0, st, p1, len1, P1, P2, v.gp, FG_CELLS, v.start, v.sorted, K,
+                           r2, dist, idx);
     } else {
-        hipLaunchKernelGGL(fg_knn_kernel, grid, block, 0, st, p1, len1, P1, P2, gp, FG_CELLS, start, sorted, K, dist,
-                           idx);
+        hipLaunchKernelGGL(fg_knn_kernel, grid, block, 0, st, p1, len1, P1, P2, v.gp, FG_CELLS, v.start, v.sorted, K,
+                           dist, idx);
     }
     TPG_RETURN_IF_LAUNCH_FAILED();
     return TPG_OK;

@@ -40,8 +40,7 @@ __global__ __launch_bounds__(GS_WAVES * 64) void gs_kernel(const float *__restri
             acc += (tpg_u64)(w * 4294967296.0f);
         }
     }
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) acc += __shfl_xor(acc, d);
+    acc = tpg_wave_add_u64(acc);
     if (lane == 0) out[q] = (double)acc * 2.3283064365386963e-10;
 }
 

@@ -5,9 +5,10 @@
 //
 // Launch shapes.  predict is one thread per particle (streaming, 24 bytes in, 24 out).  lambda, dp and finish are
 // rr_kernel's shape (csrc/radius_reduce.hip): one wave per particle, the 27 cells around it as 9 runs of 3 x-adjacent
-// cells of the cell-sorted array, 64 candidates of the concatenated runs per trip, an xor butterfly of integer additions
-// at the end, no LDS.  A neighbour's position comes from the grid's cell-sorted COPY (x, y, z, index), its lambda or
-// previous position through the index; a wave writes its own particle only, and only into arrays no wave of the launch
+// cells of the cell-sorted array, 64 candidates of the concatenated runs per trip, the wave totals by tpg_wave_add_u64 at
+// the end, no LDS.  The walk is pbf_walk below, not fg_walk of frnn_grid_build.hpp: through the shared helper the three
+// passes ran 0.7 to 1.7 % slower (profiles/refactor_grid_walk.txt).  A neighbour's position comes from the grid's
+// cell-sorted COPY (x, y, z, index), its lambda or previous position through the index; a wave writes its own particle only, and only into arrays no wave of the launch
 // reads a neighbour from, so the Jacobi passes have no races by construction.
 //
 // Summation order.  The order inside a cell follows an atomic cursor (frnn_grid_build.hpp), so every neighbourhood sum
@@ -56,7 +57,8 @@ __device__ __forceinline__ float pbf_w(float d2, float h2) {
     return (u * u) * u;
 }
 
-// every candidate of the 27 cells around (px, py, pz), 64 per trip: f(candidate) on the lane that holds it
+// every candidate of the 27 cells around (px, py, pz), 64 per trip: f(candidate) on the lane that holds it.  fg_walk
+// of frnn_grid_build.hpp around the particle's own cell, clamped into the grid, written out: see the note above
 template <class F>
 __device__ __forceinline__ void pbf_walk(const GridParams &g, const int *__restrict__ st, const float4 *__restrict__ pts,
                                          float px, float py, float pz, int lane, F &&f) {
@@ -90,13 +92,6 @@ __device__ __forceinline__ void pbf_walk(const GridParams &g, const int *__restr
         if (at >= 0 && base + lane < total) f(pts[at]);
     }
 }
-
-__device__ __forceinline__ tpg_u64 pbf_wave_add(tpg_u64 v) {
-#pragma unroll
-    for (int s = 32; s > 0; s >>= 1) v += __shfl_xor(v, s);
-    return v;
-}
-__device__ __forceinline__ long long pbf_wave_add(long long v) { return (long long)pbf_wave_add((tpg_u64)v); }
 
 // step 1: v += dt g; p = clamp(x + dt v)                 grid (ceil(N/256), chunk of scenes)
 __global__ __launch_bounds__(256) void pbf_predict_kernel(const float *__restrict__ x, const float *__restrict__ v,
@@ -140,11 +135,11 @@ __global__ __launch_bounds__(FG_WAVES * 64) void pbf_lambda_kernel(
         ay += (long long)(gy * PBF_U32);
         az += (long long)(gz * PBF_U32);
     });
-    an = pbf_wave_add(an);
-    ag2 = pbf_wave_add(ag2);
-    ax = pbf_wave_add(ax);
-    ay = pbf_wave_add(ay);
-    az = pbf_wave_add(az);
+    an = tpg_wave_add_u64(an);
+    ag2 = tpg_wave_add_u64(ag2);
+    ax = tpg_wave_add_u64(ax);
+    ay = tpg_wave_add_u64(ay);
+    az = tpg_wave_add_u64(az);
     if (lane == 0) {
         const float n = (float)an * PBF_INV_U32, sg2 = (float)ag2 * PBF_INV_U32;
         const float sx = (float)ax * PBF_INV_U32, sy = (float)ay * PBF_INV_U32, sz = (float)az * PBF_INV_U32;
@@ -181,9 +176,9 @@ __global__ __launch_bounds__(FG_WAVES * 64) void pbf_dp_kernel(
         ay += pbf_fix30(co * (t2 * ((py - c.y) / d)));
         az += pbf_fix30(co * (t2 * ((pz - c.z) / d)));
     });
-    ax = pbf_wave_add(ax);
-    ay = pbf_wave_add(ay);
-    az = pbf_wave_add(az);
+    ax = tpg_wave_add_u64(ax);
+    ay = tpg_wave_add_u64(ay);
+    az = tpg_wave_add_u64(az);
     if (lane == 0) {
         const float dp[3] = {dp_scale * ((float)ax * PBF_INV_U30), dp_scale * ((float)ay * PBF_INV_U30),
                              dp_scale * ((float)az * PBF_INV_U30)};
@@ -220,9 +215,9 @@ __global__ __launch_bounds__(FG_WAVES * 64) void pbf_finish_kernel(
         ay += pbf_fix30(((c.y - xj[1]) / dt - vy) * w);
         az += pbf_fix30(((c.z - xj[2]) / dt - vz) * w);
     });
-    ax = pbf_wave_add(ax);
-    ay = pbf_wave_add(ay);
-    az = pbf_wave_add(az);
+    ax = tpg_wave_add_u64(ax);
+    ay = tpg_wave_add_u64(ay);
+    az = tpg_wave_add_u64(az);
     if (lane == 0) {
         v_out[q * 3] = vx + cs * ((float)ax * PBF_INV_U30);
         v_out[q * 3 + 1] = vy + cs * ((float)ay * PBF_INV_U30);
@@ -286,8 +281,8 @@ extern "C" int tpg_pbf_grid_f32(const float *p, const int64_t *lengths, int B, i
     const int chk = pbf_shape(B, N);
     if (chk) return chk > 0 ? TPG_OK : chk;
     if (!p) return TPG_ERR_ARG;
-    GridParams *gp; int *start; float4 *sorted;
-    const int rc = fg_build(p, lengths, B, N, h, 0, ws, tpg_stream(stream), &gp, &start, &sorted);
+    GridView v;
+    const int rc = fg_build(p, lengths, B, N, h, 0, ws, tpg_stream(stream), &v);
     if (rc) return rc;
     TPG_RETURN_IF_LAUNCH_FAILED();
     return TPG_OK;
@@ -300,10 +295,9 @@ extern "C" int tpg_pbf_lambda_f32(const float *p, const int64_t *lengths, int B,
     const int chk = pbf_shape(B, N);
     if (chk) return chk > 0 ? TPG_OK : chk;
     if (!p) return TPG_ERR_ARG;
-    GridParams *gp; int *counts, *start, *cellid; float4 *sorted;
-    fg_carve(const_cast<void *>(ws), B, N, &gp, &counts, &start, &cellid, &sorted);
+    const GridView v = fg_view(ws, B, N);
     hipLaunchKernelGGL(pbf_lambda_kernel, dim3(fg_query_blocks(N), B), dim3(FG_WAVES * 64), 0, tpg_stream(stream), p,
-                       lengths, N, gp, start, sorted, h, h * h, S0, eps, lam, C_out);
+                       lengths, N, v.gp, v.start, v.sorted, h, h * h, S0, eps, lam, C_out);
     TPG_RETURN_IF_LAUNCH_FAILED();
     return TPG_OK;
 }
@@ -318,14 +312,13 @@ extern "C" int tpg_pbf_dp_f32(const float *p, const float *lam, const int64_t *l
     const int chk = pbf_shape(B, N);
     if (chk) return chk > 0 ? TPG_OK : chk;
     if (!p || !lam || !box || !pbf_box_ok(box, B)) return TPG_ERR_ARG;
-    GridParams *gp; int *counts, *start, *cellid; float4 *sorted;
-    fg_carve(const_cast<void *>(ws), B, N, &gp, &counts, &start, &cellid, &sorted);
+    const GridView v = fg_view(ws, B, N);
     for (int b0 = 0; b0 < B; b0 += PBF_BOX_CHUNK) {
         const int nb = min(PBF_BOX_CHUNK, B - b0);
         PbfBoxes bx;
         pbf_fill_boxes(bx, box, b0, nb);
         hipLaunchKernelGGL(pbf_dp_kernel, dim3(fg_query_blocks(N), nb), dim3(FG_WAVES * 64), 0, tpg_stream(stream), p, lam,
-                           lengths, bx, b0, N, gp, start, sorted, h, h * h, a, wq, k, dp_scale, p_out, dp_out);
+                           lengths, bx, b0, N, v.gp, v.start, v.sorted, h, h * h, a, wq, k, dp_scale, p_out, dp_out);
     }
     TPG_RETURN_IF_LAUNCH_FAILED();
     return TPG_OK;
@@ -338,10 +331,9 @@ extern "C" int tpg_pbf_finish_f32(const float *p, const float *x, const int64_t 
     const int chk = pbf_shape(B, N);
     if (chk) return chk > 0 ? TPG_OK : chk;
     if (!p || !x) return TPG_ERR_ARG;
-    GridParams *gp; int *counts, *start, *cellid; float4 *sorted;
-    fg_carve(const_cast<void *>(ws), B, N, &gp, &counts, &start, &cellid, &sorted);
+    const GridView v = fg_view(ws, B, N);
     hipLaunchKernelGGL(pbf_finish_kernel, dim3(fg_query_blocks(N), B), dim3(FG_WAVES * 64), 0, tpg_stream(stream), p, x,
-                       lengths, N, gp, start, sorted, h * h, dt, cs, x_out, v_out);
+                       lengths, N, v.gp, v.start, v.sorted, h * h, dt, cs, x_out, v_out);
     TPG_RETURN_IF_LAUNCH_FAILED();
     return TPG_OK;
 }

@@ -8,10 +8,10 @@
 // Membership: d2 <= r2, INCLUSIVE (scipy's query_ball_point / query_ball_tree are), with the project's canonical fp32
 // distance (t = q - p per axis; d = t0*t0; d = d + t1*t1; d = d + t2*t2; no FMA) and r2 = fp32(r) * fp32(r).
 //
-// Two launch shapes of one kernel body, one wave per query, no LDS:
-//   grid        the uniform grid of frnn_grid_build.hpp (cell edge >= r * 1.0001, so no pair within r sits more than
-//               one cell apart): the 27 cells around the query's cell are 9 runs of 3 x-adjacent cells, each a
-//               contiguous range of the cell-sorted array; the lanes take 64 candidates of the concatenated runs per step
+// Two launch shapes of one kernel body, one wave per query, no LDS (fg_candidates of frnn_grid_build.hpp hands out the
+// candidates of either):
+//   grid        the uniform grid (cell edge >= r * 1.0001, so no pair within r sits more than one cell apart): the walk
+//               over the 27 cells around the query's cell, 64 candidates per trip
 //   exhaustive  the lanes stride over the whole stored cloud (small clouds: no build launches)
 //
 // Summation order.  The grid's fill places the points of a cell through an atomic cursor, so the order in which a
@@ -37,27 +37,12 @@ __device__ __forceinline__ tpg_u64 rr_term(float d2, float r, int kernel) {
     const float d = sqrtf(d2);
     if (kernel == RR_CUBIC) {
         // analysis_helper.py:102-113 with coefficient 1; sqrt(d2) / r may exceed 1 by an ulp at the rim
-        const float q = fminf(d / r, 1.0f);
-        float w;
-        if (q <= 0.5f) {
-            const float q2 = q * q;
-            w = 6.0f * (q2 * q - q2) + 1.0f;
-        } else {
-            const float t = 1.0f - q;
-            w = 2.0f * (t * t * t);
-        }
-        return (tpg_u64)(fmaxf(w, 0.0f) * 4294967296.0f);
+        return (tpg_u64)(tpg_cubic_spline_w(fminf(d / r, 1.0f)) * 4294967296.0f);
     }
     // train_utils.py:258-266
     if (d < 1.0e-8f) return 0;
     const float w = fminf(fmaxf(r / d - 1.0f, 0.0f), 1099511627776.0f);
     return (tpg_u64)(w * 8388608.0f);
-}
-
-// cell_axis for a query that may lie anywhere (a lattice around the fluid, a dummy at 999): the same value inside
-// [-2, FG_MAXDIM + 2), clamped in float before the conversion outside it (and NaN -> -2), where nothing is selected
-__device__ __forceinline__ int rr_cell(float p, float lo, float inv_h) {
-    return (int)floorf(fminf(fmaxf((p - lo) * inv_h, -2.0f), (float)(FG_MAXDIM + 2)));
 }
 
 __device__ __forceinline__ tpg_u64 rr_sat_add(tpg_u64 a, tpg_u64 b) {
@@ -83,57 +68,16 @@ __global__ __launch_bounds__(FG_WAVES * 64) void rr_kernel(
     tpg_u64 acc = 0;
     if (i < nq) {
         const float qx = query[q * 3], qy = query[q * 3 + 1], qz = query[q * 3 + 2];
-        if (GRID) {
-            const GridParams g = gp[b];
-            const int cx = rr_cell(qx, g.lo[0], g.inv_h), cy = rr_cell(qy, g.lo[1], g.inv_h);
-            const int cz = rr_cell(qz, g.lo[2], g.inv_h);
-            const int x0 = max(cx - 1, 0), x1 = min(cx + 1, g.dim[0] - 1);
-            const int *st = start + (size_t)b * (cstride + 1);
-            const float4 *pts = sorted + (size_t)b * Np;
-            // the 9 (dz, dy) runs: [begin, end) of the cell-sorted array, and their running total
-            int rb[9], re[9], total = 0;
-#pragma unroll
-            for (int t = 0; t < 9; ++t) {
-                const int zz = cz + t / 3 - 1, yy = cy + t % 3 - 1;
-                int bgn = 0, end = 0;
-                if (x0 <= x1 && zz >= 0 && zz < g.dim[2] && yy >= 0 && yy < g.dim[1]) {
-                    const int row = (zz * g.dim[1] + yy) * g.dim[0];
-                    bgn = st[row + x0];
-                    end = st[row + x1 + 1];
-                }
-                rb[t] = bgn;
-                re[t] = end;
-                total += end - bgn;
-            }
-            for (int base = 0; base < total; base += 64) {
-                // candidate number base + lane of the concatenated runs
-                int c = base + lane, at = -1;
-#pragma unroll
-                for (int t = 0; t < 9; ++t) {
-                    const int n = re[t] - rb[t];
-                    if (at < 0 && c < n) at = rb[t] + c;
-                    c -= (at < 0) ? n : 0;
-                }
-                if (at >= 0 && base + lane < total) {
-                    const float4 p = pts[at];
-                    const float d = tpg_sq3(qx, qy, qz, p.x, p.y, p.z);
-                    if (d <= r2) {
-                        ++cnt;
-                        if (sum) acc = rr_sat_add(acc, rr_term(d, r, kernel));
-                    }
-                }
-            }
-        } else {
-            const int np = lenp ? min(max((int)lenp[b], 0), Np) : Np;
-            const float *x = pos + (size_t)b * Np * 3;
-            for (int j = lane; j < np; j += 64) {
-                const float d = tpg_sq3(qx, qy, qz, x[(size_t)j * 3], x[(size_t)j * 3 + 1], x[(size_t)j * 3 + 2]);
-                if (d <= r2) {
-                    ++cnt;
-                    if (sum) acc = rr_sat_add(acc, rr_term(d, r, kernel));
-                }
-            }
-        }
+        // the exhaustive shape reads lenp itself (the grid's own count is fg_build's business)
+        const int np = GRID ? 0 : (lenp ? min(max((int)lenp[b], 0), Np) : Np);
+        fg_candidates<GRID>(qx, qy, qz, gp, b, cstride, start, sorted, pos, np, Np, lane,
+                            [&](float px, float py, float pz, int) {
+                                const float d = tpg_sq3(qx, qy, qz, px, py, pz);
+                                if (d <= r2) {
+                                    ++cnt;
+                                    if (sum) acc = rr_sat_add(acc, rr_term(d, r, kernel));
+                                }
+                            });
     }
     // wave totals: xor butterfly of integer additions (the whole wave is here: every branch above is wave-uniform)
 #pragma unroll
@@ -173,11 +117,11 @@ extern "C" int tpg_radius_reduce_f32(const float *query, const float *pos, const
     if (B > 0 && Nq > 0 && Np > 0 && !fg_workspace_ok(ws)) return TPG_ERR_ARG;
     const int chk = rr_check(query, pos, B, Nq, Np, r, kernel, count, sum, st);
     if (chk) return chk > 0 ? TPG_OK : chk;
-    GridParams *gp; int *start; float4 *sorted;
-    const int rc = fg_build(pos, lenp, B, Np, r, 0, ws, st, &gp, &start, &sorted);
+    GridView v;
+    const int rc = fg_build(pos, lenp, B, Np, r, 0, ws, st, &v);
     if (rc) return rc;
     hipLaunchKernelGGL(rr_kernel<true>, dim3(fg_query_blocks(Nq), B), dim3(FG_WAVES * 64), 0, st, query, pos,
-                       lenq, lenp, Nq, Np, gp, FG_CELLS, start, sorted, r, r * r, kernel, count, sum);
+                       lenq, lenp, Nq, Np, v.gp, FG_CELLS, v.start, v.sorted, r, r * r, kernel, count, sum);
     TPG_RETURN_IF_LAUNCH_FAILED();
     return TPG_OK;
 }

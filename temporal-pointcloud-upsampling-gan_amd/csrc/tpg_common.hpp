@@ -1,7 +1,8 @@
 // Shared helpers for the gfx950 kernels: launch plumbing, the canonical 3-D distance, cross-lane moves, wave
-// reductions.  wave = 64 lanes everywhere.  (Row chunks and bf16 conversion: tpg_rows.hpp; the BatchNorm finalize
-// pieces: tpg_bn_finalize.hpp; the samplers' radix select, LDS sort and clip tables: tpg_select.hpp; the neighbour
-// searches' 64-bit key, padding row and rank merge: knn_select.hpp; the uniform grid's build and workspace rules:
+// reductions (among them the fixed-point sums' 64-bit integer total), the cubic spline weight.  wave = 64 lanes
+// everywhere.  (Row chunks and bf16 conversion: tpg_rows.hpp; the BatchNorm finalize pieces: tpg_bn_finalize.hpp; the
+// samplers' radix select, LDS sort and clip tables: tpg_select.hpp; the neighbour searches' 64-bit key, padding row and
+// rank merge: knn_select.hpp; the uniform grid's parameters, workspace rules, build entry and 27-cell walk:
 // frnn_grid_build.hpp.)
 //
 // Every translation unit is compiled with -ffp-contract=off: the canonical
@@ -156,6 +157,29 @@ __device__ __forceinline__ float tpg_wave_sum(float v) {
 #pragma unroll
     for (int d = 32; d > 0; d >>= 1) v += __shfl_xor(v, d);
     return v;
+}
+
+// the fixed-point sums' wave total in every lane: the same butterfly of 64-bit integer additions (wrapping, hence the
+// signed form is the unsigned one)
+__device__ __forceinline__ tpg_u64 tpg_wave_add_u64(tpg_u64 v) {
+#pragma unroll
+    for (int d = 32; d > 0; d >>= 1) v += __shfl_xor(v, d);
+    return v;
+}
+__device__ __forceinline__ long long tpg_wave_add_u64(long long v) { return (long long)tpg_wave_add_u64((tpg_u64)v); }
+
+// cubic spline weight of q = distance / support in [0, 1], coefficient 1, never negative (the operation order is part
+// of the results' bits; cubic_interp.hip's bicubic_w is another function)
+__device__ __forceinline__ float tpg_cubic_spline_w(float q) {
+    float w;
+    if (q <= 0.5f) {
+        const float q2 = q * q;
+        w = 6.0f * (q2 * q - q2) + 1.0f;
+    } else {
+        const float t = 1.0f - q;
+        w = 2.0f * (t * t * t);
+    }
+    return fmaxf(w, 0.0f);
 }
 
 // clamp an index into [0, n) -- invalid indices are undefined behaviour upstream;

@@ -168,6 +168,12 @@ class HipBackend:
     KNN_GRID_MIN_POINTS = 2048
     CHAMFER_GRID_MIN_POINTS = 8192
 
+    def _use_grid(self, B, Nq, Np, min_points=None):
+        """The size switch of every op that has a grid form: enough searched points per cloud (GRID_MIN_POINTS, or the
+        op's own floor) and enough query x point pairs in the call."""
+        floor = self.GRID_MIN_POINTS if min_points is None else min_points
+        return Np >= floor and float(B) * Nq * Np >= self.GRID_MIN_PAIRS
+
     def _grid_ws(self, ref, B, P2):
         return self._workspace("frnn", ref, self.lib.tpg_frnn_grid_workspace_bytes(B, P2), dtype=torch.uint8)
 
@@ -176,14 +182,12 @@ class HipBackend:
         P2 = p2.shape[1]
         dist = torch.empty((B, P1, K), dtype=torch.float32, device=p1.device)
         idx = torch.empty((B, P1, K), dtype=torch.int64, device=p1.device)
-        if (r is not None and r2 is not None and D == 3 and K <= 64 and P2 >= self.GRID_MIN_POINTS
-                and float(B) * P1 * P2 >= self.GRID_MIN_PAIRS and float(r) > 0):
+        if r is not None and r2 is not None and D == 3 and K <= 64 and self._use_grid(B, P1, P2) and float(r) > 0:
             self._call("tpg_frnn_grid_f32", "frnn_grid", 4 * B * D * (P1 + P2) + 12 * B * P1 * K, p1,
                        _ptr(p1), _ptr(p2), _ptr(len1), _ptr(len2), B, P1, P2, K, float(np.float32(r)), _ptr(dist),
                        _ptr(idx), _ptr(self._grid_ws(p1, B, P2)))
             return dist, idx
-        if (r2 is None and D == 3 and K <= 64 and P2 >= self.KNN_GRID_MIN_POINTS
-                and float(B) * P1 * P2 >= self.GRID_MIN_PAIRS):
+        if r2 is None and D == 3 and K <= 64 and self._use_grid(B, P1, P2, self.KNN_GRID_MIN_POINTS):
             # plain 3-D kNN on the uniform grid (first EdgeConv at cfg5 / rollout sizes, Chamfer at 16384 points):
             # measured (tools/tune_frnn.py) B = 40, 4096 points, K = 20: 431 us exhaustive
             self._call("tpg_knn_grid_f32", "knn_grid", 4 * B * D * (P1 + P2) + 12 * B * P1 * K, p1,
@@ -239,7 +243,7 @@ class HipBackend:
         count = torch.empty((B, Nq), dtype=torch.int32, device=query.device) if want_count else None
         total = torch.empty((B, Nq), dtype=torch.float32, device=query.device) if want_sum else None
         if grid is None:
-            grid = Np >= self.GRID_MIN_POINTS and float(B) * Nq * Np >= self.GRID_MIN_PAIRS
+            grid = self._use_grid(B, Nq, Np)
         nbytes = 12 * B * (Nq + Np) + 4 * B * Nq * (int(want_count) + int(want_sum))
         args = (_ptr(query), _ptr(pos), _ptr(lenq), _ptr(lenp), B, Nq, Np, float(np.float32(r)), int(kernel),
                 _ptr(count), _ptr(total))
@@ -501,7 +505,7 @@ class HipBackend:
                    torch.empty((B, N), dtype=torch.float32, device=pos.device),
                    torch.empty((B, N), dtype=torch.int32, device=pos.device))
         if grid is None:
-            grid = N >= self.GRID_MIN_POINTS and float(B) * N * N >= self.GRID_MIN_PAIRS
+            grid = self._use_grid(B, N, N)
         symbol = "tpg_aniso_kernels_f32" if grid else "tpg_aniso_kernels_exhaustive_f32"
         self._call(symbol, "aniso_kernels", 12 * B * N + 44 * B * N, pos, _ptr(pos), _ptr(lengths), B, N, rc, lam, ks, kr,
                    s_min, s_max, kn, int(n_eps), int(stages), *[_ptr(t) for t in out], _ptr(self._aniso_ws(pos, B, N)))
@@ -513,7 +517,7 @@ class HipBackend:
         Np = centres.shape[1]
         total = torch.empty((B, Nq), dtype=torch.float32, device=query.device)
         if grid is None:
-            grid = Np >= self.GRID_MIN_POINTS and float(B) * Nq * Np >= self.GRID_MIN_PAIRS
+            grid = self._use_grid(B, Nq, Np)
         args = (_ptr(query), _ptr(centres), _ptr(G), _ptr(det), _ptr(lenq), _ptr(lenp), B, Nq, Np, support, reach,
                 _ptr(total))
         nbytes = 12 * B * Nq + 44 * B * Np + 4 * B * Nq

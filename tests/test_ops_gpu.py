@@ -1075,3 +1075,27 @@ def test_frnn_grid_walk_on_a_flat_lattice_with_far_queries(hip):
     assert (ri[0, -4:] == -1).all() and (ri[0, :-4, 0] >= 0).all()
     assert np.array_equal(i.cpu().numpy(), ri)
     assert np.array_equal(d.cpu().numpy(), rd)
+
+
+def test_frnn_grid_queries_beyond_any_cell_select_nothing(hip):
+    """A query may lie anywhere: its cell index is clamped in float before the conversion to int (fg_cell_any), so a
+    coordinate at +-1e30, 3e38 (times 1/h: an overflow to inf), +inf or NaN meets no cell, whichever axis carries it
+    (x fails the run's x0 <= x1, y and z reject every run).  Those rows are all -1 / -1.0, asserted directly; the 36
+    lattice rows beside them equal the oracle's."""
+    p = lattice(6, 6, 1)[None]
+    extra = []
+    for axis in range(3):
+        for v in (1e30, -1e30, 3e38, np.inf):
+            row = [0.1, 0.1, 0.0]                                   # inside the lattice's box on the other two axes
+            row[axis] = v
+            extra.append(row)
+    extra.append([np.nan] * 3)
+    q = np.concatenate([p, np.asarray(extra, np.float32)[None]], 1)
+    d, i = _grid(hip, q, p, 64, LATTICE_R)
+    d, i = d.cpu().numpy(), i.cpu().numpy()
+    assert d.shape == (1, 36 + 13, 64) and i.shape == d.shape
+    assert (i[0, 36:] == -1).all() and (d[0, 36:] == -1.0).all()
+    rd, ri = R.knn(p, p, 64, r=LATTICE_R)
+    assert (ri[0, :, 0] >= 0).all()
+    assert np.array_equal(i[:, :36], ri)
+    assert np.array_equal(d[:, :36], rd)
