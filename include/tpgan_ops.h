@@ -862,6 +862,50 @@ int tpg_pbf_dp_f32(const float *p, const float *lam, const int64_t *lengths, con
 int tpg_pbf_finish_f32(const float *p, const float *x, const int64_t *lengths, int B, int N, float h, float dt, float cs,
                        const void *ws, float *x_out, float *v_out, void *stream);
 
+/* ---- vorticity confinement and per-particle viscosity in the particle fluid simulator (csrc/pbf.hip) ----------------
+ * The third velocity stage of Macklin and Mueller's solver, and an XSPH coefficient per particle instead of one per
+ * batch.  Both live in the tail of the substep, on the grid of the final p that finish walks, and both use finish's pair
+ * quantity u = v_j - v_i: together they cost ONE more neighbourhood walk.  With either in use a substep ends
+ *     grid | finish_ex | vorticity          (vorticity only when its strength is > 0)
+ * Notation, pair membership (d2 < h2; gradient pairs also d2 != 0), W, t2, G_ij = t2 * (p_i - p_j) / d per axis and the
+ * fixed-point sums are those of the section above; fix30(t) is the clamp of t into [-1024, 1024] followed by
+ * (int64)(t * 2^30).  Every fp32 operation is rounded on its own; only + - * / and sqrtf are used.
+ *
+ * tpg_pbf_finish_ex_f32: finish with two options, each switched on by a pointer.  v_i = (p_i - x_i) / dt and, per pair,
+ * u = (c_j - x_j) / dt - v_i per axis (c_j: the neighbour's position in the grid's copy), exactly as in finish.
+ *   cs_tab == NULL      v_out = v_i + cs * sum fix30(u * W)                                     (finish itself)
+ *   cs_tab (B,N) f32    cij = 0.5f * (cs_tab[i] + cs_tab[j]);  term = fix30(cij * (u * W));  v_out = v_i + sum term, no
+ *                       outer factor, cs unused.  cij and u * W are symmetric resp. antisymmetric in (i, j) bit for bit,
+ *                       so term_ij = -term_ji in integers: the table moves momentum between particles, it makes none.
+ *   omega_out (B,N,4)   over gradient pairs, on the velocities BEFORE XSPH (the u of this walk):
+ *                           omega_i = sum u x G_ij:  x: fix30(u_y*G_z - u_z*G_y),  y: fix30(u_z*G_x - u_x*G_z),
+ *                                                    z: fix30(u_x*G_y - u_y*G_x)   (two products, one subtraction)
+ *                       stored as (omega_x, omega_y, omega_z, m), m = sqrtf((omega_x^2 + omega_y^2) + omega_z^2).
+ *                       Right-handed: a rigid rotation Omega about +y gives omega_y > 0.
+ *   With both pointers NULL the launch is finish's, bit for bit.
+ *
+ * tpg_pbf_vorticity_f32: a second walk on the same grid (no new build), p the final positions (finish's x_out):
+ *     eta_i = sum over gradient pairs of fix30((m_i - m_j) * G_ij) per axis     m_j = omega[index_j].w, one 16-byte load;
+ *                                                                                the difference form: uniform m -> eta = 0
+ *     len = sqrtf((eta_x^2 + eta_y^2) + eta_z^2);  N = eta / (len + delta) per axis;  f = N x omega_i
+ *         f_x = N_y*omega_z - N_z*omega_y,  f_y = N_z*omega_x - N_x*omega_z,  f_z = N_x*omega_y - N_y*omega_x
+ *     v_out = v_i + (dt * vs) * f per axis
+ * A wave reads only its own row of v, so v_out may be v.  Rows at or beyond lengths[b] are never read or written.
+ *
+ * Normalisation, in the manner of S0: R0 = (1/3) * sum over z in Z^3, 0 < |z| < 2, of ((2 - |z|)/2)^2 |z| (26 points,
+ * 1.06818514...).  In a cubic lattice of spacing s = h/2 that rotates rigidly at Omega the curl above is s * R0 * 2 Omega,
+ * so omega in 1/s is omega / (s * R0), and the host passes vs = fp32(strength / (s * R0)) with the strength in m/s.
+ * delta > 0 keeps N finite where eta is rounding noise (ops.PBF_VORT_DELTA).
+ *
+ * Checks, in the order of the section above.  TPG_ERR_ARG: h, dt (and delta) not positive and finite, cs (vs) negative or
+ * not finite, a NULL x_out or v_out, x_out == x, a bad workspace (when B, N > 0), negative B or N.  Then B == 0 or
+ * N == 0: TPG_OK before any other pointer is looked at.  Then B > 65535 or N > 2^22: TPG_ERR_UNSUPPORTED; a NULL p, x,
+ * omega or v: TPG_ERR_ARG. */
+int tpg_pbf_finish_ex_f32(const float *p, const float *x, const int64_t *lengths, int B, int N, float h, float dt, float cs,
+                          const float *cs_tab, const void *ws, float *x_out, float *v_out, float *omega_out, void *stream);
+int tpg_pbf_vorticity_f32(const float *p, const float *omega, const float *v, const int64_t *lengths, int B, int N, float h,
+                          float dt, float vs, float delta, const void *ws, float *v_out, void *stream);
+
 /* ---- solid obstacles in the particle fluid simulator (csrc/pbf.hip) ----------------------------------------------
  * Static solids in the way of the fluid: the three shapes the fluid bodies use, each in a rotated frame of its own.  A
  * scene has up to PBF_MAX_OBSTACLES = 8 of them, in a DEVICE table obstacles (B,M,16) f32, one row per obstacle:

@@ -92,6 +92,8 @@ SIGNATURES = {
     "tpg_pbf_lambda_f32": [_P, _P, _I, _I, _F, _F, _F, _P, _P, _P, _P],
     "tpg_pbf_dp_f32": [_P, _P, _P, _P, _I, _I, _F, _F, _F, _F, _F, _P, _P, _P, _P],
     "tpg_pbf_finish_f32": [_P, _P, _P, _I, _I, _F, _F, _F, _P, _P, _P, _P],
+    "tpg_pbf_finish_ex_f32": [_P, _P, _P, _I, _I, _F, _F, _F, _P, _P, _P, _P, _P, _P],
+    "tpg_pbf_vorticity_f32": [_P, _P, _P, _P, _I, _I, _F, _F, _F, _F, _P, _P, _P],
     "tpg_pbf_collide_f32": [_P, _P, _P, _P, _I, _I, _I, _F, _P, _P, _P],
     "tpg_pbf_collide_sdf_f32": [_P, _P, _P, _P, _P, _L, _I, _I, _I, _F, _P, _P, _P],
     "tpg_mesh_sdf_f32": [_P, _P, _P, _I, _I, _I, _P, _F, _P, _P, _P],

@@ -1,7 +1,9 @@
 // Position Based Fluids, Jacobi iterations in gather form (the rule in full: include/tpgan_ops.h, "particle fluid
 // simulator"; the numpy statement: tests/pbf_rule.py).  One substep of every scene of a batch is
 //     predict | iters x ( grid | lambda | dp ) | grid | finish
-// with the scenes on gridDim.y and ragged lengths, as in the grid searches.
+// with the scenes on gridDim.y and ragged lengths, as in the grid searches.  With a per-particle XSPH table or vorticity
+// confinement the tail is grid | finish_ex | vorticity (the rule: "vorticity confinement and per-particle viscosity" in
+// the header; the numpy statement: tests/pbf_vort_rule.py): one more walk of the same grid.
 //
 // Launch shapes.  predict is one thread per particle (streaming, 24 bytes in, 24 out).  lambda, dp and finish are
 // rr_kernel's shape (csrc/radius_reduce.hip): one wave per particle, the 27 cells around it as 9 runs of 3 x-adjacent
@@ -192,10 +194,16 @@ __global__ __launch_bounds__(FG_WAVES * 64) void pbf_dp_kernel(
 }
 
 // step 3: v = (p - x) / dt, XSPH, x = p                     grid (ceil(N/FG_WAVES), B)
+// TABLE: the XSPH coefficient of a pair is the mean of the two particles' entries of cs_tab (B,N), inside the term, so
+// that term_ij = -term_ji in integers; CURL: omega_i = sum u x G over the gradient pairs, on the velocities BEFORE XSPH
+// (the ones this walk has), stored as (x, y, z, |omega|).  <false, false> is the pass of tpg_pbf_finish_f32: h, cs_tab and
+// omega_out are not looked at there.
+template <bool TABLE, bool CURL>
 __global__ __launch_bounds__(FG_WAVES * 64) void pbf_finish_kernel(
     const float *__restrict__ p, const float *__restrict__ x, const int64_t *__restrict__ lengths, int N,
-    const GridParams *__restrict__ gp, const int *__restrict__ start, const float4 *__restrict__ sorted, float h2, float dt,
-    float cs, float *__restrict__ x_out, float *__restrict__ v_out) {
+    const GridParams *__restrict__ gp, const int *__restrict__ start, const float4 *__restrict__ sorted, float h, float h2,
+    float dt, float cs, const float *__restrict__ cs_tab, float *__restrict__ x_out, float *__restrict__ v_out,
+    float4 *__restrict__ omega_out) {
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int b = blockIdx.y, i = blockIdx.x * FG_WAVES + wave;
@@ -205,26 +213,105 @@ __global__ __launch_bounds__(FG_WAVES * 64) void pbf_finish_kernel(
     const float px = p[q * 3], py = p[q * 3 + 1], pz = p[q * 3 + 2];
     const float vx = (px - x[q * 3]) / dt, vy = (py - x[q * 3 + 1]) / dt, vz = (pz - x[q * 3 + 2]) / dt;
     const float *xb = x + (size_t)b * N * 3;
-    long long ax = 0, ay = 0, az = 0;
+    float ci = 0.0f;
+    const float *cb = nullptr;
+    if constexpr (TABLE) {
+        cb = cs_tab + (size_t)b * N;
+        ci = cb[i];
+    }
+    long long ax = 0, ay = 0, az = 0, wx = 0, wy = 0, wz = 0;
     pbf_walk(gp[b], start + (size_t)b * (FG_CELLS + 1), sorted + (size_t)b * N, px, py, pz, lane, [&](const float4 c) {
         const float d2 = tpg_sq3(px, py, pz, c.x, c.y, c.z);
         if (!(d2 < h2)) return;
         const float w = pbf_w(d2, h2);
-        const float *xj = xb + (size_t)tpg_clamp_idx(__float_as_int(c.w), n) * 3;
-        ax += pbf_fix30(((c.x - xj[0]) / dt - vx) * w);
-        ay += pbf_fix30(((c.y - xj[1]) / dt - vy) * w);
-        az += pbf_fix30(((c.z - xj[2]) / dt - vz) * w);
+        const int j = tpg_clamp_idx(__float_as_int(c.w), n);
+        const float *xj = xb + (size_t)j * 3;
+        const float ux = (c.x - xj[0]) / dt - vx, uy = (c.y - xj[1]) / dt - vy, uz = (c.z - xj[2]) / dt - vz;
+        if constexpr (TABLE) {
+            const float cij = 0.5f * (ci + cb[j]);
+            ax += pbf_fix30(cij * (ux * w));
+            ay += pbf_fix30(cij * (uy * w));
+            az += pbf_fix30(cij * (uz * w));
+        } else {
+            ax += pbf_fix30(ux * w);
+            ay += pbf_fix30(uy * w);
+            az += pbf_fix30(uz * w);
+        }
+        if constexpr (CURL) {
+            if (d2 == 0.0f) return;
+            const float d = sqrtf(d2), t = (h - d) / h, t2 = t * t;
+            const float gx = t2 * ((px - c.x) / d), gy = t2 * ((py - c.y) / d), gz = t2 * ((pz - c.z) / d);
+            wx += pbf_fix30(uy * gz - uz * gy);
+            wy += pbf_fix30(uz * gx - ux * gz);
+            wz += pbf_fix30(ux * gy - uy * gx);
+        }
+    });
+    ax = tpg_wave_add_u64(ax);
+    ay = tpg_wave_add_u64(ay);
+    az = tpg_wave_add_u64(az);
+    if constexpr (CURL) {
+        wx = tpg_wave_add_u64(wx);
+        wy = tpg_wave_add_u64(wy);
+        wz = tpg_wave_add_u64(wz);
+    }
+    if (lane == 0) {
+        if constexpr (TABLE) {
+            v_out[q * 3] = vx + (float)ax * PBF_INV_U30;
+            v_out[q * 3 + 1] = vy + (float)ay * PBF_INV_U30;
+            v_out[q * 3 + 2] = vz + (float)az * PBF_INV_U30;
+        } else {
+            v_out[q * 3] = vx + cs * ((float)ax * PBF_INV_U30);
+            v_out[q * 3 + 1] = vy + cs * ((float)ay * PBF_INV_U30);
+            v_out[q * 3 + 2] = vz + cs * ((float)az * PBF_INV_U30);
+        }
+        x_out[q * 3] = px;
+        x_out[q * 3 + 1] = py;
+        x_out[q * 3 + 2] = pz;
+        if constexpr (CURL) {
+            const float ox = (float)wx * PBF_INV_U30, oy = (float)wy * PBF_INV_U30, oz = (float)wz * PBF_INV_U30;
+            omega_out[q] = make_float4(ox, oy, oz, sqrtf((ox * ox + oy * oy) + oz * oz));
+        }
+    }
+}
+
+// vorticity confinement: eta_i = sum (m_i - m_j) G_ij over the gradient pairs, m = |omega| of the finish pass (the
+// difference form: a uniform |omega| gives eta = 0 exactly); N = eta / (|eta| + delta); v_out = v + (dt * vs) * (N x omega_i).
+// v_out may be v (a wave reads only its own row of v; a neighbour's m comes from omega, which no wave writes), hence
+// no __restrict__ on the two                                  grid (ceil(N/FG_WAVES), B)
+__global__ __launch_bounds__(FG_WAVES * 64) void pbf_vorticity_kernel(
+    const float *__restrict__ p, const float4 *__restrict__ omega, const float *v, const int64_t *__restrict__ lengths,
+    int N, const GridParams *__restrict__ gp, const int *__restrict__ start, const float4 *__restrict__ sorted, float h,
+    float h2, float dt, float vs, float delta, float *v_out) {
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int b = blockIdx.y, i = blockIdx.x * FG_WAVES + wave;
+    const int n = pbf_len(lengths, b, N);
+    if (i >= n) return;
+    const size_t q = (size_t)b * N + i;
+    const float px = p[q * 3], py = p[q * 3 + 1], pz = p[q * 3 + 2];
+    const float4 *ob = omega + (size_t)b * N;
+    const float4 oi = ob[i];
+    long long ax = 0, ay = 0, az = 0;
+    pbf_walk(gp[b], start + (size_t)b * (FG_CELLS + 1), sorted + (size_t)b * N, px, py, pz, lane, [&](const float4 c) {
+        const float d2 = tpg_sq3(px, py, pz, c.x, c.y, c.z);
+        if (!(d2 < h2) || d2 == 0.0f) return;
+        const float dm = oi.w - ob[tpg_clamp_idx(__float_as_int(c.w), n)].w;
+        const float d = sqrtf(d2), t = (h - d) / h, t2 = t * t;
+        ax += pbf_fix30(dm * (t2 * ((px - c.x) / d)));
+        ay += pbf_fix30(dm * (t2 * ((py - c.y) / d)));
+        az += pbf_fix30(dm * (t2 * ((pz - c.z) / d)));
     });
     ax = tpg_wave_add_u64(ax);
     ay = tpg_wave_add_u64(ay);
     az = tpg_wave_add_u64(az);
     if (lane == 0) {
-        v_out[q * 3] = vx + cs * ((float)ax * PBF_INV_U30);
-        v_out[q * 3 + 1] = vy + cs * ((float)ay * PBF_INV_U30);
-        v_out[q * 3 + 2] = vz + cs * ((float)az * PBF_INV_U30);
-        x_out[q * 3] = px;
-        x_out[q * 3 + 1] = py;
-        x_out[q * 3 + 2] = pz;
+        const float ex = (float)ax * PBF_INV_U30, ey = (float)ay * PBF_INV_U30, ez = (float)az * PBF_INV_U30;
+        const float den = sqrtf((ex * ex + ey * ey) + ez * ez) + delta;
+        const float nx = ex / den, ny = ey / den, nz = ez / den;
+        const float s = dt * vs;
+        v_out[q * 3] = v[q * 3] + s * (ny * oi.z - nz * oi.y);
+        v_out[q * 3 + 1] = v[q * 3 + 1] + s * (nz * oi.x - nx * oi.z);
+        v_out[q * 3 + 2] = v[q * 3 + 2] + s * (nx * oi.y - ny * oi.x);
     }
 }
 
@@ -332,8 +419,51 @@ extern "C" int tpg_pbf_finish_f32(const float *p, const float *x, const int64_t 
     if (chk) return chk > 0 ? TPG_OK : chk;
     if (!p || !x) return TPG_ERR_ARG;
     const GridView v = fg_view(ws, B, N);
-    hipLaunchKernelGGL(pbf_finish_kernel, dim3(fg_query_blocks(N), B), dim3(FG_WAVES * 64), 0, tpg_stream(stream), p, x,
-                       lengths, N, v.gp, v.start, v.sorted, h * h, dt, cs, x_out, v_out);
+    hipLaunchKernelGGL((pbf_finish_kernel<false, false>), dim3(fg_query_blocks(N), B), dim3(FG_WAVES * 64), 0,
+                       tpg_stream(stream), p, x, lengths, N, v.gp, v.start, v.sorted, h, h * h, dt, cs,
+                       (const float *)nullptr, x_out, v_out, (float4 *)nullptr);
+    TPG_RETURN_IF_LAUNCH_FAILED();
+    return TPG_OK;
+}
+
+// finish with a per-particle XSPH table and / or the curl (the rule: include/tpgan_ops.h, "vorticity confinement and
+// per-particle viscosity"); with neither it is tpg_pbf_finish_f32
+extern "C" int tpg_pbf_finish_ex_f32(const float *p, const float *x, const int64_t *lengths, int B, int N, float h, float dt,
+                                     float cs, const float *cs_tab, const void *ws, float *x_out, float *v_out,
+                                     float *omega_out, void *stream) {
+    if (!pbf_pos(h) || !pbf_pos(dt) || !(cs >= 0.0f) || !(cs <= 3.0e38f) || !x_out || !v_out || x_out == x) return TPG_ERR_ARG;
+    if (B > 0 && N > 0 && !fg_workspace_ok(ws)) return TPG_ERR_ARG;
+    const int chk = pbf_shape(B, N);
+    if (chk) return chk > 0 ? TPG_OK : chk;
+    if (!p || !x) return TPG_ERR_ARG;
+    const GridView v = fg_view(ws, B, N);
+    const dim3 grid(fg_query_blocks(N), B), block(FG_WAVES * 64);
+    hipStream_t st = tpg_stream(stream);
+    float4 *om = reinterpret_cast<float4 *>(omega_out);
+#define PBF_FINISH(TABLE, CURL)                                                                                        \
+    hipLaunchKernelGGL((pbf_finish_kernel<TABLE, CURL>), grid, block, 0, st, p, x, lengths, N, v.gp, v.start, v.sorted, h, \
+                       h * h, dt, cs, cs_tab, x_out, v_out, om)
+    if (cs_tab && om) PBF_FINISH(true, true);
+    else if (cs_tab) PBF_FINISH(true, false);
+    else if (om) PBF_FINISH(false, true);
+    else PBF_FINISH(false, false);
+#undef PBF_FINISH
+    TPG_RETURN_IF_LAUNCH_FAILED();
+    return TPG_OK;
+}
+
+extern "C" int tpg_pbf_vorticity_f32(const float *p, const float *omega, const float *v, const int64_t *lengths, int B,
+                                     int N, float h, float dt, float vs, float delta, const void *ws, float *v_out,
+                                     void *stream) {
+    if (!pbf_pos(h) || !pbf_pos(dt) || !(vs >= 0.0f) || !(vs <= 3.0e38f) || !pbf_pos(delta) || !v_out) return TPG_ERR_ARG;
+    if (B > 0 && N > 0 && !fg_workspace_ok(ws)) return TPG_ERR_ARG;
+    const int chk = pbf_shape(B, N);
+    if (chk) return chk > 0 ? TPG_OK : chk;
+    if (!p || !omega || !v) return TPG_ERR_ARG;
+    const GridView g = fg_view(ws, B, N);
+    hipLaunchKernelGGL(pbf_vorticity_kernel, dim3(fg_query_blocks(N), B), dim3(FG_WAVES * 64), 0, tpg_stream(stream), p,
+                       reinterpret_cast<const float4 *>(omega), v, lengths, N, g.gp, g.start, g.sorted, h, h * h, dt, vs,
+                       delta, v_out);
     TPG_RETURN_IF_LAUNCH_FAILED();
     return TPG_OK;
 }

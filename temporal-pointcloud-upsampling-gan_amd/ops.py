@@ -412,6 +412,19 @@ class HipBackend:
         self._call("tpg_pbf_finish_f32", "pbf_finish", 48 * B * N, p, _ptr(p), _ptr(x), _ptr(lengths), B, N, prm.h, dt,
                    prm.cs, _ptr(ws), _ptr(x_out), _ptr(v_out))
 
+    def pbf_finish_ex(self, p, x, lengths, dt, prm, ws, x_out, v_out, cs_tab=None, omega_out=None):
+        """finish with a per-particle XSPH table cs_tab (B,N) and / or the curl into omega_out (B,N,4)."""
+        B, N, _ = p.shape
+        extra = (8 if cs_tab is not None else 0) + (16 if omega_out is not None else 0)
+        self._call("tpg_pbf_finish_ex_f32", "pbf_finish_ex", (48 + extra) * B * N, p, _ptr(p), _ptr(x), _ptr(lengths), B, N,
+                   prm.h, dt, prm.cs, _ptr(cs_tab), _ptr(ws), _ptr(x_out), _ptr(v_out), _ptr(omega_out))
+
+    def pbf_vorticity(self, p, omega, v, lengths, dt, prm, ws, v_out):
+        """v_out = v + confinement force (v_out may be v), on the grid and the omega the finish pass left."""
+        B, N, _ = p.shape
+        self._call("tpg_pbf_vorticity_f32", "pbf_vorticity", 68 * B * N, p, _ptr(p), _ptr(omega), _ptr(v), _ptr(lengths),
+                   B, N, prm.h, dt, prm.vs, prm.delta, _ptr(ws), _ptr(v_out))
+
     def pbf_collide(self, p, lengths, box, obstacles, prm, p_out, hit_out=None):
         """p_out = collide(p) (p_out may be p): the obstacles (B,M,16) in index order, then the box clamp."""
         B, N, _ = p.shape
@@ -426,11 +439,13 @@ class HipBackend:
                    _ptr(p), _ptr(lengths), box.ctypes.data, _ptr(table), _ptr(fields), fields.numel(), B, N, table.shape[1],
                    prm.radius, _ptr(p_out), _ptr(hit_out))
 
-    def pbf_substep(self, x, v, lengths, box, dt, prm, x_out, v_out, obstacles=None, sdf_obstacles=None):
+    def pbf_substep(self, x, v, lengths, box, dt, prm, x_out, v_out, obstacles=None, sdf_obstacles=None, xsph=None):
         """One substep of every scene: predict | iters x (grid | lambda | dp) | grid | finish.  x_out / v_out receive the
         rows below lengths; p and lambda are per-stream workspaces, the dp pass updates p in place.  obstacles (B,M,16):
         a collide launch in place after predict and after every dp; None: no such launch.  sdf_obstacles (table, fields):
-        a collide_sdf launch in the same places, behind collide; None: no such launch."""
+        a collide_sdf launch in the same places, behind collide; None: no such launch.  xsph (B,N): the per-particle XSPH
+        table; with it or with prm.vorticity > 0 the tail is grid | finish_ex | vorticity (the last only for vorticity
+        > 0, in place on v_out, reading the per-stream workspace omega that finish_ex wrote)."""
         B, N, _ = x.shape
         ws = self.pbf_ws(x, B, N)
         p = self._workspace("pbf_p", x, B * N * 3)[:B * N * 3].view(B, N, 3)
@@ -449,7 +464,13 @@ class HipBackend:
             self.pbf_dp(p, lam, lengths, box, prm, ws, p)
             solids()
         self.pbf_grid(p, lengths, prm, ws)
-        self.pbf_finish(p, x, lengths, dt, prm, ws, x_out, v_out)
+        if xsph is None and prm.vorticity == 0.0:
+            self.pbf_finish(p, x, lengths, dt, prm, ws, x_out, v_out)
+            return x_out, v_out
+        omega = self._workspace("pbf_omega", x, B * N * 4)[:B * N * 4].view(B, N, 4) if prm.vorticity > 0.0 else None
+        self.pbf_finish_ex(p, x, lengths, dt, prm, ws, x_out, v_out, xsph, omega)
+        if omega is not None:
+            self.pbf_vorticity(p, omega, v_out, lengths, dt, prm, ws, v_out)
         return x_out, v_out
 
     # ---- signed distance to a triangle mesh (csrc/mesh_sdf.hip; the rule: include/tpgan_ops.h)
@@ -2097,6 +2118,16 @@ PBF_K = 0.2                            # tensile term: at 0.1 and below a splash
 #                                        above 0.4 s while a pool at rest stays within 2 % of the lattice density
 PBF_XSPH = 0.05                        # XSPH c: a pool's rms speed falls below 0.02 m/s within 2 s, splashes are not damped
 PBF_MAX_N = 1 << 22                    # particles per scene: the fixed-point sums' headroom (csrc/pbf.hip)
+PBF_XSPH_MAX = 0.5                     # cap of c(viscosity): one XSPH application scales a velocity deviation by
+#                                        1 - c n / S0, a contraction while c n / S0 < 2: at 0.5 up to 4 x the rest density
+PBF_VISCOSITY = 0.01                   # the viscosity whose coefficient is PBF_XSPH: the liquid of every scene so far
+PBF_VORTICITY = 0.4                    # shipped confinement strength in m/s: the largest rung of 0.0125 * 2^k, k = 0..5, at
+#                                        which a dropped body keeps the bounds of tests/test_simulate_cpu.py and comes to
+#                                        rest as without it (the ladder and the energy it adds: DESIGN.md, section 4s)
+PBF_VORT_DELTA = 2.0 ** -13            # N = eta / (|eta| + delta).  Smallest power of two that keeps |N| < 2^-10 on every
+#                                        interior particle of a rigidly rotating lattice, where eta is exactly 0 in exact
+#                                        arithmetic: the rounding noise measured there (7^3 particles, 3 rad/s,
+#                                        tests/pbf_vort_cases.py) is |eta| <= 8.6e-8 against m = 0.16, so 2^-14 fails
 _F32 = np.float32
 
 
@@ -2108,12 +2139,27 @@ def pbf_lattice_sum():
     return float((np.clip(1.0 - z2 / 4.0, 0.0, None) ** 3).sum())
 
 
+def pbf_lattice_curl():
+    """R0 = (1/3) sum of ((2 - |z|) / 2)^2 |z| over the points z of Z^3 with 0 < |z| < 2 (26 of them), in float64: in a
+    cubic lattice of spacing s = h / 2 that rotates rigidly at Omega, the curl of the rule (include/tpgan_ops.h,
+    "vorticity confinement") is s * R0 * 2 Omega."""
+    r = np.arange(-2, 3, dtype=np.float64)
+    z = np.sqrt((r[:, None, None] ** 2 + r[None, :, None] ** 2) + r[None, None, :] ** 2)
+    return float((np.clip((2.0 - z) / 2.0, 0.0, None) ** 2 * z).sum() / 3.0)
+
+
 class PbfParams:
     """The constants of one simulation, each rounded to fp32 once (include/tpgan_ops.h): radius a, h = 4a, S0, wq,
-    dp_scale = -7 h S0 / 64, cs = c / S0, eps, k, gravity, and the iteration count."""
+    dp_scale = -7 h S0 / 64, cs = c / S0, eps, k, gravity, and the iteration count.  vorticity: the confinement strength
+    in m/s (0: none, and no launch for it), carried as vs = vorticity / (s R0) with s = 2a, beside delta."""
 
-    def __init__(self, radius=PBF_RADIUS, iters=PBF_ITERS, eps=PBF_EPS, k=PBF_K, c=PBF_XSPH, gravity=PBF_GRAVITY):
+    def __init__(self, radius=PBF_RADIUS, iters=PBF_ITERS, eps=PBF_EPS, k=PBF_K, c=PBF_XSPH, gravity=PBF_GRAVITY,
+                 vorticity=0.0):
         S0 = pbf_lattice_sum()
+        self.vorticity = float(vorticity)
+        self.vs = float(_F32(float(vorticity) / (2.0 * float(radius) * pbf_lattice_curl())))
+        self.delta = float(_F32(PBF_VORT_DELTA))
+        _need(np.isfinite(self.vs) and self.vs >= 0.0, "vorticity must be finite and not negative")
         self.radius = float(_F32(radius))
         self.h = float(_F32(4.0 * float(radius)))
         self.S0 = float(_F32(S0))
@@ -2130,7 +2176,10 @@ class PbfParams:
         _need(all(np.isfinite(v) for v in (self.eps, self.k, self.cs) + self.gravity), "parameters must be finite")
 
     def as_dict(self):
-        return dict(radius=self.radius, iters=self.iters, eps=self.eps, k=self.k, c=self.c, gravity=list(self.gravity))
+        d = dict(radius=self.radius, iters=self.iters, eps=self.eps, k=self.k, c=self.c, gravity=list(self.gravity))
+        if self.vorticity != 0.0:                           # without confinement: the dict of before
+            d["vorticity"] = self.vorticity
+        return d
 
 
 def _pbf_candidates_torch(p, h):
@@ -2221,13 +2270,41 @@ def _pbf_dp_torch(p, lam, pr, lo, hi, prm):
     return _pbf_clamp(p + dp, lo, hi, f(prm.radius)), dp
 
 
-def _pbf_finish_torch(p, x, dt, prm, neighbours=_pbf_candidates_torch):
-    """Velocity and XSPH for one cloud -> v."""
+def _pbf_finish_torch(p, x, dt, prm, neighbours=_pbf_candidates_torch, cs_tab=None, curl=False, pairs=None):
+    """Velocity and XSPH for one cloud -> v.  cs_tab (n,): the per-particle table of finish_ex (the pair's mean inside the
+    term, no outer factor); curl: -> (v, omega (n,4)) with omega = sum u x G on the velocities before XSPH and its length
+    in the last column; pairs: the `_PbfPairs` of p, when the caller has them."""
     f = lambda v: torch.tensor(v, dtype=torch.float32, device=p.device)          # noqa: E731
-    pr = _PbfPairs(p, prm, neighbours)
+    pr = _PbfPairs(p, prm, neighbours) if pairs is None else pairs
     v = (p - x) / f(dt)
-    acc = pr.total(pr.i, _pbf_fix30((v[pr.j] - v[pr.i]) * pr.W.unsqueeze(1)))
-    return v + f(prm.cs) * (acc.to(torch.float32) * (1.0 / _PBF_U30))
+    uw = (v[pr.j] - v[pr.i]) * pr.W.unsqueeze(1)
+    if cs_tab is None:
+        out = v + f(prm.cs) * (pr.total(pr.i, _pbf_fix30(uw)).to(torch.float32) * (1.0 / _PBF_U30))
+    else:
+        cij = 0.5 * (cs_tab[pr.i] + cs_tab[pr.j])
+        out = v + pr.total(pr.i, _pbf_fix30(cij.unsqueeze(1) * uw)).to(torch.float32) * (1.0 / _PBF_U30)
+    if not curl:
+        return out
+    u, G = v[pr.gj] - v[pr.gi], pr.G
+    cross = torch.stack([u[:, 1] * G[:, 2] - u[:, 2] * G[:, 1], u[:, 2] * G[:, 0] - u[:, 0] * G[:, 2],
+                         u[:, 0] * G[:, 1] - u[:, 1] * G[:, 0]], 1)
+    om = pr.total(pr.gi, _pbf_fix30(cross)).to(torch.float32) * (1.0 / _PBF_U30)
+    m = torch.sqrt(((om[:, 0] * om[:, 0] + om[:, 1] * om[:, 1]) + om[:, 2] * om[:, 2]).double()).float()
+    return out, torch.cat([om, m.unsqueeze(1)], 1)
+
+
+def _pbf_vorticity_torch(p, omega, v, dt, prm, neighbours=_pbf_candidates_torch, pairs=None):
+    """Vorticity confinement for one cloud: p (n,3) the final positions, omega (n,4) of `_pbf_finish_torch(curl=True)`,
+    v (n,3) the velocities after XSPH -> v + (dt vs) (N x omega), N = eta / (|eta| + delta), eta = sum (m_i - m_j) G."""
+    f = lambda s: torch.tensor(s, dtype=torch.float32, device=p.device)          # noqa: E731
+    pr = _PbfPairs(p, prm, neighbours) if pairs is None else pairs
+    m = omega[:, 3]
+    eta = pr.total(pr.gi, _pbf_fix30((m[pr.gi] - m[pr.gj]).unsqueeze(1) * pr.G)).to(torch.float32) * (1.0 / _PBF_U30)
+    length = torch.sqrt(((eta[:, 0] * eta[:, 0] + eta[:, 1] * eta[:, 1]) + eta[:, 2] * eta[:, 2]).double()).float()
+    n = eta / (length + f(prm.delta)).unsqueeze(1)
+    force = torch.stack([n[:, 1] * omega[:, 2] - n[:, 2] * omega[:, 1], n[:, 2] * omega[:, 0] - n[:, 0] * omega[:, 2],
+                         n[:, 0] * omega[:, 1] - n[:, 1] * omega[:, 0]], 1)
+    return v + (f(dt) * f(prm.vs)) * force
 
 
 def _pbf_collide_torch(p, lo, hi, table, prm, hit=None):
@@ -2279,12 +2356,13 @@ def _pbf_collide_torch(p, lo, hi, table, prm, hit=None):
 
 
 def _pbf_substep_torch(x, v, lengths, box, dt, prm, neighbours=_pbf_candidates_torch, obstacles=None,
-                       sdf_obstacles=None):
+                       sdf_obstacles=None, xsph=None):
     """`pbf_substep` composed of torch ops, scene by scene: the same fp32 operations in the same order and the same
     fixed-point sums as csrc/pbf.hip (the rule: include/tpgan_ops.h), so the results are EQUAL to the kernels'.
     `neighbours(p, h) -> (i, j)` supplies candidate pairs (any superset of the pairs within h).  obstacles (B,M,16) or
     None: collide after predict and after every dp; sdf_obstacles (table (B,M,24), fields) or None: collide_sdf in the
-    same places, behind collide."""
+    same places, behind collide.  xsph (B,N) or None: the per-particle XSPH table of finish_ex; prm.vorticity > 0: the
+    curl in the finish pass and the confinement pass behind it."""
     B, N, _ = x.shape
     x_out, v_out = x.clone(), v.clone()
     lens = [N] * B if lengths is None else [min(max(int(n), 0), N) for n in lengths.tolist()]
@@ -2307,7 +2385,17 @@ def _pbf_substep_torch(x, v, lengths, box, dt, prm, neighbours=_pbf_candidates_t
             lam, _, pr = _pbf_lambda_torch(p, prm, neighbours)
             p, _ = _pbf_dp_torch(p, lam, pr, lo, hi, prm)
             p = solids(p)
-        v_out[b, :n] = _pbf_finish_torch(p, xb, dt, prm, neighbours)
+        if xsph is None and prm.vorticity == 0.0:
+            v_out[b, :n] = _pbf_finish_torch(p, xb, dt, prm, neighbours)
+        else:
+            pr = _PbfPairs(p, prm, neighbours)
+            tab = None if xsph is None else xsph[b, :n]
+            if prm.vorticity > 0.0:
+                vb, omega = _pbf_finish_torch(p, xb, dt, prm, neighbours, tab, True, pr)
+                vb = _pbf_vorticity_torch(p, omega, vb, dt, prm, neighbours, pr)
+            else:
+                vb = _pbf_finish_torch(p, xb, dt, prm, neighbours, tab, False, pr)
+            v_out[b, :n] = vb
         x_out[b, :n] = p
     return x_out, v_out
 
@@ -2406,7 +2494,27 @@ def pbf_collide(p, lengths, box_lo, box_hi, obstacles, params=None, return_hit=F
     return (out, hit) if return_hit else out
 
 
-def pbf_substep(x, v, lengths, box_lo, box_hi, dt, params=None, obstacles=None, sdf_obstacles=None):
+def pbf_xsph_coefficient(viscosity):
+    """c(nu) = min(PBF_XSPH * nu / PBF_VISCOSITY, PBF_XSPH_MAX) in float64, elementwise.  nu is a knob of THIS solver (the
+    XSPH blend of a particle's velocity with its neighbours'), not a physical viscosity and not SPlisHSPlasH's."""
+    return np.minimum(PBF_XSPH * np.asarray(viscosity, np.float64) / PBF_VISCOSITY, PBF_XSPH_MAX)
+
+
+def pbf_xsph(viscosity, params=None, device="cuda"):
+    """The per-particle XSPH table of `pbf_substep(xsph=)`: viscosity (B,N), a host array or a tensor of nu per
+    particle (finite, not negative; rows beyond a scene's length hold anything valid, 0 say) -> cs = fp32(c(nu) / S0),
+    a (B,N) fp32 tensor on `device` (a tensor's own device when `viscosity` is one).  Build it once per batch."""
+    if isinstance(viscosity, torch.Tensor):
+        device, viscosity = viscosity.device, viscosity.detach().cpu().numpy()
+    nu = np.asarray(viscosity, np.float64)
+    _need(nu.ndim == 2, "viscosity must be (B,N)")
+    _need(bool(np.isfinite(nu).all()) and bool((nu >= 0.0).all()), "viscosity must be finite and not negative")
+    prm = PbfParams() if params is None else params
+    cs = (pbf_xsph_coefficient(nu) / prm.S0).astype(np.float32)
+    return torch.from_numpy(np.ascontiguousarray(cs)).to(device)
+
+
+def pbf_substep(x, v, lengths, box_lo, box_hi, dt, params=None, obstacles=None, sdf_obstacles=None, xsph=None):
     """One substep of the particle fluid simulator (Position Based Fluids, Jacobi, gather form; csrc/pbf.hip, the rule
     in full: include/tpgan_ops.h) for every scene of a ragged batch.
 
@@ -2415,7 +2523,10 @@ def pbf_substep(x, v, lengths, box_lo, box_hi, dt, params=None, obstacles=None, 
     box_lo, box_hi: HOST values, 3 shared by the batch or (B,3); dt > 0; params: a `PbfParams` (None: the defaults);
     obstacles: the device table (B,M,16) of `pbf_obstacles`: static solids, applied after predict and after every dp
     pass (None: no obstacles, and no launch for them); sdf_obstacles: the (table, fields) pair of `pbf_sdf_obstacles`:
-    mesh obstacles as sampled distance fields, applied in the same places behind the analytic ones (None: no launch).
+    mesh obstacles as sampled distance fields, applied in the same places behind the analytic ones (None: no launch);
+    xsph: the (B,N) device table of `pbf_xsph`, an XSPH coefficient per particle in place of params.c (None: params.c).
+    With xsph or params.vorticity > 0 the substep ends grid | finish_ex | vorticity (include/tpgan_ops.h, "vorticity
+    confinement and per-particle viscosity"); with neither it is the substep of before, launch for launch.
     -> (x, v) new tensors.  Bit-identical from run to run, at every batch position, and equal to `_pbf_substep_torch`,
     which backends without the kernels run (CPU tensors need a registered checker, as everywhere).  No gradient."""
     _check_float(x, "x", 3)
@@ -2434,8 +2545,20 @@ def pbf_substep(x, v, lengths, box_lo, box_hi, dt, params=None, obstacles=None, 
     _need(np.isfinite(dt) and dt > 0.0, "dt must be positive and finite")
     box = pbf_box(box_lo, box_hi, B)
     lengths = _lengths(lengths, B, N, x.device)
+    if xsph is not None:
+        _check_float(xsph, "xsph", 2)
+        _need(xsph.shape == (B, N), "xsph must be (B,N)")
+        _same_device(x, xsph)
+        xsph = xsph.detach()
     be = backend_for(x)
     with torch.no_grad():
+        if xsph is not None or prm.vorticity != 0.0:
+            if hasattr(be, "pbf_finish_ex"):
+                return be.pbf_substep(x.detach(), v.detach(), lengths, box, dt, prm, x.clone(), v.clone(), obstacles,
+                                      sdf_obstacles, xsph)
+            # a backend without finish_ex (the CPU checker): the whole substep as torch ops, as for sdf_obstacles below
+            return _pbf_substep_torch(x.detach(), v.detach(), lengths, box, dt, prm, obstacles=obstacles,
+                                      sdf_obstacles=sdf_obstacles, xsph=xsph)
         if sdf_obstacles is None:                       # the calls of before, argument for argument
             if hasattr(be, "pbf_substep"):
                 return be.pbf_substep(x.detach(), v.detach(), lengths, box, dt, prm, x.clone(), v.clone(), obstacles)

@@ -4,6 +4,7 @@
         [--particle_radius 0.0125 --substeps 4 --iters 4 --box 3 2.5 3 --body_size 0.68 --batch 8 --device cuda]
         [--obstacles 2 --obstacle_size 0.3 0.6]
         [--fluid_mesh SPEC ... --obstacle_mesh SPEC ...]          SPEC: a .obj / .ply path, icosphere:3, torus:0.5,0.2,48,24
+        [--viscosity exponential|uniform|log10_uniform --vorticity [EPS]]
 
 writes `DATA/case{c}/data_{s}.npz` (`pos`, `vel`: float32 (N,3)) for c = 1.., s = 0.., the layout `data.FluidSequences`
 and `python -m tpgan_amd.train --train_dataset_path DATA` read, and `DATA/case{c}/scene.json` beside them.
@@ -12,7 +13,10 @@ obstacles") into the lower half of every scene; `scene.json` records them and `D
 surface (`obstacle_mesh`), to be loaded beside the fluid's meshes.  --fluid_mesh / --obstacle_mesh add closed triangle
 meshes to the shapes the bodies / the obstacles are drawn from: a mesh body is filled with the lattice nodes at least a
 particle radius inside it (`ops.mesh_sdf`), a mesh obstacle is its distance field sampled once per batch
-(`ops.pbf_sdf_obstacles`, the rule: include/tpgan_ops.h, "mesh obstacles").
+(`ops.pbf_sdf_obstacles`, the rule: include/tpgan_ops.h, "mesh obstacles").  --viscosity LAW draws a viscosity per fluid
+body as the reference's recipe does and turns it into an XSPH coefficient per particle (`ops.pbf_xsph`; a knob of this
+solver, not a physical viscosity); --vorticity adds vorticity confinement (the rule: include/tpgan_ops.h, "vorticity
+confinement and per-particle viscosity").  `scene.json` records the viscosities per body and the strength in `params`.
 
 The reference makes these directories with an external solver (fluid_data_generation/ drives SPlisHSPlasH's DFSPH on
 scenes from create_physics_scenes.py, with models it does not ship).  Here the solver is the project's own: Position
@@ -81,7 +85,8 @@ def mesh_distance(spec, size, points, device=None):
 
 class Scene:
     """A box and the fluid in it at t = 0.  `bodies`: dicts of shape, size (the scaled edge), rotation (3x3, row-major),
-    centre and velocity, from which `particles()` rebuilds the same points; or explicit `pos` / `vel` (n,3).
+    centre and velocity, from which `particles()` rebuilds the same points, and optionally "viscosity" (`viscosity()`); or
+    explicit `pos` / `vel` (n,3).
     `obstacles`: the static solids in the box, dicts as `ops.pbf_obstacles` takes them (shape, centre, rotation, size).
     A body or obstacle of shape "mesh" names its triangle mesh in "mesh" (a SPEC); its size is the largest extent."""
 
@@ -90,6 +95,7 @@ class Scene:
         self.box_hi = [float(v) for v in box_hi]
         self.bodies, self.seed, self.radius = list(bodies), seed, float(radius)
         self.obstacles = list(obstacles)
+        self._counts = None                                  # particles per body, once `particles()` has built them
         self._pos = None if pos is None else np.ascontiguousarray(pos, dtype=np.float32).reshape(-1, 3)
         self._vel = None if vel is None else np.ascontiguousarray(vel, dtype=np.float32).reshape(-1, 3)
 
@@ -97,12 +103,24 @@ class Scene:
         """-> pos, vel (n,3) float32."""
         if self._pos is None:
             pos = [body_points(b, 2.0 * self.radius) for b in self.bodies]
+            self._counts = [p.shape[0] for p in pos]
             vel = [np.broadcast_to(np.asarray(b["velocity"], np.float64), p.shape) for b, p in zip(self.bodies, pos)]
             self._pos = np.concatenate(pos).astype(np.float32) if pos else np.zeros((0, 3), np.float32)
             self._vel = np.concatenate(vel).astype(np.float32) if vel else np.zeros((0, 3), np.float32)
         if self._vel is None:
             self._vel = np.zeros_like(self._pos)
         return self._pos, self._vel
+
+    def viscosity(self):
+        """-> the viscosity of every particle (n,) float64, from the bodies' "viscosity" (`ops.PBF_VISCOSITY` for a body
+        without one); None when no body has the key, or the scene was given as explicit particles."""
+        if not any("viscosity" in b for b in self.bodies):
+            return None
+        self.particles()
+        if self._counts is None:
+            return None
+        return np.concatenate([np.full(n, float(b.get("viscosity", ops.PBF_VISCOSITY)))
+                               for b, n in zip(self.bodies, self._counts)])
 
     def to_json(self):
         d = {"seed": self.seed, "box_lo": self.box_lo, "box_hi": self.box_hi, "particle_radius": self.radius,
@@ -197,8 +215,23 @@ def random_obstacles(rng, count, box, spacing, size_range=OBSTACLE_SIZE, max_tri
     raise RuntimeError(f"no room for {count} obstacles of {size_range} m in the lower half of the box {box.tolist()}")
 
 
+VISCOSITY_LAWS = ("exponential", "uniform", "log10_uniform")
+
+
+def draw_viscosity(rng, law):
+    """One body's viscosity by the reference recipe's laws: exponential with scale 1/20 plus 0.01 (its default), U(0.01,
+    0.3), or 0.01 * 10^U(0, 1.5).  A knob of this project's solver (`ops.pbf_xsph`), not SPlisHSPlasH's viscosity."""
+    if law == "exponential":
+        return float(rng.exponential(scale=1.0 / 20.0) + 0.01)
+    if law == "uniform":
+        return float(rng.uniform(0.01, 0.3))
+    if law == "log10_uniform":
+        return float(0.01 * 10.0 ** rng.uniform(0.0, 1.5))
+    raise ValueError(f"viscosity must be None or one of {VISCOSITY_LAWS}")
+
+
 def random_scene(seed, box=DEFAULT_BOX, radius=ops.PBF_RADIUS, body_size=BODY_SIZE, count_range=None, max_tries=1000,
-                 obstacles=0, obstacle_size=OBSTACLE_SIZE, fluid_meshes=(), obstacle_meshes=()):
+                 obstacles=0, obstacle_size=OBSTACLE_SIZE, fluid_meshes=(), obstacle_meshes=(), viscosity=None):
     """The scene of `seed` (an int or a sequence of ints), everything drawn from numpy.random.default_rng(seed): one to
     three bodies, each a box, ball or upright cylinder of `body_size` scaled by U(0.5, 1.5) and rotated at random, placed
     by rejection so that the bodies' bounding spheres stay a particle spacing apart and inside the box, thrown with a
@@ -209,8 +242,13 @@ def random_scene(seed, box=DEFAULT_BOX, radius=ops.PBF_RADIUS, body_size=BODY_SI
     a body is then also rejected unless its bounding sphere stays a spacing clear of every obstacle's.
     fluid_meshes / obstacle_meshes: SPECs of closed triangle meshes that join the shapes bodies / obstacles are drawn from.
     Which draw becomes a mesh is decided by generators of their own (spawn keys 2 and 3) after the draw has taken its
-    values, so that without these options every seed gives the scene it gave, draw for draw."""
+    values, so that without these options every seed gives the scene it gave, draw for draw.
+    viscosity: None, or one of VISCOSITY_LAWS: every accepted body gets a "viscosity" drawn by `draw_viscosity` from a
+    generator of its own (spawn key 4), so that every other draw of the seed is what it was."""
     fluid_meshes, obstacle_meshes = [str(m) for m in fluid_meshes], [str(m) for m in obstacle_meshes]
+    if viscosity is not None and viscosity not in VISCOSITY_LAWS:
+        raise ValueError(f"viscosity must be None or one of {VISCOSITY_LAWS}")
+    thick = np.random.default_rng(np.random.SeedSequence(seed, spawn_key=(4,))) if viscosity is not None else None
     if not 0 <= int(obstacles) <= MAX_RANDOM_OBSTACLES:
         raise ValueError(f"obstacles must be 0 .. {MAX_RANDOM_OBSTACLES}")
     rng = np.random.default_rng(seed)
@@ -248,6 +286,8 @@ def random_scene(seed, box=DEFAULT_BOX, radius=ops.PBF_RADIUS, body_size=BODY_SI
                                    "centre": centre.tolist(), "velocity": velocity})
                     if spec is not None:
                         bodies[-1]["mesh"] = spec
+                    if thick is not None:
+                        bodies[-1]["viscosity"] = draw_viscosity(thick, viscosity)
                     break
         seed_out = seed if isinstance(seed, (int, np.integer)) else [int(s) for s in seed]
         scene = Scene([0.0, 0.0, 0.0], box.tolist(), bodies, seed_out, radius, obstacles=solids)
@@ -311,12 +351,27 @@ def sdf_obstacle_table(scenes, device, step=None):
     return ops.pbf_sdf_obstacles(per_scene, len(scenes), dev)
 
 
+def xsph_table(scenes, prm, device):
+    """The batch's per-particle XSPH table (B,N) of `ops.pbf_xsph`, from the bodies' viscosities; a scene without any gets
+    `ops.PBF_VISCOSITY`, rows beyond a scene's count 0.  None when no scene has a viscosity (the substeps then take
+    params.c, in the launches of before)."""
+    nus = [s.viscosity() for s in scenes]
+    if all(nu is None for nu in nus):
+        return None
+    counts = [s.particles()[0].shape[0] for s in scenes]
+    table = np.zeros((len(scenes), max(counts + [0])), np.float64)
+    for b, (nu, n) in enumerate(zip(nus, counts)):
+        table[b, :n] = ops.PBF_VISCOSITY if nu is None else nu
+    return ops.pbf_xsph(table, prm, torch.device(device))
+
+
 def simulate(scenes, frames, substeps=SUBSTEPS, iters=ops.PBF_ITERS, params=None, device="cuda"):
     """`frames` exported frames of every scene, frame 0 being the start state and each further one 1/40 s later, made of
     `substeps` substeps of dt = 1 / (40 * substeps).  All scenes advance in the same launches; the frames stay on the
     device.  params: an `ops.PbfParams` (its `iters` wins); None: the defaults with `iters`, at the first scene's radius.
     The scenes' obstacles go into one table, built once and passed to every substep; mesh obstacles into a table and a
-    field buffer of their own (`sdf_obstacle_table`), also built once.
+    field buffer of their own (`sdf_obstacle_table`), also built once.  Bodies with a "viscosity" make a per-particle XSPH
+    table (`xsph_table`), built once; params.vorticity > 0 adds vorticity confinement to every substep.
     -> pos, vel (B, frames, N, 3) fp32, lengths (B,) int64 (rows beyond a scene's length are 0)."""
     if frames < 1 or substeps < 1:
         raise ValueError("frames and substeps must be >= 1")
@@ -325,6 +380,9 @@ def simulate(scenes, frames, substeps=SUBSTEPS, iters=ops.PBF_ITERS, params=None
     table = obstacle_table(scenes, torch.device(device))
     sdf = sdf_obstacle_table(scenes, torch.device(device))
     extra = {} if sdf is None else {"sdf_obstacles": sdf}    # without mesh obstacles: the call of before
+    xsph = xsph_table(scenes, prm, device)
+    if xsph is not None:                                     # without viscosities: the call of before
+        extra["xsph"] = xsph
     B, N, _ = x.shape
     pos, vel = x.new_zeros((B, frames, N, 3)), x.new_zeros((B, frames, N, 3))
     dt = 1.0 / (FPS * substeps)
@@ -428,14 +486,22 @@ def main(argv=None):
                     help="closed meshes that join the shapes bodies are drawn from: a .obj/.ply path, icosphere:N, torus:R,r,nu,nv")
     ap.add_argument("--obstacle_mesh", type=str, nargs="*", default=[], metavar="SPEC",
                     help="closed meshes that join the shapes obstacles are drawn from (needs --obstacles >= 1)")
+    ap.add_argument("--viscosity", choices=("default",) + VISCOSITY_LAWS, default="default",
+                    help="the law every fluid body's viscosity is drawn from (the reference recipe's); default: every "
+                         "body is the liquid of viscosity 0.01, and nothing is recorded")
+    ap.add_argument("--vorticity", type=float, nargs="?", const=ops.PBF_VORTICITY, default=0.0, metavar="EPS",
+                    help=f"vorticity confinement of strength EPS m/s (the bare flag: {ops.PBF_VORTICITY}); absent: none")
     a = ap.parse_args(argv)
+    if not (np.isfinite(a.vorticity) and a.vorticity >= 0.0):
+        ap.error("--vorticity EPS >= 0")
     if a.obstacle_mesh and not a.obstacles:
         ap.error("--obstacle_mesh adds shapes to the obstacles' draw: give --obstacles 1 .. 3 as well")
     if a.cases < 0 or a.test_cases < 0 or a.frames < 1 or a.batch < 1 or a.substeps < 1 or a.iters < 0:
         ap.error("--cases, --test_cases, --iters >= 0; --frames, --batch, --substeps >= 1")
     if not 0 <= a.obstacles <= MAX_RANDOM_OBSTACLES or not 0 < a.obstacle_size[0] <= a.obstacle_size[1]:
         ap.error(f"--obstacles 0 .. {MAX_RANDOM_OBSTACLES}; --obstacle_size 0 < LO <= HI")
-    prm = ops.PbfParams(radius=a.particle_radius, iters=a.iters)
+    prm = ops.PbfParams(radius=a.particle_radius, iters=a.iters, vorticity=a.vorticity)
+    law = None if a.viscosity == "default" else a.viscosity
     settings = {"box": list(a.box), "body_size": a.body_size}
     if a.obstacles:                                          # without obstacles scene.json holds what it always held
         settings["obstacle_size"] = list(a.obstacle_size)
@@ -448,7 +514,7 @@ def main(argv=None):
         for c0 in range(0, cases, a.batch):
             scenes = [random_scene([a.seed, split, c], tuple(a.box), a.particle_radius, a.body_size, obstacles=a.obstacles,
                                    obstacle_size=tuple(a.obstacle_size), fluid_meshes=a.fluid_mesh,
-                                   obstacle_meshes=a.obstacle_mesh)
+                                   obstacle_meshes=a.obstacle_mesh, viscosity=law)
                       for c in range(c0, min(c0 + a.batch, cases))]
             write_cases(out, scenes, c0 + 1, a.frames, a.substeps, prm, a.device, settings)
     return 0
