@@ -318,8 +318,11 @@ int tpg_rowbn_bwd_sums_consts(const void *gy, int dtype_g, const void *x, int dt
  * nseg segments = nseg calls of the layer on equal consecutive row blocks, each with its own
  * statistics and (w_per_seg != 0) its own weight W[seg] (successive spectral-norm iterates).
  * Supported (Cin,Cout): (64,64) (64,128) (128,64) (128,128) (128,256) (256,128) (256,256);
- * ws: tpg_mlp_workspace_bytes(max(Cin,Cout), nseg) bytes, 16-byte aligned. */
+ * ws: tpg_mlp_workspace_bytes(max(Cin,Cout), nseg) bytes, 16-byte aligned; after the call it holds the
+ * per-workgroup partials (nseg, G, 3, Cout) f32 = mean | M2 | n with G = tpg_mlp_fwd_blocks(P, Cin, Cout, nseg)
+ * workgroups per segment (host only, no launch; 0 for bad arguments or an unsupported shape). */
 size_t tpg_mlp_workspace_bytes(int C, int nseg);
+int tpg_mlp_fwd_blocks(long long P, int Cin, int Cout, int nseg);
 int tpg_mlp_fwd(const void *x, long long P, int Cin, int Cout, int nseg, const float *ss_in, int ss_stride,
                 float slope_in, const float *W, int w_per_seg, void *y, float eps, float momentum,
                 float *running_mean, float *running_var, long long *num_batches_tracked, const float *mean_shift,

@@ -636,6 +636,310 @@ def err_ratio(got, ref, bound):
     return float(r.max()) if r.numel() else 0.0
 
 
+# ---- the fused MLP tail's forward (mlp_fwd_kernel + mlp_stats_finalize_kernel): geometry, restatement, bounds --------
+# The launcher's constants, copied: a retuned constant must be copied here too (tests/test_oracle_cpu.py holds the
+# restated G equal to tpg_mlp_fwd_blocks, and every GPU case re-asserts which launch edge it still reaches).
+TPG_ML_WAVES = 4              # csrc/mlp_fused.hip, ML_THREADS / 64
+TPG_ML_MAX_BLOCKS = 512       # csrc/mlp_fused.hip
+TPG_ML_WPAD = 8               # csrc/mlp_fused.hip
+MLP_FWD_SAFETY = 2.0          # second-order terms of the first-order statistics bounds, once (as SMALL_SAFETY)
+
+
+def mlp_fwd_geometry(P, nseg, Cin, Cout):
+    """The integer decisions of one tpg_mlp_fwd call with P rows per segment (fwd_strips, fwd_smem, the `slots` rule of
+    fwd_launch, fwd_blocks; tpg_bn::split and the `fits` test of mlp_stats_finalize_kernel) -> dict: STRIPS, BM (rows
+    per tile), smem, slots, tiles, G (workgroups = partials per segment), tiles_wg (G,) tiles of each workgroup (it
+    walks tiles b, b + G, ...), n_wave (G, 4) valid rows of each wave over its workgroup's tiles, n_wg (G,), lane_rows
+    (most rows one lane accumulates), last_wg (the workgroup of the last tile), fin_SP / fin_L, fits, sweeps, dead
+    (lane groups without a segment in the last sweep)."""
+    strips = 2 if (Cout <= 128 and Cin <= 128) else 1
+    rows_wave = strips * 16
+    bm = TPG_ML_WAVES * rows_wave
+    w, red = Cout * (Cin + TPG_ML_WPAD) * 2, 4 * TPG_ML_WAVES * 3 * Cout
+    smem = max(w, red) + 4 * 2 * Cin
+    slots = 256 if 2 * smem > 160 * 1024 else TPG_ML_MAX_BLOCKS
+    tiles = -(-P // bm)
+    G = min(tiles, max(16, slots // nseg))
+    b = np.arange(G)
+    tiles_wg = (tiles - b + G - 1) // G
+    r = np.arange(P)
+    slot = ((r // bm) % G) * TPG_ML_WAVES + (r % bm) // rows_wave
+    n_wave = np.bincount(slot, minlength=G * TPG_ML_WAVES).reshape(G, TPG_ML_WAVES)
+    sp, L = _bn_split(nseg)
+    return dict(P=P, nseg=nseg, Cin=Cin, Cout=Cout, STRIPS=strips, BM=bm, smem=smem, slots=slots, tiles=tiles, G=G,
+                tiles_wg=tiles_wg, n_wave=n_wave, n_wg=n_wave.sum(1), lane_rows=int(tiles_wg.max()) * strips * 4,
+                last_wg=(tiles - 1) % G, fin_SP=sp, fin_L=L, fits=G <= L * TPG_BN_FIN_R, sweeps=-(-nseg // sp),
+                dead=-(-nseg // sp) * sp - nseg)
+
+
+MLP_FWD_MU_CHANNEL = 5        # the output channel of mlp_fwd_case with |mean| / sigma ~ 1e3
+
+
+def mlp_fwd_case(Cin, Cout, P, nseg, per_seg, ss_kind, seed, device="cpu"):
+    """Inputs of one tpg_mlp_fwd call: bf16 rows x (nseg*P, Cin) with per-channel and per-segment offsets; ss_kind None
+    (no input BatchNorm), "ss" ((nseg,2,Cin) = sc | sh) or "ci" (a (nseg,4,Cin) block whose last two rows the forward
+    must not read); W fp32 (nseg, Cout, Cin) (per_seg) or (1, Cout, Cin), / sqrt(Cin); gamma, beta, mean_shift (Cout);
+    running_mean / running_var away from 0 / 1, num_batches_tracked = 3; eps, momentum.
+    Output channel MLP_FWD_MU_CHANNEL is 8 + lrelu(x0): input channel 1 is exactly 1 after the prologue (sc = 0,
+    sh = 1; without ss the rows hold 1) and carries a weight of 8, input channel 0 is +-2^-4 on one row in 61 (0
+    elsewhere, sc = 1, sh = 0) with weight 1: |mean| / sigma ~ 1e3 in the stored bf16 values."""
+    g = torch.Generator().manual_seed(seed)
+    N = nseg * P
+    x = torch.randn(N, Cin, generator=g) * 0.7 + 0.3 * torch.randn(Cin, generator=g)
+    x = x + (0.2 * torch.randn(nseg, Cin, generator=g)).repeat_interleave(P, 0)
+    r = torch.arange(N) % P
+    x[:, 0] = torch.where(r % 122 == 0, 1.0, torch.where(r % 122 == 61, -1.0, 0.0)) * 2.0 ** -4
+    if ss_kind is None:
+        ss = None
+        x[:, 1] = 1.0
+    else:
+        ss = torch.stack([torch.rand(nseg, Cin, generator=g) + 0.5, 0.3 * torch.randn(nseg, Cin, generator=g)], 1)
+        ss[:, 0, 0], ss[:, 1, 0] = 1.0, 0.0
+        ss[:, 0, 1], ss[:, 1, 1] = 0.0, 1.0
+        if ss_kind == "ci":
+            ss = torch.cat([ss, 1e3 * torch.randn(nseg, 2, Cin, generator=g)], 1)
+        else:
+            assert ss_kind == "ss", ss_kind
+    W = torch.randn(nseg if per_seg else 1, Cout, Cin, generator=g) / Cin ** 0.5
+    W[:, MLP_FWD_MU_CHANNEL] = 0.0
+    W[:, MLP_FWD_MU_CHANNEL, 0], W[:, MLP_FWD_MU_CHANNEL, 1] = 1.0, 8.0
+    case = dict(x=x.bfloat16(), ss=ss, W=W, nseg=nseg, P=P, per_seg=per_seg,
+                gamma=torch.rand(Cout, generator=g) + 0.5, beta=0.3 * torch.randn(Cout, generator=g),
+                mean_shift=torch.randn(Cout, generator=g), running_mean=0.5 * torch.randn(Cout, generator=g),
+                running_var=torch.rand(Cout, generator=g) + 0.5, num_batches_tracked=torch.tensor(3, dtype=torch.int64),
+                eps=1e-5, momentum=0.1)
+    return {n: (v.to(device) if isinstance(v, torch.Tensor) else v) for n, v in case.items()}
+
+
+def mlp_fwd_operand(case, slope):
+    """The MFMA A operand of mlp_fwd_kernel, bit for bit: a = bf16(max(t, fp32(t * slope))), t = fma(x, sc, sh) (sc = 1,
+    sh = 0 without ss: t = x), float64 carriers (nseg*P, Cin)."""
+    x = _f64(case["x"])
+    P = case["P"]
+    if case["ss"] is None:
+        t = x
+    else:
+        ss = _f64(case["ss"], x)
+        t = fma32(x, _rows(ss[:, 0], P), _rows(ss[:, 1], P))
+    return rbf16(torch.maximum(t, r32(t * slope32(slope))))
+
+
+def mlp_fwd_ref(case, slope, a=None, W=None):
+    """y64 = a . bf16(W)^T per segment in float64 and M = |a| . |bf16(W)|^T, (nseg*P, Cout) each (a, W: overrides of the
+    operand and the weight, for the planted defects)."""
+    a = mlp_fwd_operand(case, slope) if a is None else a
+    Wb = rbf16(_f64(case["W"] if W is None else W, a))
+    Wb = Wb.view(-1, *Wb.shape[-2:])
+    P, nseg = case["P"], case["nseg"]
+    y, M = [], []
+    for s in range(nseg):
+        w = Wb[s if Wb.shape[0] > 1 else 0]
+        y.append(a[s * P:(s + 1) * P] @ w.t())
+        M.append(a[s * P:(s + 1) * P].abs() @ w.abs().t())
+    return dict(y=torch.cat(y), M=torch.cat(M), a=a)
+
+
+def mlp_fwd_stored_interval(ref, kappa):
+    """The kernel's fp32 accumulator lies within kappa * M of y64 and rounding is monotone: the stored bf16 value lies
+    in [bf16(y64 - kappa M), bf16(y64 + kappa M)] -> (lo, hi); where they coincide the check is bit for bit."""
+    return rbf16(ref["y"] - kappa * ref["M"]), rbf16(ref["y"] + kappa * ref["M"])
+
+
+def mlp_fwd_stored_ratio(got, ref, kappa):
+    """The stored bf16 y against mlp_fwd_stored_interval: the largest distance from the interval's centre over its
+    half-width (0 where both ends coincide and the bits match, inf where they coincide and the bits differ)."""
+    lo, hi = mlp_fwd_stored_interval(ref, kappa)
+    return err_ratio(got, 0.5 * (lo + hi), 0.5 * (hi - lo))
+
+
+def _mlp_fwd_slots(geo, device):
+    P, bm, G = geo["P"], geo["BM"], geo["G"]
+    r = torch.arange(P, device=device)
+    slot = ((r // bm) % G) * TPG_ML_WAVES + (r % bm) // (geo["STRIPS"] * 16)
+    piv_row = (torch.arange(G, device=device)[:, None] * bm +
+               torch.arange(TPG_ML_WAVES, device=device)[None] * geo["STRIPS"] * 16).reshape(-1)
+    return slot, piv_row
+
+
+def mlp_fwd_stats(y, case, geo):
+    """The statistics of the STORED rows y (nseg*P, Cout; bf16 values, exact in float64) and how far the kernels' may
+    lie from them, from the geometry alone.
+    Per wave (workgroup b, wave w; pivot = its first row, d = y - pivot): s1 = sum d and s2 = sum d^2 run down a lane's
+    rows (tiles_wg * STRIPS * 4) and two shuffles, h = that depth; d rounds once, the fma once per row:
+        E_s1 = (h + 1) u A,  E_s2 = (h + 3) u Q                       A = sum |d|, Q = sum d^2
+        m = s1 / n,  mean_w = pivot + m:  E_mean_w = E_s1 / n + u |m| + u |mean_w|
+        M2_w = s2 - s1 m:                 E_M2_w = E_s2 + 2 |m| E_s1 + 2u |s1 m| + u M2_w
+    Chan's combination of the waves with rows, in wave order, fp32 (nothing rounds for the first one):
+        delta = mean_w - mean,  r = n_w / tot,  mean' = mean + delta r,  M2' = M2 + (M2_w + delta^2 (n n_w / tot))
+        E_mean' = (1 - r) E_mean + r E_mean_w + 3u |delta| r + u |mean'|
+        E_M2'   = E_M2 + E_M2_w + 2 |delta| c (E_mean + E_mean_w + u |delta|) + 4u |term| + u |M2_w + term| + u M2'
+    The finalize is fp64: mean = sum n_g mean_g / N, var = sum (M2_g + n_g (mean_g - mean)^2) / N carry the partials'
+    bounds, then round once; rstd moves by 0.5 dvar / (var + eps) of itself, plus its rounding.  The running statistics
+    follow the kernel's chain (fp64, one fp32 rounding per segment, call order, mean_shift in the mean only, unbiased
+    variance where N > 1), their bounds E' = (1 - mom) E + mom E_new + u |running'|.  u = MLP_FWD_SAFETY * 2^-24.
+    -> dict: part_n, part_mean, part_M2 with E_part_mean, E_part_M2 (nseg, G, Cout); mean, var, rstd with E_mean,
+    E_rstd (nseg, Cout); running_mean, running_var with E_running_mean, E_running_var (Cout) if the case has them."""
+    y = _f64(y)
+    dev = y.device
+    nseg, P = case["nseg"], case["P"]
+    C = y.shape[1]
+    G, nwv = geo["G"], TPG_ML_WAVES
+    u = MLP_FWD_SAFETY * U32
+    yv = y.view(nseg, P, C)
+    slot, piv_row = _mlp_fwd_slots(geo, dev)
+    n = torch.as_tensor(geo["n_wave"], dtype=torch.float64, device=dev).reshape(1, G * nwv, 1)
+    piv = yv[:, piv_row.clamp(max=P - 1)]                           # (nseg, G*4, C); unused where n == 0
+    d = yv - piv[:, slot]
+
+    def per_wave(t):
+        return torch.zeros(nseg, G * nwv, C, dtype=torch.float64, device=dev).index_add_(1, slot, t)
+    s1, A, Q = per_wave(d), per_wave(d.abs()), per_wave(d * d)
+    del d
+    h = torch.as_tensor(geo["tiles_wg"] * geo["STRIPS"] * 4 + 2, dtype=torch.float64, device=dev)
+    h = h.repeat_interleave(nwv).reshape(1, G * nwv, 1)
+    n1 = n.clamp_min(1.0)
+    m = s1 / n1
+    mean_w = piv + m
+    M2_w = (Q - s1 * m).clamp_min(0.0)
+    E_s1, E_s2 = (h + 1.0) * u * A, (h + 3.0) * u * Q
+    E_mean_w = E_s1 / n1 + u * m.abs() + u * mean_w.abs()
+    E_M2_w = E_s2 + 2.0 * m.abs() * E_s1 + 2.0 * u * (s1 * m).abs() + u * M2_w
+
+    def wv(t, w):
+        return t.view(t.shape[0], G, nwv, -1)[:, :, w]
+    zero = torch.zeros(nseg, G, C, dtype=torch.float64, device=dev)
+    na, mean, M2, Em, Eq = zero[..., :1].clone(), zero.clone(), zero.clone(), zero.clone(), zero.clone()
+    for w in range(nwv):
+        nw_, mw, qw, Emw, Eqw = wv(n, w), wv(mean_w, w), wv(M2_w, w), wv(E_mean_w, w), wv(E_M2_w, w)
+        act, first = nw_ > 0, na == 0
+        tot = (na + nw_).clamp_min(1.0)
+        r = nw_ / tot
+        delta = mw - mean
+        c = na * nw_ / tot
+        term = delta * delta * c
+        mean_n = mean + delta * r
+        M2_n = M2 + (qw + term)
+        Em_n = (1.0 - r) * Em + r * Emw + torch.where(first, zero, 3.0 * u * delta.abs() * r + u * mean_n.abs())
+        Eq_n = Eq + Eqw + torch.where(first, zero, 2.0 * delta.abs() * c * (Em + Emw + u * delta.abs()) +
+                                      4.0 * u * term + u * (qw + term) + u * M2_n)
+        mean, M2 = torch.where(act, mean_n, mean), torch.where(act, M2_n, M2)
+        Em, Eq = torch.where(act, Em_n, Em), torch.where(act, Eq_n, Eq)
+        na = na + nw_
+    eps, mom = slope32(case["eps"]), slope32(case["momentum"])
+    N = float(P)
+    mean64, var = yv.mean(1), yv.var(1, unbiased=False)
+    E_m64 = (na * Em).sum(1) / N
+    E_var = (Eq + 2.0 * na * (mean - mean64[:, None]).abs() * (Em + E_m64[:, None])).sum(1) / N
+    rstd = 1.0 / torch.sqrt(var + eps)
+    out = dict(part_n=na.expand(nseg, G, C), part_mean=mean, part_M2=M2, E_part_mean=Em, E_part_M2=Eq,
+               mean=mean64, var=var, rstd=rstd, E_mean=E_m64 + u * mean64.abs(),
+               E_rstd=rstd * (0.5 * E_var / (var + eps)) + u * rstd, E_var=E_var)
+    if case.get("running_mean") is not None:
+        rm, rv = _f64(case["running_mean"], y).clone(), _f64(case["running_var"], y).clone()
+        sh = 0.0 if case.get("mean_shift") is None else _f64(case["mean_shift"], y)
+        sc = N / (N - 1.0) if P > 1 else 1.0
+        Erm, Erv = torch.zeros_like(rm), torch.zeros_like(rv)
+        for s in range(nseg):
+            rm = r32((1.0 - mom) * rm + mom * (mean64[s] + sh))
+            rv = r32((1.0 - mom) * rv + mom * var[s] * sc)
+            Erm = (1.0 - mom) * Erm + mom * E_m64[s] + u * rm.abs()
+            Erv = (1.0 - mom) * Erv + mom * E_var[s] * sc + u * rv.abs()
+        out.update(running_mean=rm, running_var=rv, E_running_mean=Erm, E_running_var=Erv)
+    return out
+
+
+def mlp_fwd_stats_ratios(st, part=None, mean=None, rstd=None, running_mean=None, running_var=None):
+    """error / bound of whatever is given against st = mlp_fwd_stats(...): part (nseg, G, 3, C) = mean | M2 | n (n must
+    be equal: ratio 0 or inf), mean / rstd (nseg, C), the running statistics (C) -> dict of floats, <= 1 passes."""
+    out = {}
+    if part is not None:
+        part = _f64(part, st["mean"])
+        out["part_n"] = 0.0 if torch.equal(part[:, :, 2], st["part_n"]) else float("inf")
+        out["part_mean"] = err_ratio(part[:, :, 0], st["part_mean"], st["E_part_mean"])
+        out["part_M2"] = err_ratio(part[:, :, 1], st["part_M2"], st["E_part_M2"])
+    for name, got in (("mean", mean), ("rstd", rstd), ("running_mean", running_mean), ("running_var", running_var)):
+        if got is not None:
+            out[name] = err_ratio(_f64(got, st["mean"]), st[name], st["E_" + name])
+    return out
+
+
+def mlp_fwd_partials_emulated(y, case, geo, pivot_zero=False):
+    """The (nseg, G, 3, Cout) partials mean | M2 | n as mlp_fwd_kernel's epilogue computes them from the stored rows y,
+    op for op in fp32 (a lane's rows in tile, strip, register order, the two shuffles, the per-wave mean and M2, Chan's
+    combination in wave order); rows past P add an exact 0.  pivot_zero: the planted defect of tests/test_oracle_cpu.py
+    (no pivot: s1 = sum y, s2 = sum y^2 in fp32).  For the CPU tests: it shows the bounds of mlp_fwd_stats hold for the
+    arithmetic the kernel is written in, and that they reject the defect."""
+    ar = FP32
+    y = _f64(y)
+    dev = y.device
+    nseg, P = case["nseg"], case["P"]
+    C = y.shape[1]
+    G, nwv, S, bm = geo["G"], TPG_ML_WAVES, geo["STRIPS"], geo["BM"]
+    T = int(geo["tiles_wg"].max())
+    yv = y.view(nseg, P, C)
+    _, piv_row = _mlp_fwd_slots(geo, dev)
+    n = torch.as_tensor(geo["n_wave"], dtype=torch.float64, device=dev).reshape(1, G, nwv, 1)
+    piv = yv[:, piv_row.clamp(max=P - 1)].view(nseg, G, nwv, 1, C)
+    if pivot_zero:
+        piv = torch.zeros_like(piv)
+    b, w, lq = (torch.arange(k, device=dev) for k in (G, nwv, 4))
+    s1 = torch.zeros(nseg, G, nwv, 4, C, dtype=torch.float64, device=dev)
+    s2 = torch.zeros_like(s1)
+    for j in range(T):
+        for st in range(S):
+            for r in range(4):
+                row = ((b[:, None, None] + j * G) * bm + (w[None, :, None] * S + st) * 16 + 4 * lq[None, None, :] + r)
+                valid = (row < P) & ((b[:, None, None] + j * G) < geo["tiles"])
+                v = yv[:, row.clamp(max=P - 1).reshape(-1)].view(nseg, G, nwv, 4, C)
+                dd = torch.where(valid[None, ..., None], ar.sub(v, piv), torch.zeros_like(v))
+                s1 = ar.add(s1, dd)
+                s2 = ar.fma(dd, dd, s2)
+
+    def lanes(t):                                   # + shfl_xor 16, + shfl_xor 32: lq pairs (0,1) (2,3), then both
+        p01, p23 = ar.add(t[..., 0, :], t[..., 1, :]), ar.add(t[..., 2, :], t[..., 3, :])
+        return ar.add(p01, p23)
+    s1, s2 = lanes(s1), lanes(s2)                   # (nseg, G, 4, C)
+    n1 = n.clamp_min(1.0)
+    has = (n > 0).expand_as(s1)
+    m = torch.where(has, ar.r(s1 / n1), torch.zeros_like(s1))
+    mean_w = ar.add(piv[..., 0, :].expand_as(m), m)
+    M2_w = torch.where(has, ar.sub(s2, ar.mul(s1, m)), torch.zeros_like(s1))
+    zero = torch.zeros(nseg, G, C, dtype=torch.float64, device=dev)
+    na, mean, M2 = zero.clone(), zero.clone(), zero.clone()
+    for k in range(nwv):
+        nw_ = n[:, :, k].expand(nseg, G, C)
+        act = nw_ > 0
+        tot = (na + nw_).clamp_min(1.0)
+        delta = ar.sub(mean_w[:, :, k], mean)
+        mean_n = ar.add(mean, ar.mul(delta, ar.r(nw_ / tot)))
+        M2_n = ar.add(M2, ar.add(M2_w[:, :, k], ar.mul(ar.mul(delta, delta), ar.r(ar.mul(na, nw_) / tot))))
+        mean, M2, na = torch.where(act, mean_n, mean), torch.where(act, M2_n, M2), torch.where(act, tot, na)
+    return torch.stack([mean, M2, na], 2)
+
+
+def mlp_fwd_finalize(part, case, order=None):
+    """mlp_stats_finalize_kernel on given partials (nseg, G, 3, C): fp64 mean = sum n_g mean_g / N and biased var =
+    sum (M2_g + n_g (mean_g - mean)^2) / N (the order of the fp64 additions is not restated: 2^-53 relative), mean and
+    rstd rounded to fp32, the running chain over the segments in `order` (default: call order) -> dict."""
+    part = _f64(part)
+    n, pm, pq = part[:, :, 2], part[:, :, 0], part[:, :, 1]
+    N = n.sum(1)
+    m = (n * pm).sum(1) / N
+    var = ((pq + n * (pm - m[:, None]) ** 2) * (n > 0)).sum(1) / N
+    var = var.clamp_min(0.0)
+    eps, mom = slope32(case["eps"]), slope32(case["momentum"])
+    out = dict(mean=r32(m), rstd=r32(1.0 / torch.sqrt(var + eps)))
+    if case.get("running_mean") is not None:
+        rm, rv = _f64(case["running_mean"], part).clone(), _f64(case["running_var"], part).clone()
+        sh = 0.0 if case.get("mean_shift") is None else _f64(case["mean_shift"], part)
+        for s in (range(part.shape[0]) if order is None else order):
+            unb = torch.where(N[s] > 1.0, var[s] * N[s] / (N[s] - 1.0).clamp_min(1.0), var[s])
+            rm = r32((1.0 - mom) * rm + mom * (m[s] + sh))
+            rv = r32((1.0 - mom) * rv + mom * unb)
+        out.update(running_mean=rm, running_var=rv)
+    return out
+
+
 # ---- the 16 -> 16 -> 32 small tails (csrc/mlp_small.hip): restatements and derived per-element bounds ---------------
 # out[n] = max_j lrelu_s2(W2 . lrelu_s1(W1 . h[n, j])) and its backward, exact in float64 on any device.  The kernels
 # compute in fp32 on v_mfma_f32_16x16x4_f32 (fmaf chains) whatever the row type, so every bound below is a first-order

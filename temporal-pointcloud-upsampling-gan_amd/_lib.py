@@ -111,7 +111,8 @@ OTHER_GETTERS = ("tpg_spectral_norm_multi_stride", "tpg_spectral_norm_multi_bwd_
                  "tpg_mlp_wgrad_workspace_bytes", "tpg_frnn_grid_workspace_bytes", "tpg_small_tail_workspace_bytes",
                  "tpg_chamfer_bwd_workspace_bytes", "tpg_rowlinear_wgrad_workspace_bytes", "tpg_rowlinear_supported",
                  "tpg_spectral_norm_split_rows", "tpg_spectral_norm_split_max_cn", "tpg_spectral_norm_split_max_rows",
-                 "tpg_patch_select_workspace_bytes", "tpg_patch_select_max_k", "tpg_mlp_infer_supported")
+                 "tpg_patch_select_workspace_bytes", "tpg_patch_select_max_k", "tpg_mlp_infer_supported",
+                 "tpg_mlp_fwd_blocks")
 STRING_GETTERS = ("tpg_version", "tpg_target_arch")
 
 STATUS = {0: "TPG_OK", -1: "TPG_ERR_ARG", -2: "TPG_ERR_LAUNCH", -3: "TPG_ERR_UNSUPPORTED"}
@@ -149,6 +150,8 @@ def load():
     lib.tpg_spectral_norm_multi_bwd_scratch.restype = C.c_longlong
     lib.tpg_mlp_wgrad_workspace_bytes.argtypes = [C.c_longlong, C.c_int, C.c_int, C.c_int]
     lib.tpg_mlp_wgrad_workspace_bytes.restype = C.c_size_t
+    lib.tpg_mlp_fwd_blocks.argtypes = [C.c_longlong, C.c_int, C.c_int, C.c_int]
+    lib.tpg_mlp_fwd_blocks.restype = C.c_int
     lib.tpg_small_tail_workspace_bytes.argtypes = [C.c_longlong, C.c_int]
     lib.tpg_small_tail_workspace_bytes.restype = C.c_size_t
     lib.tpg_frnn_grid_workspace_bytes.argtypes = [C.c_int, C.c_int]

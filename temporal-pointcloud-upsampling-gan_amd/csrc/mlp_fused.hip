@@ -1092,15 +1092,20 @@ int fwd_blocks(long long P, int bm, int nseg, int slots = ML_MAX_BLOCKS) {
     return (int)(tiles < cap ? tiles : cap);
 }
 
+// workgroups per segment of the forward launch of one layer shape (P rows per segment)
+template <int CIN, int COUT> int fwd_grid(long long P, int nseg) {
+    constexpr int BM = ML_WAVES * fwd_strips<CIN, COUT>() * 16;
+    return fwd_blocks(P, BM, nseg, 2 * fwd_smem<CIN, COUT>() > 160 * 1024 ? 256 : 512);
+}
+
 template <int CIN, int COUT>
 int fwd_launch(const void *x, long long P, int nseg, const float *ss, int ss_stride, float slope, const float *W,
                int w_per_seg, void *y, float *part, int *G_out, hipStream_t st) {
     constexpr int STRIPS = fwd_strips<CIN, COUT>();
-    constexpr int BM = ML_WAVES * STRIPS * 16;
     constexpr size_t smem = fwd_smem<CIN, COUT>();
     constexpr auto kern = mlp_fwd_kernel<CIN, COUT, STRIPS>;
     if (smem > 64 * 1024 && !tpg_allow_dynamic_lds<kern>((int)smem)) return TPG_ERR_UNSUPPORTED;
-    const int G = fwd_blocks(P, BM, nseg, 2 * smem > 160 * 1024 ? 256 : 512);
+    const int G = fwd_grid<CIN, COUT>(P, nseg);
     *G_out = G;
     hipLaunchKernelGGL(kern, dim3(G, nseg), dim3(ML_THREADS), smem, st, static_cast<const __hip_bfloat16 *>(x), P, ss,
                        ss_stride, slope, W, w_per_seg, static_cast<__hip_bfloat16 *>(y), part);
@@ -1184,6 +1189,16 @@ extern "C" size_t tpg_mlp_workspace_bytes(int C, int nseg) {
     // per-workgroup partials (mean | M2 | n) of the forward, (sum g | sum g xhat) of the backward,
     // C = the larger channel count of the layer
     return sizeof(float) * ((size_t)nseg * ML_MAX_BLOCKS * 3 * C + 64);
+}
+
+extern "C" int tpg_mlp_fwd_blocks(long long P, int Cin, int Cout, int nseg) {
+    if (P <= 0 || nseg < 1 || nseg > 65535 || P % nseg) return 0;
+    int G = 0;
+#define TPG_ML_FWD_G(CI, CO) \
+    if (Cin == CI && Cout == CO) G = fwd_grid<CI, CO>(P / nseg, nseg);
+    TPG_ML_SHAPES(TPG_ML_FWD_G)
+#undef TPG_ML_FWD_G
+    return G;
 }
 
 extern "C" int tpg_mlp_fwd(const void *x, long long P, int Cin, int Cout, int nseg, const float *ss_in, int ss_stride,

@@ -609,3 +609,102 @@ def test_mlp_bwd_launches_at_slopes_0_and_1(hip, Cin, Cout, mode_max, slope):
     """LeakyReLU slopes 0 (ReLU: y == 0 on the negative side, the gradient 0 either way) and 1 (no activation), for the
     input's activation and the max-prep slope, at 1000 rows, K = 8."""
     _run_bwd_case(hip, Cin, Cout, 1000, 1, False, 8, mode_max, slope_in=slope, slope_out=slope)
+
+
+# ------------------------------------------------------------------ the tail's forward launch against the fp64 oracle
+# tpg_mlp_fwd (mlp_fwd_kernel + mlp_stats_finalize_kernel), called directly, at its launch edges (tests/mlp_fwd_cases.py).
+# Stored rows: the MFMA operands are restated bit for bit, the product is float64 on the GPU, and the stored bf16 value
+# must lie in [bf16(y64 - kappa M), bf16(y64 + kappa M)] (rounding is monotone; for most elements both ends coincide).
+# Statistics: from the kernel's OWN stored rows in float64, within bounds derived from the launch geometry
+# (oracle.ref_ops.mlp_fwd_stats), the per-workgroup partials included; ci bit for bit from the kernel's mean / rstd.
+# tests/test_oracle_cpu.py shows that these checks reject the planted defects at the grid's shapes.
+import mlp_fwd_cases as FWD
+
+_WORST_FWD = {}         # (Cin, Cout) -> check -> largest error / bound ("exact": the smallest bit-for-bit share of y)
+
+
+def _note_fwd(pair, check, ratio):
+    _WORST_FWD.setdefault(pair, {})[check] = max(_WORST_FWD.get(pair, {}).get(check, 0.0), ratio)
+    _note("fwd " + check, ratio)
+
+
+@pytest.fixture(scope="module", autouse=True)
+def _report_worst_fwd():
+    yield
+    for (Cin, Cout), w in sorted(_WORST_FWD.items()):
+        exact = w.pop("exact", None)
+        print(f"\nfwd {Cin:3d} -> {Cout:3d}: " + ", ".join(f"{k} {v:.3g}" for k, v in sorted(w.items())) +
+              ("" if exact is None else f"; y checked bit for bit: >= {100.0 * (1.0 - exact):.1f} % of a case's elements"), end="")
+
+
+def _fwd_launch(hip, c, slope, affine=True, running=True):
+    """One call on fresh copies of the state it updates -> (y, ci, mean, rstd, running_mean, running_var, nbt, part)."""
+    Cout = c["W"].shape[-2]
+    rm, rv, nbt = (c[k].clone() if running else None for k in ("running_mean", "running_var", "num_batches_tracked"))
+    y, ci, mean, rstd = hip.mlp_fwd(c["x"], c["ss"], slope, c["W"], c["nseg"], c["eps"], c["momentum"], rm, rv, nbt,
+                                    c["mean_shift"] if running else None, c["gamma"] if affine else None,
+                                    c["beta"] if affine else None, mean_rstd=True)
+    G = hip.lib.tpg_mlp_fwd_blocks(c["x"].shape[0], c["x"].shape[1], Cout, c["nseg"])
+    ws = hip._mlp_ws(c["x"], max(c["x"].shape[1], Cout), c["nseg"])
+    part = ws[:c["nseg"] * G * 3 * Cout].view(c["nseg"], G, 3, Cout).clone()
+    return y, ci, mean, rstd, rm, rv, nbt, part
+
+
+def _run_fwd_case(hip, Cin, Cout, P, nseg, per_seg, edge=None, ss_kind="ss", slope=0.01, affine=True, running=True):
+    from oracle import ref_ops as R
+    kap = R.MLP_KAPPA
+    geo = R.mlp_fwd_geometry(P, nseg, Cin, Cout)
+    assert geo["G"] == hip.lib.tpg_mlp_fwd_blocks(P * nseg, Cin, Cout, nseg)
+    if edge is not None:
+        FWD.check_reaches(geo, edge)
+    # the deepest fp32 chains: the k-loop's Cin products into one accumulator; a lane's rows, 2 shuffles, 4 waves
+    assert Cin * R.U32 <= kap and (geo["lane_rows"] + 6) * R.U32 <= kap
+    c = R.mlp_fwd_case(Cin, Cout, P, nseg, per_seg, ss_kind, seed=Cin * 7 + Cout + P + nseg, device="cuda")
+    c = dict(c, running_mean=c["running_mean"] if running else None)
+    y, ci, mean, rstd, rm, rv, nbt, part = _fwd_launch(hip, c, slope, affine, running)
+    torch.cuda.synchronize()
+    again = _fwd_launch(hip, c, slope, affine, running)
+    for name, u, v in zip("y ci mean rstd rm rv nbt part".split(), (y, ci, mean, rstd, rm, rv, nbt, part), again):
+        assert (u is None and v is None) or torch.equal(_bits(u) if u.is_floating_point() else u,
+                                                        _bits(v) if v.is_floating_point() else v), ("repro", name)
+    # without statistics: the same rows, no constants (and no finalize launch: nothing it writes is passed)
+    y2, none = hip.mlp_fwd(c["x"], c["ss"], slope, c["W"], nseg, stats=False)
+    assert none is None and torch.equal(_bits(y2), _bits(y)), "stats=False"
+    ref = R.mlp_fwd_ref(c, slope)
+    _note_fwd((Cin, Cout), "y", R.mlp_fwd_stored_ratio(y, ref, kap))
+    lo, hi = R.mlp_fwd_stored_interval(ref, kap)
+    _WORST_FWD[(Cin, Cout)]["exact"] = max(_WORST_FWD[(Cin, Cout)].get("exact", 0.0), float((lo != hi).double().mean()))
+    del ref, lo, hi
+    st = R.mlp_fwd_stats(y, c, geo)
+    for k, v in R.mlp_fwd_stats_ratios(st, part, mean, rstd, rm, rv).items():
+        _note_fwd((Cin, Cout), k, v)
+    want_ci = R.mlp_consts(mean, rstd, c["gamma"] if affine else None, c["beta"] if affine else None, None)[0]
+    assert _same_bits(ci, want_ci), "ci"
+    if P == 1:
+        assert torch.equal(rstd, torch.full_like(rstd, float(np.float32(1.0 / np.sqrt(np.float64(np.float32(1e-5)))))))
+    if running:
+        assert int(nbt) == int(c["num_batches_tracked"]) + nseg
+    else:
+        assert rm is None and rv is None and nbt is None
+
+
+@pytest.mark.parametrize("P,nseg,per_seg,edge", FWD.SHAPES)
+@pytest.mark.parametrize("Cin,Cout", FWD.PAIRS)
+def test_mlp_fwd_launch_matches_fp64_oracle(hip, Cin, Cout, P, nseg, per_seg, edge):
+    """The grid: every channel pair x the launch edges of tests/mlp_fwd_cases.py (several tiles per workgroup with uneven
+    counts and a partial last tile, fewer rows than a tile, one row, the finalize's re-fetch path, two sweeps, dead lane
+    groups, shared and per-segment weights); input constants as (nseg,2,Cin), slope 0.01, mean_shift, running
+    statistics that start away from 0 / 1."""
+    _run_fwd_case(hip, Cin, Cout, P, nseg, per_seg, edge)
+
+
+@pytest.mark.parametrize("ss_kind,slope,affine,running", [
+    (None, 0.01, True, True), ("ss", 0.0, True, True), ("ci", 0.2, True, True), ("ss", 1.0, True, True),
+    ("ci", 0.01, False, True), ("ss", 0.2, True, False), (None, 0.0, False, False)],
+    ids=["noss", "slope0", "ci-slope0.2", "slope1", "ci-noaffine", "norunning", "noss-slope0-bare"])
+@pytest.mark.parametrize("nseg", [1, 3])
+@pytest.mark.parametrize("Cin,Cout", FWD.PAIRS)
+def test_mlp_fwd_launch_variants_match_fp64_oracle(hip, Cin, Cout, nseg, ss_kind, slope, affine, running):
+    """At 1000 rows per segment: no input constants / (nseg,2,Cin) / a ci block (nseg,4,Cin), LeakyReLU slopes 0, 0.01,
+    0.2 and 1, gamma and beta both None, no running statistics (per-segment weights at nseg = 3)."""
+    _run_fwd_case(hip, Cin, Cout, 1000, nseg, nseg > 1, None, ss_kind, slope, affine, running)

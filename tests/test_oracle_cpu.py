@@ -468,3 +468,151 @@ def test_mlp_contract_bound_rejects_an_uncentred_operand():
     unc = dict(centred)
     unc["d"] = R.r32(R.rbf16(R.fma32(a, g, R.r32(-f * x))) + fm)
     assert R.err_ratio(R.r32(R.mlp_wgrad_ref(unc)["dW"]), wg["dW"], bound) > 1.0
+
+
+# ------------------------------------------------------------------ the fused MLP forward: geometry, bounds, planted defects
+def test_mlp_fwd_geometry_equals_the_launcher(hip_lib):
+    """R.mlp_fwd_geometry against tpg_mlp_fwd_blocks over the whole grid of tests/mlp_fwd_cases.py (and a few row counts
+    around the caps), and every shape reaches the launch edge its row names."""
+    import mlp_fwd_cases as S
+    for Cin, Cout in S.PAIRS:
+        for P, nseg, _, edge in S.SHAPES:
+            geo = R.mlp_fwd_geometry(P, nseg, Cin, Cout)
+            assert geo["G"] == hip_lib.tpg_mlp_fwd_blocks(P * nseg, Cin, Cout, nseg), (Cin, Cout, P, nseg)
+            assert int(geo["n_wg"].sum()) == P and int(geo["tiles_wg"].sum()) == geo["tiles"]
+            S.check_reaches(geo, edge)
+        for P, nseg in [(16384, 6), (32768, 1), (65, 1), (128 * 512 + 1, 1), (64 * 256, 2), (3000, 40)]:
+            assert R.mlp_fwd_geometry(P, nseg, Cin, Cout)["G"] == hip_lib.tpg_mlp_fwd_blocks(P * nseg, Cin, Cout, nseg)
+    assert hip_lib.tpg_mlp_fwd_blocks(4096, 64, 256, 1) == 0 and hip_lib.tpg_mlp_fwd_blocks(7, 64, 64, 2) == 0
+    # the real configuration the issue names: six segments of 16384 rows leave the finalize's registers
+    geo = R.mlp_fwd_geometry(16384, 6, 64, 128)
+    assert (geo["fin_L"], geo["G"], geo["fits"]) == (8, 85, False)
+
+
+def _stored_rows(P, nseg, C, seed):
+    """bf16 rows as a forward launch might have stored them: per-channel and per-segment offsets, channel
+    R.MLP_FWD_MU_CHANNEL at 8 + 2^-4 on one row in 61 (|mean| / sigma ~ 1e3)."""
+    import torch
+    g = torch.Generator().manual_seed(seed)
+    y = torch.randn(nseg * P, C, generator=g) + torch.randn(C, generator=g)
+    y = y + (0.3 * torch.randn(nseg, C, generator=g)).repeat_interleave(P, 0)
+    r = torch.arange(nseg * P) % P
+    y[:, R.MLP_FWD_MU_CHANNEL] = 8.0 + (r % 61 == 0) * 2.0 ** -4
+    return y.bfloat16()
+
+
+def _stats_case(P, nseg, C, seed):
+    import torch
+    g = torch.Generator().manual_seed(seed + 1)
+    return dict(nseg=nseg, P=P, eps=1e-5, momentum=0.1, mean_shift=torch.randn(C, generator=g),
+                running_mean=0.5 * torch.randn(C, generator=g), running_var=torch.rand(C, generator=g) + 0.5)
+
+
+def test_mlp_fwd_statistics_bounds_hold_for_the_kernels_arithmetic():
+    """The forward epilogue's statistics restated op for op in fp32 (R.mlp_fwd_partials_emulated) and finalized in fp64
+    lie within the bounds R.mlp_fwd_stats derives from the geometry alone, at every shape of the GPU grid and the
+    geometry of every channel pair (8 stored channels stand for Cout: the bounds are per channel)."""
+    import mlp_fwd_cases as S
+    worst = {}
+    for Cin, Cout in [(64, 128), (128, 256), (256, 256)]:           # 128-row tiles; 64-row tiles; the cap of 256
+        for P, nseg, per_seg, edge in S.SHAPES:
+            if not per_seg and (P, nseg, True, edge) in S.SHAPES:
+                continue
+            geo = R.mlp_fwd_geometry(P, nseg, Cin, Cout)
+            case, y = _stats_case(P, nseg, 8, P + nseg), _stored_rows(P, nseg, 8, P + Cin)
+            st = R.mlp_fwd_stats(y, case, geo)
+            part = R.mlp_fwd_partials_emulated(y, case, geo)
+            fin = R.mlp_fwd_finalize(part, case)
+            for k, v in R.mlp_fwd_stats_ratios(st, part, **fin).items():
+                worst[k] = max(worst.get(k, 0.0), v)
+                assert v <= 1.0, (Cin, Cout, P, nseg, k, v)
+            assert (geo["lane_rows"] + 6) * R.U32 <= R.MLP_KAPPA
+            if P == 1:
+                assert float(st["var"].abs().max()) == 0.0 and float(st["E_rstd"].max()) <= 2.1 * R.U32 * 1e5 ** 0.5
+    print("\nemulated epilogue, largest error / bound: " + ", ".join(f"{k} {v:.3g}" for k, v in sorted(worst.items())))
+
+
+def test_mlp_fwd_bounds_reject_planted_defects():
+    """Each defect planted into a correct float64-derived result of the forward at the GPU grid's shapes must fail the
+    check that tests/test_mlp_gpu.py applies (the stored-value interval at kappa = R.MLP_KAPPA, the statistics bounds of
+    R.mlp_fwd_stats); the unmodified result passes each."""
+    import torch
+    kap = R.MLP_KAPPA
+    seen = []
+
+    def rej(name, ratio):
+        seen.append(f"{name}: {ratio:.3g}")
+        assert ratio > 1.0, (name, ratio)
+    # ---- 64 -> 128 at 70001 rows: 547 tiles of 128 rows on 512 workgroups, the first 35 walk two tiles
+    Cin, Cout, P, nseg = 64, 128, 70001, 1
+    geo = R.mlp_fwd_geometry(P, nseg, Cin, Cout)
+    case = R.mlp_fwd_case(Cin, Cout, P, nseg, False, "ss", seed=1)
+    ref = R.mlp_fwd_ref(case, 0.01)
+    y_ok = R.rbf16(R.r32(ref["y"]))
+    assert Cin * R.U32 <= kap and R.mlp_fwd_stored_ratio(y_ok, ref, kap) <= 1.0
+    y = y_ok.clone()                                    # one row's product computed from the neighbouring row
+    y[P // 2] = y_ok[P // 2 + 1]
+    rej("y: a row's product from the neighbouring row", R.mlp_fwd_stored_ratio(y, ref, kap))
+    G, BM = geo["G"], geo["BM"]                         # one k-step dropped on a workgroup's second tile
+    assert geo["tiles_wg"][3] == 2
+    rows = slice((3 + G) * BM, (4 + G) * BM)
+    a = ref["a"].clone()
+    a[rows, 32:64] = 0.0
+    y = y_ok.clone()
+    y[rows] = R.rbf16(R.r32(R.mlp_fwd_ref(case, 0.01, a=a)["y"][rows]))
+    rej("y: one k-step dropped on a second tile", R.mlp_fwd_stored_ratio(y, ref, kap))
+    T = Cout // 16                                      # two output channels swapped (column j*T + t read as t*16 + j)
+    y = y_ok.clone()
+    y[:, [1, T]] = y_ok[:, [T, 1]]
+    rej("y: two output channels swapped", R.mlp_fwd_stored_ratio(y, ref, kap))
+    # statistics of the stored rows
+    st = R.mlp_fwd_stats(y_ok, case, geo)
+    part_ok = torch.stack([st["part_mean"], st["part_M2"], st["part_n"]], 2)
+    ok = R.mlp_fwd_finalize(R.r32(part_ok), case)
+    assert max(R.mlp_fwd_stats_ratios(st, R.r32(part_ok), **ok).values()) <= 1.0
+    emu = R.mlp_fwd_partials_emulated(y_ok, case, geo)
+    assert max(R.mlp_fwd_stats_ratios(st, emu, **R.mlp_fwd_finalize(emu, case)).values()) <= 1.0
+    tail = dict(case, P=P + 1)                          # the clamped tail row counted as a row
+    y_t = torch.cat([y_ok, y_ok[-1:]])
+    geo_t = R.mlp_fwd_geometry(P + 1, nseg, Cin, Cout)
+    assert geo_t["G"] == G and geo_t["last_wg"] == geo["last_wg"]
+    bad = R.mlp_fwd_partials_emulated(y_t, tail, geo_t)
+    r = R.mlp_fwd_stats_ratios(st, bad, **R.mlp_fwd_finalize(bad, tail))
+    for k in ("part_n", "part_mean", "mean", "rstd", "running_mean"):
+        rej("a clamped tail row counted, " + k, r[k])
+    bad = emu.clone()                                   # a partial's n off by one, nothing else
+    bad[0, geo["last_wg"], 2] += 1.0
+    rej("a partial's n off by one, part_n", R.mlp_fwd_stats_ratios(st, bad)["part_n"])
+    bad = R.mlp_fwd_partials_emulated(y_ok, case, geo, pivot_zero=True)      # E[x^2] - E[x]^2 in fp32
+    r = R.mlp_fwd_stats_ratios(st, bad, **R.mlp_fwd_finalize(bad, case))
+    mu = R.MLP_FWD_MU_CHANNEL
+    sig = float(st["var"][0, mu].sqrt())
+    assert 300.0 < float(st["mean"][0, mu].abs()) / sig < 3000.0
+    for k in ("part_M2", "rstd"):
+        rej("no pivot, sums in fp32, " + k, r[k])
+    rej("no pivot, part_M2 of the |mean| >> sigma channel",
+        R.err_ratio(bad[:, :, 1, mu], st["part_M2"][..., mu], st["E_part_M2"][..., mu]))
+    # ---- 70 segments of 1100 rows: the running chain in the wrong segment order across the two sweeps
+    Cin, Cout, P, nseg = 64, 64, 1100, 70
+    geo = R.mlp_fwd_geometry(P, nseg, Cin, Cout)
+    case = R.mlp_fwd_case(Cin, Cout, P, nseg, True, "ci", seed=2)
+    y_ok = R.rbf16(R.r32(R.mlp_fwd_ref(case, 0.01)["y"]))
+    st = R.mlp_fwd_stats(y_ok, case, geo)
+    emu = R.mlp_fwd_partials_emulated(y_ok, case, geo)
+    assert max(R.mlp_fwd_stats_ratios(st, emu, **R.mlp_fwd_finalize(emu, case)).values()) <= 1.0
+    fin = R.mlp_fwd_finalize(emu, case, order=list(range(64, 70)) + list(range(64)))
+    r = R.mlp_fwd_stats_ratios(st, emu, **fin)
+    assert r["mean"] <= 1.0 and r["rstd"] <= 1.0, r
+    for k in ("running_mean", "running_var"):
+        rej("second sweep's segments chained first, " + k, r[k])
+    # ---- 3 x 2997 rows, one weight for all: segment 1 multiplied by a weight of its own
+    Cin, Cout, P, nseg = 128, 128, 2997, 3
+    case = R.mlp_fwd_case(Cin, Cout, P, nseg, False, None, seed=3)
+    ref = R.mlp_fwd_ref(case, 0.2)
+    y_ok = R.rbf16(R.r32(ref["y"]))
+    assert R.mlp_fwd_stored_ratio(y_ok, ref, kap) <= 1.0
+    other = R.mlp_fwd_case(Cin, Cout, P, nseg, True, None, seed=3)["W"]
+    assert not torch.equal(other[1], case["W"][0])
+    y = R.rbf16(R.r32(R.mlp_fwd_ref(case, 0.2, W=other)["y"]))
+    rej("y: a shared weight read as per-segment", R.mlp_fwd_stored_ratio(y, ref, kap))
+    print("\nplanted defects, error / bound: " + "; ".join(seen))
