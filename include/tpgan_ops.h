@@ -184,7 +184,10 @@ int tpg_three_interp_bwd_f32(const float *gout, const int32_t *idx, const float 
  * U (B,N,C), QE (B,S,C) of dtype_in; idx (B,S,K) int32; out (B,S,K,C) of dtype_out.  Rows
  * are channels-last; C % 4 == 0 when both types are f32, else C % 8 == 0; 16-B aligned bases.
  * Arithmetic is fp32 in registers with one rounding on store (f32 in -> bf16 out keeps the
- * difference U - QE exact before the single bf16 rounding). */
+ * difference U - QE exact before the single bf16 rounding).
+ * An idx entry outside [0, N) reads row N - 1, in the forward, in tpg_invert_index and in the backward alike.
+ * The LeakyReLU's derivative at a difference of exactly 0 (every point of a kNN graph is its own neighbour) is
+ * `slope` on the neighbour side and on the centre side, so the two cancel; the front end's lrelu'(0) is slope_a. */
 typedef enum { TPG_DTYPE_F32 = 0, TPG_DTYPE_BF16 = 1 } tpg_dtype;
 
 int tpg_rowcombine_fwd(const void *U, const void *QE, const int32_t *idx, int mode, int dtype_in,

@@ -1426,3 +1426,139 @@ def rowbn_dx_bound(ref, Ec12, nseg, bf16):
     E = ref["E"] if Ec12 is None else \
         ref["E"] + _rows(ref["a"], P).abs() * (_rows(Ec12[:, 0], P) + ref["xhat"].abs() * _rows(Ec12[:, 1], P))
     return small_stored_bound(ref["dx"], E, bf16) + (2.0 ** -134 if bf16 else 0.0)    # half a bf16 denormal step
+
+
+# ---- the row-gather kernels (csrc/rowgather.hip): geometry, FP64 twins, per-element bounds --------------------------
+# The launcher's constants, copied (tests/test_rowgather_cpu.py reads the #define defaults out of csrc/rowgather.hip and
+# fails when they differ, and re-asserts which launch edge every case of tests/rowgather_cases.py still reaches).
+TPG_RC_FWD_U = 1                  # csrc/rowgather.hip
+TPG_RC_FWD_CAP = 16384            # csrc/rowgather.hip
+TPG_RC_BWD_CAP = 4096             # csrc/rowgather.hip
+TPG_RC_BWD_WAVE_CAP = 16384       # csrc/rowgather.hip
+TPG_RC_ROWSUM_CAP = 16384         # csrc/rowgather.hip, grid_for's default cap (rowsum_neg_kernel)
+ROW_GATHER, ROW_SUB, ROW_EDGE = 0, 1, 2
+
+
+def rowcombine_geometry(mode, B, N, S, K, C, dtype_in, dtype_out):
+    """The integer decisions of fwd_go / bwd_go (csrc/rowgather.hip) -> dict: ne, cpr; forward: total (chunks), wgs,
+    wgs_launched (rounded up to a multiple of 8 under the XCD ordering), xcd, idle (workgroups without a chunk),
+    passes_fwd; backward: form ("wave" / "thread"), G (64 / cpr, wave form only), grid_bwd, passes_bwd; passes_rowsum
+    (SUB's rowsum_neg launch, else 0)."""
+    ne = 8 if (_is_bf16(dtype_in) or _is_bf16(dtype_out)) else 4
+    assert C > 0 and C % ne == 0 and (mode != ROW_EDGE or S == N)
+    cpr = C // ne
+    total = B * S * K * cpr
+    wgs = max(1, min(TPG_RC_FWD_CAP, -(-total // (256 * TPG_RC_FWD_U))))
+    xcd = wgs >= 64
+    launched = (wgs + 7) & ~7 if xcd else wgs
+    rows = B * N
+    wave = cpr <= 32 and 64 % cpr == 0 and not (mode == ROW_EDGE and cpr <= 2)
+    if wave:
+        grid = max(1, min(TPG_RC_BWD_WAVE_CAP, -(-rows // 4)))
+        passes = -(-rows // (4 * grid))
+    else:
+        grid = max(1, min(TPG_RC_BWD_CAP, -(-rows * cpr // 256)))
+        passes = -(-rows * cpr // (256 * grid))
+    totq = B * S * cpr
+    pq = -(-totq // (256 * max(1, min(TPG_RC_ROWSUM_CAP, -(-totq // 256))))) if mode == ROW_SUB else 0
+    return dict(ne=ne, cpr=cpr, total=total, wgs=wgs, wgs_launched=launched, xcd=xcd,
+                idle=launched - -(-total // 256), passes_fwd=-(-total // (launched * 256 * TPG_RC_FWD_U)),
+                form="wave" if wave else "thread", G=64 // cpr if wave else None, grid_bwd=grid, passes_bwd=passes,
+                passes_rowsum=pq)
+
+
+def rowcombine_clamp(idx, N):
+    """tpg_clamp_idx: anything outside [0, N) reads row N - 1 -> int64 indices.  (oracle/tpgref.c does not clamp.)"""
+    i = idx.long()
+    return torch.where((i >= 0) & (i < N), i, torch.full_like(i, N - 1))
+
+
+def _rc_gather(T, idxc):
+    B, S, K = idxc.shape
+    Cc = T.shape[2]
+    return torch.gather(T, 1, idxc.reshape(B, S * K, 1).expand(-1, -1, Cc)).view(B, S, K, Cc)
+
+
+def rowcombine_fwd_twin(U, QE, idx, mode, slope=0.2, slope_u=1.0, dt=torch.float64):
+    """tpg_rowcombine_fwd on values of the row type, before the store's rounding.  dt = float64: the exact value (the
+    LeakyReLU's branch from the fp32 difference, whose sign is the exact one's; the slope as the launch's C float).
+    dt = float32: the kernel op for op -- one rounding per subtraction, product and sum, nothing contracted.
+    slope_u != 1: the front end's LeakyReLU of the gathered U row (tpg_rowcombine_edge_fwd)."""
+    idxc = rowcombine_clamp(idx, U.shape[1])
+    u = _rc_gather(U.to(dt).contiguous(), idxc)
+    if mode == ROW_GATHER:
+        return u
+    QE = QE.to(dt).contiguous()
+    if mode == ROW_SUB:
+        return u - QE[:, :, None]
+    d = _rc_gather(QE, idxc) - QE[:, :, None]
+    a = u if slope_u == 1.0 else torch.where(u > 0, u, u * slope32(slope_u))
+    return a + torch.where(d > 0, d, d * slope32(slope))
+
+
+def rowcombine_edge_fwd_twin(Y, idx, slope_a=0.2, slope_e=0.2, dt=torch.float64):
+    Cc = Y.shape[2] // 2
+    return rowcombine_fwd_twin(Y[:, :, Cc:], Y[:, :, :Cc], idx, ROW_EDGE, slope_e, slope_a, dt)
+
+
+def rowcombine_bwd_twin(g, idx, E, mode, N, slope=0.2, Uraw=None, slope_u=1.0, defect=None):
+    """tpg_rowcombine_bwd in float64 -> {name: dict(v, n, A, depth)} per output element: the exact value, its number of
+    terms, the sum of |term| and the factor of the fp32 bound depth * 2^-24 * A (rowcombine_bound):
+      gU   (B,N,C)  sum over the destination's list (L entries; indices clamped as the forward reads them)    depth L
+      gQE  SUB  (B,S,C): -sum_k g                                                                            depth K
+           EDGE (B,N,C): sum over the list of g lrelu'(E[n] - E[s]) - sum_k g lrelu'(E[idx[n,k]] - E[n]);
+                lrelu' = 1 where the fp32 difference is > 0, else the slope -- at 0 too, on BOTH sides; one more
+                rounding for the slope's product                                                     depth L + K + 1
+      gA   (Uraw given: the front end) gU * lrelu'(Uraw), the slope at 0                                  depth L + 1
+    and L (B,N), the list lengths.  defect (tests/test_rowgather_cpu.py): "nbr_ge" takes >= on the neighbour side only,
+    "a_zero" leaves slope_u out where Uraw == 0."""
+    g = g.double()
+    B, S, K, Cc = g.shape
+    idxc = rowcombine_clamp(idx, N)
+    flat = idxc.reshape(B, S * K)
+
+    def scatter(v):
+        out = torch.zeros(B, N, Cc, dtype=torch.float64, device=g.device)
+        return out.scatter_add_(1, flat[:, :, None].expand(-1, -1, Cc), v.reshape(B, S * K, Cc))
+    L = torch.zeros(B, N, dtype=torch.float64, device=g.device).scatter_add_(1, flat, torch.ones_like(flat, dtype=torch.float64))
+    Ln = L[:, :, None].expand(B, N, Cc)
+    r = dict(L=L, gU=dict(v=scatter(g), n=Ln, A=scatter(g.abs()), depth=Ln))
+    if mode == ROW_SUB:
+        kk = torch.full((B, S, Cc), float(K), dtype=torch.float64, device=g.device)
+        r["gQE"] = dict(v=-g.sum(2), n=kk, A=g.abs().sum(2), depth=kk)
+    elif mode == ROW_EDGE:
+        E = E.double().contiguous()
+        d = _rc_gather(E, idxc) - E[:, :, None]
+        s = slope32(slope)
+        gs = g * s
+        ge_n = torch.where((d >= 0) if defect == "nbr_ge" else (d > 0), g, gs)
+        ge_c = torch.where(d > 0, g, gs)
+        r["gQE"] = dict(v=scatter(ge_n) - ge_c.sum(2), n=Ln + K, A=scatter(ge_n.abs()) + ge_c.abs().sum(2),
+                        depth=Ln + (K + 1))
+        if Uraw is not None:
+            Ur = Uraw.double()
+            f = torch.where((Ur >= 0) if defect == "a_zero" else (Ur > 0), 1.0, slope32(slope_u))
+            r["gA"] = dict(v=r["gU"]["v"] * f, n=Ln, A=r["gU"]["A"] * f, depth=Ln + 1)
+    return r
+
+
+def rowcombine_edge_bwd_twin(g, idx, Y, slope_a=0.2, slope_e=0.2, defect=None):
+    """tpg_rowcombine_edge_bwd: gY = [gE | gA] -> the twin's dict with gE (= gQE of mode EDGE) and gA."""
+    Cc = Y.shape[2] // 2
+    r = rowcombine_bwd_twin(g, idx, Y[:, :, :Cc], ROW_EDGE, Y.shape[1], slope_e, Y[:, :, Cc:], slope_a, defect)
+    r["gE"] = r.pop("gQE")
+    return r
+
+
+def rowcombine_bound(t, bf16):
+    """A gradient element summed in fp32 in ANY order, every term rounded at most once before: within depth * u * A of the
+    exact sum (first order in u = 2^-24; depth terms meet at most depth roundings on their way).  Stored as bf16: one
+    round-to-nearest-even of that fp32 value on top.  No additive slack: an element without terms is exactly 0."""
+    fb = t["depth"] * U32 * t["A"]
+    return fb + BF16_REL * (t["v"].abs() + fb) if bf16 else fb
+
+
+def rowcombine_lists(idx, N):
+    """tpg_invert_index of one cloud: idx (S*K) -> (offs (N + 1), list (S*K)) numpy, a stable sort by clamped destination."""
+    ic = rowcombine_clamp(torch.as_tensor(idx).reshape(-1), N).cpu().numpy()
+    return np.concatenate([[0], np.cumsum(np.bincount(ic, minlength=N))]), np.argsort(ic, kind="stable")

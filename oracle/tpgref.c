@@ -383,7 +383,9 @@ int tpgref_rowcombine_fwd_f32(const float *U, const float *QE, const int32_t *id
     return TPG_OK;
 }
 
-/* sums run in (s,k) order per destination (the HIP order is unspecified -> 1e-5) */
+/* sums run in (s,k) order per destination; the HIP order is unspecified, so the kernels are judged per element
+ * against the float64 twin: depth * 2^-24 * sum |term| (oracle/ref_ops.py rowcombine_bound, tests/rowgather_rule.py).
+ * idx is NOT clamped here: callers pass indices inside [0, N). */
 int tpgref_rowcombine_bwd_f32(const float *gout, const int32_t *idx, const float *E, int mode, int B,
                               int N, int S, int K, int C, float slope, float *gU, float *gQE) {
     if (B < 0 || N <= 0 || S < 0 || K < 0 || C <= 0 || mode < 0 || mode > 2) return TPG_ERR_ARG;
