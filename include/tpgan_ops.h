@@ -800,6 +800,83 @@ int tpg_surface_shade_f32(const float *depth, const int32_t *winner, const float
                           int ncam, int W, int H, float lo, float hi, const uint8_t *lut, const uint8_t *background,
                           const float *shade, uint8_t *image, void *stream);
 
+/* ---- mesh pictures (csrc/mesh_render.hip) -----------------------------------------------------------------------
+ * A z-buffered rasteriser of indexed triangle meshes in two entries: the nearest face per pixel (a), then deferred
+ * shading of that face (b).  (The reference hands its geometry to an external renderer; the look here is this
+ * project's own.)  vertices (M,V,3) f32; vlengths (M) int64 or NULL: vlen = vlengths[m] taken into 0..V (NULL: V), rows
+ * at or beyond it are never read; faces (M,T,3) int32; flengths (M) int64 or NULL: tlen likewise, faces at or beyond it
+ * are never read.  M = 1: one mesh drawn in all F frames (an obstacle); M = F: mesh f in frame f.  cams, ncam, W, H,
+ * keys and the projection of a vertex to u, v, zv, t = zv - near are tpg_render_points_f32's, word for word (fp32, each
+ * operation rounded on its own, dot products as (a.x*b.x + a.y*b.y) + a.z*b.z).  The depth is perspective-correct;
+ * every other attribute is interpolated linearly in SCREEN space, also under a pinhole camera (stated, not an error).
+ *
+ * Per face j < tlen with the indices i0, i1, i2:
+ *   dropped unless all three lie in 0..vlen-1 (such a face never addresses memory; neither clamped nor an error);
+ *   dropped unless every vertex passes  t >= 0 && zv <= far && fabsf(u) < 32768 && fabsf(v) < 32768  (TPG_MESH_GUARD),
+ *     which a NaN or an infinity anywhere fails; the test comes BEFORE any conversion to an integer.  There is NO
+ *     clipping: a triangle that crosses the near plane or leaves the guard band is not drawn.
+ *   Snap, 8 subpixel bits: X = (int)floorf(u*256.0f + 0.5f), Y = (int)floorf(v*256.0f + 0.5f); below the guard band the
+ *     product and the sum are exact.  The centre of pixel (x, y) is (256x+128, 256y+128).
+ *   Edge function, int64 and exact (differences < 2^25): E(a, b, p) = (bx-ax)*(py-ay) - (by-ay)*(px-ax).
+ *     A = E(v0, v1, v2); the face is dropped if A == 0.  s = the sign of A.  At a pixel centre p
+ *       w0 = s*E(v1, v2, p),  w1 = s*E(v2, v0, p),  w2 = s*E(v0, v1, p)          (w0 + w1 + w2 = |A|)
+ *     and the edge a -> b of w_i has the direction (dx, dy) = s*(b - a).  The pixel is covered iff for every i
+ *       w_i > 0  ||  (w_i == 0 && (dy < 0 || (dy == 0 && dx > 0)))
+ *     With y pointing down and the inside where E > 0 the owning edges are the left ones and the horizontal top ones:
+ *     the rule depends on the edge's direction only and opposite directions get opposite answers, so a centre exactly on
+ *     an edge shared by two triangles on opposite sides of it belongs to exactly one of them, and a centre on the shared
+ *     vertex of a closed fan to exactly one triangle of the fan.  Both sides are drawn; there is no culling.
+ *   Candidate pixels: those whose centres lie in the snapped bounding box, columns (Xmin + 127) >> 8 .. (Xmax - 128) >> 8
+ *     (>> rounding down), rows likewise, clipped to the image.  Every covered pixel is a candidate.
+ *   Depth of a covered pixel, in float64, every operation rounded on its own (the library is built with contraction
+ *     off): l_i = (double)w_i / (double)|A|;
+ *       ortho:    t = (float)((l0*t0 + l1*t1) + l2*t2)
+ *       pinhole:  Z = 1.0 / ((l0/zv0 + l1/zv1) + l2/zv2);  t = (float)(Z - (double)near)
+ *     and t is replaced by 0.0f unless t > 0, as the sphere fronts are.  Key (bits(t) << 32) | j, 64-bit atomic min on
+ *     `keys`, (F,H,W) uint64, 8-byte aligned, set to all ones by the call itself.
+ * (a) tpg_render_mesh_f32 -> depth (F,H,W) f32: the float whose bits are the key's high word, +inf for background;
+ *   winner (F,H,W) int32: the key's low word, -1 for background.  Equal depths show the lower face index; the result
+ *   does not depend on the order of execution nor on which lane draws which pixel (faces whose clipped box holds at most
+ *   TPG_MESH_SMALL pixels are drawn by one lane, the others by a whole wave, and those of more than TPG_MESH_HUGE
+ *   pixels by a second launch over 32 x 32 tiles from a list of TPG_MESH_LIST faces per frame, a face that finds the
+ *   list full being drawn by a wave; tuning values, not part of the rule).  list: (F * (1 + TPG_MESH_LIST)) int32, a
+ *   workspace the call itself initialises.
+ * (b) tpg_mesh_shade_f32: depth, winner as (a) wrote them, the mesh, normals (M,V,3) f32 or NULL, scalar (M,V) f32 or
+ *   NULL, lo, hi, lut, background as for tpg_render_points_f32, base (3) uint8 on the device or NULL, shade: the HOST
+ *   table of tpg_surface_shade_f32 -> image (F,H,W,3) uint8.  A pixel whose winner j is outside 0..tlen-1, or names a
+ *   face that (a) drops, gets `background`.  Otherwise l0..l2 of face j at the pixel's centre are computed exactly as in
+ *   (a) and the view-space normal is
+ *     with normals:  nw_k = (float)((l0*(double)n0_k + l1*(double)n1_k) + l2*(double)n2_k) per component k (n_i the
+ *       normal of vertex i_i), then n = (nw.r, nw.d, nw.f) with the camera's rows, fp32 dot products;
+ *     without: with P_i = (xv, yv, zv) of vertex i in fp32, a = P1 - P0, b = P2 - P0, n = cross(a, b), each component
+ *       a*b - c*d:  nx = a.y*b.z - a.z*b.y;  ny = a.z*b.x - a.x*b.z;  nz = a.x*b.y - a.y*b.x.
+ *   len = sqrtf((nx*nx + ny*ny) + nz*nz); n = n / len componentwise if len > 0, else (0,0,-1); then n = -n if nz > 0, so
+ *   both sides are lit.  Base colour: `base` if given; else lut[level] by tpg_render_points_f32's level rule with
+ *   s = (float)((l0*(double)s0 + l1*(double)s1) + l2*(double)s2) of the vertices' scalars, or s = depth at the pixel
+ *   when scalar is NULL.  dif, sp, fr, val and the final rounding are tpg_surface_shade_f32's, word for word.
+ *
+ * Checks, all before anything is launched.  TPG_ERR_ARG: negative F, M, V or T, a NULL output, W or H < 1; for (b) also
+ * hi <= lo and the shade table's conditions.  Then F == 0, T == 0 or V == 0: TPG_OK, nothing written (the caller's
+ * outputs stay what they were: the Python layer sets them to background).  Then another NULL pointer (lut may be NULL
+ * with a base), a NULL list, keys not 8-byte aligned, M not 1 or F, and the camera and lo / inv conditions of tpg_render_points_f32:
+ * TPG_ERR_ARG; its limits on W, H, F and the pixels in all, and T or V above TPG_MESH_MAX_ROWS (2^31 / 3):
+ * TPG_ERR_UNSUPPORTED. */
+#define TPG_MESH_GUARD 32768
+#ifndef TPG_MESH_SMALL             /* tools/mesh_render_time.py builds the library with other values to time them */
+#define TPG_MESH_SMALL 16
+#endif
+#define TPG_MESH_HUGE 2048
+#define TPG_MESH_LIST 256
+#define TPG_MESH_MAX_ROWS 715827882
+int tpg_render_mesh_f32(const float *vertices, const int64_t *vlengths, const int32_t *faces, const int64_t *flengths,
+                        int M, int V, int T, int F, const float *cams, int ncam, int W, int H, void *keys, int32_t *list,
+                        float *depth, int32_t *winner, void *stream);
+int tpg_mesh_shade_f32(const float *depth, const int32_t *winner, const float *vertices, const int64_t *vlengths,
+                       const int32_t *faces, const int64_t *flengths, const float *normals, const float *scalar, int M,
+                       int V, int T, int F, const float *cams, int ncam, int W, int H, float lo, float hi,
+                       const uint8_t *lut, const uint8_t *base, const uint8_t *background, const float *shade,
+                       uint8_t *image, void *stream);
+
 /* ---- particle fluid simulator (csrc/pbf.hip) ---------------------------------------------------------------------
  * Position Based Fluids (Macklin and Mueller 2013) with Jacobi iterations in gather form: the simulator that writes the
  * training sequences (the reference drives an external DFSPH solver, fluid_data_generation/; look and statistics here

@@ -2,7 +2,7 @@
 
     python -m tpgan_amd.mesh --frames 'out/pcd_{i}.npy' --count 200 --out meshes [--format ply|obj --spacing 0.025
         --support 0.05 --step 0.0125 --iso 0.5 --stats stats.npz --kernel isotropic|anisotropic --cov_radius 0.1
-        --smooth_lambda 0.9]
+        --smooth_lambda 0.9 --render PNGDIR (and the options of tpgan_amd.render)]
 
 The reference ends its demo (train_fluid/demo.ipynb, cell 5) by writing every upsampled frame to a geometry file for an
 external renderer that reconstructs the fluid's surface.  Here the surface is built on the device: the particles' cubic
@@ -408,10 +408,10 @@ def load_spec(spec):
 class SequenceMesher:
     """Meshes of a sequence, `pcd_{i:04d}.ply` (or .obj) in `out_dir`.  `push(frames, first)`: frames = list of (n_t,3)
     clouds, first = index of the first one -> one record per frame (frame, points, vertices, faces, volume, area), also
-    appended to `records`."""
+    appended to `records`.  on_mesh(index, mesh): called with every mesh after its file is written."""
 
     def __init__(self, out_dir, fmt="ply", spacing=analysis.BASE_RADIUS, support=None, step=None, iso=0.5, device="cuda",
-                 kernel="isotropic", cov_radius=None, smooth_lambda=0.9):
+                 kernel="isotropic", cov_radius=None, smooth_lambda=0.9, on_mesh=None):
         if fmt not in WRITERS:
             raise ValueError(f"format must be one of {sorted(WRITERS)}")
         if kernel not in KERNELS:
@@ -419,7 +419,7 @@ class SequenceMesher:
         self.out_dir, self.fmt, self.device = out_dir, fmt, torch.device(device)
         self.spacing, self.support, self.step, self.iso = spacing, support, step, iso
         self.kernel, self.cov_radius, self.smooth_lambda = kernel, cov_radius, smooth_lambda
-        self.records = []
+        self.records, self.on_mesh = [], on_mesh
         os.makedirs(out_dir, exist_ok=True)
 
     def push(self, frames, first):
@@ -429,6 +429,8 @@ class SequenceMesher:
             m = surface_mesh(p, self.spacing, self.support, self.step, self.iso, kernel=self.kernel,
                              cov_radius=self.cov_radius, smooth_lambda=self.smooth_lambda)
             WRITERS[self.fmt](os.path.join(self.out_dir, f"pcd_{first + t:04d}.{self.fmt}"), m)
+            if self.on_mesh is not None:
+                self.on_mesh(first + t, m)
             out.append(dict(frame=first + t, points=int(_valid_rows(p).shape[0]), vertices=int(m.vertices.shape[0]),
                             faces=int(m.faces.shape[0]), volume=volume(m), area=area(m)))
         self.records += out
@@ -461,6 +463,28 @@ def mesher_from(a, out_dir, device):
                           a.smooth_lambda)
 
 
+class MeshPictures:
+    """`--render`: every mesh that was written, drawn with its vertex normals to `pcd_{i:04d}.png` in `out_dir` under one
+    camera, fitted to the first mesh; `a` holds the options of `render.add_render_options` (its --solids are drawn too)."""
+
+    def __init__(self, a, out_dir):
+        self.a, self.out_dir, self.camera = a, out_dir, None
+        self.solids = load_spec(a.solids) if a.solids else None
+        os.makedirs(out_dir, exist_ok=True)
+
+    def __call__(self, index, m):
+        a = self.a
+        if self.camera is None:
+            ops._need(m.vertices.shape[0] > 0, "--render: the first frame has no surface to fit the camera to")
+            self.camera = render.Camera.fit(m.vertices, direction=a.direction, mode=a.mode, width=a.width, height=a.height)
+        image, depth = render.render_mesh(m, self.camera, return_depth=True)
+        if self.solids is not None:
+            image, _ = render._with_solids(image[None], depth[None], self.solids, a.solids_color, self.camera.row()[None],
+                                           self.camera, 1, (255, 255, 255), ops.RENDER_KEY_BYTES)
+            image = image[0]
+        render.write_png(os.path.join(self.out_dir, f"pcd_{index:04d}.png"), image)
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(prog="python -m tpgan_amd.mesh",
                                  description="Mesh the fluid surface of a sequence of frames to PLY / OBJ files.")
@@ -470,12 +494,16 @@ def main(argv=None):
     add_mesh_options(ap)
     ap.add_argument("--stats", default=None, metavar="FILE.npz", help="per-frame volume, area and their first differences")
     ap.add_argument("--device", default="cuda")
+    ap.add_argument("--render", default=None, metavar="PNGDIR", help="also draw every mesh to PNGDIR/pcd_{i:04d}.png")
+    render.add_render_options(ap)
     a = ap.parse_args(argv)
     if "{i}" not in a.frames:
         ap.error("--frames must contain '{i}'")
     if a.count < 1:
         ap.error("--count must be at least 1")
     seq = mesher_from(a, a.out, a.device)
+    if a.render:
+        seq.on_mesh = MeshPictures(a, a.render)
     for i in range(a.count):
         for record in seq.push([render.load_frame(a.frames.format(i=i))], i):
             print(json.dumps(record), flush=True)

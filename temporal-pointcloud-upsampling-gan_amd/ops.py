@@ -383,6 +383,38 @@ class HipBackend:
                        _ptr(image[f0:f1]))
         return image, depth, winner
 
+    def render_mesh(self, vertices, vlengths, faces, flengths, normals, scalar, cams, F, W, H, lo, hi, lut, base,
+                    background, shade, max_key_bytes):
+        """csrc/mesh_render.hip: raster + resolve, then the deferred shading; cams and shade are host fp32 arrays,
+        vertices (M,V,3) / faces (M,T,3) with M = 1 (one mesh in every frame) or F.  -> (image (F,H,W,3) uint8, depth
+        (F,H,W) fp32, winner (F,H,W) int32).  Frames go in chunks as in `render_points`, on the same key workspace."""
+        M, V, _ = vertices.shape
+        T = faces.shape[1]
+        dev = vertices.device
+        image = torch.empty((F, H, W, 3), dtype=torch.uint8, device=dev)
+        depth = torch.empty((F, H, W), dtype=torch.float32, device=dev)
+        winner = torch.empty((F, H, W), dtype=torch.int32, device=dev)
+        chunk = max(1, min(65535, int(max_key_bytes) // (8 * H * W)))
+        keys = self._workspace("render_keys", vertices, min(chunk, F) * H * W, dtype=torch.int64)
+        huge = self._workspace("mesh_list", vertices, min(chunk, F) * (1 + MESH_LIST), dtype=torch.int32)
+
+        def part(t, f0, f1):                        # the rows of a per-mesh tensor that frames f0 .. f1-1 read
+            return None if t is None else (t if M == 1 else t[f0:f1])
+        for f0 in range(0, F, chunk):
+            f1 = min(F, f0 + chunk)
+            n, pix = f1 - f0, (f1 - f0) * H * W
+            c = cams if cams.shape[0] == 1 else np.ascontiguousarray(cams[f0:f1])
+            m = 1 if M == 1 else n
+            mesh = (_ptr(part(vertices, f0, f1)), _ptr(part(vlengths, f0, f1)), _ptr(part(faces, f0, f1)),
+                    _ptr(part(flengths, f0, f1)))
+            self._call("tpg_render_mesh_f32", "render_mesh", n * (48 * T + 24 * H * W), vertices, *mesh, m, V, T, n,
+                       c.ctypes.data, c.shape[0], W, H, _ptr(keys), _ptr(huge), _ptr(depth[f0:f1]), _ptr(winner[f0:f1]))
+            self._call("tpg_mesh_shade_f32", "mesh_shade", 59 * pix, vertices, _ptr(depth[f0:f1]), _ptr(winner[f0:f1]),
+                       *mesh, _ptr(part(normals, f0, f1)), _ptr(part(scalar, f0, f1)), m, V, T, n, c.ctypes.data,
+                       c.shape[0], W, H, lo, hi, _ptr(lut), _ptr(base), _ptr(background), shade.ctypes.data,
+                       _ptr(image[f0:f1]))
+        return image, depth, winner
+
     # ---- the fluid simulator's launch kinds (csrc/pbf.hip); box (B,6) and gravity (3) are host fp32 arrays ----------
     def pbf_ws(self, ref, B, N):
         return self._workspace("pbf", ref, max(int(self.lib.tpg_pbf_workspace_bytes(B, N)), 1), dtype=torch.uint8)
@@ -2014,8 +2046,22 @@ def _picture_args(points, cams, width, height, lut, lengths, scalar, lo, hi, bac
     return F, N, W, H, cams, scalar, lo, hi, lut, background, lengths
 
 
+def _winner_depth_torch(points, cams, winner):
+    """The depth layer of a splat picture: t = zv - near of the winner point per pixel, by the projection of
+    `_render_points_torch` (the same fp32 operations in the same order), +inf where winner is -1 -> (F,H,W) fp32."""
+    F = points.shape[0]
+    depth = torch.full(winner.shape, float("inf"), dtype=torch.float32, device=points.device)
+    for f in range(F):
+        cam = torch.from_numpy(cams[f if cams.shape[0] > 1 else 0]).to(points.device)
+        hit = winner[f] >= 0
+        q = points[f][winner[f][hit].long()] - cam[0:3]
+        zv = (q[:, 0] * cam[9] + q[:, 1] * cam[10]) + q[:, 2] * cam[11]
+        depth[f][hit] = zv - cam[15]
+    return depth
+
+
 def render_points(points, cams, width, height, lut, size=1, lengths=None, scalar=None, lo=None, hi=None,
-                  background=(255, 255, 255), max_key_bytes=RENDER_KEY_BYTES):
+                  background=(255, 255, 255), max_key_bytes=RENDER_KEY_BYTES, return_depth=False):
     """One picture per cloud of a ragged batch: a z-buffered square splat (csrc/render.hip; the rule in full:
     include/tpgan_ops.h).
 
@@ -2028,21 +2074,28 @@ def render_points(points, cams, width, height, lut, size=1, lengths=None, scalar
     size: the splat's edge in pixels, 1..16.  max_key_bytes: cap of the kernel's 64-bit key buffer; F is rendered in
     chunks that stay under it (the pictures do not depend on it).
     -> (image (F,height,width,3) uint8, winner (F,height,width) int32: the visible point's index, -1 = background).
+    return_depth: also depth (F,height,width) fp32, the winner's t (torch ops after the kernel, `_winner_depth_torch`),
+    +inf = background: what `compose_layers` orders the splat by.
     Bit-identical from run to run and at every batch position; no gradient."""
     size = int(size)
     _need(1 <= size <= RENDER_MAX_SIZE, f"size must be 1..{RENDER_MAX_SIZE}")
     F, N, W, H, cams, scalar, lo, hi, lut, background, lengths = _picture_args(
         points, cams, width, height, lut, lengths, scalar, lo, hi, background, max_key_bytes)
     if F == 0 or N == 0:
-        return (background.view(1, 1, 1, 3).expand(F, H, W, 3).contiguous(),
-                torch.full((F, H, W), -1, dtype=torch.int32, device=points.device))
+        out = (background.view(1, 1, 1, 3).expand(F, H, W, 3).contiguous(),
+               torch.full((F, H, W), -1, dtype=torch.int32, device=points.device))
+        if return_depth:
+            out += (torch.full((F, H, W), float("inf"), dtype=torch.float32, device=points.device),)
+        return out
     be = backend_for(points)
     with torch.no_grad():
         args = (points.detach(), lengths, None if scalar is None else scalar.detach(), cams, W, H, size, lo, hi, lut,
                 background)
         if hasattr(be, "render_points"):
-            return be.render_points(*args, int(max_key_bytes))
-        return _render_points_torch(*args)
+            out = be.render_points(*args, int(max_key_bytes))
+        else:
+            out = _render_points_torch(*args)
+        return out + (_winner_depth_torch(points.detach(), cams, out[1]),) if return_depth else out
 
 
 # ---------------------------------------------------------------------- fluid surface pictures (csrc/surface.hip)
@@ -2105,6 +2158,266 @@ def render_surface(points, cams, width, height, lut, radius, lengths=None, scala
     with torch.no_grad():
         return be.render_surface(points.detach(), lengths, None if scalar is None else scalar.detach(), cams, W, H,
                                  radius, lo, hi, lut, background, half_width, iters, delta, shade, int(max_key_bytes))
+
+
+# -------------------------------------------------------------------------- mesh pictures (csrc/mesh_render.hip)
+MESH_GUARD = 32768.0                   # a face with a vertex at or beyond this many pixels from the origin is not drawn
+MESH_SMALL = 16                        # the kernel's class edge (tuning, not part of the rule): include/tpgan_ops.h
+MESH_HUGE = 2048                       # a box of more pixels is drawn by the tile launch, from a list of
+MESH_LIST = 256                        # this many faces per frame (tuning as well)
+MESH_MAX_ROWS = 715827882              # vertices or faces per mesh: 2^31 / 3
+_MESH_EDGES = ((1, 2), (2, 0), (0, 1))  # w_i is the edge function of the edge opposite vertex i
+
+
+def _mesh_edge(ax, ay, bx, by, px, py):
+    return (bx - ax) * (py - ay) - (by - ay) * (px - ax)
+
+
+def _mesh_faces_torch(vertices, faces, cam_row, vlen, tlen):
+    """The kept faces of one mesh (V,3) / (T,3) under one camera (host fp32 (18,)), by the rule of include/tpgan_ops.h:
+    -> None if there is none, else a dict of index (K,), tri (K,3), X, Y (K,3) int64, d (K,3) fp32 (zv under a pinhole
+    camera, else t), area = |A| and sign (K,) int64, own (K,3) bool, view (vlen,3) fp32 (xv, yv, zv of every vertex)."""
+    if vlen == 0 or tlen == 0:
+        return None
+    cam = torch.from_numpy(cam_row).to(vertices.device)
+    q = vertices[:vlen] - cam[0:3]
+
+    def dot(b):
+        return (q[:, 0] * b[0] + q[:, 1] * b[1]) + q[:, 2] * b[2]
+    xv, yv, zv = dot(cam[3:6]), dot(cam[6:9]), dot(cam[9:12])
+    pinhole = float(cam_row[17]) != 0.0
+    if pinhole:
+        u, v = (xv / zv) * cam[12] + cam[13], (yv / zv) * cam[12] + cam[14]
+    else:
+        u, v = xv * cam[12] + cam[13], yv * cam[12] + cam[14]
+    t = zv - cam[15]
+    good = (t >= 0) & (zv <= cam[16]) & (u.abs() < MESH_GUARD) & (v.abs() < MESH_GUARD)      # false for NaN and inf
+    zero = torch.zeros_like(u)
+    X = torch.floor(torch.where(good, u, zero) * 256.0 + 0.5).long()          # only rows that passed are converted
+    Y = torch.floor(torch.where(good, v, zero) * 256.0 + 0.5).long()
+    tri = faces[:tlen].long()
+    ok = ((tri >= 0) & (tri < vlen)).all(1)
+    ok = ok & good[torch.where(ok.unsqueeze(1), tri, torch.zeros_like(tri))].all(1)
+    index = torch.nonzero(ok).view(-1)
+    tri = tri[index]
+    X, Y = X[tri], Y[tri]
+    A = _mesh_edge(X[:, 0], Y[:, 0], X[:, 1], Y[:, 1], X[:, 2], Y[:, 2])
+    keep = A != 0
+    if not bool(keep.any()):
+        return None
+    index, tri, X, Y, A = index[keep], tri[keep], X[keep], Y[keep], A[keep]
+    sign = torch.sign(A)
+    own = []
+    for a, b in _MESH_EDGES:
+        dx, dy = sign * (X[:, b] - X[:, a]), sign * (Y[:, b] - Y[:, a])
+        own.append((dy < 0) | ((dy == 0) & (dx > 0)))
+    return dict(index=index, tri=tri, X=X, Y=Y, d=(zv if pinhole else t)[tri], area=A.abs(), sign=sign,
+                own=torch.stack(own, 1), view=torch.stack([xv, yv, zv], 1), pinhole=pinhole, near=float(cam_row[15]))
+
+
+def _mesh_weights_torch(fc, rows, px, py):
+    """w0..w2 (int64) and l0..l2 (float64) of the kept faces `rows` at the points (px, py) (1/256 pixel), broadcast."""
+    X, Y, s, area = fc["X"][rows], fc["Y"][rows], fc["sign"][rows], fc["area"][rows].double()
+    if px.dim() == 2:                               # (1, pixels) against (faces, 1); else one face per point
+        X, Y, s, area = X.unsqueeze(-1), Y.unsqueeze(-1), s.unsqueeze(-1), area.unsqueeze(-1)
+    w = [s * _mesh_edge(X[:, a], Y[:, a], X[:, b], Y[:, b], px, py) for a, b in _MESH_EDGES]
+    return w, [wi.double() / area for wi in w]
+
+
+def _mesh_depth_torch(fc, rows, lam):
+    d = fc["d"][rows].double()
+    d = [d[:, k].unsqueeze(-1) if lam[0].dim() == 2 else d[:, k] for k in range(3)]
+    if fc["pinhole"]:
+        Z = 1.0 / ((lam[0] / d[0] + lam[1] / d[1]) + lam[2] / d[2])
+        t = (Z - float(np.float32(fc["near"]))).float()
+    else:
+        t = ((lam[0] * d[0] + lam[1] * d[1]) + lam[2] * d[2]).float()
+    return torch.where(t > 0, t, torch.zeros_like(t))
+
+
+def _render_mesh_torch(vertices, vlengths, faces, flengths, cams, F, W, H, pairs_per_chunk=1 << 22):
+    """Entry (a) of the mesh pictures composed of torch ops (backends without the kernel): every kept face against every
+    pixel centre, `pairs_per_chunk` face x pixel pairs at a time -> (depth (F,H,W) fp32, winner (F,H,W) int32).  The
+    candidate box of the rule is not needed: a covered pixel always lies in it."""
+    M, V, _ = vertices.shape
+    T = faces.shape[1]
+    dev = vertices.device
+    depth = torch.empty((F, H, W), dtype=torch.float32, device=dev)
+    winner = torch.empty((F, H, W), dtype=torch.int32, device=dev)
+    vl = [V] * M if vlengths is None else [min(max(int(v), 0), V) for v in vlengths.tolist()]
+    fl = [T] * M if flengths is None else [min(max(int(v), 0), T) for v in flengths.tolist()]
+    at = torch.arange(H * W, device=dev)
+    px, py = (256 * (at % W) + 128).view(1, -1), (256 * (at // W) + 128).view(1, -1)
+    step = max(1, int(pairs_per_chunk) // (H * W))
+    for f in range(F):
+        m = f if M > 1 else 0
+        fc = _mesh_faces_torch(vertices[m], faces[m], cams[f if cams.shape[0] > 1 else 0], vl[m], fl[m])
+        keys = torch.full((H * W,), 2 ** 63 - 1, dtype=torch.int64, device=dev)
+        for k0 in range(0, 0 if fc is None else fc["index"].shape[0], step):
+            rows = torch.arange(k0, min(k0 + step, fc["index"].shape[0]), device=dev)
+            w, lam = _mesh_weights_torch(fc, rows, px, py)
+            inside = torch.ones_like(w[0], dtype=torch.bool)
+            for k in range(3):
+                inside &= (w[k] > 0) | ((w[k] == 0) & fc["own"][rows, k].unsqueeze(-1))
+            t = _mesh_depth_torch(fc, rows, lam)
+            key = (((t.view(torch.int32).long() & 0xFFFFFFFF) << 32) | fc["index"][rows].unsqueeze(-1)) ^ _KEY_FLIP
+            key = torch.where(inside, key, torch.full_like(key, 2 ** 63 - 1))
+            keys = torch.minimum(keys, key.amin(0))
+        hit = keys != 2 ** 63 - 1
+        ukey = keys ^ _KEY_FLIP
+        winner[f] = torch.where(hit, ukey & 0xFFFFFFFF, torch.full_like(keys, -1)).to(torch.int32).view(H, W)
+        bits = ((ukey >> 32) & 0xFFFFFFFF).to(torch.int32).view(torch.float32)
+        depth[f] = torch.where(hit, bits, torch.full_like(bits, float("inf"))).view(H, W)
+    return depth, winner
+
+
+def _mesh_shade_torch(depth, winner, vertices, vlengths, faces, flengths, normals, scalar, cams, lo, hi, lut, base,
+                      background, shade):
+    """Entry (b) of the mesh pictures composed of torch ops -> image (F,H,W,3) uint8."""
+    F, H, W = depth.shape
+    M, V, _ = vertices.shape
+    T = faces.shape[1]
+    dev = vertices.device
+    vl = [V] * M if vlengths is None else [min(max(int(v), 0), V) for v in vlengths.tolist()]
+    fl = [T] * M if flengths is None else [min(max(int(v), 0), T) for v in flengths.tolist()]
+    sh = torch.from_numpy(np.ascontiguousarray(shade, dtype=np.float32)).to(dev)
+    lo_t = torch.tensor(np.float32(lo), device=dev)
+    inv = torch.tensor(np.float32(255.0) / (np.float32(hi) - np.float32(lo)), device=dev)
+    image = background.view(1, 1, 3).expand(F, H * W, 3).contiguous()
+    at = torch.arange(H * W, device=dev)
+    for f in range(F):
+        m = f if M > 1 else 0
+        cam_row = cams[f if cams.shape[0] > 1 else 0]
+        fc = _mesh_faces_torch(vertices[m], faces[m], cam_row, vl[m], fl[m])
+        if fc is None:
+            continue
+        cam = torch.from_numpy(cam_row).to(dev)
+        slot = torch.full((T + 1,), -1, dtype=torch.int64, device=dev)
+        slot[fc["index"]] = torch.arange(fc["index"].shape[0], device=dev)
+        win = winner[f].view(-1).long()
+        k = torch.where((win >= 0) & (win < fl[m]), slot[win.clamp(0, T)], torch.full_like(win, -1))
+        pix = at[k >= 0]
+        rows = k[pix]
+        _, lam = _mesh_weights_torch(fc, rows, 256 * (pix % W) + 128, 256 * (pix // W) + 128)
+        tri = fc["tri"][rows]
+
+        def mix(a):                                 # a (V,) fp32 -> the pixel's value, float64 and rounded once
+            a = a.double()
+            return ((lam[0] * a[tri[:, 0]] + lam[1] * a[tri[:, 1]]) + lam[2] * a[tri[:, 2]]).float()
+        if normals is not None:
+            nw = [mix(normals[m][:, j]) for j in range(3)]
+            n = [(nw[0] * cam[3 + 3 * r] + nw[1] * cam[4 + 3 * r]) + nw[2] * cam[5 + 3 * r] for r in range(3)]
+        else:
+            P = fc["view"]
+            a, b = P[tri[:, 1]] - P[tri[:, 0]], P[tri[:, 2]] - P[tri[:, 0]]
+            n = [a[:, 1] * b[:, 2] - a[:, 2] * b[:, 1], a[:, 2] * b[:, 0] - a[:, 0] * b[:, 2],
+                 a[:, 0] * b[:, 1] - a[:, 1] * b[:, 0]]
+        length = torch.sqrt((n[0] * n[0] + n[1] * n[1]) + n[2] * n[2])
+        ok = length > 0
+        n = [torch.where(ok, c / length, torch.full_like(c, d)) for c, d in zip(n, (0.0, 0.0, -1.0))]
+        back = n[2] > 0
+        n = [torch.where(back, -c, c) for c in n]
+        zero = torch.zeros_like(length)
+        dif = torch.fmax((n[0] * sh[0] + n[1] * sh[1]) + n[2] * sh[2], zero)
+        sp = torch.fmax((n[0] * sh[3] + n[1] * sh[4]) + n[2] * sh[5], zero)
+        for _ in range(int(shade[10])):
+            sp = sp * sp
+        mm = 1.0 - torch.fmax(-n[2], zero)
+        m2 = mm * mm
+        fr = (m2 * m2) * mm
+        lit, gloss = sh[6] + sh[7] * dif, 255.0 * (sh[8] * sp + sh[9] * fr)
+        if base is not None:
+            col = base.view(1, 3).expand(pix.shape[0], 3)
+        else:
+            s = mix(scalar[m]) if scalar is not None else depth[f].view(-1)[pix]
+            c = (s - lo_t) * inv
+            c = torch.where(c > 0, c, torch.zeros_like(c)).clamp(max=255.0)     # NaN: c > 0 is false, level 0
+            col = lut[torch.where(c >= 255.0, torch.full_like(pix, 255), (c + 0.5).long())]
+        val = col.float() * lit.unsqueeze(1) + gloss.unsqueeze(1)
+        val = torch.where(val > 0, val, torch.zeros_like(val)).clamp(max=255.0)
+        image[f, pix] = torch.where(val >= 255.0, torch.full_like(val, 255.0), torch.floor(val + 0.5)).to(torch.uint8)
+    return image.view(F, H, W, 3)
+
+
+def render_mesh(vertices, faces, cams, width, height, lut, vlengths=None, flengths=None, normals=None, scalar=None,
+                lo=None, hi=None, base=None, shade=None, background=(255, 255, 255), max_key_bytes=RENDER_KEY_BYTES):
+    """One picture per frame of indexed triangle meshes: a z-buffered rasteriser with deferred shading
+    (csrc/mesh_render.hip; the rule in full: include/tpgan_ops.h, "mesh pictures").
+
+    vertices (M,V,3) fp32 and faces (M,T,3) int32 with M = 1 (one mesh drawn under every camera, as an obstacle) or M =
+    the number of cameras F (mesh f in frame f); vlengths / flengths (M,) or None: vertices and faces at or beyond them
+    are never read.  A face with an index outside its mesh's vertices, a vertex that is not finite, behind the near
+    plane, beyond far or beyond 32768 pixels, or no area is not drawn; there is NO clipping.  cams: HOST fp32 (18,) /
+    (F,18) as for `render_points`; with one camera F = M.  normals (M,V,3) fp32 or None (the face's own normal);
+    scalar (M,V) fp32 with lo / hi, or None (the depth, 0 .. far - near): the base colour lut[level], interpolated in
+    screen space; base: 3 values 0..255 that replace it.  shade: `surface_shade()`'s table.  Both sides are lit.
+    -> (image (F,height,width,3) uint8, depth (F,height,width) fp32: the nearest face's distance from the near plane,
+    perspective-correct, +inf = background, winner (F,height,width) int32: that face's index, -1 = background).
+    Bit-identical from run to run, at every batch position and under every chunking, and equal to `_render_mesh_torch`
+    + `_mesh_shade_torch`, which backends without the kernel run.  No gradient."""
+    _check_float(vertices, "vertices", 3)
+    _check_int(faces, "faces", 3)
+    _same_device(vertices, faces)
+    _need(vertices.shape[2] == 3 and faces.shape[2] == 3, "vertices must be (M,V,3) and faces (M,T,3)")
+    M, V, _ = vertices.shape
+    T = faces.shape[1]
+    _need(faces.shape[0] == M, f"vertices and faces must hold the same number of meshes, got {M} and {faces.shape[0]}")
+    _need(V <= MESH_MAX_ROWS and T <= MESH_MAX_ROWS, f"at most {MESH_MAX_ROWS} vertices and faces per mesh")
+    ncam = (cams.numel() if isinstance(cams, torch.Tensor) else int(np.size(cams))) // RENDER_CAM_FLOATS
+    F = max(M, ncam)
+    _need(M in (1, F), f"{M} meshes do not go with {ncam} cameras: one mesh, or one per camera")
+    proxy = torch.empty((F, 0, 3), dtype=torch.float32, device=vertices.device)     # the frames `_picture_args` counts
+    if scalar is not None:
+        _check_float(scalar, "scalar", 2)
+        _same_device(vertices, scalar)
+        _need(tuple(scalar.shape) == (M, V), f"scalar must be ({M}, {V})")
+        _need(lo is not None and hi is not None, "a scalar colour needs its range lo / hi")
+    _, _, W, H, cams, _, lo, hi, lut, background, _ = _picture_args(
+        proxy, cams, width, height, lut, None, None, 0.0 if lo is None else lo, hi, background, max_key_bytes)
+    if normals is not None:
+        _check_float(normals, "normals", 3)
+        _same_device(vertices, normals)
+        _need(tuple(normals.shape) == (M, V, 3), f"normals must be ({M}, {V}, 3)")
+    if base is not None:
+        bs = np.asarray(base)
+        _need(bs.shape == (3,) and bs.dtype.kind in "iu" and 0 <= bs.min() and bs.max() <= 255, "base must be 3 values 0..255")
+        base = torch.tensor(bs.tolist(), dtype=torch.uint8).to(vertices.device)
+    shade = surface_shade() if shade is None else np.ascontiguousarray(np.asarray(shade, dtype=np.float32).reshape(-1))
+    _need(shade.shape == (SURFACE_SHADE_FLOATS,) and bool(np.isfinite(shade).all()),
+          f"shade must be {SURFACE_SHADE_FLOATS} finite floats (surface_shade() builds them)")
+    _need(shade[10] == int(shade[10]) and 0 <= shade[10] <= 8, "p must be an integer 0..8")
+    vlengths, flengths = _lengths(vlengths, M, V, vertices.device), _lengths(flengths, M, T, vertices.device)
+    if F == 0 or T == 0 or V == 0:
+        return (background.view(1, 1, 1, 3).expand(F, H, W, 3).contiguous(),
+                torch.full((F, H, W), float("inf"), dtype=torch.float32, device=vertices.device),
+                torch.full((F, H, W), -1, dtype=torch.int32, device=vertices.device))
+    be = backend_for(vertices)
+    with torch.no_grad():
+        vertices, faces = vertices.detach(), faces.detach()
+        normals, scalar = None if normals is None else normals.detach(), None if scalar is None else scalar.detach()
+        if hasattr(be, "render_mesh"):
+            return be.render_mesh(vertices, vlengths, faces, flengths, normals, scalar, cams, F, W, H, lo, hi, lut, base,
+                                  background, shade, int(max_key_bytes))
+        depth, winner = _render_mesh_torch(vertices, vlengths, faces, flengths, cams, F, W, H)
+        image = _mesh_shade_torch(depth, winner, vertices, vlengths, faces, flengths, normals, scalar, cams, lo, hi, lut,
+                                  base, background, shade)
+        return image, depth, winner
+
+
+def compose_layers(layers):
+    """[(image (...,H,W,3) uint8, depth (...,H,W) fp32), ...] -> (image, depth): per pixel the layer of smallest depth
+    (+inf: background, which every surface is in front of); on equality the EARLIER layer.  Every picture op writes such a
+    depth: `render_surface`, `render_mesh`, `render_points(return_depth=True)`.  Plain torch, no kernel."""
+    layers = list(layers)
+    _need(len(layers) >= 1, "compose_layers needs at least one layer")
+    image, depth = layers[0]
+    for img, dep in layers[1:]:
+        _need(img.shape == image.shape and dep.shape == depth.shape and tuple(img.shape[:-1]) == tuple(dep.shape),
+              "the layers of one picture share its shape")
+        take = dep < depth
+        image = torch.where(take.unsqueeze(-1), img, image)
+        depth = torch.where(take, dep, depth)
+    return image, depth
 
 
 # ------------------------------------------------------------------- particle fluid simulator (csrc/pbf.hip)

@@ -3,7 +3,8 @@
     python -m tpgan_amd.render --frames 'bunny_demo/pcd_{i}.npy' --count 800 --out PNGDIR
         [--size 3 --width 768 --height 768 --mode pinhole --color depth|density|free_surface
          --cutoff 0.0775 --direction x y z --frames_per_call T
-         --style points|surface --particle_radius 0.025 --smooth_iters 3 --smooth_half_width 2]
+         --style points|surface|surface_mesh --particle_radius 0.025 --smooth_iters 3 --smooth_half_width 2
+         --solids obstacles.ply|icosphere:2 --solids_color 150 150 150]
 
 The reference looks at its results through an Open3D window (train_utils.py:224-238) and hands its demo frames to an
 external renderer; neither works on a display-less GPU node.  Here a picture is one op, `ops.render_points`
@@ -12,7 +13,10 @@ layer above it: `Camera` (host maths in float64, rounded to fp32 once), the colo
 density / free surface / speed the project already computes on the device), a closed-form colour ramp and a PNG writer
 on the standard library.  `--style surface` draws the fluid's surface instead of its particles, `ops.render_surface`
 (csrc/surface.hip): spheres, a depth image smoothed within silhouettes, normals, shading -- what the reference leaves to
-an external renderer.  The look is this project's own: no parity with Open3D's or any renderer's picture is claimed.
+an external renderer.  Triangle meshes -- the surface `mesh.surface_mesh` builds (`--style surface_mesh`), the solids of a simulated
+scene (`--solids`), any .obj / .ply file -- are drawn by `ops.render_mesh` (csrc/mesh_render.hip) and composed with the
+fluid by depth, `ops.compose_layers`.  The look is this project's own: no parity with Open3D's or any renderer's picture
+is claimed.
 """
 import argparse
 import os
@@ -27,7 +31,8 @@ from . import analysis, ops
 PADDING = 900.0                # rows with any |coordinate| >= this are the 999 padding of hard masking, not points
 FRAMES_PER_CALL = 16
 MODES = {"ortho": ops.RENDER_ORTHO, "pinhole": ops.RENDER_PINHOLE}
-STYLES = ("points", "surface")
+STYLES = ("points", "surface", "surface_mesh")
+SOLIDS_COLOR = (150, 150, 150)
 
 
 def _unit(v, what):
@@ -209,38 +214,139 @@ def _prepare(points, camera, color, lengths, lo, hi, cutoff, radius, velocity):
 
 def render(points, camera, color=None, size=3, lengths=None, lo=None, hi=None, cutoff=None, radius=analysis.BASE_RADIUS,
            velocity=None, lut=None, background=(255, 255, 255), return_winner=False,
-           max_key_bytes=ops.RENDER_KEY_BYTES):
+           max_key_bytes=ops.RENDER_KEY_BYTES, return_depth=False, solids=None, solids_color=SOLIDS_COLOR):
     """Pictures of a cloud (N,3) -> (H,W,3) uint8, or of a batch (F,N,3) with optional lengths (F,) -> (F,H,W,3), on the
     points' device.  camera: one `Camera` for all frames or a list of F.  color: None / "depth" (the distance from the
     near plane, range 0 .. far - near), "density", "free_surface", "speed" (`point_scalar`), or a tensor (F,N) / (N,)
     of values per point.  lo / hi: the values that map to the ramp's ends; taken from the finite values when not
-    given.  return_winner: also the (F,H,W) int32 map of the visible point per pixel (-1: background)."""
+    given.  return_winner: also the (F,H,W) int32 map of the visible point per pixel (-1: background).  return_depth:
+    also the (F,H,W) fp32 depth of what is seen (+inf: background).  solids: a mesh (`render_mesh`'s single forms) drawn
+    in every frame in `solids_color` and composed with the points by depth; the winner map stays the points' own."""
     single, pts, cams, scalar, lo, hi = _prepare(points, camera, color, lengths, lo, hi, cutoff, radius, velocity)
-    image, winner = ops.render_points(pts, np.stack([c.row() for c in cams]), cams[0].width, cams[0].height,
-                                      default_lut() if lut is None else lut, size, lengths, scalar, lo, hi, background,
-                                      max_key_bytes)
+    rows = np.stack([c.row() for c in cams])
+    out = ops.render_points(pts, rows, cams[0].width, cams[0].height, default_lut() if lut is None else lut, size,
+                            lengths, scalar, lo, hi, background, max_key_bytes,
+                            return_depth=return_depth or solids is not None)
+    image, winner, depth = out if len(out) == 3 else out + (None,)
+    if solids is not None:
+        image, depth = _with_solids(image, depth, solids, solids_color, rows, cams[0], pts.shape[0], background,
+                                    max_key_bytes)
     if single:
-        image, winner = image[0], winner[0]
-    return (image, winner) if return_winner else image
+        image, winner, depth = image[0], winner[0], None if depth is None else depth[0]
+    extra = ((winner,) if return_winner else ()) + ((depth,) if return_depth else ())
+    return (image,) + extra if extra else image
 
 
 def render_surface(points, camera, particle_radius=analysis.BASE_RADIUS, color=None, lengths=None, lo=None, hi=None,
                    cutoff=None, radius=analysis.BASE_RADIUS, velocity=None, lut=None, background=(255, 255, 255),
                    half_width=2, iters=3, delta=None, light=None, return_depth=False, return_winner=False,
-                   max_key_bytes=ops.RENDER_KEY_BYTES):
+                   max_key_bytes=ops.RENDER_KEY_BYTES, solids=None, solids_color=SOLIDS_COLOR):
     """Pictures of the fluid's SURFACE (`ops.render_surface`: every point a sphere of `particle_radius`, the nearest
     fronts smoothed `iters` times over a window of half-width `half_width` without crossing depth steps above `delta`,
     default 2 x particle_radius, then shaded).  points, camera, color, lengths, lo, hi, cutoff, radius, velocity, lut
     and background are `render`'s and give the surface's base colour.  light: the direction towards the light in view
     coordinates (x right, y down, z forward; None: `ops.surface_shade()`'s).  return_depth / return_winner: also the
-    smoothed depth (F,H,W) fp32 (+inf: background) / the (F,H,W) int32 map of the point in front."""
+    smoothed depth (F,H,W) fp32 (+inf: background) / the (F,H,W) int32 map of the point in front.  solids: a mesh
+    (`render_mesh`'s single forms) drawn in every frame in `solids_color` under the same light and composed with the
+    fluid by depth; the depth returned is then the composed one, the winner map stays the fluid's own."""
     single, pts, cams, scalar, lo, hi = _prepare(points, camera, color, lengths, lo, hi, cutoff, radius, velocity)
-    out = ops.render_surface(pts, np.stack([c.row() for c in cams]), cams[0].width, cams[0].height,
-                             default_lut() if lut is None else lut, particle_radius, lengths, scalar, lo, hi, half_width,
-                             iters, delta, None if light is None else ops.surface_shade(light), background, max_key_bytes)
+    rows = np.stack([c.row() for c in cams])
+    shade = None if light is None else ops.surface_shade(light)
+    out = ops.render_surface(pts, rows, cams[0].width, cams[0].height, default_lut() if lut is None else lut,
+                             particle_radius, lengths, scalar, lo, hi, half_width, iters, delta, shade, background,
+                             max_key_bytes)
+    if solids is not None:
+        out = _with_solids(out[0], out[1], solids, solids_color, rows, cams[0], pts.shape[0], background, max_key_bytes,
+                           shade) + (out[2],)
     image, depth, winner = (o[0] for o in out) if single else out
     extra = ((depth,) if return_depth else ()) + ((winner,) if return_winner else ())
     return (image,) + extra if extra else image
+
+
+def _mesh_parts(mesh, device):
+    """A `mesh.Mesh`, or (vertices, faces[, normals]) of arrays / tensors -> (vertices (V,3) fp32, faces (T,3) int32,
+    normals (V,3) fp32 or None) on `device` (None: where the vertices are)."""
+    if hasattr(mesh, "_fields"):
+        mesh = (mesh.vertices, mesh.faces, mesh.normals)
+    if not isinstance(mesh, tuple) or len(mesh) not in (2, 3):
+        raise ValueError("a mesh is a mesh.Mesh or a tuple (vertices, faces[, normals])")
+    v = torch.as_tensor(mesh[0]).detach()
+    device = v.device if device is None else torch.device(device)
+    v = v.to(device).float().reshape(-1, 3)
+    f = torch.as_tensor(mesh[1]).detach().to(device).to(torch.int32).reshape(-1, 3)
+    n = None if len(mesh) < 3 or mesh[2] is None else torch.as_tensor(mesh[2]).detach().to(device).float().reshape(-1, 3)
+    if n is not None and n.shape != v.shape:
+        raise ValueError("normals go with the vertices, one each")
+    return v, f, n
+
+
+def pad_meshes(meshes, device=None):
+    """list of F meshes (`_mesh_parts`' forms) -> the ragged batch `ops.render_mesh` takes: (vertices (F,max V,3) fp32,
+    faces (F,max T,3) int32, normals (F,max V,3) or None unless every mesh has them, vlengths (F,), flengths (F,)); rows
+    beyond a mesh's own are zero and never read."""
+    parts = [_mesh_parts(m, device) for m in meshes]
+    device = parts[0][0].device
+    vl, fl = [p[0].shape[0] for p in parts], [p[1].shape[0] for p in parts]
+    vertices = torch.zeros((len(parts), max(max(vl), 1), 3), dtype=torch.float32, device=device)
+    faces = torch.zeros((len(parts), max(max(fl), 1), 3), dtype=torch.int32, device=device)
+    normals = torch.zeros_like(vertices) if all(p[2] is not None for p in parts) else None
+    for m, (v, f, n) in enumerate(parts):
+        vertices[m, :vl[m]], faces[m, :fl[m]] = v.to(device), f.to(device)
+        if normals is not None:
+            normals[m, :vl[m]] = n.to(device)
+    return (vertices, faces, normals, torch.tensor(vl, dtype=torch.int64, device=device),
+            torch.tensor(fl, dtype=torch.int64, device=device))
+
+
+def render_mesh(mesh, camera, color=None, base=None, lo=None, hi=None, lut=None, background=(255, 255, 255), light=None,
+                return_depth=False, return_winner=False, max_key_bytes=ops.RENDER_KEY_BYTES, device=None):
+    """Pictures of triangle meshes (`ops.render_mesh`: a z-buffered rasteriser, both sides lit).  mesh: a `mesh.Mesh`,
+    a tuple (vertices (V,3), faces (T,3)[, normals (V,3)]) of tensors or arrays, or a LIST of F of either, one per frame
+    (padded into a ragged batch).  camera: one `Camera`, or a list of F; one mesh under F cameras gives F pictures.  One
+    mesh under one camera -> (H,W,3) uint8, else (F,H,W,3), on the vertices' device (arrays go to `device`).  The base
+    colour: `base` (3 values 0..255), else the ramp of `color`, a tensor (V,) / (F,V) of values per vertex with lo / hi
+    (taken from the finite values when not given), else of the depth.  Vertex normals shade smoothly; without them
+    every face has its own.  light: as for `render_surface`.  return_depth / return_winner: also the depth (+inf:
+    background) / the face index per pixel (-1: background)."""
+    cams = [camera] if isinstance(camera, Camera) else list(camera)
+    if any((c.width, c.height) != (cams[0].width, cams[0].height) for c in cams):
+        raise ValueError("the cameras of one call share the picture's size")
+    many = isinstance(mesh, list)
+    vertices, faces, normals, vlengths, flengths = pad_meshes(mesh if many else [mesh], device)
+    single = not many and len(cams) == 1
+    scalar = None
+    if color is not None and not (isinstance(color, str) and color == "depth"):
+        if isinstance(color, str):
+            raise ValueError('a mesh is coloured by "depth", by values per vertex, or by `base`')
+        scalar = torch.zeros(vertices.shape[:2], dtype=torch.float32, device=vertices.device)
+        values = color if isinstance(color, (list, tuple)) else ([color] if not many else list(color))
+        for m, c in enumerate(values):
+            scalar[m, :int(vlengths[m])] = torch.as_tensor(c).detach().to(vertices.device).float().reshape(-1)
+        if lo is None or hi is None:
+            a, b = _finite_range(scalar, vlengths)
+            lo, hi = a if lo is None else lo, b if hi is None else hi
+        if not hi > lo:
+            hi = lo + 1.0
+    image, depth, winner = ops.render_mesh(
+        vertices, faces, np.stack([c.row() for c in cams]), cams[0].width, cams[0].height,
+        default_lut() if lut is None else lut, vlengths, flengths, normals, scalar, lo, hi, base,
+        None if light is None else ops.surface_shade(light), background, max_key_bytes)
+    if single:
+        image, depth, winner = image[0], depth[0], winner[0]
+    extra = ((depth,) if return_depth else ()) + ((winner,) if return_winner else ())
+    return (image,) + extra if extra else image
+
+
+def _with_solids(image, depth, solids, color, rows, camera, F, background, max_key_bytes, shade=None):
+    """The fluid's layer (image, depth) of F frames composed with `solids` drawn under the same cameras -> (image,
+    depth).  On equal depth the fluid shows."""
+    v, f, n = _mesh_parts(solids, image.device)
+    rows = rows if rows.shape[0] == F else np.repeat(rows, F, axis=0)          # one mesh, F frames
+    solid = ops.render_mesh(v.unsqueeze(0).contiguous(), f.unsqueeze(0).contiguous(), rows, camera.width, camera.height,
+                            default_lut(), normals=None if n is None else n.unsqueeze(0).contiguous(),
+                            base=tuple(int(c) for c in color), shade=shade, background=background,
+                            max_key_bytes=max_key_bytes)
+    return ops.compose_layers([(image, depth), (solid[0], solid[1])])
 
 
 def write_png(path, image):
@@ -275,15 +381,22 @@ class SequenceRenderer:
     `push` unless `camera` is given.  The range of a "density" colour is that of the first `push` as well, so the
     pictures of a sequence are comparable.  `push(frames, first)`: frames = list of (n_t,3) clouds, first = index of
     the first one; they are rendered in one call.  style: "points" (`render`, squares of `size` pixels) or "surface"
-    (`render_surface`: spheres of `particle_radius`, `smooth_iters` passes of half-width `half_width`)."""
+    (`render_surface`: spheres of `particle_radius`, `smooth_iters` passes of half-width `half_width`) or "surface_mesh" (every
+    frame meshed by `mesh.surface_mesh(**mesh_options)` and drawn with its vertex normals by `render_mesh`, coloured by
+    depth).  solids: a mesh (`render_mesh`'s single forms) drawn into every picture in `solids_color`; the camera is
+    still fitted to the frames alone."""
 
     def __init__(self, out_dir, size=3, width=768, height=768, mode="pinhole", color="depth", cutoff=None,
                  direction=(0.0, 0.0, -1.0), camera=None, device="cuda", style="points",
-                 particle_radius=analysis.BASE_RADIUS, smooth_iters=3, half_width=2):
+                 particle_radius=analysis.BASE_RADIUS, smooth_iters=3, half_width=2, solids=None,
+                 solids_color=SOLIDS_COLOR, mesh_options=None):
         if color not in ("depth", "density", "free_surface"):
             raise ValueError("color must be depth, density or free_surface")
         if style not in STYLES:
             raise ValueError(f"style must be one of {STYLES}")
+        if style == "surface_mesh" and color != "depth":
+            raise ValueError('style "surface_mesh" colours the surface by depth')
+        self.solids, self.solids_color, self.mesh_options = solids, tuple(solids_color), dict(mesh_options or {})
         self.style, self.particle_radius = style, float(particle_radius)
         self.smooth_iters, self.half_width = int(smooth_iters), int(half_width)
         self.out_dir, self.size, self.width, self.height, self.mode = out_dir, int(size), int(width), int(height), mode
@@ -304,11 +417,19 @@ class SequenceRenderer:
         if self.color == "density" and lo is None:
             s = point_scalar(batch, "density", lengths, self.cutoff)
             self.range = lo, hi = 0.0, max(_finite_range(s, lengths)[1], 1e-12)
-        if self.style == "surface":
+        solids = {} if self.solids is None else dict(solids=self.solids, solids_color=self.solids_color)
+        if self.style == "surface_mesh":
+            from . import mesh                      # mesh imports this module
+            meshes = [mesh.surface_mesh(batch[t, :int(lengths[t])], **self.mesh_options) for t in range(len(frames))]
+            images, depth = render_mesh(meshes, self.camera, return_depth=True)
+            if self.solids is not None:
+                images, _ = _with_solids(images, depth, self.solids, self.solids_color, self.camera.row()[None],
+                                         self.camera, len(frames), (255, 255, 255), ops.RENDER_KEY_BYTES)
+        elif self.style == "surface":
             images = render_surface(batch, self.camera, self.particle_radius, self.color, lengths, lo, hi, self.cutoff,
-                                    half_width=self.half_width, iters=self.smooth_iters)
+                                    half_width=self.half_width, iters=self.smooth_iters, **solids)
         else:
-            images = render(batch, self.camera, self.color, self.size, lengths, lo, hi, self.cutoff)
+            images = render(batch, self.camera, self.color, self.size, lengths, lo, hi, self.cutoff, **solids)
         images = images.cpu().numpy()
         for t, image in enumerate(images):
             write_png(os.path.join(self.out_dir, f"pcd_{first + t:04d}.png"), image)
@@ -324,18 +445,33 @@ def add_render_options(ap):
     ap.add_argument("--direction", type=float, nargs=3, default=(0.0, 0.0, -1.0), metavar=("X", "Y", "Z"),
                     help="viewing direction (y is up)")
     ap.add_argument("--style", choices=STYLES, default="points",
-                    help="points: a square per point; surface: the shaded fluid surface")
+                    help="points: a square per point; surface: the shaded fluid surface; surface_mesh: the meshed surface")
     ap.add_argument("--particle_radius", type=float, default=analysis.BASE_RADIUS,
                     help="--style surface: a point's sphere radius in world units")
     ap.add_argument("--smooth_iters", type=int, default=3, help="--style surface: smoothing passes over the depth")
     ap.add_argument("--smooth_half_width", type=int, default=2,
                     help="--style surface: half-width of the smoothing window, 1..4")
+    ap.add_argument("--solids", default=None, metavar="PATH|SPEC",
+                    help="a mesh drawn into every picture: an .obj / .ply file (a scene's obstacles.ply), icosphere:N or "
+                         "torus:R,r,nu,nv")
+    ap.add_argument("--solids_color", type=int, nargs=3, default=SOLIDS_COLOR, metavar=("R", "G", "B"))
+
+
+MESH_OPTIONS = ("spacing", "support", "step", "iso", "kernel", "cov_radius", "smooth_lambda")    # mesh.add_mesh_options'
 
 
 def renderer_from(a, out_dir, device):
+    """The renderer of the options `add_render_options` added; --style surface_mesh takes the mesher's options where the parser
+    has them too (`mesh.add_mesh_options`), and `mesh.surface_mesh`'s defaults otherwise."""
+    solids = None
+    if getattr(a, "solids", None):
+        from . import mesh                          # mesh imports this module
+        solids = mesh.load_spec(a.solids)
     return SequenceRenderer(out_dir, a.size, a.width, a.height, a.mode, a.color, a.cutoff, a.direction, device=device,
                             style=a.style, particle_radius=a.particle_radius, smooth_iters=a.smooth_iters,
-                            half_width=a.smooth_half_width)
+                            half_width=a.smooth_half_width, solids=solids,
+                            solids_color=getattr(a, "solids_color", SOLIDS_COLOR),
+                            mesh_options={k: getattr(a, k) for k in MESH_OPTIONS if hasattr(a, k)})
 
 
 def load_frame(path):

@@ -89,6 +89,10 @@ def add_sample_options(ap, default=0):
                          "one JSON line with their Chamfer distances (0: off)")
     ap.add_argument("--samples_width", type=int, default=512, help="width of the sample pictures")
     ap.add_argument("--samples_height", type=int, default=512, help="height of the sample pictures")
+    ap.add_argument("--solids", default=None, metavar="PATH|SPEC",
+                    help="a mesh drawn into every sample picture: an .obj / .ply file (a scene's obstacles.ply), "
+                         "icosphere:N or torus:R,r,nu,nv")
+    ap.add_argument("--solids_color", type=int, nargs=3, default=(150, 150, 150), metavar=("R", "G", "B"))
 
 
 def add_graph_option(ap):
@@ -149,20 +153,22 @@ class HeldOutPass:
     start-up -- are upsampled by `predict(sr_net, clip) -> (P,3)` in eval mode and written as
     `{gt,input,pred}_iter:{n_iter}_{j}.png` into `sample_dir` (the reference's names): coloured by depth, one camera per
     clip fitted to its ground truth, so that the three pictures of a clip and those of successive checkpoints compare;
-    splats of 3 pixels, 5 for the sparse input.  -> {"n_iter", "test_cd": Chamfer distance of prediction against ground
+    splats of 3 pixels, 5 for the sparse input; `solids` (a mesh, `render.render`'s) is drawn into all of them.  -> {"n_iter", "test_cd": Chamfer distance of prediction against ground
     truth per clip (losses.chamfer_distance), "test_points": predicted points per clip}.
 
     The pass draws no random number, runs on the current stream like the step (the prefetcher's hand-off is untouched)
     and puts the generator back into the mode it found it in."""
 
-    def __init__(self, clips, predict, sample_dir, width, height, amp_dtype=None):
+    def __init__(self, clips, predict, sample_dir, width, height, amp_dtype=None, solids=None,
+                 solids_color=(150, 150, 150)):
         from . import render
         self.clips, self.predict, self.sample_dir, self.amp_dtype = clips, predict, sample_dir, amp_dtype
+        self.solids = {} if solids is None else dict(solids=solids, solids_color=tuple(solids_color))
         self.cameras = [render.Camera.fit(c["gt"], width=width, height=height) for c in clips]
         os.makedirs(sample_dir, exist_ok=True)
         for j, (clip, cam) in enumerate(zip(clips, self.cameras)):           # what does not change is rendered once
-            clip["pictures"] = {"gt": render.render(clip["gt"], cam, size=3).cpu(),
-                                "input": render.render(clip["input"], cam, size=5).cpu()}
+            clip["pictures"] = {"gt": render.render(clip["gt"], cam, size=3, **self.solids).cpu(),
+                                "input": render.render(clip["input"], cam, size=5, **self.solids).cpu()}
 
     def __call__(self, sr_net, n_iter):
         from . import render
@@ -178,7 +184,7 @@ class HeldOutPass:
                         pred = self.predict(sr_net, clip).float().reshape(-1, 3).contiguous()
                     cds.append(float(chamfer_distance(pred[None], clip["gt"][None])))
                     counts.append(int(pred.shape[0]))
-                    pictures = dict(clip["pictures"], pred=render.render(pred, cam, size=3).cpu())
+                    pictures = dict(clip["pictures"], pred=render.render(pred, cam, size=3, **self.solids).cpu())
                     for name, image in pictures.items():
                         render.write_png(os.path.join(self.sample_dir, f"{name}_iter:{n_iter}_{j}.png"), image)
         finally:
@@ -249,8 +255,12 @@ def run(opt, nets_of, sched_of, sampler_of, step, samples_of=None, graph_step_of
             raise ValueError("--samples needs the trainer's samples_of")
         # before the prefetcher starts: its side stream waits for what the current stream has been given so far
         clips, predict = samples_of(dev, torch.Generator().manual_seed(opt.seed), opt.samples)
+        solids = None
+        if getattr(opt, "solids", None):
+            from . import mesh
+            solids = mesh.load_spec(opt.solids)
         held_out = HeldOutPass(clips, predict, os.path.join(opt.log_dir, "samples"), opt.samples_width,
-                               opt.samples_height, amp_dtype)
+                               opt.samples_height, amp_dtype, solids, getattr(opt, "solids_color", (150, 150, 150)))
     batches = prefetch(sampler)
     for net in nets:
         net.train()
