@@ -800,6 +800,53 @@ int tpg_surface_shade_f32(const float *depth, const int32_t *winner, const float
                           int ncam, int W, int H, float lo, float hi, const uint8_t *lut, const uint8_t *background,
                           const float *shade, uint8_t *image, void *stream);
 
+/* ---- fluid thickness and absorption (csrc/surface.hip) ------------------------------------------------------------
+ * The second half of screen-space fluid rendering: how much fluid a pixel looks through up to the first solid (a), and
+ * the shaded surface mixed with what lies behind it by a transmittance that falls with that thickness (c).  Between the
+ * two the thickness is blurred (b).  Everything is fp32, each operation rounded on its own.
+ *
+ * (a) tpg_render_thickness_f32 -> thickness (F,H,W) f32.  points, lengths, F, N, cams, ncam, W, H, rad as for
+ *   tpg_render_spheres_f32.  limit (F,H,W) f32 or NULL: the opaque scene's depth (distance from the near plane, +inf
+ *   where there is nothing); fluid beyond it is not counted.  acc (F,H,W) uint64, 8-byte aligned, zeroed by the call
+ *   itself.  Per point the projection, rp (with the 64-pixel cap), the drop test, the candidate box and the coverage
+ *   test s < 1.0f are those of entry (a) of "fluid surface pictures", word for word.  For a covered pixel (x, y):
+ *       h = sqrtf(1.0f - s);  half = rad*h;  tp = t - half;  tb = t + half
+ *       a = tp > 0 ? tp : 0.0f                       (the near-plane clamp of the fronts)
+ *       b = (limit && lim < tb) ? lim : tb            (lim = limit[f][y][x]; a NaN lim leaves the whole chord)
+ *       term = b - a
+ *   The pixel contributes iff term > 0, and then q = (long long)(term * 16777216.0f): units of 2^-24, truncated; a
+ *   64-bit integer atomic add on acc.  Then per pixel thickness = (float)acc * 2^-24f, the uint64 -> fp32 conversion
+ *   rounding to nearest even.  Integer sums: the result does not depend on the order of execution nor on how the discs
+ *   are spread over the lanes; bit-identical from run to run, at every batch position and under every chunking.
+ *   rad <= TPG_THICKNESS_MAX_RAD keeps a term at or below 2^35 units, N <= TPG_THICKNESS_MAX_N the sum below 2^63.
+ *
+ * (b) Smoothing the thickness needs no entry of its own: tpg_surface_smooth_f32 with delta = FLT_MAX is a plain binomial
+ *   blur whose window leaves out the pixels outside the image and nothing else (every finite difference passes the
+ *   test).  Zeros are finite and take part: the fluid's outline fades out, it is not kept sharp.
+ *
+ * (c) tpg_surface_absorb_u8: fluid (F,H,W,3) uint8, fdepth (F,H,W) f32, thickness (F,H,W) f32: the shaded fluid layer,
+ *   its depth and (a)'s image; behind (F,H,W,3) uint8, bdepth (F,H,W) f32: the solids over the background (no solid:
+ *   the background colour with +inf); th_max > 0; table: a HOST table of 256 x 3 f32 transmittances, each finite and in
+ *   [0,1] (a table, not expf, so that kernel, torch and numpy agree bit for bit)
+ *   -> image (F,H,W,3) uint8, depth (F,H,W) f32.  Per pixel: if fdepth is not finite or bdepth < fdepth, image = behind
+ *   and depth = bdepth (on equality the fluid wins, as the earlier layer does when layers are composed).  Otherwise
+ *   level by tpg_render_points_f32's level rule with s = thickness, lo = 0, inv = 255/th_max rounded to fp32 once; per
+ *   channel T = table[level][c], val = (float)fluid_c*(1.0f - T) + (float)behind_c*T, stored as
+ *   tpg_surface_shade_f32 stores: 0 unless val > 0, 255 if val >= 255, else (int)(val + 0.5f); depth = fdepth.
+ *
+ * Checks, all before anything is launched.  (a): those of tpg_render_spheres_f32 (thickness the output, acc the 8-byte
+ * aligned buffer), and rad > TPG_THICKNESS_MAX_RAD: TPG_ERR_ARG, N > TPG_THICKNESS_MAX_N: TPG_ERR_UNSUPPORTED.
+ * (c): negative F, a NULL output or table, a table entry that is not finite or outside [0,1], th_max not positive and
+ * finite, W or H < 1: TPG_ERR_ARG.  Then F == 0: TPG_OK, nothing written.  Then another NULL pointer or a th_max so
+ * small that inv is not finite: TPG_ERR_ARG; the limits on W, H, F and the pixels in all: TPG_ERR_UNSUPPORTED. */
+#define TPG_THICKNESS_MAX_RAD 1024
+#define TPG_THICKNESS_MAX_N 134217728
+int tpg_render_thickness_f32(const float *points, const int64_t *lengths, int F, int N, const float *cams, int ncam, int W,
+                             int H, float rad, const float *limit, void *acc, float *thickness, void *stream);
+int tpg_surface_absorb_u8(const uint8_t *fluid, const float *fdepth, const float *thickness, const uint8_t *behind,
+                          const float *bdepth, int F, int W, int H, float th_max, const float *table, uint8_t *image,
+                          float *depth, void *stream);
+
 /* ---- mesh pictures (csrc/mesh_render.hip) -----------------------------------------------------------------------
  * A z-buffered rasteriser of indexed triangle meshes in two entries: the nearest face per pixel (a), then deferred
  * shading of that face (b).  (The reference hands its geometry to an external renderer; the look here is this

@@ -87,6 +87,8 @@ SIGNATURES = {
     "tpg_render_spheres_f32": [_P, _P, _I, _I, _P, _I, _I, _I, _F, _P, _P, _P, _P],
     "tpg_surface_smooth_f32": [_P, _I, _I, _I, _I, _F, _P, _P],
     "tpg_surface_shade_f32": [_P, _P, _P, _I, _I, _P, _I, _I, _I, _F, _F, _P, _P, _P, _P, _P],
+    "tpg_render_thickness_f32": [_P, _P, _I, _I, _P, _I, _I, _I, _F, _P, _P, _P, _P],
+    "tpg_surface_absorb_u8": [_P, _P, _P, _P, _P, _I, _I, _I, _F, _P, _P, _P, _P],
     "tpg_render_mesh_f32": [_P, _P, _P, _P, _I, _I, _I, _I, _P, _I, _I, _I, _P, _P, _P, _P, _P],
     "tpg_mesh_shade_f32": [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _I, _I, _I, _F, _F, _P, _P, _P, _P, _P, _P],
     "tpg_pbf_predict_f32": [_P, _P, _P, _P, _I, _I, _F, _F, _P, _P, _P, _P],

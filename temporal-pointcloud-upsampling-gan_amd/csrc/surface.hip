@@ -25,7 +25,16 @@
 //       different rows of 32 consecutive floats, no bank conflict.
 //   tpg_surface_shade_f32    the same tiling with a halo of 1; normals from one-sided differences of the view-space
 //       points, Blinn-Phong plus a Fresnel rim, the colour from the look-up table.
-// No scratch, no floating-point atomics; the only atomic is the 64-bit integer min.
+// The second half of the technique makes the fluid translucent ("fluid thickness and absorption" in the header):
+//   tpg_render_thickness_f32 fill (zeros) + thickness + resolve
+//       thickness: the spheres launch again -- the per-point setup (sf_disc) and the wave-draws-the-disc loop
+//       (sf_draw_discs) are the same functions -- but a covered pixel adds the length of the ray's chord through the
+//       sphere, clipped at the near plane and at the opaque scene's depth, as an integer of 2^-24 units: one 64-bit
+//       atomic add per sphere per covered pixel.  Integer sums: any order, any lane layout, the same bits.
+//       resolve: one lane per pixel, the sum as a float.
+//   tpg_surface_absorb_u8    one lane per pixel: the shaded fluid over what lies behind it, mixed by a transmittance
+//       looked up by thickness (Beer-Lambert; the HOST table travels as a kernel argument and is read from there).
+// No scratch, no floating-point atomics; the only atomics are the 64-bit integer min and the 64-bit integer add.
 #include "render_common.hpp"
 
 #include <math.h>
@@ -45,40 +54,46 @@ __device__ __forceinline__ float sf_lane(float x, int lane) {
 
 __device__ __forceinline__ bool sf_finite(float x) { return fabsf(x) < INFINITY; }          // false for NaN
 
-// frames f0 .. f0 + gridDim.y - 1; per_frame == 0: every frame uses camera 0 of `cams`
-__global__ __launch_bounds__(RD_THREADS) void surface_spheres_kernel(
-    const float *__restrict__ points, const int64_t *__restrict__ lengths, RenderCams cams, int per_frame, int f0, int N,
-    int W, int H, float rad, tpg_u64 *__restrict__ keys) {
-    const int f = f0 + blockIdx.y;
-    const int i = blockIdx.x * RD_THREADS + threadIdx.x;
-    const int lane = threadIdx.x & (TPG_WAVE - 1);
+// What one lane knows of its point after entry (a)'s per-point rule: the projection, rp with its cap, the drop test and
+// the candidate box.  Both disc passes (sphere fronts, thickness) take it from here, so they cannot drift apart.
+struct SfDisc {
+    float u, v, t, rp;
+    int x0, x1, y0, y1;
+    bool keep;
+};
+
+__device__ __forceinline__ SfDisc sf_disc(const float *__restrict__ points, const int64_t *__restrict__ lengths,
+                                          const float *cam, int f, int i, int N, int W, int H, float rad) {
+    SfDisc d{0.0f, 0.0f, 0.0f, 1.0f, 0, -1, 0, -1, false};
     int n = N;
     if (lengths) {
         const long long l = lengths[f];
         n = l < 0 ? 0 : (l < N ? (int)l : N);
     }
-    const float *cam = cams.c[per_frame ? blockIdx.y : 0];
-    bool keep = false;
-    float u = 0.0f, v = 0.0f, t = 0.0f, rp = 1.0f;
-    int x0 = 0, x1 = -1, y0 = 0, y1 = -1;
-    if (i < n) {                                    // no early return: the whole wave draws the discs below
+    if (i < n) {                                    // no early return: the whole wave draws the discs
         float zv;
-        rd_project(points + ((size_t)f * N + i) * 3, cam, u, v, zv, t);
-        rp = cam[17] != 0.0f ? (rad / zv) * cam[12] : rad * cam[12];
-        rp = fminf(rp, (float)TPG_SURFACE_MAX_RADIUS);
+        rd_project(points + ((size_t)f * N + i) * 3, cam, d.u, d.v, zv, d.t);
+        d.rp = cam[17] != 0.0f ? (rad / zv) * cam[12] : rad * cam[12];
+        d.rp = fminf(d.rp, (float)TPG_SURFACE_MAX_RADIUS);
         // every comparison is false for a NaN operand: only a point for which ALL hold goes on
-        keep = t >= 0.0f && zv <= cam[16] && rp > 0.0f && u >= -rp && u < (float)W + rp && v >= -rp && v < (float)H + rp;
-        if (keep) {                                 // u - rp >= -128, u + rp < W + 128: the conversions are safe
-            x0 = max((int)floorf(u - rp), 0), x1 = min((int)floorf(u + rp), W - 1);
-            y0 = max((int)floorf(v - rp), 0), y1 = min((int)floorf(v + rp), H - 1);
+        d.keep = d.t >= 0.0f && zv <= cam[16] && d.rp > 0.0f && d.u >= -d.rp && d.u < (float)W + d.rp && d.v >= -d.rp &&
+                 d.v < (float)H + d.rp;
+        if (d.keep) {                               // u - rp >= -128, u + rp < W + 128: the conversions are safe
+            d.x0 = max((int)floorf(d.u - d.rp), 0), d.x1 = min((int)floorf(d.u + d.rp), W - 1);
+            d.y0 = max((int)floorf(d.v - d.rp), 0), d.y1 = min((int)floorf(d.v + d.rp), H - 1);
         }
     }
-    tpg_u64 *img = keys + (size_t)f * H * W;
-    for (tpg_u64 todo = __ballot(keep); todo != 0; todo &= todo - 1) {
+    return d;
+}
+
+// The wave draws the discs of its kept lanes one after the other; pixel(x, y, s, t, index) is called by one lane for
+// every covered pixel (s < 1) of the disc of point `index`, whose depth is t.
+template <class Pixel> __device__ __forceinline__ void sf_draw_discs(const SfDisc &d, int i, int lane, Pixel pixel) {
+    for (tpg_u64 todo = __ballot(d.keep); todo != 0; todo &= todo - 1) {
         const int src = __builtin_amdgcn_readfirstlane(__ffsll((long long)todo) - 1);
-        const float su = sf_lane(u, src), sv = sf_lane(v, src), st = sf_lane(t, src), srp = sf_lane(rp, src);
-        const int bx0 = __builtin_amdgcn_readlane(x0, src), bx1 = __builtin_amdgcn_readlane(x1, src);
-        const int by0 = __builtin_amdgcn_readlane(y0, src), by1 = __builtin_amdgcn_readlane(y1, src);
+        const float su = sf_lane(d.u, src), sv = sf_lane(d.v, src), st = sf_lane(d.t, src), srp = sf_lane(d.rp, src);
+        const int bx0 = __builtin_amdgcn_readlane(d.x0, src), bx1 = __builtin_amdgcn_readlane(d.x1, src);
+        const int by0 = __builtin_amdgcn_readlane(d.y0, src), by1 = __builtin_amdgcn_readlane(d.y1, src);
         const int bw = bx1 - bx0 + 1;
         if (bw < 1 || by1 < by0) continue;          // rounding can leave a box just outside the picture
         const int sh = bw <= 1 ? 0 : min(32 - __builtin_clz((unsigned)(bw - 1)), 6);
@@ -89,15 +104,90 @@ __global__ __launch_bounds__(RD_THREADS) void surface_spheres_kernel(
             for (int x = bx0 + (lane & (lw - 1)); x <= bx1; x += lw) {
                 const float dx = (((float)x + 0.5f) - su) / srp;
                 const float s = dx * dx + dy * dy;
-                if (!(s < 1.0f)) continue;
-                float tp = st - rad * sqrtf(1.0f - s);
-                if (!(tp > 0.0f)) tp = 0.0f;        // the front is clamped at the near plane
-                const tpg_u64 key = ((tpg_u64)__float_as_uint(tp) << 32) | index;
-                tpg_u64 *k = img + (size_t)y * W + x;
-                if (__hip_atomic_load(k, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) > key) atomicMin(k, key);
+                if (s < 1.0f) pixel(x, y, s, st, index);
             }
         }
     }
+}
+
+// frames f0 .. f0 + gridDim.y - 1; per_frame == 0: every frame uses camera 0 of `cams`
+__global__ __launch_bounds__(RD_THREADS) void surface_spheres_kernel(
+    const float *__restrict__ points, const int64_t *__restrict__ lengths, RenderCams cams, int per_frame, int f0, int N,
+    int W, int H, float rad, tpg_u64 *__restrict__ keys) {
+    const int f = f0 + blockIdx.y;
+    const int i = blockIdx.x * RD_THREADS + threadIdx.x;
+    const int lane = threadIdx.x & (TPG_WAVE - 1);
+    const SfDisc d = sf_disc(points, lengths, cams.c[per_frame ? blockIdx.y : 0], f, i, N, W, H, rad);
+    tpg_u64 *img = keys + (size_t)f * H * W;
+    sf_draw_discs(d, i, lane, [&](int x, int y, float s, float t, unsigned index) {
+        float tp = t - rad * sqrtf(1.0f - s);
+        if (!(tp > 0.0f)) tp = 0.0f;                // the front is clamped at the near plane
+        const tpg_u64 key = ((tpg_u64)__float_as_uint(tp) << 32) | index;
+        tpg_u64 *k = img + (size_t)y * W + x;
+        if (__hip_atomic_load(k, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) > key) atomicMin(k, key);
+    });
+}
+
+// The thickness pass: the same discs, but every covered pixel ADDS its chord, clipped at the near plane and at `limit`,
+// in units of 2^-24 and truncated: an integer sum, so neither the order nor the lane layout can change a bit.
+__global__ __launch_bounds__(RD_THREADS) void surface_thickness_kernel(
+    const float *__restrict__ points, const int64_t *__restrict__ lengths, RenderCams cams, int per_frame, int f0, int N,
+    int W, int H, float rad, const float *__restrict__ limit, tpg_u64 *__restrict__ acc) {
+    const int f = f0 + blockIdx.y;
+    const int i = blockIdx.x * RD_THREADS + threadIdx.x;
+    const int lane = threadIdx.x & (TPG_WAVE - 1);
+    const SfDisc d = sf_disc(points, lengths, cams.c[per_frame ? blockIdx.y : 0], f, i, N, W, H, rad);
+    const size_t frame = (size_t)f * H * W;
+    sf_draw_discs(d, i, lane, [&](int x, int y, float s, float t, unsigned) {
+        const size_t at = frame + (size_t)y * W + x;
+        const float half = rad * sqrtf(1.0f - s);
+        const float tp = t - half, tb = t + half;
+        const float a = tp > 0.0f ? tp : 0.0f;      // the near-plane clamp of the fronts
+        float b = tb;
+        if (limit) {
+            const float lim = limit[at];
+            if (lim < tb) b = lim;                  // false for a NaN: the whole chord
+        }
+        const float term = b - a;
+        if (term > 0.0f) atomicAdd(acc + at, (tpg_u64)(long long)(term * 16777216.0f));     // term <= 2 rad <= 2^11
+    });
+}
+
+__global__ __launch_bounds__(RD_THREADS) void surface_thickness_resolve_kernel(const tpg_u64 *__restrict__ acc,
+                                                                               long long pixels,
+                                                                               float *__restrict__ thickness) {
+    const long long at = (long long)blockIdx.x * RD_THREADS + threadIdx.x;
+    if (at >= pixels) return;
+    thickness[at] = (float)acc[at] * 5.9604644775390625e-8f;          // round to nearest even, then 2^-24 exactly
+}
+
+struct AbsorbTable {
+    float v[256 * 3];
+};
+
+// one lane per pixel of all frames
+__global__ __launch_bounds__(RD_THREADS) void surface_absorb_kernel(
+    const uint8_t *__restrict__ fluid, const float *__restrict__ fdepth, const float *__restrict__ thickness,
+    const uint8_t *__restrict__ behind, const float *__restrict__ bdepth, AbsorbTable table, long long pixels, float inv,
+    uint8_t *__restrict__ image, float *__restrict__ depth) {
+    const long long at = (long long)blockIdx.x * RD_THREADS + threadIdx.x;
+    if (at >= pixels) return;
+    const float fd = fdepth[at], bd = bdepth[at];
+    uint8_t out[3] = {behind[at * 3], behind[at * 3 + 1], behind[at * 3 + 2]};
+    float z = bd;
+    if (sf_finite(fd) && !(bd < fd)) {              // on equality the fluid is in front
+        const float *T = table.v + rd_level(thickness[at], 0.0f, inv) * 3;
+#pragma unroll
+        for (int ch = 0; ch < 3; ++ch) {
+            const float val = (float)fluid[at * 3 + ch] * (1.0f - T[ch]) + (float)out[ch] * T[ch];
+            out[ch] = !(val > 0.0f) ? 0 : (val >= 255.0f ? 255 : (int)(val + 0.5f));
+        }
+        z = fd;
+    }
+    image[at * 3] = out[0];
+    image[at * 3 + 1] = out[1];
+    image[at * 3 + 2] = out[2];
+    depth[at] = z;
 }
 
 __global__ __launch_bounds__(RD_THREADS) void surface_resolve_kernel(const tpg_u64 *__restrict__ keys, long long pixels,
@@ -271,6 +361,57 @@ extern "C" int tpg_render_spheres_f32(const float *points, const int64_t *length
     }
     hipLaunchKernelGGL(surface_resolve_kernel, dim3((unsigned)((pixels + RD_THREADS - 1) / RD_THREADS)), dim3(RD_THREADS),
                        0, st, (const tpg_u64 *)keys, pixels, depth, winner);
+    TPG_RETURN_IF_LAUNCH_FAILED();
+    return TPG_OK;
+}
+
+extern "C" int tpg_render_thickness_f32(const float *points, const int64_t *lengths, int F, int N, const float *cams,
+                                        int ncam, int W, int H, float rad, const float *limit, void *acc,
+                                        float *thickness, void *stream) {
+    if (F < 0 || N < 0 || !thickness) return TPG_ERR_ARG;
+    if (W < 1 || H < 1 || !(rad > 0.0f) || !(rad <= (float)TPG_THICKNESS_MAX_RAD)) return TPG_ERR_ARG;
+    if (F == 0 || N == 0) return TPG_OK;
+    if (!points || !cams || !acc || ((uintptr_t)acc & 7) != 0) return TPG_ERR_ARG;
+    if (ncam != 1 && ncam != F) return TPG_ERR_ARG;
+    if (!rd_cams_ok(cams, ncam)) return TPG_ERR_ARG;
+    if (sf_extents(F, W, H) != TPG_OK || N > TPG_THICKNESS_MAX_N) return TPG_ERR_UNSUPPORTED;
+    const long long pixels = (long long)F * H * W;
+    hipStream_t st = tpg_stream(stream);
+    if (hipMemsetAsync(acc, 0, sizeof(tpg_u64) * (size_t)pixels, st) != hipSuccess) return TPG_ERR_LAUNCH;
+    const int blocks = (N + RD_THREADS - 1) / RD_THREADS;
+    RenderCams rc;
+    const int group = ncam == 1 ? F : RD_GROUP;
+    for (int f0 = 0; f0 < F; f0 += group) {
+        const int nf = F - f0 < group ? F - f0 : group;
+        rd_fill_cams(rc, cams, ncam, f0, nf);
+        hipLaunchKernelGGL(surface_thickness_kernel, dim3(blocks, nf), dim3(RD_THREADS), 0, st, points, lengths, rc,
+                           ncam == 1 ? 0 : 1, f0, N, W, H, rad, limit, (tpg_u64 *)acc);
+        TPG_RETURN_IF_LAUNCH_FAILED();
+    }
+    hipLaunchKernelGGL(surface_thickness_resolve_kernel, dim3((unsigned)((pixels + RD_THREADS - 1) / RD_THREADS)),
+                       dim3(RD_THREADS), 0, st, (const tpg_u64 *)acc, pixels, thickness);
+    TPG_RETURN_IF_LAUNCH_FAILED();
+    return TPG_OK;
+}
+
+extern "C" int tpg_surface_absorb_u8(const uint8_t *fluid, const float *fdepth, const float *thickness,
+                                     const uint8_t *behind, const float *bdepth, int F, int W, int H, float th_max,
+                                     const float *table, uint8_t *image, float *depth, void *stream) {
+    if (F < 0 || !image || !depth || !table) return TPG_ERR_ARG;
+    if (W < 1 || H < 1 || !(th_max > 0.0f) || !rd_finite(th_max)) return TPG_ERR_ARG;
+    AbsorbTable tab;
+    for (int j = 0; j < 256 * 3; ++j) {             // HOST table, checked before anything is launched
+        if (!(table[j] >= 0.0f && table[j] <= 1.0f)) return TPG_ERR_ARG;
+        tab.v[j] = table[j];
+    }
+    if (F == 0) return TPG_OK;
+    if (!fluid || !fdepth || !thickness || !behind || !bdepth) return TPG_ERR_ARG;
+    const float inv = 255.0f / th_max;
+    if (!rd_finite(inv)) return TPG_ERR_ARG;
+    if (sf_extents(F, W, H) != TPG_OK) return TPG_ERR_UNSUPPORTED;
+    const long long pixels = (long long)F * H * W;
+    hipLaunchKernelGGL(surface_absorb_kernel, dim3((unsigned)((pixels + RD_THREADS - 1) / RD_THREADS)), dim3(RD_THREADS), 0,
+                       tpg_stream(stream), fluid, fdepth, thickness, behind, bdepth, tab, pixels, inv, image, depth);
     TPG_RETURN_IF_LAUNCH_FAILED();
     return TPG_OK;
 }

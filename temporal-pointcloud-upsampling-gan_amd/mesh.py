@@ -501,6 +501,9 @@ def main(argv=None):
         ap.error("--frames must contain '{i}'")
     if a.count < 1:
         ap.error("--count must be at least 1")
+    if a.translucent:
+        ap.error("--translucent goes with pictures of the particles (--style surface of tpgan_amd.render and "
+                 "tpgan_amd.rollout): --render here draws the mesh, which is opaque")
     seq = mesher_from(a, a.out, a.device)
     if a.render:
         seq.on_mesh = MeshPictures(a, a.render)

@@ -383,6 +383,45 @@ class HipBackend:
                        _ptr(image[f0:f1]))
         return image, depth, winner
 
+    def render_thickness(self, points, lengths, cams, W, H, radius, limit, max_key_bytes):
+        """csrc/surface.hip: the fluid a pixel looks through, up to `limit` (F,H,W) or None -> (F,H,W) fp32.  Frames go
+        in chunks as in `render_points`; the 64-bit sums live on the same key workspace."""
+        F, N, _ = points.shape
+        thickness = torch.empty((F, H, W), dtype=torch.float32, device=points.device)
+        chunk = max(1, min(65535, int(max_key_bytes) // (8 * H * W)))
+        acc = self._workspace("render_keys", points, min(chunk, F) * H * W, dtype=torch.int64)
+        for f0 in range(0, F, chunk):
+            f1 = min(F, f0 + chunk)
+            n, pix = f1 - f0, (f1 - f0) * H * W
+            c = cams if cams.shape[0] == 1 else np.ascontiguousarray(cams[f0:f1])
+            self._call("tpg_render_thickness_f32", "render_thickness", 12 * n * N + (24 if limit is None else 28) * pix,
+                       points, _ptr(points[f0:f1]), _ptr(None if lengths is None else lengths[f0:f1]), n, N,
+                       c.ctypes.data, c.shape[0], W, H, radius, _ptr(None if limit is None else limit[f0:f1]), _ptr(acc),
+                       _ptr(thickness[f0:f1]))
+        return thickness
+
+    def surface_smooth(self, image, half_width, delta, iters):
+        """csrc/surface.hip: `iters` >= 1 passes of tpg_surface_smooth_f32 over image (F,H,W) -> a new (F,H,W); the
+        passes alternate between the result and one per-stream workspace."""
+        F, H, W = image.shape
+        out = torch.empty_like(image)
+        other = self._workspace("surface_depth0", image, F * H * W) if iters > 1 else None
+        src = image
+        for it in range(iters):
+            dst = out if (iters - 1 - it) % 2 == 0 else other
+            self._call("tpg_surface_smooth_f32", "surface_smooth", 8 * F * H * W, image, _ptr(src), F, W, H, half_width,
+                       delta, _ptr(dst))
+            src = dst
+        return out
+
+    def absorb_layers(self, fluid, fdepth, thickness, behind, bdepth, table, th_max):
+        """csrc/surface.hip: the absorption composite; table is a host fp32 array (256,3) -> (image, depth)."""
+        F, H, W = fdepth.shape
+        image, depth = torch.empty_like(fluid), torch.empty_like(fdepth)
+        self._call("tpg_surface_absorb_u8", "surface_absorb", 22 * F * H * W, fluid, _ptr(fluid), _ptr(fdepth),
+                   _ptr(thickness), _ptr(behind), _ptr(bdepth), F, W, H, th_max, table.ctypes.data, _ptr(image), _ptr(depth))
+        return image, depth
+
     def render_mesh(self, vertices, vlengths, faces, flengths, normals, scalar, cams, F, W, H, lo, hi, lut, base,
                     background, shade, max_key_bytes):
         """csrc/mesh_render.hip: raster + resolve, then the deferred shading; cams and shade are host fp32 arrays,
@@ -2418,6 +2457,207 @@ def compose_layers(layers):
         image = torch.where(take.unsqueeze(-1), img, image)
         depth = torch.where(take, dep, depth)
     return image, depth
+
+
+# --------------------------------------------------------------- fluid thickness and absorption (csrc/surface.hip)
+THICKNESS_MAX_RADIUS = 1024.0          # world units: a chord stays at or below 2^35 units of 2^-24
+THICKNESS_MAX_N = 1 << 27              # points per frame: the 64-bit sum cannot overflow
+THICKNESS_UNIT = 16777216.0            # 2^24 units per world unit
+SMOOTH_ALL = float(np.finfo(np.float32).max)      # the delta that makes `surface_smooth` a plain blur: FLT_MAX
+
+
+def _render_thickness_torch(points, lengths, cams, W, H, radius, limit, pairs_per_chunk=1 << 22):
+    """`render_thickness` composed of torch ops (backends without the kernel): every kept point against every pixel
+    centre, `pairs_per_chunk` point x pixel pairs at a time, the contributions summed as int64 -> (F,H,W) fp32.  The
+    candidate box of the rule is not needed: a covered pixel always lies in it."""
+    F, N, _ = points.shape
+    dev = points.device
+    out = torch.empty((F, H, W), dtype=torch.float32, device=dev)
+    lens = [N] * F if lengths is None else [min(max(int(v), 0), N) for v in lengths.tolist()]
+    at = torch.arange(H * W, device=dev)
+    cx, cy = ((at % W).float() + 0.5).view(1, -1), ((at // W).float() + 0.5).view(1, -1)
+    rad = torch.tensor(np.float32(radius), device=dev)
+    step = max(1, int(pairs_per_chunk) // (H * W))
+    for f in range(F):
+        row = cams[f if cams.shape[0] > 1 else 0]
+        cam = torch.from_numpy(row).to(dev)
+        q = points[f, :lens[f]] - cam[0:3]
+
+        def dot(b):
+            return (q[:, 0] * b[0] + q[:, 1] * b[1]) + q[:, 2] * b[2]
+        xv, yv, zv = dot(cam[3:6]), dot(cam[6:9]), dot(cam[9:12])
+        if float(row[17]) != 0.0:
+            u, v = (xv / zv) * cam[12] + cam[13], (yv / zv) * cam[12] + cam[14]
+            rp = (rad / zv) * cam[12]
+        else:
+            u, v = xv * cam[12] + cam[13], yv * cam[12] + cam[14]
+            rp = (rad * cam[12]).expand_as(zv)
+        rp = torch.fmin(rp, torch.full_like(rp, float(SURFACE_MAX_RADIUS)))
+        t = zv - cam[15]
+        keep = (t >= 0) & (zv <= cam[16]) & (rp > 0) & (u >= -rp) & (u < W + rp) & (v >= -rp) & (v < H + rp)
+        index = torch.nonzero(keep).view(-1)
+        lim = None if limit is None else limit[f].reshape(1, -1)
+        acc = torch.zeros((H * W,), dtype=torch.int64, device=dev)
+        for k0 in range(0, index.shape[0], step):
+            rows = index[k0:k0 + step]
+            pu, pv, pt, pr = (a[rows].view(-1, 1) for a in (u, v, t, rp))
+            dx, dy = (cx - pu) / pr, (cy - pv) / pr
+            s = dx * dx + dy * dy
+            covered = s < 1.0
+            # sqrtf: torch's vectorised fp32 sqrt is not correctly rounded on every backend; the float64 root rounded to
+            # fp32 is (53 bits are more than twice 24 plus two: the second rounding cannot change the answer)
+            half = rad * torch.sqrt(torch.where(covered, 1.0 - s, torch.zeros_like(s)).double()).float()
+            tp, tb = pt - half, pt + half
+            a = torch.where(tp > 0, tp, torch.zeros_like(tp))
+            b = tb if lim is None else torch.where(lim < tb, lim.expand_as(tb), tb)      # false for a NaN: the whole chord
+            term = b - a
+            units = (torch.where(covered & (term > 0), term, torch.zeros_like(term)) * THICKNESS_UNIT).long()
+            acc += units.sum(0)
+        out[f] = (acc.to(torch.float32) * (1.0 / THICKNESS_UNIT)).view(H, W)
+    return out
+
+
+def render_thickness(points, cams, width, height, radius, lengths=None, limit=None, max_key_bytes=RENDER_KEY_BYTES):
+    """How much fluid every pixel looks through (csrc/surface.hip; the rule in full: include/tpgan_ops.h, "fluid
+    thickness and absorption"): every point is a sphere of `radius` world units (at most 1024) as in `render_surface`,
+    and a pixel's value is the sum over the spheres that cover it of the ray's chord through the sphere, in front of the
+    near plane and in front of `limit` (F,height,width) fp32 or None: the opaque scene's depth, +inf where there is
+    nothing.  points, cams, width, height, lengths and max_key_bytes are `render_points`'s.
+    -> thickness (F,height,width) fp32 in world units, 0 where there is no fluid.
+    The chords are summed as 64-bit integers of 2^-24 units: bit-identical from run to run, at every batch position and
+    under every chunking, and equal to `_render_thickness_torch`, which backends without the kernel run.  No
+    gradient."""
+    dummy = torch.zeros((256, 3), dtype=torch.uint8)
+    F, N, W, H, cams, _, _, _, _, _, lengths = _picture_args(points, cams, width, height, dummy, lengths, None, None, None,
+                                                             (0, 0, 0), max_key_bytes)
+    radius = float(np.float32(radius))
+    _need(np.isfinite(radius) and 0.0 < radius <= THICKNESS_MAX_RADIUS,
+          f"radius must be positive and at most {THICKNESS_MAX_RADIUS:g}")
+    _need(N <= THICKNESS_MAX_N, f"at most {THICKNESS_MAX_N} points per frame")
+    if limit is not None:
+        _check_float(limit, "limit", 3)
+        _same_device(points, limit)
+        _need(tuple(limit.shape) == (F, H, W), f"limit must be ({F}, {H}, {W})")
+    if F == 0 or N == 0:
+        return torch.zeros((F, H, W), dtype=torch.float32, device=points.device)
+    be = backend_for(points)
+    with torch.no_grad():
+        args = (points.detach(), lengths, cams, W, H, radius, None if limit is None else limit.detach())
+        if hasattr(be, "render_thickness"):
+            return be.render_thickness(*args, int(max_key_bytes))
+        return _render_thickness_torch(*args)
+
+
+def _surface_smooth_torch(image, half_width, delta):
+    """One pass of entry (b) of the fluid surface pictures composed of torch ops -> (F,H,W) fp32."""
+    F, H, W = image.shape
+    k = half_width
+    bw = [1]
+    for _ in range(2 * k):
+        bw = [a + b for a, b in zip([0] + bw, bw + [0])]
+    pad = torch.full((F, H + 2 * k, W + 2 * k), float("inf"), dtype=torch.float32, device=image.device)
+    pad[:, k:k + H, k:k + W] = image
+    acc, ws = torch.zeros_like(image), torch.zeros_like(image)
+    for oy in range(2 * k + 1):
+        for ox in range(2 * k + 1):
+            zj = pad[:, oy:oy + H, ox:ox + W]
+            ok = (zj - image).abs() <= delta        # false for background, NaN and what lies outside
+            w = float(bw[oy] * bw[ox])
+            acc = torch.where(ok, acc + w * zj, acc)
+            ws = torch.where(ok, ws + w, ws)
+    return torch.where(torch.isfinite(image), acc / ws, image)
+
+
+def surface_smooth(image, half_width=2, delta=None, iters=1):
+    """`iters` passes of the surface renderer's smoothing (tpg_surface_smooth_f32) over any image (F,H,W) fp32: a
+    binomial window of half-width `half_width` = 1..4 that leaves out pixels outside the image, pixels that are not finite
+    and neighbours further than `delta` from the centre.  delta None: FLT_MAX, a plain blur, which is how a thickness
+    image is smoothed (its zeros are finite and take part).  -> a new (F,H,W) fp32; iters = 0 returns `image` itself.
+    The kernel on the HIP backend, `_surface_smooth_torch` elsewhere; the two are equal.  No gradient."""
+    _check_float(image, "image", 3)
+    half_width, iters = int(half_width), int(iters)
+    _need(1 <= half_width <= SURFACE_MAX_HALF, f"half_width must be 1..{SURFACE_MAX_HALF}")
+    _need(iters >= 0, "iters must not be negative")
+    delta = float(np.float32(SMOOTH_ALL if delta is None else delta))
+    _need(np.isfinite(delta) and delta > 0.0, "delta must be positive and finite")
+    F, H, W = image.shape
+    _need(1 <= W <= RENDER_MAX_EXTENT and 1 <= H <= RENDER_MAX_EXTENT, f"width and height must be 1..{RENDER_MAX_EXTENT}")
+    if iters == 0 or F == 0:
+        return image
+    with torch.no_grad():
+        image = image.detach()
+        if image.is_cuda:
+            return backend_for(image).surface_smooth(image, half_width, delta, iters)
+        for _ in range(iters):
+            image = _surface_smooth_torch(image, half_width, delta)
+        return image
+
+
+def absorb_table(sigma, th_max):
+    """The (256,3) fp32 transmittance table `absorb_layers` looks thickness up in: table[l][c] = exp(-sigma_c * th_max *
+    l / 255) (Beer-Lambert), sigma: 3 finite absorption coefficients >= 0 per world unit, th_max > 0: the thickness of
+    level 255.  Host maths in float64, rounded to fp32 once."""
+    sigma = np.asarray(sigma, dtype=np.float64).reshape(-1)
+    th_max = float(th_max)
+    _need(sigma.shape == (3,) and bool(np.isfinite(sigma).all()) and bool((sigma >= 0).all()),
+          "sigma must be 3 finite values >= 0")
+    _need(np.isfinite(th_max) and th_max > 0.0, "th_max must be positive and finite")
+    level = np.arange(256, dtype=np.float64).reshape(256, 1)
+    return np.exp(-sigma.reshape(1, 3) * th_max * level / 255.0).astype(np.float32)
+
+
+def _absorb_torch(fluid, fdepth, thickness, behind, bdepth, table, th_max):
+    """`absorb_layers` in plain torch -> (image, depth)."""
+    dev = fluid.device
+    tab = torch.tensor(table, dtype=torch.float32, device=dev)
+    inv = torch.tensor(np.float32(255.0) / np.float32(th_max), device=dev)
+    c = thickness * inv
+    c = torch.where(c > 0, c, torch.zeros_like(c)).clamp(max=255.0)             # NaN: c > 0 is false, level 0
+    level = torch.where(c >= 255.0, torch.full_like(c, 255.0), torch.floor(c + 0.5)).long()
+    T = tab[level]
+    val = fluid.float() * (1.0 - T) + behind.float() * T
+    val = torch.where(val > 0, val, torch.zeros_like(val)).clamp(max=255.0)
+    mixed = torch.where(val >= 255.0, torch.full_like(val, 255.0), torch.floor(val + 0.5)).to(torch.uint8)
+    back = ~torch.isfinite(fdepth) | (bdepth < fdepth)
+    return torch.where(back.unsqueeze(-1), behind, mixed), torch.where(back, bdepth, fdepth)
+
+
+def absorb_layers(fluid_image, fluid_depth, thickness, behind_image, behind_depth, table, th_max):
+    """The translucent fluid over what lies behind it (csrc/surface.hip; the rule in full: include/tpgan_ops.h, "fluid
+    thickness and absorption").  fluid_image (F,H,W,3) uint8 and fluid_depth (F,H,W) fp32: the shaded fluid
+    (`render_surface`); thickness (F,H,W) fp32 (`render_thickness`, smoothed or not); behind_image / behind_depth: the
+    opaque scene, e.g. `render_mesh`'s picture, or the background colour with +inf.  Where there is no fluid, or the
+    opaque scene is nearer, the pixel is behind's; elsewhere per channel fluid * (1 - T) + behind * T with T =
+    table[level][c], level = thickness * 255 / th_max rounded, 0 .. 255.  table: `absorb_table(sigma, th_max)`, HOST
+    (256,3) fp32 in [0,1].  -> (image (F,H,W,3) uint8, depth (F,H,W) fp32: fluid_depth where the fluid shows).
+    The kernel on the HIP backend, `_absorb_torch` elsewhere; the two are equal.  No gradient."""
+    for t, name, ndim in ((fluid_depth, "fluid_depth", 3), (thickness, "thickness", 3), (behind_depth, "behind_depth", 3)):
+        _check_float(t, name, ndim)
+    F, H, W = fluid_depth.shape
+    for t, name in ((fluid_image, "fluid_image"), (behind_image, "behind_image")):
+        _need(isinstance(t, torch.Tensor) and t.dtype == torch.uint8 and tuple(t.shape) == (F, H, W, 3) and
+              t.is_contiguous(), f"{name} must be a contiguous uint8 tensor ({F}, {H}, {W}, 3)")
+    _need(thickness.shape == fluid_depth.shape and behind_depth.shape == fluid_depth.shape,
+          "the layers of one picture share its shape")
+    _same_device(fluid_image, fluid_depth, thickness, behind_image, behind_depth)
+    _need(1 <= W <= RENDER_MAX_EXTENT and 1 <= H <= RENDER_MAX_EXTENT, f"width and height must be 1..{RENDER_MAX_EXTENT}")
+    if isinstance(table, torch.Tensor):
+        _need(not table.is_cuda, "table is a host table: pass a CPU tensor or a numpy array")
+        table = table.numpy()
+    table = np.ascontiguousarray(np.asarray(table, dtype=np.float32))
+    _need(table.shape == (256, 3) and bool(((table >= 0) & (table <= 1)).all()), "table must be (256,3) values in [0,1]")
+    th_max = float(np.float32(th_max))
+    with np.errstate(all="ignore"):
+        _need(np.isfinite(th_max) and th_max > 0.0 and np.isfinite(np.float32(255.0) / np.float32(th_max)),
+              "th_max must be positive and finite")
+    if F == 0:
+        return torch.empty_like(fluid_image), torch.empty_like(fluid_depth)
+    with torch.no_grad():
+        args = (fluid_image.detach(), fluid_depth.detach(), thickness.detach(), behind_image.detach(),
+                behind_depth.detach(), table, th_max)
+        if fluid_image.is_cuda:
+            return backend_for(fluid_image).absorb_layers(*args)
+        return _absorb_torch(*args)
 
 
 # ------------------------------------------------------------------- particle fluid simulator (csrc/pbf.hip)

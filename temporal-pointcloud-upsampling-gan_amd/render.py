@@ -4,7 +4,8 @@
         [--size 3 --width 768 --height 768 --mode pinhole --color depth|density|free_surface
          --cutoff 0.0775 --direction x y z --frames_per_call T
          --style points|surface|surface_mesh --particle_radius 0.025 --smooth_iters 3 --smooth_half_width 2
-         --solids obstacles.ply|icosphere:2 --solids_color 150 150 150]
+         --solids obstacles.ply|icosphere:2 --solids_color 150 150 150
+         --translucent --absorption 0.2 0.07 0.03 --thickness_iters 2]
 
 The reference looks at its results through an Open3D window (train_utils.py:224-238) and hands its demo frames to an
 external renderer; neither works on a display-less GPU node.  Here a picture is one op, `ops.render_points`
@@ -13,8 +14,10 @@ layer above it: `Camera` (host maths in float64, rounded to fp32 once), the colo
 density / free surface / speed the project already computes on the device), a closed-form colour ramp and a PNG writer
 on the standard library.  `--style surface` draws the fluid's surface instead of its particles, `ops.render_surface`
 (csrc/surface.hip): spheres, a depth image smoothed within silhouettes, normals, shading -- what the reference leaves to
-an external renderer.  Triangle meshes -- the surface `mesh.surface_mesh` builds (`--style surface_mesh`), the solids of a simulated
-scene (`--solids`), any .obj / .ply file -- are drawn by `ops.render_mesh` (csrc/mesh_render.hip) and composed with the
+an external renderer; `--translucent` adds the technique's second half, a thickness image (`ops.render_thickness`) and a
+Beer-Lambert composite over what lies behind the fluid (`ops.absorb_layers`).  Triangle meshes -- the surface
+`mesh.surface_mesh` builds (`--style surface_mesh`), the solids of a simulated scene (`--solids`), any .obj / .ply file
+-- are drawn by `ops.render_mesh` (csrc/mesh_render.hip) and composed with the
 fluid by depth, `ops.compose_layers`.  The look is this project's own: no parity with Open3D's or any renderer's picture
 is claimed.
 """
@@ -33,6 +36,10 @@ FRAMES_PER_CALL = 16
 MODES = {"ortho": ops.RENDER_ORTHO, "pinhole": ops.RENDER_PINHOLE}
 STYLES = ("points", "surface", "surface_mesh")
 SOLIDS_COLOR = (150, 150, 150)
+# --translucent: absorption per particle diameter (red, green, blue).  Red goes first, as in water: one diameter still
+# transmits 0.82 / 0.93 / 0.97, twenty diameters 0.018 / 0.25 / 0.55.
+ABSORPTION = (0.20, 0.07, 0.03)
+THICKNESS_DIAMETERS = 40.0     # the absorption table's last level: this many particle diameters of fluid
 
 
 def _unit(v, what):
@@ -240,7 +247,8 @@ def render(points, camera, color=None, size=3, lengths=None, lo=None, hi=None, c
 def render_surface(points, camera, particle_radius=analysis.BASE_RADIUS, color=None, lengths=None, lo=None, hi=None,
                    cutoff=None, radius=analysis.BASE_RADIUS, velocity=None, lut=None, background=(255, 255, 255),
                    half_width=2, iters=3, delta=None, light=None, return_depth=False, return_winner=False,
-                   max_key_bytes=ops.RENDER_KEY_BYTES, solids=None, solids_color=SOLIDS_COLOR):
+                   max_key_bytes=ops.RENDER_KEY_BYTES, solids=None, solids_color=SOLIDS_COLOR, translucent=False,
+                   absorption=None, thickness_iters=2, return_thickness=False):
     """Pictures of the fluid's SURFACE (`ops.render_surface`: every point a sphere of `particle_radius`, the nearest
     fronts smoothed `iters` times over a window of half-width `half_width` without crossing depth steps above `delta`,
     default 2 x particle_radius, then shaded).  points, camera, color, lengths, lo, hi, cutoff, radius, velocity, lut
@@ -248,18 +256,45 @@ def render_surface(points, camera, particle_radius=analysis.BASE_RADIUS, color=N
     coordinates (x right, y down, z forward; None: `ops.surface_shade()`'s).  return_depth / return_winner: also the
     smoothed depth (F,H,W) fp32 (+inf: background) / the (F,H,W) int32 map of the point in front.  solids: a mesh
     (`render_mesh`'s single forms) drawn in every frame in `solids_color` under the same light and composed with the
-    fluid by depth; the depth returned is then the composed one, the winner map stays the fluid's own."""
+    fluid by depth; the depth returned is then the composed one, the winner map stays the fluid's own.
+    translucent: the fluid absorbs light instead of hiding what is behind it: the solids (or the bare background) are
+    drawn first, `ops.render_thickness` measures the fluid in front of them per pixel, that image is blurred
+    `thickness_iters` times with the window of `half_width`, and `ops.absorb_layers` mixes the shaded surface with what
+    lies behind it.  absorption: three coefficients (red, green, blue) per particle DIAMETER, default `ABSORPTION`; the
+    table reaches `THICKNESS_DIAMETERS` diameters, thicker fluid absorbs like that much.  return_thickness: also the
+    blurred thickness (F,H,W) fp32 in world units, after depth and winner (with `translucent` only)."""
     single, pts, cams, scalar, lo, hi = _prepare(points, camera, color, lengths, lo, hi, cutoff, radius, velocity)
+    if return_thickness and not translucent:
+        raise ValueError("return_thickness goes with translucent=True")
     rows = np.stack([c.row() for c in cams])
     shade = None if light is None else ops.surface_shade(light)
     out = ops.render_surface(pts, rows, cams[0].width, cams[0].height, default_lut() if lut is None else lut,
                              particle_radius, lengths, scalar, lo, hi, half_width, iters, delta, shade, background,
                              max_key_bytes)
-    if solids is not None:
+    if translucent:
+        F, (W, H) = pts.shape[0], (cams[0].width, cams[0].height)
+        if solids is not None:
+            behind, limit = _solid_layer(out[0].device, solids, solids_color, rows, cams[0], F, background, max_key_bytes,
+                                         shade)
+        else:
+            behind = torch.tensor([int(c) for c in background], dtype=torch.uint8, device=pts.device)
+            behind, limit = behind.view(1, 1, 1, 3).expand(F, H, W, 3).contiguous(), None
+        thickness = ops.render_thickness(pts, rows, W, H, particle_radius, lengths, limit, max_key_bytes)
+        thickness = ops.surface_smooth(thickness, half_width, None, thickness_iters)
+        diameter = 2.0 * float(particle_radius)
+        th_max = THICKNESS_DIAMETERS * diameter
+        sigma = np.asarray(ABSORPTION if absorption is None else absorption, dtype=np.float64).reshape(-1) / diameter
+        if limit is None:
+            limit = torch.full((F, H, W), float("inf"), dtype=torch.float32, device=pts.device)
+        out = ops.absorb_layers(out[0], out[1], thickness, behind, limit, ops.absorb_table(sigma, th_max), th_max) + \
+            (out[2], thickness)
+    elif solids is not None:
         out = _with_solids(out[0], out[1], solids, solids_color, rows, cams[0], pts.shape[0], background, max_key_bytes,
                            shade) + (out[2],)
-    image, depth, winner = (o[0] for o in out) if single else out
-    extra = ((depth,) if return_depth else ()) + ((winner,) if return_winner else ())
+    out = tuple(o[0] for o in out) if single else out
+    image, depth, winner = out[:3]
+    extra = ((depth,) if return_depth else ()) + ((winner,) if return_winner else ()) + \
+        ((out[3],) if return_thickness else ())
     return (image,) + extra if extra else image
 
 
@@ -337,16 +372,22 @@ def render_mesh(mesh, camera, color=None, base=None, lo=None, hi=None, lut=None,
     return (image,) + extra if extra else image
 
 
-def _with_solids(image, depth, solids, color, rows, camera, F, background, max_key_bytes, shade=None):
-    """The fluid's layer (image, depth) of F frames composed with `solids` drawn under the same cameras -> (image,
-    depth).  On equal depth the fluid shows."""
-    v, f, n = _mesh_parts(solids, image.device)
+def _solid_layer(device, solids, color, rows, camera, F, background, max_key_bytes, shade=None):
+    """`solids` drawn over `background` under the cameras of F frames -> (image, depth)."""
+    v, f, n = _mesh_parts(solids, device)
     rows = rows if rows.shape[0] == F else np.repeat(rows, F, axis=0)          # one mesh, F frames
     solid = ops.render_mesh(v.unsqueeze(0).contiguous(), f.unsqueeze(0).contiguous(), rows, camera.width, camera.height,
                             default_lut(), normals=None if n is None else n.unsqueeze(0).contiguous(),
                             base=tuple(int(c) for c in color), shade=shade, background=background,
                             max_key_bytes=max_key_bytes)
-    return ops.compose_layers([(image, depth), (solid[0], solid[1])])
+    return solid[0], solid[1]
+
+
+def _with_solids(image, depth, solids, color, rows, camera, F, background, max_key_bytes, shade=None):
+    """The fluid's layer (image, depth) of F frames composed with `solids` drawn under the same cameras -> (image,
+    depth).  On equal depth the fluid shows."""
+    return ops.compose_layers([(image, depth), _solid_layer(image.device, solids, color, rows, camera, F, background,
+                                                            max_key_bytes, shade)])
 
 
 def write_png(path, image):
@@ -384,18 +425,28 @@ class SequenceRenderer:
     (`render_surface`: spheres of `particle_radius`, `smooth_iters` passes of half-width `half_width`) or "surface_mesh" (every
     frame meshed by `mesh.surface_mesh(**mesh_options)` and drawn with its vertex normals by `render_mesh`, coloured by
     depth).  solids: a mesh (`render_mesh`'s single forms) drawn into every picture in `solids_color`; the camera is
-    still fitted to the frames alone."""
+    still fitted to the frames alone.  translucent, absorption, thickness_iters: `render_surface`'s, style "surface"
+    only."""
 
     def __init__(self, out_dir, size=3, width=768, height=768, mode="pinhole", color="depth", cutoff=None,
                  direction=(0.0, 0.0, -1.0), camera=None, device="cuda", style="points",
                  particle_radius=analysis.BASE_RADIUS, smooth_iters=3, half_width=2, solids=None,
-                 solids_color=SOLIDS_COLOR, mesh_options=None):
+                 solids_color=SOLIDS_COLOR, mesh_options=None, translucent=False, absorption=None, thickness_iters=2):
         if color not in ("depth", "density", "free_surface"):
             raise ValueError("color must be depth, density or free_surface")
         if style not in STYLES:
             raise ValueError(f"style must be one of {STYLES}")
         if style == "surface_mesh" and color != "depth":
             raise ValueError('style "surface_mesh" colours the surface by depth')
+        if translucent and style != "surface":
+            raise ValueError(f'translucent goes with style "surface", not with "{style}"')
+        if absorption is not None:
+            absorption = tuple(float(c) for c in absorption)
+            if len(absorption) != 3 or not all(np.isfinite(c) and c >= 0.0 for c in absorption):
+                raise ValueError("absorption must be 3 finite values >= 0")
+        if int(thickness_iters) < 0:
+            raise ValueError("thickness_iters must not be negative")
+        self.translucent, self.absorption, self.thickness_iters = bool(translucent), absorption, int(thickness_iters)
         self.solids, self.solids_color, self.mesh_options = solids, tuple(solids_color), dict(mesh_options or {})
         self.style, self.particle_radius = style, float(particle_radius)
         self.smooth_iters, self.half_width = int(smooth_iters), int(half_width)
@@ -403,6 +454,12 @@ class SequenceRenderer:
         self.color, self.cutoff, self.direction, self.camera = color, cutoff, tuple(direction), camera
         self.device, self.range = torch.device(device), (None, None)
         os.makedirs(out_dir, exist_ok=True)
+
+    def _translucent(self):
+        """`render_surface`'s extra arguments; none without `translucent`: that route is the one of before."""
+        if not self.translucent:
+            return {}
+        return dict(translucent=True, absorption=self.absorption, thickness_iters=self.thickness_iters)
 
     def fit(self, frames):
         self.camera = Camera.fit(list(frames), direction=self.direction, mode=self.mode, width=self.width,
@@ -427,7 +484,7 @@ class SequenceRenderer:
                                          self.camera, len(frames), (255, 255, 255), ops.RENDER_KEY_BYTES)
         elif self.style == "surface":
             images = render_surface(batch, self.camera, self.particle_radius, self.color, lengths, lo, hi, self.cutoff,
-                                    half_width=self.half_width, iters=self.smooth_iters, **solids)
+                                    half_width=self.half_width, iters=self.smooth_iters, **solids, **self._translucent())
         else:
             images = render(batch, self.camera, self.color, self.size, lengths, lo, hi, self.cutoff, **solids)
         images = images.cpu().numpy()
@@ -451,10 +508,26 @@ def add_render_options(ap):
     ap.add_argument("--smooth_iters", type=int, default=3, help="--style surface: smoothing passes over the depth")
     ap.add_argument("--smooth_half_width", type=int, default=2,
                     help="--style surface: half-width of the smoothing window, 1..4")
+    ap.add_argument("--translucent", action="store_true",
+                    help="--style surface: the fluid absorbs light by its thickness and shows what is behind it")
+    ap.add_argument("--absorption", type=float, nargs=3, default=None, metavar=("R", "G", "B"),
+                    help=f"--translucent: absorption per particle diameter (default {' '.join(map(str, ABSORPTION))})")
+    ap.add_argument("--thickness_iters", type=int, default=2, metavar="K",
+                    help="--translucent: blur passes over the thickness image")
     ap.add_argument("--solids", default=None, metavar="PATH|SPEC",
                     help="a mesh drawn into every picture: an .obj / .ply file (a scene's obstacles.ply), icosphere:N or "
                          "torus:R,r,nu,nv")
     ap.add_argument("--solids_color", type=int, nargs=3, default=SOLIDS_COLOR, metavar=("R", "G", "B"))
+
+
+def check_render_options(ap, a):
+    """The argument errors of `add_render_options`' translucency options, raised at parse time."""
+    if a.translucent and a.style != "surface":
+        ap.error(f"--translucent needs --style surface: it is the fluid's surface that absorbs light, not --style {a.style}")
+    if a.thickness_iters < 0:
+        ap.error("--thickness_iters must not be negative")
+    if a.absorption is not None and not all(np.isfinite(c) and c >= 0.0 for c in a.absorption):
+        ap.error("--absorption takes three finite values >= 0")
 
 
 MESH_OPTIONS = ("spacing", "support", "step", "iso", "kernel", "cov_radius", "smooth_lambda")    # mesh.add_mesh_options'
@@ -471,6 +544,8 @@ def renderer_from(a, out_dir, device):
                             style=a.style, particle_radius=a.particle_radius, smooth_iters=a.smooth_iters,
                             half_width=a.smooth_half_width, solids=solids,
                             solids_color=getattr(a, "solids_color", SOLIDS_COLOR),
+                            translucent=getattr(a, "translucent", False), absorption=getattr(a, "absorption", None),
+                            thickness_iters=getattr(a, "thickness_iters", 2),
                             mesh_options={k: getattr(a, k) for k in MESH_OPTIONS if hasattr(a, k)})
 
 
@@ -497,6 +572,7 @@ def main(argv=None):
         ap.error("--frames must contain '{i}'")
     if a.count < 1 or a.frames_per_call < 1:
         ap.error("--count and --frames_per_call must be at least 1")
+    check_render_options(ap, a)
     seq = renderer_from(a, a.out, torch.device(a.device))
     # one camera for the whole sequence: the union box of the first, the middle and the last frame
     seq.fit([load_frame(a.frames.format(i=i)) for i in sorted({0, a.count // 2, a.count - 1})])

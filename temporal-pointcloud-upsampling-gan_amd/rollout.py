@@ -147,6 +147,7 @@ def main(argv=None):
     a = ap.parse_args(argv)
     if "{i}" not in a.frames:
         ap.error("--frames must contain '{i}'")
+    render.check_render_options(ap, a)
     dev = torch.device(a.device)
     net = load_generator(a.checkpoint, a.in_feats, dev)
     os.makedirs(a.out, exist_ok=True)

@@ -78,6 +78,7 @@ def parse_args(argv=None):
     add_graph_option(ap)
     opt = ap.parse_args(argv)
     check_graph_option(ap, opt)
+    check_sample_options(ap, opt)
     if opt.samples is None:
         opt.samples = 4 if opt.dump_visualization else 0
     return opt
@@ -93,6 +94,39 @@ def add_sample_options(ap, default=0):
                     help="a mesh drawn into every sample picture: an .obj / .ply file (a scene's obstacles.ply), "
                          "icosphere:N or torus:R,r,nu,nv")
     ap.add_argument("--solids_color", type=int, nargs=3, default=(150, 150, 150), metavar=("R", "G", "B"))
+    ap.add_argument("--samples_style", choices=("points", "surface"), default="points",
+                    help="points: a square per point; surface: the shaded fluid surface (render.render_surface)")
+    ap.add_argument("--particle_radius", type=float, default=0.025,
+                    help="--samples_style surface: a point's sphere radius in the clips' units")
+    ap.add_argument("--translucent", action="store_true",
+                    help="--samples_style surface: the fluid absorbs light by its thickness and shows what is behind it")
+    ap.add_argument("--absorption", type=float, nargs=3, default=None, metavar=("R", "G", "B"),
+                    help="--translucent: absorption per particle diameter (default: render.ABSORPTION)")
+    ap.add_argument("--thickness_iters", type=int, default=2, metavar="K",
+                    help="--translucent: blur passes over the thickness image")
+
+
+def check_sample_options(ap, opt):
+    """The sample pictures' argument errors, raised at parse time."""
+    if opt.translucent and opt.samples_style != "surface":
+        ap.error("--translucent needs --samples_style surface: it is the fluid's surface that absorbs light, not "
+                 f"--samples_style {opt.samples_style}")
+    if opt.thickness_iters < 0:
+        ap.error("--thickness_iters must not be negative")
+    if opt.absorption is not None and not all(np.isfinite(c) and c >= 0.0 for c in opt.absorption):
+        ap.error("--absorption takes three finite values >= 0")
+    if not (np.isfinite(opt.particle_radius) and opt.particle_radius > 0.0):
+        ap.error("--particle_radius must be positive")
+
+
+def sample_surface_options(opt):
+    """`HeldOutPass`'s `surface`: None for --samples_style points, else `render.render_surface`'s arguments."""
+    if getattr(opt, "samples_style", "points") != "surface":
+        return None
+    surface = dict(particle_radius=opt.particle_radius)
+    if opt.translucent:
+        surface.update(translucent=True, absorption=opt.absorption, thickness_iters=opt.thickness_iters)
+    return surface
 
 
 def add_graph_option(ap):
@@ -153,22 +187,30 @@ class HeldOutPass:
     start-up -- are upsampled by `predict(sr_net, clip) -> (P,3)` in eval mode and written as
     `{gt,input,pred}_iter:{n_iter}_{j}.png` into `sample_dir` (the reference's names): coloured by depth, one camera per
     clip fitted to its ground truth, so that the three pictures of a clip and those of successive checkpoints compare;
-    splats of 3 pixels, 5 for the sparse input; `solids` (a mesh, `render.render`'s) is drawn into all of them.  -> {"n_iter", "test_cd": Chamfer distance of prediction against ground
-    truth per clip (losses.chamfer_distance), "test_points": predicted points per clip}.
+    splats of 3 pixels, 5 for the sparse input; `solids` (a mesh, `render.render`'s) is drawn into all of them; with
+    `surface` (a dict of `render.render_surface`'s arguments, `sample_surface_options`) the fluid's surface is drawn
+    instead of splats.  -> {"n_iter", "test_cd": Chamfer distance of prediction against ground truth per clip
+    (losses.chamfer_distance), "test_points": predicted points per clip}.
 
     The pass draws no random number, runs on the current stream like the step (the prefetcher's hand-off is untouched)
     and puts the generator back into the mode it found it in."""
 
     def __init__(self, clips, predict, sample_dir, width, height, amp_dtype=None, solids=None,
-                 solids_color=(150, 150, 150)):
+                 solids_color=(150, 150, 150), surface=None):
         from . import render
+        self.surface = surface
         self.clips, self.predict, self.sample_dir, self.amp_dtype = clips, predict, sample_dir, amp_dtype
         self.solids = {} if solids is None else dict(solids=solids, solids_color=tuple(solids_color))
         self.cameras = [render.Camera.fit(c["gt"], width=width, height=height) for c in clips]
         os.makedirs(sample_dir, exist_ok=True)
         for j, (clip, cam) in enumerate(zip(clips, self.cameras)):           # what does not change is rendered once
-            clip["pictures"] = {"gt": render.render(clip["gt"], cam, size=3, **self.solids).cpu(),
-                                "input": render.render(clip["input"], cam, size=5, **self.solids).cpu()}
+            clip["pictures"] = {"gt": self._draw(clip["gt"], cam, 3).cpu(), "input": self._draw(clip["input"], cam, 5).cpu()}
+
+    def _draw(self, points, cam, size):
+        from . import render
+        if self.surface is None:
+            return render.render(points, cam, size=size, **self.solids)
+        return render.render_surface(points, cam, **self.surface, **self.solids)
 
     def __call__(self, sr_net, n_iter):
         from . import render
@@ -184,7 +226,7 @@ class HeldOutPass:
                         pred = self.predict(sr_net, clip).float().reshape(-1, 3).contiguous()
                     cds.append(float(chamfer_distance(pred[None], clip["gt"][None])))
                     counts.append(int(pred.shape[0]))
-                    pictures = dict(clip["pictures"], pred=render.render(pred, cam, size=3, **self.solids).cpu())
+                    pictures = dict(clip["pictures"], pred=self._draw(pred, cam, 3).cpu())
                     for name, image in pictures.items():
                         render.write_png(os.path.join(self.sample_dir, f"{name}_iter:{n_iter}_{j}.png"), image)
         finally:
@@ -260,7 +302,8 @@ def run(opt, nets_of, sched_of, sampler_of, step, samples_of=None, graph_step_of
             from . import mesh
             solids = mesh.load_spec(opt.solids)
         held_out = HeldOutPass(clips, predict, os.path.join(opt.log_dir, "samples"), opt.samples_width,
-                               opt.samples_height, amp_dtype, solids, getattr(opt, "solids_color", (150, 150, 150)))
+                               opt.samples_height, amp_dtype, solids, getattr(opt, "solids_color", (150, 150, 150)),
+                               sample_surface_options(opt))
     batches = prefetch(sampler)
     for net in nets:
         net.train()

@@ -24,7 +24,7 @@ from .data import ActionClipSampler, ActionSequences, held_out_action_clips
 from .gan_step import tempo_gan_step_no_mask
 from .set_abstraction import ActionSpatialDis, ActionTempoDis
 from .srnet import NoMaskSRNet
-from .train import add_graph_option, add_sample_options, check_graph_option, run
+from .train import add_graph_option, add_sample_options, check_graph_option, check_sample_options, run
 
 
 def parse_args(argv=None):
@@ -54,6 +54,7 @@ def parse_args(argv=None):
     add_graph_option(ap)
     opt = ap.parse_args(argv)
     check_graph_option(ap, opt)
+    check_sample_options(ap, opt)
     return opt
 
 
